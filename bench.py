@@ -48,7 +48,7 @@ def parse():
                     help="exercise ONLY the launcher and the collectives of the selected mode (weak / --strong / --train) on the CPU with "
                          "the gloo backend and a stand-in for the render (no GPU, no HIP library): proves that --gpus N starts N ranks which "
                          "join the same collectives and that rank 0 prints one JSON line with n_gpus = N.  Not a measurement")
-    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--steps", type=int, default=10, help="timed steps (at least 1); ms_per_step is their mean")
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--hw", type=int, default=512, help="image side (BASELINE configs[1]: 512)")
     ap.add_argument("--samples", type=int, default=64)
@@ -121,7 +121,16 @@ def parse():
                     help="secondary mode: time the eager-PyTorch restatement of the path (oracle/train_oracle.py) on this GPU "
                          "the way the reference runs it (3072-ray chunks; 8192-ray training step), nearest-face searches "
                          "excluded - SURVEY 8d baseline (i)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last timed step rendered, as render_rays returns it, to DIR/<name>.npy "
+                         "(float32, finite: NaN / inf entries - disp_map on rays with acc_map = 0 - written as 0 and coded in <name>_nonfinite.npy; "
+                         "z_vals on a fixed seeded sample of the rays): two builds run with the same arguments on the same "
+                         "inputs can be compared output for output.  The headline line only (not --train / --strong / --eager-baseline "
+                         "/ --emulate-world / --dry-launch)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def main():
@@ -132,6 +141,9 @@ def main():
     world, rank, dev, use_dist = rk.world, rk.rank, rk.dev, rk.on
     if world > 1 and not (args.weak or args.train or args.eager_baseline):
         args.strong = True          # N > 1: the metric's frame partitioned over the ranks, unless --weak
+    if args.dump_outputs and (args.dry_launch or args.train or args.eager_baseline or args.strong or args.emulate_world > 1):
+        raise SystemExit("bench.py: --dump-outputs writes the headline line's frame only (not --train, --strong, --eager-baseline, "
+                         "--emulate-world or --dry-launch; with --gpus N > 1 add --weak)")
     if args.dry_launch:
         from benchlib.dry import dry_launch
         return dry_launch(args, rk)

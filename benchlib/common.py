@@ -35,6 +35,41 @@ def load_weights(synth, name):
     return synth.make_state_dict()
 
 
+DUMP_SAMPLE_ROWS = 16384                     # --dump-outputs: rays of a per-sample array ([R, S]) that are written
+DUMP_SEED = 20261015
+
+
+def dump_outputs(path, out):
+    """--dump-outputs: the arrays of one render_rays result as path/<name>.npy in float32.  Per-ray arrays are written whole; a
+    per-sample array ([R, S], 64 MiB at the headline frame) only on DUMP_SAMPLE_ROWS rays drawn with a fixed seed (the row indices go
+    to path/<name>_rows.npy, float64), so the files stay small and the same for every run with the same arguments.  Every file is
+    finite: an array with NaN / inf entries (disp_map is NaN on rays with acc_map = 0, 0 / 0 like the reference) is written with them
+    set to 0, and path/<name>_nonfinite.npy (float32, same shape) says which they were: 0 finite, 1 NaN, 2 +inf, 3 -inf."""
+    os.makedirs(path, exist_ok=True)
+    written = {}
+    for k, v in out.items():
+        if v is None:
+            continue
+        a = v.detach()
+        if a.dim() == 2 and a.shape[1] > 3 and a.shape[0] > DUMP_SAMPLE_ROWS:
+            rows = np.sort(np.random.default_rng(DUMP_SEED).choice(a.shape[0], DUMP_SAMPLE_ROWS, replace=False))
+            a = a[torch.from_numpy(rows).to(a.device)]
+            np.save(os.path.join(path, f"{k}_rows.npy"), rows.astype(np.float64))
+            written[f"{k}_rows"] = [DUMP_SAMPLE_ROWS]
+        a = a.float().cpu().numpy()
+        if not np.isfinite(a).all():
+            code = np.zeros(a.shape, np.float32)
+            code[np.isnan(a)] = 1.0
+            code[np.isposinf(a)] = 2.0
+            code[np.isneginf(a)] = 3.0
+            a = np.where(code == 0.0, a, np.float32(0.0)).astype(np.float32)
+            np.save(os.path.join(path, f"{k}_nonfinite.npy"), code)
+            written[f"{k}_nonfinite"] = list(code.shape)
+        np.save(os.path.join(path, f"{k}.npy"), a)
+        written[k] = list(a.shape)
+    return written
+
+
 def _flush_c_stdio():
     """RCCL prints its banner through C stdio; push it (and ours) out so that the JSON line really is the last line."""
     import ctypes

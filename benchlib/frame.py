@@ -10,7 +10,7 @@ import numpy as np
 import torch
 
 from .common import (LAZY_LISTS, FLOP_ALL_PER_SAMPLE, FLOP_FIELD_FWD_PER_SAMPLE, FLOP_FIELD_REV_PER_SAMPLE, PEAK_F16_MATRIX_TFLOPS, ROOT,
-                     SPLIT_PRODUCTS, load_weights, _flush_c_stdio)
+                     SPLIT_PRODUCTS, dump_outputs, load_weights, _flush_c_stdio)
 
 
 def frame_bench(args, dsnerf_amd, _lib, synth, rk):
@@ -194,6 +194,10 @@ def frame_bench(args, dsnerf_amd, _lib, synth, rk):
         step()
     barrier()
     dt = time.perf_counter() - t0
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # (the last timed step's frame, before the frames below reuse its slot's output buffers)
+        dumped = dump_outputs(args.dump_outputs, outs[(k_step - 1) % depth])
     # latency of one frame alone (no overlap with a neighbour), for the record
     k_step = 0
     share_cus[0] = False
@@ -275,6 +279,8 @@ def frame_bench(args, dsnerf_amd, _lib, synth, rk):
                         "forward_samples": n_fwd, "reverse_samples": n_rev, "shaded_samples": n_lit},
     }
 
+    if dumped is not None:
+        result["dumped_outputs"] = {"dir": os.path.abspath(args.dump_outputs), "shapes": dumped}
     if rank == 0 and world == 1 and not args.no_extras and not (args.dense or args.fp32):
         # The frame time is a property of the CHECKPOINT as much as of the kernels: the same frame, same pipeline,
         # 5 timed frames each, for every parameter set the repo pins with reference-generated goldens.  w4 is the converged one.

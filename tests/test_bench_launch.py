@@ -129,3 +129,78 @@ def test_ranks_are_counted_before_anything_is_timed():
     assert p.returncode != 0
     errs = [j for j in js if j.get("error")]
     assert errs and all("counted 1 rank(s)" in j["error"] for j in errs), (p.stdout, p.stderr[-1500:])
+
+
+# ---- --dump-outputs / --steps: what the timed path computed, and how many steps were timed ----
+def test_steps_below_one_are_refused():
+    p = subprocess.run([sys.executable, BENCH, "--dry-launch", "--steps", "0"], env=_env(), capture_output=True, text=True, timeout=300)
+    assert p.returncode == 2 and "--steps must be at least 1" in p.stderr
+    assert not _json_lines(p.stdout)
+
+
+def test_dump_outputs_refuses_a_mode_it_does_not_dump(tmp_path):
+    p = subprocess.run([sys.executable, BENCH, "--dry-launch", "--train", "--steps", "1", "--dump-outputs", str(tmp_path / "d")], env=_env(),
+                       capture_output=True, text=True, timeout=300)
+    assert p.returncode != 0 and "--dump-outputs" in p.stderr
+    assert not os.path.exists(tmp_path / "d")
+
+
+def test_dump_outputs_writes_float_arrays_within_64_mb(tmp_path):
+    """render_rays' result at the headline size (512 x 512 rays x 64 samples): every array as float32, the [R, S] one on a fixed seeded
+    row sample, and the same rows in every run"""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    from benchlib.common import DUMP_SAMPLE_ROWS, dump_outputs
+    R, S = 512 * 512, 64
+    g = torch.Generator().manual_seed(1)
+    out = {"color": torch.rand(R, 3, generator=g), "disp_map": torch.rand(R, generator=g), "acc_map": torch.rand(R, generator=g),
+           "depth_map": torch.rand(R, generator=g), "z_vals": torch.rand(R, S, generator=g)}
+    out["disp_map"][::7] = float("nan")           # (rays with acc_map = 0: 0 / 0, like the reference)
+    out["disp_map"][3] = float("inf")
+    out["disp_map"][5] = -float("inf")
+    shapes = dump_outputs(str(tmp_path / "a"), out)
+    dump_outputs(str(tmp_path / "b"), out)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == sorted(f"{k}.npy" for k in shapes) and "z_vals_rows.npy" in files
+    assert "disp_map_nonfinite.npy" in files and "color_nonfinite.npy" not in files
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 64 * 2 ** 20
+    rows = np.load(tmp_path / "a" / "z_vals_rows.npy")
+    assert rows.dtype == np.float64 and rows.shape == (DUMP_SAMPLE_ROWS,) and len(np.unique(rows)) == DUMP_SAMPLE_ROWS
+    for f in files:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype in (np.float32, np.float64) and np.isfinite(a).all() and np.array_equal(a, b), f
+    d, code = out["disp_map"].numpy(), np.load(tmp_path / "a" / "disp_map_nonfinite.npy")
+    assert np.array_equal(code == 1, np.isnan(d)) and code[3] == 2 and code[5] == 3 and int((code > 0).sum()) == int((~np.isfinite(d)).sum())
+    fin = np.isfinite(d)
+    assert np.array_equal(np.load(tmp_path / "a" / "disp_map.npy")[fin], d[fin]) and not np.load(tmp_path / "a" / "disp_map.npy")[~fin].any()
+    for k in ("color", "acc_map", "depth_map"):
+        assert np.array_equal(np.load(tmp_path / "a" / f"{k}.npy"), out[k].numpy()), k
+    assert np.array_equal(np.load(tmp_path / "a" / "z_vals.npy"), out["z_vals"].numpy()[rows.astype(np.int64)])
+
+
+@pytest.mark.gpu
+def test_bench_dumps_the_last_timed_frame(tmp_path):
+    """a small headline line with --dump-outputs, twice: the result line names the dump, ms_per_step is per timed step, and two runs
+    with the same arguments write the same arrays (the inputs are seeded)"""
+    import numpy as np
+    cmd = [sys.executable, BENCH, "--gpus", "1", "--hw", "128", "--steps", "3", "--warmup", "1", "--no-extras", "--no-roofline",
+           "--no-cpu-baseline"]
+    js = []
+    for d in ("a", "b"):
+        p = subprocess.run(cmd + ["--dump-outputs", str(tmp_path / d)], capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, p.stderr[-2000:]
+        js.append(_json_lines(p.stdout)[-1])
+    j = js[0]
+    assert j["steps"] == 3 and j["ms_per_step"] > 0 and abs(j["value"] - 128 * 128 / (j["ms_per_step"] * 1e-3)) < 1e-6 * j["value"]
+    assert j["dumped_outputs"]["shapes"]["color"] == [128 * 128, 3]
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert {"color.npy", "acc_map.npy", "depth_map.npy", "disp_map.npy", "z_vals.npy"} <= set(files)
+    for f in files:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype in (np.float32, np.float64) and np.isfinite(a).all() and np.array_equal(a, b), f
+    acc = np.load(tmp_path / "a" / "acc_map.npy")
+    assert float(acc.max()) > 0.05          # the frame shows the body
+    # disp_map is NaN exactly on the rays with acc_map = 0 (DESIGN.md: like the reference): written as 0, coded 1
+    code = np.load(tmp_path / "a" / "disp_map_nonfinite.npy") if "disp_map_nonfinite.npy" in files else np.zeros_like(acc)
+    assert np.array_equal(code == 1, acc == 0) and not (code > 1).any()
