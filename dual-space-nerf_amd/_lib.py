@@ -42,6 +42,7 @@ EXPORTS = [
     "dsn_early_stop_eps_scaled", "dsn_set_early_stop_colour_scale", "dsn_nn_header_offsets", "dsn_render_workspace_bytes_for",
     "dsn_render_workspace_record_capacity", "dsn_stop_slice_len", "dsn_stop_stats_slice_len", "dsn_early_stop_colour_headroom", "dsn_render_rays_ex",
     "dsn_render_rays_grad_ex", "dsn_render_rays_train_ex", "dsn_aux_create", "dsn_aux_destroy",
+    "dsn_render_lights_scratch_bytes", "dsn_render_rays_lights",
 ]
 
 SKIP_TRANSPARENT = 1
@@ -91,6 +92,8 @@ def lib():
                   "dsn_grad_workspace_bytes", "dsn_image_workspace_bytes", "dsn_pose_state_bytes",
                   "dsn_calibrate_workspace_bytes"):
             getattr(L, n).restype = C.c_size_t
+        L.dsn_render_lights_scratch_bytes.restype = C.c_size_t
+        L.dsn_render_lights_scratch_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int64]
         if L.dsn_abi_version() != 8:
             raise RuntimeError(f"{LIB_PATH} has ABI version {L.dsn_abi_version()}, this binding needs 8 - rebuild it "
                                "(python dual-space-nerf_amd/build.py)")
@@ -635,6 +638,7 @@ class RenderWorkspace:
         self.fraction = float(fraction)      # in force for the buffer
         self.want_fraction = float(fraction)      # asked for: applied by begin_frame()
         self._sized = None
+        self.light_scratch = None                 # compact colours of render_rays_lights (grown on demand)
 
     def fit_records(self, positive_fraction: float, headroom: float = 1.25) -> float:
         """a frame put this share of its samples on the sigma > 0 list: make the record capacity cover `headroom` x that from the next
@@ -733,6 +737,107 @@ def render_rays(scene: Scene, packed: PackedParams, ws: RenderWorkspace, ray_o, 
                                     _ptr(out["disp_map"]), _ptr(out["acc_map"]), _ptr(out["depth_map"]),
                                     _ptr(out.get("weights")), _ptr(out["z_vals"]), _ptr(buf), C.c_size_t(ws.cap), sched, n_sched, _stream()),
            "dsn_render_rays")
+    return out
+
+
+LIGHT_RECORD_FLOATS = 12            # = DSN_LIGHT_RECORD_FLOATS (include/dsnerf.h)
+LIGHT_SCRATCH_BUDGET = 256 << 20    # render_rays_lights: bytes of compact colours a sweep keeps at most (lights are grouped to fit)
+
+
+def light_records(lights, th_mean, device):
+    """The light settings of a relighting sweep as the [K, 12] float32 records of dsn_render_rays_lights.  Each light is a dict with
+    the optional keys `light_center` (world point, 3), `rot` (2 x 2) and `rot_center` (2): what DualSpaceNeRF.set_light_center /
+    set_rot / set_rot_center would hold.  light_shift = light_center - th_mean, computed as DualSpaceNeRF.frame_args does (th_mean: the
+    mean of the batch's Th, or Th itself: it is averaged here the same way); the rotation applies only with both `rot` and `rot_center` - one without the other is a ValueError
+    (frame_args would silently ignore it)."""
+    rows = []
+    for i, lt in enumerate(lights):
+        unknown = set(lt) - {"light_center", "rot", "rot_center"}
+        if unknown:
+            raise ValueError(f"light {i}: unknown keys {sorted(unknown)} (light_center, rot, rot_center)")
+        rec_t = torch.zeros(LIGHT_RECORD_FLOATS, dtype=torch.float32)
+        lc = lt.get("light_center")
+        if lc is not None:
+            lc = torch.as_tensor(lc)
+            th = torch.as_tensor(th_mean).to(lc).reshape(-1, 3).mean(dim=0)
+            rec_t[0] = 1.0
+            rec_t[1:4] = (lc.reshape(-1)[:3] - th).to(torch.float32).cpu()
+        rot, rc = lt.get("rot"), lt.get("rot_center")
+        if (rot is None) != (rc is None):
+            raise ValueError(f"light {i}: a rotation needs both `rot` and `rot_center`")
+        if rot is not None:
+            rec_t[4] = 1.0
+            rec_t[5:9] = torch.as_tensor(rot).reshape(-1)[:4].to(torch.float32).cpu()
+            rec_t[9:11] = torch.as_tensor(rc).reshape(-1)[:2].to(torch.float32).cpu()
+        rows.append(rec_t)
+    if not rows:
+        raise ValueError("a relighting sweep needs at least one light")
+    return torch.stack(rows).to(device)
+
+
+def render_rays_lights(scene: Scene, packed: PackedParams, ws: RenderWorkspace, ray_o, ray_d, near, far, S, t_vals, lights,
+                       skip_transparent=True, screen=False, audit=False, early_stop=False, stop_stats=False, stop_schedule=None,
+                       uniform=False, want_weights=True, scratch_budget=None, fp32=False, scratch_bytes=None):
+    """Relighting sweep (dsn_render_rays_lights): the eval-mode frame of render_rays(skip_transparent=True) under K light settings
+    with one geometry / field / normal pass.  `lights`: [K, 12] device records (light_records).  Returns render_rays' dict with
+    "color" of shape [K, R, 3]; disp / acc / depth / weights / z_vals do not depend on the light.  Synchronises once (the shading
+    list's length sizes the groups of lights).  scratch_budget: bytes of compact colours at most (default LIGHT_SCRATCH_BUDGET; never
+    less than one light's colours on a frame whose every sample is shaded).  scratch_bytes (tests): exactly this much scratch - the
+    library fails when it does not hold one light's colours."""
+    R = ray_o.shape[0]
+    K = int(lights.shape[0])
+    dev = scene.device
+    lights = lights.to(device=dev, dtype=torch.float32).contiguous()
+    assert lights.dim() == 2 and lights.shape[1] == LIGHT_RECORD_FLOATS, "lights: [K, 12] records (light_records)"
+    out = {
+        "color": torch.empty(K, R, 3, dtype=torch.float32, device=dev),
+        "disp_map": torch.empty(R, dtype=torch.float32, device=dev),
+        "acc_map": torch.empty(R, dtype=torch.float32, device=dev),
+        "depth_map": torch.empty(R, dtype=torch.float32, device=dev),
+        "z_vals": torch.empty(R, S, dtype=torch.float32, device=dev),
+    }
+    if want_weights:
+        out["weights"] = torch.empty(R, S, dtype=torch.float32, device=dev)
+    if not skip_transparent:
+        raise ValueError("render_rays_lights: eval mode with the transparent skip only")
+    if fp32:
+        raise ValueError("render_rays_lights: the exact-fp32 field is not supported (the sweep's lighting is the split-fp16 kernel's)")
+    flags = SKIP_TRANSPARENT
+    if uniform:
+        flags |= SAMPLE_UNIFORM
+    if screen:
+        flags |= DENSITY_SCREEN
+        if audit:
+            flags |= SCREEN_AUDIT
+    if early_stop:
+        flags |= EARLY_STOP
+    if stop_stats:
+        flags |= STOP_STATS
+    if scene.lazy:
+        flags |= LAZY_LISTS
+    ws.begin_frame()
+    buf = ws.get(R, S)
+    # compact colours: every light in one group when that fits the budget, else as many as fit - and always at least one light of the
+    # largest possible shading list (every sample)
+    budget = LIGHT_SCRATCH_BUDGET if scratch_budget is None else int(scratch_budget)
+    L = lib()
+    need = max(min(budget, L.dsn_render_lights_scratch_bytes(R, S, K, R * S)), L.dsn_render_lights_scratch_bytes(R, S, 1, R * S))
+    if scratch_bytes is not None:
+        need = int(scratch_bytes)
+    ls = ws.light_scratch
+    if ls is None or ls.numel() < need:
+        ls = ws.light_scratch = _scratch(need, dev)
+    sched, n_sched = None, 0
+    if stop_schedule is not None and early_stop:
+        n_sched = len(stop_schedule)
+        sched = (C.c_int32 * n_sched)(*[int(x) for x in stop_schedule])
+    _check(L.dsn_render_rays_lights(_ptr(scene.buf), scene.V, scene.F, _ptr(packed.buf), _ptr(ray_o, torch.float32),
+                                    _ptr(ray_d, torch.float32), _ptr(near, torch.float32), _ptr(far, torch.float32), R, S,
+                                    _ptr(t_vals, torch.float32), None, None, flags, _ptr(lights), K, _ptr(out["color"]),
+                                    _ptr(out["disp_map"]), _ptr(out["acc_map"]), _ptr(out["depth_map"]), _ptr(out.get("weights")),
+                                    _ptr(out["z_vals"]), _ptr(buf), C.c_size_t(ws.cap), _ptr(ls), C.c_size_t(min(ls.numel(), need)),
+                                    sched, n_sched, _stream()),
+           "dsn_render_rays_lights")
     return out
 
 

@@ -567,7 +567,9 @@ class Renderer:
         return {"skip_transparent": skip, "uniform": (self.sample_points_mode == "uniform"), "screen": screen,
                 "audit": audit, "early_stop": stop, "stop_stats": stats, "stop_schedule": sched}
 
-    def _render_eval(self, scene, ws, o, d, near, far, S, jitter, noise, screen=None, plan=None, phases=0, out=None):
+    def _render_eval(self, scene, ws, o, d, near, far, S, jitter, noise, screen=None, plan=None, phases=0, out=None, lights=None):
+        """lights: [K, 12] light records (_lib.light_records) - the frame is a relighting sweep (_lib.render_rays_lights; one call, no
+        phases), its "color" is [K, R, 3]"""
         packed = self.net.packed(self.device)
         if (plan is None and screen is None and phases == 0 and noise is None and packed.screen is None and self.density_screen
                 and self.skip_transparent and not self.net.training):
@@ -579,6 +581,8 @@ class Renderer:
                                    out=out, **geo)
             self._screen_usable(frame=(scene, ws, o.shape[0], S))
             phases = _lib.PHASE_FIELD | _lib.PHASE_SHADE
+            if lights is not None:
+                out = None      # (a sweep runs whole: its geometry phase again behind the calibration)
         plan = self._eval_plan(noise, screen) if plan is None else plan
         # what this frame ran with (early stop is the one default-on feature whose output is error-bounded, not
         # bit-identical - a caller can see per frame whether it was in use and with which threshold)
@@ -590,8 +594,12 @@ class Renderer:
                                 "early_stop_bound_x_max_colour": (S + 1) * _lib.early_stop_eps(S, cs) if plan["early_stop"] else 0.0,
                                 # (absolute, for colours up to the scale)
                                 "early_stop_bound_abs": (S + 1) * _lib.early_stop_eps(S, cs) * cs if plan["early_stop"] else 0.0}
-        out = _lib.render_rays(scene, packed, ws, o, d, near, far, S, self._t_vals(S), jitter, noise, phases=phases, out=out,
-                               share_cus=getattr(self, "_frames_overlap", False), **plan)
+        if lights is not None:
+            self.last_frame_info["lights"] = int(lights.shape[0])
+            out = _lib.render_rays_lights(scene, packed, ws, o, d, near, far, S, self._t_vals(S), lights, **plan)
+        else:
+            out = _lib.render_rays(scene, packed, ws, o, d, near, far, S, self._t_vals(S), jitter, noise, phases=phases, out=out,
+                                   share_cus=getattr(self, "_frames_overlap", False), **plan)
         if plan["stop_stats"] and (phases == 0 or phases & _lib.PHASE_SHADE):
             self._probe_samples = int(o.shape[0]) * int(S)
             self._probe_shape = (int(o.shape[0]), int(S))
@@ -862,6 +870,58 @@ class Renderer:
         # fresh pageable tensors (clone() of a page-locked tensor allocates page-locked memory again: 2-3 ms per image), copied
         # by one thread (see _dev)
         return {k: torch.from_numpy(stage[k].numpy().copy()) for k in keys}
+
+    def render_view_lights(self, batch, lights, chunk=None, device_output=False):
+        """render_view under several light settings from ONE geometry / field pass (not in the reference: its vis_lighting.py renders
+        every view once per light).  `lights`: a list of dicts with the optional keys `light_center`, `rot`, `rot_center` - what
+        net.set_light_center / set_rot / set_rot_center would set (rot and rot_center go together; {} = no light edit).  Returns one
+        dict per light with render_view's keys; every image equals render_view's with that light set on the net.  The net's own
+        light attributes are neither used nor changed; early stop, the density screen and its audit follow render_view's per-frame
+        plan, and a sweep that weighed a colour above the early-stop scale under ANY light is rendered again in one pass
+        (last_frame_info["rendered_again_in_one_pass"]).  Eval mode only.  Sampling, geometry, the field, the normals and the
+        compositing weights run once; each light costs its lighting MLP and its rgb sums (dsn_render_rays_lights)."""
+        lights = list(lights)
+        if not lights:
+            raise ValueError("render_view_lights: no lights given")
+        if self.net.training:
+            raise RuntimeError("render_view_lights: eval mode only (Renderer.eval()); a sweep has no training forward")
+        if not self.skip_transparent:
+            raise RuntimeError("render_view_lights: needs skip_transparent = True (the eval-mode path)")
+        with _HostPoolGuard(self.host_pool_limit):
+            imgs = self._view_images_lights(batch, lights, chunk)
+            imgs = self._hand_over(imgs, lambda: self._view_images_lights(batch, lights, chunk))
+            self.last_frame_info = dict(self.last_frame_info, lights=len(lights),
+                                        rendered_again_in_one_pass=self.last_frame_info.get("rendered_again_in_one_pass", False))
+            if device_output:
+                return imgs
+            torch.cuda.current_stream(self.device).synchronize()
+            return [{k: v.cpu() for k, v in img.items()} for img in imgs]
+
+    def _view_images_lights(self, batch, lights, chunk):
+        scene, ws = self.scene, self._ws
+        # the frame without a light edit (the sweep brings its own); zero_code as DualSpaceNeRF.frame_args has it
+        frame = int(torch.as_tensor(batch["frame"]).reshape(-1)[0])
+        xyz = self._dev(batch["xyz"][0])
+        poses = batch["poses"][0].to(device=self.device, dtype=torch.float32).contiguous()
+        scene.set_frame(self.net.packed(self.device), xyz, poses, frame, self.net.nerf.w is not None, None, None, None, fine_only=True,
+                        lazy=self.lazy_lists)
+        self._frame_src = None      # (the scene's frame state now lacks the net's light edit: stage calls set their frame again)
+        th = batch["Th"][0] if any(lt.get("light_center") is not None for lt in lights) else None
+        recs = _lib.light_records(lights, th, self.device)
+        o, d = self._dev(batch["ray_o"][0]), self._dev(batch["ray_d"][0])
+        n, f = self._dev(batch["near"][0]).clone(), self._dev(batch["far"][0]).clone()
+        S = self.cfg.MODEL.COARSE_RAY_SAMPLING
+        R = o.shape[0]
+        chunk = R if chunk is None else int(chunk)
+        outs = []
+        for i in range(0, R, chunk):
+            j = min(R, i + chunk)
+            outs.append(self._render_eval(scene, ws, o[i:j].contiguous(), d[i:j].contiguous(), n[i:j].contiguous(), f[i:j].contiguous(),
+                                          S, None, None, lights=recs))
+        coarse = outs[0] if len(outs) == 1 else {k: torch.cat([x[k] for x in outs], 1 if k == "color" else 0) for k in outs[0]}
+        _, H, W, _ = batch["img"].shape
+        mask = self._dev(batch["mask_at_box"][0], torch.uint8)
+        return [_lib.image_scatter(dict(coarse, color=coarse["color"][k]), mask, H, W) for k in range(len(lights))]
 
     def render_views(self, batches, frames_in_flight=3, device_output=True, chunk=None):
         """The per-frame loop of novel_pose_vis.py:41-66 / test.py:55-64 (`for batch in loader: render.render_view(batch)`) as

@@ -624,11 +624,65 @@ int dsn_render_rays(const void* scene, int V, int F, const void* packed, const f
                               out_depth, out_weights, out_z, workspace, 0, nullptr, 0, stream);
 }
 
+// dsn_render_rays_lights: what replaces the shading phase of a frame (NULL: the frame's own light, dsn_render_rays_ex)
+struct DsnLightSweep {
+    const float* lights;      // [n_lights][DSN_LIGHT_RECORD_FLOATS] (device)
+    int n_lights;
+    void* scratch;            // compact colours of a group of lights: [G][n_shaded][3]
+    size_t scratch_bytes;
+};
+static int dsn_render_frame(const void* scene, int V, int F, const void* packed, const float* ray_o, const float* ray_d, float* near,
+                            float* far, int R, int S, const float* t_vals, const float* jitter, const float* noise,
+                            int flags, float* out_rgb, float* out_disp, float* out_acc, float* out_depth,
+                            float* out_weights, float* out_z, void* workspace, size_t workspace_bytes, const int32_t* slice_lengths_host,
+                            int n_slices, void* stream, const DsnLightSweep* sweep);
+
 int dsn_render_rays_ex(const void* scene, int V, int F, const void* packed, const float* ray_o, const float* ray_d, float* near,
                        float* far, int R, int S, const float* t_vals, const float* jitter, const float* noise,
                        int flags, float* out_rgb, float* out_disp, float* out_acc, float* out_depth,
                        float* out_weights, float* out_z, void* workspace, size_t workspace_bytes, const int32_t* slice_lengths_host,
                        int n_slices, void* stream) {
+    return dsn_render_frame(scene, V, F, packed, ray_o, ray_d, near, far, R, S, t_vals, jitter, noise, flags, out_rgb, out_disp, out_acc,
+                            out_depth, out_weights, out_z, workspace, workspace_bytes, slice_lengths_host, n_slices, stream, nullptr);
+}
+
+static_assert(DSN_LIGHT_RECORD_FLOATS == 12, "dsn_common.h and include/dsnerf.h disagree on the light record");
+
+size_t dsn_render_lights_scratch_bytes(int R, int S, int n_lights, int64_t n_shaded) {
+    if (R <= 0 || S <= 0 || n_lights < 1 || n_shaded < 0 || n_shaded > (int64_t)R * S) return 0;
+    return dsn_align256(sizeof(float) * 3 * (size_t)n_lights * (size_t)std::max<int64_t>(n_shaded, 1));
+}
+
+int dsn_render_rays_lights(const void* scene, int V, int F, const void* packed, const float* ray_o, const float* ray_d, float* near,
+                           float* far, int R, int S, const float* t_vals, const float* jitter, const float* noise, int flags,
+                           const float* lights, int n_lights, float* out_rgb, float* out_disp, float* out_acc, float* out_depth,
+                           float* out_weights, float* out_z, void* workspace, size_t workspace_bytes, void* light_scratch,
+                           size_t light_scratch_bytes, const int32_t* slice_lengths_host, int n_slices, void* stream) {
+    DSN_REQUIRE(R > 0 && S > 0, "dsn_render_rays_lights: empty ray batch");
+    DSN_REQUIRE(scene && packed && ray_o && ray_d && near && far && t_vals && workspace && lights && light_scratch,
+                "dsn_render_rays_lights: null argument");
+    DSN_REQUIRE(out_rgb && out_disp && out_acc && out_depth, "dsn_render_rays_lights: null output");
+    DSN_REQUIRE(n_lights >= 1, "dsn_render_rays_lights: n_lights must be at least 1");
+    DSN_REQUIRE(!jitter && !noise, "dsn_render_rays_lights: eval mode only (no jitter, no noise)");
+    DSN_REQUIRE(flags & DSN_SKIP_TRANSPARENT, "dsn_render_rays_lights: eval mode only (flags must hold DSN_SKIP_TRANSPARENT)");
+    DSN_REQUIRE(!(flags & DSN_FIELD_FP32), "dsn_render_rays_lights: DSN_FIELD_FP32 is not supported (split-fp16 lighting only)");
+    DSN_REQUIRE(!(flags & (DSN_PHASE_GEOMETRY | DSN_PHASE_FIELD | DSN_PHASE_SHADE)),
+                "dsn_render_rays_lights: DSN_PHASE_* bits are not supported (one call renders the whole sweep)");
+    DSN_REQUIRE(S == 64 || S == 128, "dsn_render_rays_lights: S must be 64 or 128 (the 16-lane compositor)");
+    DSN_REQUIRE((((uintptr_t)workspace | (uintptr_t)out_weights | (uintptr_t)out_z) & 15) == 0,
+                "dsn_render_rays_lights: workspace, out_weights and out_z must be 16-byte aligned");
+    DSN_REQUIRE(light_scratch_bytes >= dsn_render_lights_scratch_bytes(R, S, 1, 0),
+                "dsn_render_rays_lights: light_scratch is too small (dsn_render_lights_scratch_bytes)");
+    const DsnLightSweep sweep = {lights, n_lights, light_scratch, light_scratch_bytes};
+    return dsn_render_frame(scene, V, F, packed, ray_o, ray_d, near, far, R, S, t_vals, jitter, noise, flags, out_rgb, out_disp, out_acc,
+                            out_depth, out_weights, out_z, workspace, workspace_bytes, slice_lengths_host, n_slices, stream, &sweep);
+}
+
+static int dsn_render_frame(const void* scene, int V, int F, const void* packed, const float* ray_o, const float* ray_d, float* near,
+                            float* far, int R, int S, const float* t_vals, const float* jitter, const float* noise,
+                            int flags, float* out_rgb, float* out_disp, float* out_acc, float* out_depth,
+                            float* out_weights, float* out_z, void* workspace, size_t workspace_bytes, const int32_t* slice_lengths_host,
+                            int n_slices, void* stream, const DsnLightSweep* sweep) {
     DSN_REQUIRE(R > 0 && S > 0, "dsn_render_rays: empty ray batch");      // (first: empty tensors come with null pointers)
     // front-to-back schedule (DSN_EARLY_STOP): uniform slices by default, the caller's lengths otherwise
     int bounds[DSN_STOP_MAX_SLICES + 1];
@@ -827,6 +881,42 @@ int dsn_render_rays_ex(const void* scene, int V, int F, const void* packed, cons
     if (!(flags & DSN_FIELD_FP32) && skip) {
         if (flags & DSN_EARLY_STOP) { list = w.slices; cnt = w.count + DSN_CNT_LIT; }
         else { list = w.pos; cnt = w.count + DSN_CNT_POS; }
+    }
+    if (do_shade && sweep) {
+    // Relighting sweep: the normals once, then per group of G lights the lighting MLP (k_light16_multi: colours by list slot in the
+    // caller's scratch) and the compositor (k_composite16_multi: weights once per ray, then every light's sums).  The shading list's
+    // length sizes G: one 4-byte read of its count word (the only synchronisation of the call).
+    int32_t n_sh = 0;
+    if (hipMemcpyAsync(&n_sh, cnt, sizeof(int32_t), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+        return dsn_fail("%s", "dsn_render_rays_lights: reading the shading list's length failed");
+    const size_t per_light = sizeof(float) * 3 * (size_t)n_sh;
+    const int G = per_light == 0 ? sweep->n_lights : (int)std::min<size_t>((size_t)sweep->n_lights, sweep->scratch_bytes / per_light);
+    if (G < 1)
+        return dsn_fail("dsn_render_rays_lights: light_scratch is too small%s: one light's colours need %lld bytes "
+                        "(dsn_render_lights_scratch_bytes)", "", (long long)per_light);
+    // the slot map takes the slice-filter list's buffer: dead after the field phase on both eval paths (early stop: its last
+    // reader is the reverse pass's selection; one pass: never used)
+    int32_t* slot = w.alive;
+    if (!dsn_composite_multi_supported(S, z, w.sigma, out_weights, slot, w.transparent))
+        return dsn_fail("%s", "dsn_render_rays_lights: unaligned arrays for the 16-lane compositor");
+    dsn_launch_normal(s, w.x_c, w.grad, N, list, cnt, nullptr, w.n_w, exh, st);
+    if (hipMemsetAsync(slot, 0xff, sizeof(int32_t) * (size_t)N, st) != hipSuccess)
+        return dsn_fail("%s", "dsn_render_rays_lights: memset failed");
+    dsn_launch_slot_map(list, cnt, n_sh, slot, st);
+    float* colours = (float*)sweep->scratch;
+    for (int g0 = 0; g0 < sweep->n_lights; g0 += G) {
+        const int Gc = std::min(G, sweep->n_lights - g0);
+        const bool first = g0 == 0;      // (the per-ray outputs that do not depend on the light: written once)
+        dsn_launch_light16_multi((const float*)packed, sweep->lights + (size_t)g0 * DSN_LIGHT_RECORD_FLOATS, Gc, w.n_w, ray_o, ray_d, z,
+                                 w.essence, n_sh, S, list, cnt, colours, st);
+        dsn_launch_composite_multi(slot, colours, n_sh, Gc, w.sigma, w.transparent, z, ray_d, R, S, out_rgb + (size_t)g0 * 3 * R,
+                                   first ? out_disp : nullptr, first ? out_acc : nullptr, first ? out_weights : nullptr,
+                                   first ? out_depth : nullptr, w.count + DSN_CNT_STOP + 3, st);
+    }
+    if (flags & DSN_STOP_STATS)
+        dsn_launch_stop_stats(w.sigma, w.transparent, z, ray_d, R, S, dsn_stats_slice_len(R, S), (const float*)packed + OFF_SCAL,
+                              w.count + DSN_CNT_STOP + 2, st, w.count + DSN_CNT_HIST, w.count + DSN_CNT_STOP + 3, dsn_slice_len(R, S));
+    return dsn_check_launch("dsn_render_rays_lights");
     }
     if (do_shade) {
     dsn_launch_normal(s, w.x_c, w.grad, N, list, cnt, nullptr, w.n_w, exh, st);

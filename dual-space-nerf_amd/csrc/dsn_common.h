@@ -283,6 +283,10 @@ __host__ __device__ inline float dsn_stop_eps_scaled(int S, float colour_scale) 
 #else
 #define DSN_OWN_SIMD_T(bit) do { if ((DSN_TRAIN_AGGRESSORS) & (bit)) DSN_OWN_SIMD(); } while (0)
 #endif
+// dsn_render_rays_lights: floats per light record {has_light, light_shift[3], has_rot, rot[4], rot_center[2], 0} (= include/dsnerf.h)
+#ifndef DSN_LIGHT_RECORD_FLOATS
+#define DSN_LIGHT_RECORD_FLOATS 12
+#endif
 #define DSN_SCREEN_MARGIN_DEFAULT 0.01f          // conservative margin of the density screen until it has been calibrated
 #define DSN_LO_SCALE 4096.0f                      // lo = (x - hi) * 2^12, products accumulated apart, folded at the end
 #define DSN_LO_INV (1.0f / 4096.0f)

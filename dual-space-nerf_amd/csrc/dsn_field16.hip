@@ -2294,3 +2294,142 @@ void dsn_launch_light16(const float* packed, const DsnFrameState* fs, const floa
     hipLaunchKernelGGL(k_light16, dim3((unsigned)std::min<int64_t>(blocks, (int64_t)dsn_cu_count())), dim3(256), 0, st, packed, fs, n_w,
                        x_w, ray_o, ray_d, z_vals, essence, N, S, active_list, active_count, colour, tr_hl1, tr_hl2, tr_pre);
 }
+
+// ---------------------------------------------------------------------------------------------
+// k_light16_multi : k_light16 for G light settings per pass over the shading list (dsn_render_rays_lights).  A light edit moves only
+// the world position the lighting MLP sees (model/spacenet.py:254-265); the normal, the view direction, the ray and the essence of a
+// sample are gathered ONCE per tile and the MLP runs G times on them.  An MFMA output column depends on its own column only, so a
+// (sample, light) pair gives k_light16's bits for that sample under that light: the per-light arithmetic below is k_light16's,
+// expression for expression (same split16, same products in the same k-order, fold16, fmaf order, __shfl_xor, expm1f).
+// lights: G records of DSN_LIGHT_RECORD_FLOATS floats {has_light, light_shift[3], has_rot, rot[4] (row-major), rot_center[2], 0}.
+// colours: [G][count][3], indexed by the sample's slot on the list (not by the sample: a dense [N,3] per light would not fit).
+// ---------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256, 1)
+k_light16_multi(const float* __restrict__ packed, const float* __restrict__ lights, int G, const float* __restrict__ n_w,
+                const float* __restrict__ ray_o, const float* __restrict__ ray_d, const float* __restrict__ z_vals,
+                const float* __restrict__ essence, int S, const int32_t* __restrict__ list, const int32_t* __restrict__ list_count,
+                float* __restrict__ colours) {
+    __shared__ __attribute__((aligned(16))) char s_w[LIGHT_LDS_BYTES];      // (k_light16's layout)
+    DSN_OWN_SIMD();
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int half = lane >> 5;
+    const int64_t count = *list_count;
+    const int64_t ntiles = (count + 127) / 128;
+    if ((int64_t)blockIdx.x >= ntiles) return;      // block-uniform
+    {
+        const char* g16 = reinterpret_cast<const char*>(packed + OFF16_BASE);
+        const uint4* g0 = reinterpret_cast<const uint4*>(g16 + (size_t)(OFF_LT0 / DSN_BLK) * 4096);
+        const uint4* g1 = reinterpret_cast<const uint4*>(g16 + (size_t)(OFF_LT1 / DSN_BLK) * 4096);
+        uint4* d = reinterpret_cast<uint4*>(s_w);
+        for (int i = threadIdx.x; i < 4 * 128; i += 256) d[i] = g0[(i >> 7) * 256 + (i & 127)];
+        for (int i = threadIdx.x; i < 16 * 256; i += 256) d[4 * 128 + i] = g1[i];
+    }
+    __syncthreads();
+    // (inputs one tile ahead, the list entry two tiles ahead: as in k_light16)
+    struct LightIn { float nw[3], o[3], d[3], z; };
+    auto tile_pt = [&](int64_t t, bool& ok) -> int64_t {
+        int64_t sl = (t * 4 + wave) * 32 + (lane & 31);
+        ok = t < ntiles && sl < count;
+        if (!ok) sl = count - 1;
+        return (int64_t)list[sl];
+    };
+    auto fetch_in = [&](int64_t p, LightIn& a) {
+        const int64_t r = p / S;
+        a.nw[0] = n_w[3 * p]; a.nw[1] = n_w[3 * p + 1]; a.nw[2] = n_w[3 * p + 2];
+        a.d[0] = ray_d[3 * r]; a.d[1] = ray_d[3 * r + 1]; a.d[2] = ray_d[3 * r + 2];
+        a.o[0] = ray_o[3 * r]; a.o[1] = ray_o[3 * r + 1]; a.o[2] = ray_o[3 * r + 2]; a.z = z_vals[p];
+    };
+    bool valid_c, valid_n, valid_nn;
+    int64_t pt_c = tile_pt(blockIdx.x, valid_c);
+    LightIn in_c, in_n;
+    fetch_in(pt_c, in_c);
+    int64_t pt_n = tile_pt((int64_t)blockIdx.x + gridDim.x, valid_n);
+  for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int64_t slot0 = (tile * 4 + wave) * 32;
+    const int64_t slot = slot0 + (lane & 31);
+    const bool valid = valid_c;
+    const int64_t pt = pt_c;
+    const LightIn cur = in_c;
+    fetch_in(pt_n, in_n);
+    const int64_t pt_nn = tile_pt(tile + 2 * (int64_t)gridDim.x, valid_nn);
+    pt_c = pt_n; valid_c = valid_n; in_c = in_n;
+    pt_n = pt_nn; valid_n = valid_nn;
+    if (slot0 >= count) continue;                    // (no barrier inside the loop)
+    const float ess[3] = {essence[3 * pt], essence[3 * pt + 1], essence[3 * pt + 2]};
+    // the light-independent part of the input: normal, unrotated world point, normalised view direction
+    const float d[3] = {cur.d[0], cur.d[1], cur.d[2]};
+    float xw0[3];
+    {
+        const float z = cur.z;
+        xw0[0] = cur.o[0] + d[0] * z; xw0[1] = cur.o[1] + d[1] * z; xw0[2] = cur.o[2] + d[2] * z;
+    }
+    const float vn = dsn_norm3(d);
+    const float vd[3] = {dsn_div(d[0], vn), dsn_div(d[1], vn), dsn_div(d[2], vn)};
+    for (int g = 0; g < G; ++g) {
+        // (keeps the bias / output-weight rows' loads inside the loop: hoisted out of it they are 192 live registers - 137 spilled)
+        asm volatile("" ::: "memory");
+        const float* lr = lights + (int64_t)g * DSN_LIGHT_RECORD_FLOATS;      // (uniform: scalar loads)
+        float in9[10];
+        in9[0] = cur.nw[0]; in9[1] = cur.nw[1]; in9[2] = cur.nw[2];
+        float xw[3] = {xw0[0], xw0[1], xw0[2]};
+        if (lr[4] != 0.0f) {
+            const float ax = xw[0] - lr[9], ay = xw[1] - lr[10];
+            const float nx = (ax * lr[5] + ay * lr[7]) + lr[9];
+            const float ny = (ax * lr[6] + ay * lr[8]) + lr[10];
+            xw[0] = nx; xw[1] = ny;
+        }
+        if (lr[0] != 0.0f) { xw[0] += lr[1]; xw[1] += lr[2]; xw[2] += lr[3]; }
+        in9[3] = xw[0]; in9[4] = xw[1]; in9[5] = xw[2];
+        in9[6] = vd[0]; in9[7] = vd[1]; in9[8] = vd[2];
+        in9[9] = 0.0f;
+        half8 xh[2], xl[2];
+        {
+            f32x16 v = zero16();
+#pragma unroll
+            for (int j = 0; j < 5; ++j) v[j] = half ? in9[2 * j + 1] : in9[2 * j];
+            split16<true>(v, xh, xl);
+        }
+        half8 h1h[4][2], h1l[4][2];
+#pragma unroll
+        for (int m = 0; m < 4; ++m) {
+            f32x16 aM = rows16(packed + OFF_BLT0, m, half), aC = zero16();
+            light_block0(s_w + m * 2048, lane, xh, xl, aM, aC);
+            f32x16 v = fold16(aM, aC);
+#pragma unroll
+            for (int r = 0; r < 16; ++r) v[r] = fmaxf(v[r], 0.0f);
+            split16<true>(v, h1h[m], h1l[m]);
+        }
+        float part = 0.0f;
+#pragma unroll
+        for (int m = 0; m < 4; ++m) {
+            f32x16 aM = rows16(packed + OFF_BLT1, m, half), aC = zero16();
+#pragma unroll
+            for (int kb = 0; kb < 4; ++kb)
+                light_block(s_w + 4 * 2048 + (m * 4 + kb) * 4096, lane, h1h[kb], h1l[kb], aM, aC, true);
+            f32x16 v = fold16(aM, aC);
+            const f32x16 w2 = rows16(packed + OFF_WLT2, m, half);
+#pragma unroll
+            for (int r = 0; r < 16; ++r) { v[r] = fmaxf(v[r], 0.0f); part = fmaf(w2[r], v[r], part); }
+        }
+        part += __shfl_xor(part, 32);
+        const float o = part + packed[OFF_SCAL + 4];
+        const float wgt = (o > 0.0f ? o : expm1f(o)) + 1.0f;   // ELU(alpha=1) + 1
+        if (valid && half == 0) {
+            float* c = colours + ((int64_t)g * count + slot) * 3;
+            c[0] = wgt * ess[0];
+            c[1] = wgt * ess[1];
+            c[2] = wgt * ess[2];
+        }
+    }
+  }
+}
+
+void dsn_launch_light16_multi(const float* packed, const float* lights, int G, const float* n_w, const float* ray_o, const float* ray_d,
+                              const float* z_vals, const float* essence, int64_t max_count, int S, const int32_t* list,
+                              const int32_t* list_count, float* colours, hipStream_t st) {
+    const int64_t blocks = (max_count + 127) / 128;
+    if (blocks == 0 || G < 1) return;
+    hipLaunchKernelGGL(k_light16_multi, dim3((unsigned)std::min<int64_t>(blocks, (int64_t)dsn_cu_count())), dim3(256), 0, st, packed,
+                       lights, G, n_w, ray_o, ray_d, z_vals, essence, S, list, list_count, colours);
+}

@@ -966,6 +966,147 @@ void dsn_launch_composite(const float* colour, const float* sigma, const uint8_t
 }
 
 // ---------------------------------------------------------------------------------------------
+// Relighting sweep (dsn_render_rays_lights): the compositor of G lights that share one geometry pass.
+// k_slot_map: slot[sample] = its position on the shading list (the buffer is -1 everywhere else beforehand).
+// k_composite16_multi: k_composite16<false, CH> in eval mode (lazy colour, no noise) with the colour of a sample read through that map
+// from the compact [G][n_shaded][3] colours of k_light16_multi - a sample off the list contributes colour 0, as a culled sample does
+// in the one-light frame.  The weights are computed once per ray (k_composite16's scan, expression for expression), then per light
+// the three rgb sums in k_composite16's order (the per-lane j loop, then dsn_row_sum_to_last): every light's pixel has the bits of
+// the one-light frame.  disp / acc / depth / weights are written where those pointers are given (the first group of a sweep);
+// colour_max (the early-stop guard word) gets the largest |colour| weighed under any of the lights.
+// ---------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) k_slot_map(const int32_t* __restrict__ list, const int32_t* __restrict__ count,
+                                                   int32_t* __restrict__ slot) {
+    const int64_t n = *count;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) slot[list[i]] = (int32_t)i;
+}
+void dsn_launch_slot_map(const int32_t* list, const int32_t* count, int64_t max_count, int32_t* slot, hipStream_t st) {
+    if (max_count <= 0) return;
+    const int64_t blocks = std::min<int64_t>((max_count + 255) / 256, 8192);
+    hipLaunchKernelGGL(k_slot_map, dim3((unsigned)blocks), dim3(256), 0, st, list, count, slot);
+}
+
+template <int CH>
+__global__ void __launch_bounds__(256) k_composite16_multi(const int32_t* __restrict__ slot_of, const float* __restrict__ colours,
+                                                            int64_t n_shaded, int G, const float* __restrict__ sigma,
+                                                            const uint8_t* __restrict__ transparent, const float* __restrict__ z_vals,
+                                                            const float* __restrict__ ray_d, int R, float* __restrict__ rgb_maps,
+                                                            float* __restrict__ disp_map, float* __restrict__ acc_map,
+                                                            float* __restrict__ weights, float* __restrict__ depth_map,
+                                                            int32_t* __restrict__ colour_max) {
+    constexpr int S = 16 * CH;
+    const int lane = threadIdx.x & 63, sub = lane & 15;
+    const int r_of_row = (blockIdx.x * 4 + (threadIdx.x >> 6)) * 4 + (lane >> 4);
+    if (r_of_row - (lane >> 4) >= R) return;              // wave-uniform
+    const bool ok = r_of_row < R;
+    const int r = ok ? r_of_row : R - 1;
+    const float d[3] = {ray_d[3 * r], ray_d[3 * r + 1], ray_d[3 * r + 2]};
+    const float dn = dsn_norm3(d);
+    const int64_t g0 = (int64_t)r * S + sub * CH;
+    float z[CH + 1], sg[CH];
+    uint8_t tr[CH];
+    int32_t sl[CH];
+#pragma unroll
+    for (int q = 0; q < CH / 4; ++q) {
+        const float4 z4 = *reinterpret_cast<const float4*>(z_vals + g0 + 4 * q);
+        const float4 s4 = *reinterpret_cast<const float4*>(sigma + g0 + 4 * q);
+        const int4 l4 = *reinterpret_cast<const int4*>(slot_of + g0 + 4 * q);
+        z[4 * q] = z4.x; z[4 * q + 1] = z4.y; z[4 * q + 2] = z4.z; z[4 * q + 3] = z4.w;
+        sg[4 * q] = s4.x; sg[4 * q + 1] = s4.y; sg[4 * q + 2] = s4.z; sg[4 * q + 3] = s4.w;
+        sl[4 * q] = l4.x; sl[4 * q + 1] = l4.y; sl[4 * q + 2] = l4.z; sl[4 * q + 3] = l4.w;
+        uchar4 t4 = make_uchar4(0, 0, 0, 0);
+        if (transparent) t4 = *reinterpret_cast<const uchar4*>(transparent + g0 + 4 * q);
+        tr[4 * q] = t4.x; tr[4 * q + 1] = t4.y; tr[4 * q + 2] = t4.z; tr[4 * q + 3] = t4.w;
+    }
+    z[CH] = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(z[0]), 0x101, 0xf, 0xf, false));
+    float alpha[CH], pre[CH];
+    float run = 1.0f;
+#pragma unroll
+    for (int j = 0; j < CH; ++j) {
+        float sv = sg[j];
+        if (tr[j]) sv = 0.f;
+        sv = sv > 0.f ? sv : 0.f;
+        sg[j] = sv;
+        const float dist = ((sub * CH + j + 1 < S) ? (z[j + 1] - z[j]) : 1e10f) * dn;
+        alpha[j] = 1.0f - expf(-sv * dist);
+        run = run * ((1.0f - alpha[j]) + 1e-10f);
+        pre[j] = run;
+    }
+    float incl = run;
+    incl = incl * dsn_row_shr(1.0f, incl, 1);
+    incl = incl * dsn_row_shr(1.0f, incl, 2);
+    incl = incl * dsn_row_shr(1.0f, incl, 4);
+    incl = incl * dsn_row_shr(1.0f, incl, 8);
+    const float before = dsn_row_shr(1.0f, incl, 1);
+    float w[CH];
+#pragma unroll
+    for (int j = 0; j < CH; ++j) w[j] = alpha[j] * (j == 0 ? before : before * pre[j - 1]);
+    if (weights && ok) {
+#pragma unroll
+        for (int q = 0; q < CH / 4; ++q)
+            *reinterpret_cast<float4*>(weights + g0 + 4 * q) = make_float4(w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]);
+    }
+    if (depth_map) {      // (pointer uniform over the launch)
+        float sdep = 0.f, sacc = 0.f;
+#pragma unroll
+        for (int j = 0; j < CH; ++j) { sdep += w[j] * z[j]; sacc += w[j]; }
+        sdep = dsn_row_sum_to_last(sdep); sacc = dsn_row_sum_to_last(sacc);
+        if (sub == 15 && ok) {
+            depth_map[r] = sdep;
+            acc_map[r] = sacc;
+            float q = dsn_div(sdep, sacc);          // NaN when acc == 0, like the reference
+            float m = (1e-10f > q) ? 1e-10f : q;    // torch.max propagates NaN
+            if (q != q) m = q;
+            disp_map[r] = dsn_div(1.0f, m);
+        }
+    }
+    float cm = 0.f;
+    for (int g = 0; g < G; ++g) {
+        const float* cg_ = colours + (int64_t)g * n_shaded * 3;
+        float sr = 0.f, sgn = 0.f, sb = 0.f;
+#pragma unroll
+        for (int j = 0; j < CH; ++j) {
+            float cr = 0.f, cg = 0.f, cb = 0.f;
+            if (sg[j] > 0.f && sl[j] >= 0) { cr = cg_[3 * (int64_t)sl[j]]; cg = cg_[3 * (int64_t)sl[j] + 1]; cb = cg_[3 * (int64_t)sl[j] + 2]; }
+            sr += w[j] * cr; sgn += w[j] * cg; sb += w[j] * cb;
+            float m = fmaxf(fabsf(cr), fmaxf(fabsf(cg), fabsf(cb)));
+            m = m == m ? m : INFINITY;
+            cm = fmaxf(cm, m);
+        }
+        sr = dsn_row_sum_to_last(sr); sgn = dsn_row_sum_to_last(sgn); sb = dsn_row_sum_to_last(sb);
+        if (sub == 15 && ok) {
+            float* rgb = rgb_maps + (int64_t)g * R * 3;
+            rgb[3 * r] = sr; rgb[3 * r + 1] = sgn; rgb[3 * r + 2] = sb;
+        }
+    }
+    if (colour_max) {
+        cm = fmaxf(cm, dsn_row_shr(0.f, cm, 1)); cm = fmaxf(cm, dsn_row_shr(0.f, cm, 2));
+        cm = fmaxf(cm, dsn_row_shr(0.f, cm, 4)); cm = fmaxf(cm, dsn_row_shr(0.f, cm, 8));
+        cm = fmaxf(cm, __shfl_xor(cm, 16));
+        cm = fmaxf(cm, __shfl_xor(cm, 32));
+        if (lane == 63 && __float_as_int(cm) > __hip_atomic_load(colour_max, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+            atomicMax(colour_max, __float_as_int(cm));
+    }
+}
+
+bool dsn_composite_multi_supported(int S, const void* z_vals, const void* sigma, const void* weights, const void* slot_of,
+                                   const void* transparent) {
+    return (S == 64 || S == 128) && (((uintptr_t)z_vals | (uintptr_t)sigma | (uintptr_t)weights | (uintptr_t)slot_of) & 15) == 0 &&
+           (((uintptr_t)transparent) & 3) == 0;
+}
+void dsn_launch_composite_multi(const int32_t* slot_of, const float* colours, int64_t n_shaded, int G, const float* sigma,
+                                const uint8_t* transparent, const float* z_vals, const float* ray_d, int R, int S, float* rgb_maps,
+                                float* disp_map, float* acc_map, float* weights, float* depth_map, int32_t* colour_max, hipStream_t st) {
+    const dim3 grid((unsigned)((R + 15) / 16)), block(256);
+    if (S == 64)
+        hipLaunchKernelGGL(k_composite16_multi<4>, grid, block, 0, st, slot_of, colours, n_shaded, G, sigma, transparent, z_vals, ray_d, R,
+                           rgb_maps, disp_map, acc_map, weights, depth_map, colour_max);
+    else
+        hipLaunchKernelGGL(k_composite16_multi<8>, grid, block, 0, st, slot_of, colours, n_shaded, G, sigma, transparent, z_vals, ray_d, R,
+                           rgb_maps, disp_map, acc_map, weights, depth_map, colour_max);
+}
+
+// ---------------------------------------------------------------------------------------------
 // Front-to-back evaluation with exact ray termination (DSN_EARLY_STOP, eval mode).
 // utils/nerf_net_utils.py:24-39: weight_i = alpha_i * T_i with T_i = prod_{j<i}(1 - alpha_j + 1e-10) non-increasing along the ray, so
 // once T < eps every later sample has weight < eps and all of them together add less than eps to acc_map (eps * colour to the

@@ -421,6 +421,31 @@ DSN_EXPORT int dsn_render_rays_ex(const void* scene, int V, int F, const void* p
                        float* out_weights, float* out_z, void* workspace, size_t workspace_bytes, const int32_t* slice_lengths_host,
                        int n_slices, void* stream);
 
+/* ---- relighting sweep (an addition within ABI 8: no existing entry point changes) ------------------------------------------------
+ * One eval-mode frame under n_lights light settings (the reference's vis_lighting.py renders every view under ten rotations of the
+ * light): geometry, field, early stop, normals and compositing weights run ONCE, each light costs its lighting MLP and its rgb sums.
+ * A light edit moves only the world position the lighting MLP sees (model/spacenet.py:254-265): every light's pixels have the bits of
+ * dsn_render_rays_ex with that light in the scene's frame state (dsn_set_frame).  The light of the scene's frame state is NOT used.
+ *   lights      device array of n_lights records of DSN_LIGHT_RECORD_FLOATS floats
+ *               {has_light, light_shift[3], has_rot, rot[4] (row-major 2 x 2), rot_center[2], 0}: the world point x is first rotated
+ *               about rot_center in xy when has_rot != 0, then shifted by light_shift when has_light != 0 (dsn_set_frame's arguments);
+ *   out_rgb     [n_lights, R, 3]; out_disp / out_acc / out_depth / out_weights / out_z as in dsn_render_rays_ex (light-independent);
+ *   light_scratch, light_scratch_bytes
+ *               the compact colours of a group of G lights, [G][n_shaded][3] by slot on the shading list: G = as many lights as the
+ *               scratch holds (at least one: otherwise the call fails).  n_shaded (<= R S) is known after the field phase: the call
+ *               reads that one count word, i.e. it SYNCHRONISES `stream` once.
+ * Eval mode only: flags must hold DSN_SKIP_TRANSPARENT; jitter, noise, DSN_FIELD_FP32 and DSN_PHASE_* are rejected; S must be 64 or
+ * 128 and workspace / out_weights / out_z 16-byte aligned.  The early-stop guard word (int32 word 59 of `workspace`) holds the largest
+ * |colour| weighed under ANY of the lights.  (DSN_COMPOSITE=wave, an A/B switch of dsn_render_rays_ex, does not apply here.) */
+#define DSN_LIGHT_RECORD_FLOATS 12
+/* bytes of light_scratch for n_lights lights in one group on a frame of n_shaded shaded samples (0: bad sizes) */
+DSN_EXPORT size_t dsn_render_lights_scratch_bytes(int R, int S, int n_lights, int64_t n_shaded);
+DSN_EXPORT int dsn_render_rays_lights(const void* scene, int V, int F, const void* packed, const float* ray_o, const float* ray_d,
+                           float* near, float* far, int R, int S, const float* t_vals, const float* jitter, const float* noise, int flags,
+                           const float* lights, int n_lights, float* out_rgb, float* out_disp, float* out_acc, float* out_depth,
+                           float* out_weights, float* out_z, void* workspace, size_t workspace_bytes, void* light_scratch,
+                           size_t light_scratch_bytes, const int32_t* slice_lengths_host, int n_slices, void* stream);
+
 /* diagnostics, NOT for the hot path (synchronises `stream`): {ncell, ok, total entries, capacity} of the four
  * nearest-face list levels (world fine/coarse, canonical fine/coarse) into a HOST array of 16 int32. */
 DSN_EXPORT int dsn_debug_nn_stats(const void* scene, int V, int F, int32_t* out16_host, void* stream);
