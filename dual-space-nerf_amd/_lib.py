@@ -667,28 +667,23 @@ class RenderWorkspace:
         return self.buf
 
 
-def render_rays(scene: Scene, packed: PackedParams, ws: RenderWorkspace, ray_o, ray_d, near, far, S, t_vals,
-                jitter=None, noise=None, skip_transparent=True, want_weights=True, out=None, exhaustive=False,
-                fp32=False, uniform=False, screen=False, train_cache=None, audit=False, early_stop=False, stop_stats=False, phases=0,
-                share_cus=False, stop_schedule=None):
-    """Whole hot path on R rays (can_render.py:137-168).  Returns dict of device tensors.
-    phases: 0 = the whole frame; PHASE_GEOMETRY | PHASE_FIELD | PHASE_SHADE = only those parts, on the current stream (the caller
-    orders the three calls of a frame with its own events and passes the same `out` / workspace to all of them: PhasePipeline).
-    screen: DSN_DENSITY_SCREEN (opt-in: the plain-fp16 density screen in front of the accurate pass, margin as calibrated).
-    early_stop: DSN_EARLY_STOP (eval mode: front-to-back slices, rays end once their transmittance is below eps(S, colour scale)).
-    stop_stats: DSN_STOP_STATS (count what early stop would leave out; read ws word CNT_STOP + 2)."""
-    R = ray_o.shape[0]
-    dev = scene.device
-    if out is None:
-        out = {
-            "color": torch.empty(R, 3, dtype=torch.float32, device=dev),
-            "disp_map": torch.empty(R, dtype=torch.float32, device=dev),
-            "acc_map": torch.empty(R, dtype=torch.float32, device=dev),
-            "depth_map": torch.empty(R, dtype=torch.float32, device=dev),
-            "z_vals": torch.empty(R, S, dtype=torch.float32, device=dev),
-        }
-        if want_weights:
-            out["weights"] = torch.empty(R, S, dtype=torch.float32, device=dev)
+def _frame_outputs(R, S, dev, want_weights, K=None):
+    """The output dict of render_rays (K given: render_rays_lights', "color" of shape [K, R, 3])."""
+    out = {
+        "color": torch.empty(*(() if K is None else (K,)), R, 3, dtype=torch.float32, device=dev),
+        "disp_map": torch.empty(R, dtype=torch.float32, device=dev),
+        "acc_map": torch.empty(R, dtype=torch.float32, device=dev),
+        "depth_map": torch.empty(R, dtype=torch.float32, device=dev),
+        "z_vals": torch.empty(R, S, dtype=torch.float32, device=dev),
+    }
+    if want_weights:
+        out["weights"] = torch.empty(R, S, dtype=torch.float32, device=dev)
+    return out
+
+
+def _frame_flags(scene: Scene, skip_transparent=True, noise=None, exhaustive=False, fp32=False, uniform=False, screen=False,
+                 audit=False, early_stop=False, stop_stats=False, phases=0, share_cus=False):
+    """The DSN_* flag word of a frame (render_rays, render_rays_lights)."""
     flags = SKIP_TRANSPARENT if (skip_transparent and noise is None) else 0
     if exhaustive:
         flags |= NN_EXHAUSTIVE
@@ -709,6 +704,32 @@ def render_rays(scene: Scene, packed: PackedParams, ws: RenderWorkspace, ray_o, 
         flags |= SHARE_CUS
     if scene.lazy:               # (the training forward takes the flag too since round 6: dsn_render_rays_train's fused geometry)
         flags |= LAZY_LISTS
+    return flags
+
+
+def _slice_schedule(stop_schedule, flags):
+    """stop_schedule (early stop only): slice lengths chosen from a probe frame's statistics (choose_stop_schedule) as the library's
+    int32 array and its length; (None, 0) = uniform slices."""
+    if stop_schedule is None or not (flags & EARLY_STOP):
+        return None, 0
+    return (C.c_int32 * len(stop_schedule))(*[int(x) for x in stop_schedule]), len(stop_schedule)
+
+
+def render_rays(scene: Scene, packed: PackedParams, ws: RenderWorkspace, ray_o, ray_d, near, far, S, t_vals,
+                jitter=None, noise=None, skip_transparent=True, want_weights=True, out=None, exhaustive=False,
+                fp32=False, uniform=False, screen=False, train_cache=None, audit=False, early_stop=False, stop_stats=False, phases=0,
+                share_cus=False, stop_schedule=None):
+    """Whole hot path on R rays (can_render.py:137-168).  Returns dict of device tensors.
+    phases: 0 = the whole frame; PHASE_GEOMETRY | PHASE_FIELD | PHASE_SHADE = only those parts, on the current stream (the caller
+    orders the three calls of a frame with its own events and passes the same `out` / workspace to all of them: PhasePipeline).
+    screen: DSN_DENSITY_SCREEN (opt-in: the plain-fp16 density screen in front of the accurate pass, margin as calibrated).
+    early_stop: DSN_EARLY_STOP (eval mode: front-to-back slices, rays end once their transmittance is below eps(S, colour scale)).
+    stop_stats: DSN_STOP_STATS (count what early stop would leave out; read ws word CNT_STOP + 2)."""
+    R = ray_o.shape[0]
+    if out is None:
+        out = _frame_outputs(R, S, scene.device, want_weights)
+    flags = _frame_flags(scene, skip_transparent, noise, exhaustive, fp32, uniform, screen, audit, early_stop, stop_stats, phases,
+                         share_cus)
     if not phases or (int(phases) & PHASE_GEOMETRY):
         ws.begin_frame()          # (a larger record capacity asked for since the last frame: the buffer may be replaced HERE, only here)
     buf = ws.get(R, S)
@@ -726,11 +747,7 @@ def render_rays(scene: Scene, packed: PackedParams, ws: RenderWorkspace, ray_o, 
                                               ax[0], ax[1], ax[2]),
                "dsn_render_rays_train")
         return out
-    # stop_schedule (early_stop only): slice lengths chosen from a probe frame's statistics (choose_stop_schedule); None = uniform slices
-    sched, n_sched = None, 0
-    if stop_schedule is not None and (flags & EARLY_STOP):
-        n_sched = len(stop_schedule)
-        sched = (C.c_int32 * n_sched)(*[int(x) for x in stop_schedule])
+    sched, n_sched = _slice_schedule(stop_schedule, flags)
     _check(lib().dsn_render_rays_ex(_ptr(scene.buf), scene.V, scene.F, _ptr(packed.buf), _ptr(ray_o, torch.float32),
                                     _ptr(ray_d, torch.float32), _ptr(near, torch.float32), _ptr(far, torch.float32), R, S,
                                     _ptr(t_vals, torch.float32), _ptr(jitter), _ptr(noise), flags, _ptr(out["color"]),
@@ -789,32 +806,12 @@ def render_rays_lights(scene: Scene, packed: PackedParams, ws: RenderWorkspace, 
     dev = scene.device
     lights = lights.to(device=dev, dtype=torch.float32).contiguous()
     assert lights.dim() == 2 and lights.shape[1] == LIGHT_RECORD_FLOATS, "lights: [K, 12] records (light_records)"
-    out = {
-        "color": torch.empty(K, R, 3, dtype=torch.float32, device=dev),
-        "disp_map": torch.empty(R, dtype=torch.float32, device=dev),
-        "acc_map": torch.empty(R, dtype=torch.float32, device=dev),
-        "depth_map": torch.empty(R, dtype=torch.float32, device=dev),
-        "z_vals": torch.empty(R, S, dtype=torch.float32, device=dev),
-    }
-    if want_weights:
-        out["weights"] = torch.empty(R, S, dtype=torch.float32, device=dev)
     if not skip_transparent:
         raise ValueError("render_rays_lights: eval mode with the transparent skip only")
     if fp32:
         raise ValueError("render_rays_lights: the exact-fp32 field is not supported (the sweep's lighting is the split-fp16 kernel's)")
-    flags = SKIP_TRANSPARENT
-    if uniform:
-        flags |= SAMPLE_UNIFORM
-    if screen:
-        flags |= DENSITY_SCREEN
-        if audit:
-            flags |= SCREEN_AUDIT
-    if early_stop:
-        flags |= EARLY_STOP
-    if stop_stats:
-        flags |= STOP_STATS
-    if scene.lazy:
-        flags |= LAZY_LISTS
+    out = _frame_outputs(R, S, dev, want_weights, K)
+    flags = _frame_flags(scene, uniform=uniform, screen=screen, audit=audit, early_stop=early_stop, stop_stats=stop_stats)
     ws.begin_frame()
     buf = ws.get(R, S)
     # compact colours: every light in one group when that fits the budget, else as many as fit - and always at least one light of the
@@ -827,10 +824,7 @@ def render_rays_lights(scene: Scene, packed: PackedParams, ws: RenderWorkspace, 
     ls = ws.light_scratch
     if ls is None or ls.numel() < need:
         ls = ws.light_scratch = _scratch(need, dev)
-    sched, n_sched = None, 0
-    if stop_schedule is not None and early_stop:
-        n_sched = len(stop_schedule)
-        sched = (C.c_int32 * n_sched)(*[int(x) for x in stop_schedule])
+    sched, n_sched = _slice_schedule(stop_schedule, flags)
     _check(L.dsn_render_rays_lights(_ptr(scene.buf), scene.V, scene.F, _ptr(packed.buf), _ptr(ray_o, torch.float32),
                                     _ptr(ray_d, torch.float32), _ptr(near, torch.float32), _ptr(far, torch.float32), R, S,
                                     _ptr(t_vals, torch.float32), None, None, flags, _ptr(lights), K, _ptr(out["color"]),

@@ -816,23 +816,31 @@ class Renderer:
         # the frame's state first: its kernels (0.45 ms of nearest-face lists for the posed mesh) need the 82 KB of vertices only and
         # run while this thread stages the 8 MB of rays through page-locked memory (-0.1 ms per render_view, A/B in one call)
         self._set_frame(batch, scene=scene, lazy=True)
+        screen = None
+        pk = self.net.packed(self.device)
+        if scene is not self.scene and pk.screen is not None:      # (not calibrated yet: _render_eval does it on this frame's points)
+            screen = self.skip_transparent and not self.net.training and self.density_screen and pk.screen_pays(self._early_stop_in_use(pk))
+
+        def render_chunk(o, d, n, f, S):
+            jitter, noise = self._draws(o.shape[0], S)
+            return self._render_eval(scene, ws, o, d, n, f, S, jitter, noise, screen=None if noise is not None else screen)
+        return self._render_chunks(ray_o, ray_d, near, far, chunk, render_chunk), {}
+
+    def _render_chunks(self, ray_o, ray_d, near, far, chunk, render_chunk, color_axis=0):
+        """The view's rays on the device, rendered `chunk` rays at a time (None: all at once) by render_chunk(o, d, near, far, S)
+        and joined along the ray axis (color_axis: that of "color", 1 for a sweep's [K, R, 3])."""
         o, d = self._dev(ray_o[0]), self._dev(ray_d[0])
         n, f = self._dev(near[0]).clone(), self._dev(far[0]).clone()
         S = self.cfg.MODEL.COARSE_RAY_SAMPLING
         R = o.shape[0]
         chunk = R if chunk is None else int(chunk)
-        screen = None
-        pk = self.net.packed(self.device)
-        if scene is not self.scene and pk.screen is not None:      # (not calibrated yet: _render_eval does it on this frame's points)
-            screen = self.skip_transparent and not self.net.training and self.density_screen and pk.screen_pays(self._early_stop_in_use(pk))
         outs = []
         for i in range(0, R, chunk):
             j = min(R, i + chunk)
-            jitter, noise = self._draws(j - i, S)
-            outs.append(self._render_eval(scene, ws, o[i:j].contiguous(), d[i:j].contiguous(), n[i:j].contiguous(),
-                                          f[i:j].contiguous(), S, jitter, noise, screen=None if noise is not None else screen))
-        coarse = outs[0] if len(outs) == 1 else {k: torch.cat([x[k] for x in outs], 0) for k in outs[0]}
-        return coarse, {}
+            outs.append(render_chunk(o[i:j].contiguous(), d[i:j].contiguous(), n[i:j].contiguous(), f[i:j].contiguous(), S))
+        if len(outs) == 1:
+            return outs[0]
+        return {k: torch.cat([x[k] for x in outs], color_axis if k == "color" else 0) for k in outs[0]}
 
     def _view_images(self, batch, chunk, scene, ws):
         coarse, _ = self.batchify_rays_view(batch["ray_o"], batch["ray_d"], batch["near"], batch["far"], batch, chunk, scene, ws)
@@ -899,7 +907,8 @@ class Renderer:
 
     def _view_images_lights(self, batch, lights, chunk):
         scene, ws = self.scene, self._ws
-        # the frame without a light edit (the sweep brings its own); zero_code as DualSpaceNeRF.frame_args has it
+        # the frame WITHOUT the net's light edit (fine_only=True, no light / rotation: each record of the sweep brings its own);
+        # zero_code as DualSpaceNeRF.frame_args has it
         frame = int(torch.as_tensor(batch["frame"]).reshape(-1)[0])
         xyz = self._dev(batch["xyz"][0])
         poses = batch["poses"][0].to(device=self.device, dtype=torch.float32).contiguous()
@@ -908,17 +917,9 @@ class Renderer:
         self._frame_src = None      # (the scene's frame state now lacks the net's light edit: stage calls set their frame again)
         th = batch["Th"][0] if any(lt.get("light_center") is not None for lt in lights) else None
         recs = _lib.light_records(lights, th, self.device)
-        o, d = self._dev(batch["ray_o"][0]), self._dev(batch["ray_d"][0])
-        n, f = self._dev(batch["near"][0]).clone(), self._dev(batch["far"][0]).clone()
-        S = self.cfg.MODEL.COARSE_RAY_SAMPLING
-        R = o.shape[0]
-        chunk = R if chunk is None else int(chunk)
-        outs = []
-        for i in range(0, R, chunk):
-            j = min(R, i + chunk)
-            outs.append(self._render_eval(scene, ws, o[i:j].contiguous(), d[i:j].contiguous(), n[i:j].contiguous(), f[i:j].contiguous(),
-                                          S, None, None, lights=recs))
-        coarse = outs[0] if len(outs) == 1 else {k: torch.cat([x[k] for x in outs], 1 if k == "color" else 0) for k in outs[0]}
+        coarse = self._render_chunks(batch["ray_o"], batch["ray_d"], batch["near"], batch["far"], chunk,
+                                     lambda o, d, n, f, S: self._render_eval(scene, ws, o, d, n, f, S, None, None, lights=recs),
+                                     color_axis=1)
         _, H, W, _ = batch["img"].shape
         mask = self._dev(batch["mask_at_box"][0], torch.uint8)
         return [_lib.image_scatter(dict(coarse, color=coarse["color"][k]), mask, H, W) for k in range(len(lights))]

@@ -626,7 +626,7 @@ int dsn_render_rays(const void* scene, int V, int F, const void* packed, const f
 
 // dsn_render_rays_lights: what replaces the shading phase of a frame (NULL: the frame's own light, dsn_render_rays_ex)
 struct DsnLightSweep {
-    const float* lights;      // [n_lights][DSN_LIGHT_RECORD_FLOATS] (device)
+    const DsnLightEdit* lights;      // [n_lights] (device)
     int n_lights;
     void* scratch;            // compact colours of a group of lights: [G][n_shaded][3]
     size_t scratch_bytes;
@@ -673,7 +673,7 @@ int dsn_render_rays_lights(const void* scene, int V, int F, const void* packed, 
                 "dsn_render_rays_lights: workspace, out_weights and out_z must be 16-byte aligned");
     DSN_REQUIRE(light_scratch_bytes >= dsn_render_lights_scratch_bytes(R, S, 1, 0),
                 "dsn_render_rays_lights: light_scratch is too small (dsn_render_lights_scratch_bytes)");
-    const DsnLightSweep sweep = {lights, n_lights, light_scratch, light_scratch_bytes};
+    const DsnLightSweep sweep = {reinterpret_cast<const DsnLightEdit*>(lights), n_lights, light_scratch, light_scratch_bytes};
     return dsn_render_frame(scene, V, F, packed, ray_o, ray_d, near, far, R, S, t_vals, jitter, noise, flags, out_rgb, out_disp, out_acc,
                             out_depth, out_weights, out_z, workspace, workspace_bytes, slice_lengths_host, n_slices, stream, &sweep);
 }
@@ -907,7 +907,7 @@ static int dsn_render_frame(const void* scene, int V, int F, const void* packed,
     for (int g0 = 0; g0 < sweep->n_lights; g0 += G) {
         const int Gc = std::min(G, sweep->n_lights - g0);
         const bool first = g0 == 0;      // (the per-ray outputs that do not depend on the light: written once)
-        dsn_launch_light16_multi((const float*)packed, sweep->lights + (size_t)g0 * DSN_LIGHT_RECORD_FLOATS, Gc, w.n_w, ray_o, ray_d, z,
+        dsn_launch_light16_multi((const float*)packed, sweep->lights + g0, Gc, w.n_w, ray_o, ray_d, z,
                                  w.essence, n_sh, S, list, cnt, colours, st);
         dsn_launch_composite_multi(slot, colours, n_sh, Gc, w.sigma, w.transparent, z, ray_d, R, S, out_rgb + (size_t)g0 * 3 * R,
                                    first ? out_disp : nullptr, first ? out_acc : nullptr, first ? out_weights : nullptr,

@@ -7,6 +7,7 @@
 // stages bit-reproducible against the oracle (oracle/dsn_oracle.c) and the reference.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 #define DSN_WAVE 64
@@ -26,17 +27,35 @@ struct DsnFaceRec {   // 16 floats = 64 B per face: everything utils/geo_utils.p
     float inv;        // 1 / (d00*d11 - d01*d01)
 };
 
+// dsn_render_rays_lights: floats per light record (= include/dsnerf.h)
+#ifndef DSN_LIGHT_RECORD_FLOATS
+#define DSN_LIGHT_RECORD_FLOATS 12
+#endif
+// A light edit (model/spacenet.py:254-265): the world point the lighting MLP sees is rotated about rot_center in xy when the rotation
+// flag is set, then shifted by light_shift when the light flag is set.  The layout of a record of dsn_render_rays_lights
+// (include/dsnerf.h); DsnFrameState holds the frame's own (k_pose_setup).  dsn_light_edit is the one place that applies it.
+struct DsnLightEdit {
+    float has_light, light_shift[3], has_rot, rot[4] /* row-major 2 x 2 */, rot_center[2], pad;
+};
+static_assert(sizeof(DsnLightEdit) == 4 * DSN_LIGHT_RECORD_FLOATS, "DsnLightEdit is one light record");
+__device__ __forceinline__ void dsn_light_edit(const DsnLightEdit& e, float (&xw)[3]) {
+    if (e.has_rot != 0.0f) {
+        const float ax = xw[0] - e.rot_center[0], ay = xw[1] - e.rot_center[1];
+        const float nx = (ax * e.rot[0] + ay * e.rot[2]) + e.rot_center[0];
+        const float ny = (ax * e.rot[1] + ay * e.rot[3]) + e.rot_center[1];
+        xw[0] = nx; xw[1] = ny;
+    }
+    if (e.has_light != 0.0f) { xw[0] += e.light_shift[0]; xw[1] += e.light_shift[1]; xw[2] += e.light_shift[2]; }
+}
+
 struct DsnFrameState {   // small per-frame vectors
     float pose_feat[16];
     float code[8];
-    float light_shift[3];
-    float has_light;
-    float rot[4];
-    float rot_center[2];
-    float has_rot;
-    float pad[29];       // (keeps bias0 256-byte aligned inside the struct)
+    DsnLightEdit light;  // the frame's light edit (dsn_set_frame's light_shift3 / rot2x2 / rot_center2)
+    float pad[28];       // (keeps bias0 256-byte aligned inside the struct)
     float bias0[256];    // stage1.0 bias with the 24 constant input columns (code, pose) folded in
 };
+static_assert(offsetof(DsnFrameState, bias0) == 256 && sizeof(DsnFrameState) == 1280, "DsnFrameState layout");
 
 __host__ __device__ inline size_t dsn_align256(size_t x) { return (x + 255) & ~(size_t)255; }
 #include "dsn_nn.h"
@@ -282,10 +301,6 @@ __host__ __device__ inline float dsn_stop_eps_scaled(int S, float colour_scale) 
 #define DSN_OWN_SIMD_T(bit) do { if (!((DSN_TRAIN_UNGUARDED) & (bit))) DSN_OWN_SIMD(); } while (0)
 #else
 #define DSN_OWN_SIMD_T(bit) do { if ((DSN_TRAIN_AGGRESSORS) & (bit)) DSN_OWN_SIMD(); } while (0)
-#endif
-// dsn_render_rays_lights: floats per light record {has_light, light_shift[3], has_rot, rot[4], rot_center[2], 0} (= include/dsnerf.h)
-#ifndef DSN_LIGHT_RECORD_FLOATS
-#define DSN_LIGHT_RECORD_FLOATS 12
 #endif
 #define DSN_SCREEN_MARGIN_DEFAULT 0.01f          // conservative margin of the density screen until it has been calibrated
 #define DSN_LO_SCALE 4096.0f                      // lo = (x - hi) * 2^12, products accumulated apart, folded at the end

@@ -519,13 +519,7 @@ k_light(const float* __restrict__ packed, const DsnFrameState* __restrict__ fs, 
         const float z = z_vals[pt];
         xw[0] = ray_o[3 * ray] + d[0] * z; xw[1] = ray_o[3 * ray + 1] + d[1] * z; xw[2] = ray_o[3 * ray + 2] + d[2] * z;
     }
-    if (fs->has_rot != 0.0f) {
-        const float ax = xw[0] - fs->rot_center[0], ay = xw[1] - fs->rot_center[1];
-        const float nx = (ax * fs->rot[0] + ay * fs->rot[2]) + fs->rot_center[0];
-        const float ny = (ax * fs->rot[1] + ay * fs->rot[3]) + fs->rot_center[1];
-        xw[0] = nx; xw[1] = ny;
-    }
-    if (fs->has_light != 0.0f) { xw[0] += fs->light_shift[0]; xw[1] += fs->light_shift[1]; xw[2] += fs->light_shift[2]; }
+    dsn_light_edit(fs->light, xw);
     in9[3] = xw[0]; in9[4] = xw[1]; in9[5] = xw[2];
     const float vn = dsn_norm3(d);
     in9[6] = dsn_div(d[0], vn); in9[7] = dsn_div(d[1], vn); in9[8] = dsn_div(d[2], vn);

@@ -2153,93 +2153,43 @@ __device__ __forceinline__ void light_block(const char* __restrict__ blkp, int l
 // memory for every 32 samples - more than a CU's L1 holds, so 2.25 KB per sample came from L2: 4.4 GB per launch on the bench frame,
 // 10 TB/s, the kernel was L2-bound (0.41 ms).  Now a workgroup stages the 20 blocks once (72 KB: two workgroups per CU) and walks
 // its tiles of 128 samples with ds_read_b128 operands.  Same products in the same order: bit-identical colours.
+// The helpers below are the whole lighting MLP of k_light16 and k_light16_multi: one copy of the arithmetic for both.
 #define LIGHT_LDS_BYTES (4 * 2048 + 16 * 4096)
-__global__ void __launch_bounds__(256, 1)
-k_light16(const float* __restrict__ packed, const DsnFrameState* __restrict__ fs, const float* __restrict__ n_w,
-          const float* __restrict__ x_w_pts, const float* __restrict__ ray_o, const float* __restrict__ ray_d,
-          const float* __restrict__ z_vals, const float* essence, int64_t N, int S,
-          const int32_t* __restrict__ active_list, const int32_t* __restrict__ active_count,
-          float* colour, float* __restrict__ tr_hl1, float* __restrict__ tr_hl2, float* __restrict__ tr_pre) {
-    // (essence and colour may be the SAME array - the fused path's workspace keeps the colour where the essence was: a tile reads its
-    //  samples' essences at its top and writes their colours at its end; hence no __restrict__ on the two)
-    // tr_*: (training forward) the two hidden layers after their ReLU, row-major [N,128], and the pre-activation of the output
-    // [N] - what the backward of the lighting MLP needs, so that it does not have to evaluate the MLP again
-    __shared__ __attribute__((aligned(16))) char s_w[LIGHT_LDS_BYTES];      // [LT0: 4 x (hi, lo of k-step 0) | LT1: 16 x 4 KB]
-#ifndef F16_SHARE_SIMD
-    DSN_OWN_SIMD();      // (round 5: this kernel too made co-resident waves of other kernels read registers early - dsn_common.h)
-#endif
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int half = lane >> 5;
-    const int64_t count = active_list ? (int64_t)(*active_count) : N;
-    const int64_t ntiles = (count + 127) / 128;
-    if ((int64_t)blockIdx.x >= ntiles) return;      // block-uniform
-    {
-        const char* g16 = reinterpret_cast<const char*>(packed + OFF16_BASE);
-        const uint4* g0 = reinterpret_cast<const uint4*>(g16 + (size_t)(OFF_LT0 / DSN_BLK) * 4096);
-        const uint4* g1 = reinterpret_cast<const uint4*>(g16 + (size_t)(OFF_LT1 / DSN_BLK) * 4096);
-        uint4* d = reinterpret_cast<uint4*>(s_w);
-        for (int i = threadIdx.x; i < 4 * 128; i += 256) d[i] = g0[(i >> 7) * 256 + (i & 127)];      // first 2 KB of each 4 KB block
-        for (int i = threadIdx.x; i < 16 * 256; i += 256) d[4 * 128 + i] = g1[i];
-    }
+// the 20 blocks into LDS: [LT0: 4 x (hi, lo of k-step 0) | LT1: 16 x 4 KB] (a whole workgroup of 256 threads)
+__device__ __forceinline__ void light16_stage_weights(const float* __restrict__ packed, char* s_w) {
+    const char* g16 = reinterpret_cast<const char*>(packed + OFF16_BASE);
+    const uint4* g0 = reinterpret_cast<const uint4*>(g16 + (size_t)(OFF_LT0 / DSN_BLK) * 4096);
+    const uint4* g1 = reinterpret_cast<const uint4*>(g16 + (size_t)(OFF_LT1 / DSN_BLK) * 4096);
+    uint4* d = reinterpret_cast<uint4*>(s_w);
+    for (int i = threadIdx.x; i < 4 * 128; i += 256) d[i] = g0[(i >> 7) * 256 + (i & 127)];      // first 2 KB of each 4 KB block
+    for (int i = threadIdx.x; i < 16 * 256; i += 256) d[4 * 128 + i] = g1[i];
     __syncthreads();
-    // The inputs of a tile (its samples' normals, depths, rays) are gathers behind a list entry: two dependent trips to memory in
-    // front of 108 MFMAs, and a CU holds only two waves per SIMD of this kernel - the kernel was bound by that latency (0.30 ms
-    // for 0.05 ms of matrix work).  They are fetched one tile ahead now (the list entry two tiles ahead).
-    struct LightIn { float nw[3], o[3], d[3], z; };
-    auto tile_pt = [&](int64_t t, bool& ok) -> int64_t {
-        int64_t sl = (t * 4 + wave) * 32 + (lane & 31);
-        ok = t < ntiles && sl < count;
-        if (!ok) sl = count - 1;
-        return active_list ? (int64_t)active_list[sl] : sl;
-    };
-    auto fetch_in = [&](int64_t p, LightIn& a) {
-        const int64_t r = p / S;
-        a.nw[0] = n_w[3 * p]; a.nw[1] = n_w[3 * p + 1]; a.nw[2] = n_w[3 * p + 2];
-        a.d[0] = ray_d[3 * r]; a.d[1] = ray_d[3 * r + 1]; a.d[2] = ray_d[3 * r + 2];
-        if (x_w_pts) { a.o[0] = x_w_pts[3 * p]; a.o[1] = x_w_pts[3 * p + 1]; a.o[2] = x_w_pts[3 * p + 2]; a.z = 0.0f; }
-        else { a.o[0] = ray_o[3 * r]; a.o[1] = ray_o[3 * r + 1]; a.o[2] = ray_o[3 * r + 2]; a.z = z_vals[p]; }
-    };
-    bool valid_c, valid_n, valid_nn;
-    int64_t pt_c = tile_pt(blockIdx.x, valid_c);
-    LightIn in_c, in_n;
-    fetch_in(pt_c, in_c);
-    int64_t pt_n = tile_pt((int64_t)blockIdx.x + gridDim.x, valid_n);
-  for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-    const int64_t slot0 = (tile * 4 + wave) * 32;
-    const bool valid = valid_c;
-    const int64_t pt = pt_c;
-    const LightIn cur = in_c;
-    // next tile's inputs and the list entry of the one after it: in flight under this tile's arithmetic
-    fetch_in(pt_n, in_n);
-    const int64_t pt_nn = tile_pt(tile + 2 * (int64_t)gridDim.x, valid_nn);
-    pt_c = pt_n; valid_c = valid_n; in_c = in_n;
-    pt_n = pt_nn; valid_n = valid_nn;
-    if (slot0 >= count) continue;                    // (no barrier inside the loop)
-    // (needed at the very end: fetched now, waited for behind the arithmetic)
-    const float ess[3] = {essence[3 * pt], essence[3 * pt + 1], essence[3 * pt + 2]};
-
-    float in9[10];
-    in9[0] = cur.nw[0]; in9[1] = cur.nw[1]; in9[2] = cur.nw[2];
-    float xw[3];
-    const float d[3] = {cur.d[0], cur.d[1], cur.d[2]};
-    if (x_w_pts) { xw[0] = cur.o[0]; xw[1] = cur.o[1]; xw[2] = cur.o[2]; }
-    else {
-        const float z = cur.z;
-        xw[0] = cur.o[0] + d[0] * z; xw[1] = cur.o[1] + d[1] * z; xw[2] = cur.o[2] + d[2] * z;
-    }
-    if (fs->has_rot != 0.0f) {
-        const float ax = xw[0] - fs->rot_center[0], ay = xw[1] - fs->rot_center[1];
-        const float nx = (ax * fs->rot[0] + ay * fs->rot[2]) + fs->rot_center[0];
-        const float ny = (ax * fs->rot[1] + ay * fs->rot[3]) + fs->rot_center[1];
-        xw[0] = nx; xw[1] = ny;
-    }
-    if (fs->has_light != 0.0f) { xw[0] += fs->light_shift[0]; xw[1] += fs->light_shift[1]; xw[2] += fs->light_shift[2]; }
-    in9[3] = xw[0]; in9[4] = xw[1]; in9[5] = xw[2];
-    const float vn = dsn_norm3(d);
-    in9[6] = dsn_div(d[0], vn); in9[7] = dsn_div(d[1], vn); in9[8] = dsn_div(d[2], vn);
-    in9[9] = 0.0f;
-
+}
+// The inputs of a tile (its samples' normals, depths, rays) are gathers behind a list entry: two dependent trips to memory in
+// front of 108 MFMAs, and a CU holds only two waves per SIMD of this kernel - the kernel was bound by that latency (0.30 ms
+// for 0.05 ms of matrix work).  They are fetched one tile ahead now (the list entry two tiles ahead).
+struct LightIn { float nw[3], o[3], d[3], z; };      // o: the ray origin (z: the depth), or the world point when x_w_pts is given
+// the list slot of this lane in tile t (the last one where the tile has none: ok = false)
+__device__ __forceinline__ int64_t light16_tile_slot(int64_t t, int wave, int lane, int64_t ntiles, int64_t count, bool& ok) {
+    int64_t sl = (t * 4 + wave) * 32 + (lane & 31);
+    ok = t < ntiles && sl < count;
+    if (!ok) sl = count - 1;
+    return sl;
+}
+__device__ __forceinline__ void light16_fetch(int64_t p, int S, const float* __restrict__ n_w, const float* __restrict__ x_w_pts,
+                                              const float* __restrict__ ray_o, const float* __restrict__ ray_d,
+                                              const float* __restrict__ z_vals, LightIn& a) {
+    const int64_t r = p / S;
+    a.nw[0] = n_w[3 * p]; a.nw[1] = n_w[3 * p + 1]; a.nw[2] = n_w[3 * p + 2];
+    a.d[0] = ray_d[3 * r]; a.d[1] = ray_d[3 * r + 1]; a.d[2] = ray_d[3 * r + 2];
+    if (x_w_pts) { a.o[0] = x_w_pts[3 * p]; a.o[1] = x_w_pts[3 * p + 1]; a.o[2] = x_w_pts[3 * p + 2]; a.z = 0.0f; }
+    else { a.o[0] = ray_o[3 * r]; a.o[1] = ray_o[3 * r + 1]; a.o[2] = ray_o[3 * r + 2]; a.z = z_vals[p]; }
+}
+// The MLP of one sample: in9 = [n_w, x_w (light edit applied), d/|d|, 0] -> the pre-activation o of the output.  tr_hl1 / tr_hl2
+// (optional, training forward): the two hidden layers after their ReLU, row-major [N,128], stored for pt where valid.
+__device__ __forceinline__ float light16_mlp(const float* __restrict__ packed, const char* s_w, int lane, const float (&in9)[10],
+                                             bool valid, int64_t pt, float* __restrict__ tr_hl1, float* __restrict__ tr_hl2) {
+    const int half = lane >> 5;
     // input operand: k-slot j of step 0 holds feature 2j + half (j < 5), zero beyond
     half8 xh[2], xl[2];
     {
@@ -2273,8 +2223,71 @@ k_light16(const float* __restrict__ packed, const DsnFrameState* __restrict__ fs
         if (tr_hl2 && valid) store16(tr_hl2 + pt * 128 + 4 * half + 32 * m, v, 1.0f);
     }
     part += __shfl_xor(part, 32);
-    const float o = part + packed[OFF_SCAL + 4];
-    const float wgt = (o > 0.0f ? o : expm1f(o)) + 1.0f;   // ELU(alpha=1) + 1
+    return part + packed[OFF_SCAL + 4];
+}
+__device__ __forceinline__ float light16_weight(float o) { return (o > 0.0f ? o : expm1f(o)) + 1.0f; }   // ELU(alpha=1) + 1
+
+__global__ void __launch_bounds__(256, 1)
+k_light16(const float* __restrict__ packed, const DsnFrameState* __restrict__ fs, const float* __restrict__ n_w,
+          const float* __restrict__ x_w_pts, const float* __restrict__ ray_o, const float* __restrict__ ray_d,
+          const float* __restrict__ z_vals, const float* essence, int64_t N, int S,
+          const int32_t* __restrict__ active_list, const int32_t* __restrict__ active_count,
+          float* colour, float* __restrict__ tr_hl1, float* __restrict__ tr_hl2, float* __restrict__ tr_pre) {
+    // (essence and colour may be the SAME array - the fused path's workspace keeps the colour where the essence was: a tile reads its
+    //  samples' essences at its top and writes their colours at its end; hence no __restrict__ on the two)
+    // tr_*: (training forward) light16_mlp's hidden layers, and the pre-activation of the output [N] - what the backward of the
+    // lighting MLP needs, so that it does not have to evaluate the MLP again
+    __shared__ __attribute__((aligned(16))) char s_w[LIGHT_LDS_BYTES];
+#ifndef F16_SHARE_SIMD
+    DSN_OWN_SIMD();      // (round 5: this kernel too made co-resident waves of other kernels read registers early - dsn_common.h)
+#endif
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int half = lane >> 5;
+    const int64_t count = active_list ? (int64_t)(*active_count) : N;
+    const int64_t ntiles = (count + 127) / 128;
+    if ((int64_t)blockIdx.x >= ntiles) return;      // block-uniform
+    light16_stage_weights(packed, s_w);
+    auto tile_pt = [&](int64_t t, bool& ok) -> int64_t {
+        const int64_t sl = light16_tile_slot(t, wave, lane, ntiles, count, ok);
+        return active_list ? (int64_t)active_list[sl] : sl;
+    };
+    bool valid_c, valid_n, valid_nn;
+    int64_t pt_c = tile_pt(blockIdx.x, valid_c);
+    LightIn in_c, in_n;
+    light16_fetch(pt_c, S, n_w, x_w_pts, ray_o, ray_d, z_vals, in_c);
+    int64_t pt_n = tile_pt((int64_t)blockIdx.x + gridDim.x, valid_n);
+  for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int64_t slot0 = (tile * 4 + wave) * 32;
+    const bool valid = valid_c;
+    const int64_t pt = pt_c;
+    const LightIn cur = in_c;
+    // next tile's inputs and the list entry of the one after it: in flight under this tile's arithmetic
+    light16_fetch(pt_n, S, n_w, x_w_pts, ray_o, ray_d, z_vals, in_n);
+    const int64_t pt_nn = tile_pt(tile + 2 * (int64_t)gridDim.x, valid_nn);
+    pt_c = pt_n; valid_c = valid_n; in_c = in_n;
+    pt_n = pt_nn; valid_n = valid_nn;
+    if (slot0 >= count) continue;                    // (no barrier inside the loop)
+    // (needed at the very end: fetched now, waited for behind the arithmetic)
+    const float ess[3] = {essence[3 * pt], essence[3 * pt + 1], essence[3 * pt + 2]};
+
+    float in9[10];
+    in9[0] = cur.nw[0]; in9[1] = cur.nw[1]; in9[2] = cur.nw[2];
+    float xw[3];
+    const float d[3] = {cur.d[0], cur.d[1], cur.d[2]};
+    if (x_w_pts) { xw[0] = cur.o[0]; xw[1] = cur.o[1]; xw[2] = cur.o[2]; }
+    else {
+        const float z = cur.z;
+        xw[0] = cur.o[0] + d[0] * z; xw[1] = cur.o[1] + d[1] * z; xw[2] = cur.o[2] + d[2] * z;
+    }
+    dsn_light_edit(fs->light, xw);
+    in9[3] = xw[0]; in9[4] = xw[1]; in9[5] = xw[2];
+    const float vn = dsn_norm3(d);
+    in9[6] = dsn_div(d[0], vn); in9[7] = dsn_div(d[1], vn); in9[8] = dsn_div(d[2], vn);
+    in9[9] = 0.0f;
+
+    const float o = light16_mlp(packed, s_w, lane, in9, valid, pt, tr_hl1, tr_hl2);
+    const float wgt = light16_weight(o);
     if (tr_pre && valid && half == 0) tr_pre[pt] = o;
     if (valid && half == 0) {
         colour[3 * pt + 0] = wgt * ess[0];
@@ -2299,51 +2312,33 @@ void dsn_launch_light16(const float* packed, const DsnFrameState* fs, const floa
 // k_light16_multi : k_light16 for G light settings per pass over the shading list (dsn_render_rays_lights).  A light edit moves only
 // the world position the lighting MLP sees (model/spacenet.py:254-265); the normal, the view direction, the ray and the essence of a
 // sample are gathered ONCE per tile and the MLP runs G times on them.  An MFMA output column depends on its own column only, so a
-// (sample, light) pair gives k_light16's bits for that sample under that light: the per-light arithmetic below is k_light16's,
-// expression for expression (same split16, same products in the same k-order, fold16, fmaf order, __shfl_xor, expm1f).
-// lights: G records of DSN_LIGHT_RECORD_FLOATS floats {has_light, light_shift[3], has_rot, rot[4] (row-major), rot_center[2], 0}.
+// (sample, light) pair gives k_light16's bits for that sample under that light: both kernels run the same light16_* helpers and
+// dsn_light_edit.
+// lights: G light records (DsnLightEdit).
 // colours: [G][count][3], indexed by the sample's slot on the list (not by the sample: a dense [N,3] per light would not fit).
 // ---------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256, 1)
-k_light16_multi(const float* __restrict__ packed, const float* __restrict__ lights, int G, const float* __restrict__ n_w,
+k_light16_multi(const float* __restrict__ packed, const DsnLightEdit* __restrict__ lights, int G, const float* __restrict__ n_w,
                 const float* __restrict__ ray_o, const float* __restrict__ ray_d, const float* __restrict__ z_vals,
                 const float* __restrict__ essence, int S, const int32_t* __restrict__ list, const int32_t* __restrict__ list_count,
                 float* __restrict__ colours) {
-    __shared__ __attribute__((aligned(16))) char s_w[LIGHT_LDS_BYTES];      // (k_light16's layout)
+    __shared__ __attribute__((aligned(16))) char s_w[LIGHT_LDS_BYTES];
+#ifndef F16_SHARE_SIMD
     DSN_OWN_SIMD();
+#endif
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int half = lane >> 5;
     const int64_t count = *list_count;
     const int64_t ntiles = (count + 127) / 128;
     if ((int64_t)blockIdx.x >= ntiles) return;      // block-uniform
-    {
-        const char* g16 = reinterpret_cast<const char*>(packed + OFF16_BASE);
-        const uint4* g0 = reinterpret_cast<const uint4*>(g16 + (size_t)(OFF_LT0 / DSN_BLK) * 4096);
-        const uint4* g1 = reinterpret_cast<const uint4*>(g16 + (size_t)(OFF_LT1 / DSN_BLK) * 4096);
-        uint4* d = reinterpret_cast<uint4*>(s_w);
-        for (int i = threadIdx.x; i < 4 * 128; i += 256) d[i] = g0[(i >> 7) * 256 + (i & 127)];
-        for (int i = threadIdx.x; i < 16 * 256; i += 256) d[4 * 128 + i] = g1[i];
-    }
-    __syncthreads();
+    light16_stage_weights(packed, s_w);
     // (inputs one tile ahead, the list entry two tiles ahead: as in k_light16)
-    struct LightIn { float nw[3], o[3], d[3], z; };
-    auto tile_pt = [&](int64_t t, bool& ok) -> int64_t {
-        int64_t sl = (t * 4 + wave) * 32 + (lane & 31);
-        ok = t < ntiles && sl < count;
-        if (!ok) sl = count - 1;
-        return (int64_t)list[sl];
-    };
-    auto fetch_in = [&](int64_t p, LightIn& a) {
-        const int64_t r = p / S;
-        a.nw[0] = n_w[3 * p]; a.nw[1] = n_w[3 * p + 1]; a.nw[2] = n_w[3 * p + 2];
-        a.d[0] = ray_d[3 * r]; a.d[1] = ray_d[3 * r + 1]; a.d[2] = ray_d[3 * r + 2];
-        a.o[0] = ray_o[3 * r]; a.o[1] = ray_o[3 * r + 1]; a.o[2] = ray_o[3 * r + 2]; a.z = z_vals[p];
-    };
+    auto tile_pt = [&](int64_t t, bool& ok) -> int64_t { return (int64_t)list[light16_tile_slot(t, wave, lane, ntiles, count, ok)]; };
     bool valid_c, valid_n, valid_nn;
     int64_t pt_c = tile_pt(blockIdx.x, valid_c);
     LightIn in_c, in_n;
-    fetch_in(pt_c, in_c);
+    light16_fetch(pt_c, S, n_w, nullptr, ray_o, ray_d, z_vals, in_c);
     int64_t pt_n = tile_pt((int64_t)blockIdx.x + gridDim.x, valid_n);
   for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
     const int64_t slot0 = (tile * 4 + wave) * 32;
@@ -2351,7 +2346,7 @@ k_light16_multi(const float* __restrict__ packed, const float* __restrict__ ligh
     const bool valid = valid_c;
     const int64_t pt = pt_c;
     const LightIn cur = in_c;
-    fetch_in(pt_n, in_n);
+    light16_fetch(pt_n, S, n_w, nullptr, ray_o, ray_d, z_vals, in_n);
     const int64_t pt_nn = tile_pt(tile + 2 * (int64_t)gridDim.x, valid_nn);
     pt_c = pt_n; valid_c = valid_n; in_c = in_n;
     pt_n = pt_nn; valid_n = valid_nn;
@@ -2369,52 +2364,14 @@ k_light16_multi(const float* __restrict__ packed, const float* __restrict__ ligh
     for (int g = 0; g < G; ++g) {
         // (keeps the bias / output-weight rows' loads inside the loop: hoisted out of it they are 192 live registers - 137 spilled)
         asm volatile("" ::: "memory");
-        const float* lr = lights + (int64_t)g * DSN_LIGHT_RECORD_FLOATS;      // (uniform: scalar loads)
         float in9[10];
         in9[0] = cur.nw[0]; in9[1] = cur.nw[1]; in9[2] = cur.nw[2];
         float xw[3] = {xw0[0], xw0[1], xw0[2]};
-        if (lr[4] != 0.0f) {
-            const float ax = xw[0] - lr[9], ay = xw[1] - lr[10];
-            const float nx = (ax * lr[5] + ay * lr[7]) + lr[9];
-            const float ny = (ax * lr[6] + ay * lr[8]) + lr[10];
-            xw[0] = nx; xw[1] = ny;
-        }
-        if (lr[0] != 0.0f) { xw[0] += lr[1]; xw[1] += lr[2]; xw[2] += lr[3]; }
+        dsn_light_edit(lights[g], xw);      // (uniform: scalar loads)
         in9[3] = xw[0]; in9[4] = xw[1]; in9[5] = xw[2];
         in9[6] = vd[0]; in9[7] = vd[1]; in9[8] = vd[2];
         in9[9] = 0.0f;
-        half8 xh[2], xl[2];
-        {
-            f32x16 v = zero16();
-#pragma unroll
-            for (int j = 0; j < 5; ++j) v[j] = half ? in9[2 * j + 1] : in9[2 * j];
-            split16<true>(v, xh, xl);
-        }
-        half8 h1h[4][2], h1l[4][2];
-#pragma unroll
-        for (int m = 0; m < 4; ++m) {
-            f32x16 aM = rows16(packed + OFF_BLT0, m, half), aC = zero16();
-            light_block0(s_w + m * 2048, lane, xh, xl, aM, aC);
-            f32x16 v = fold16(aM, aC);
-#pragma unroll
-            for (int r = 0; r < 16; ++r) v[r] = fmaxf(v[r], 0.0f);
-            split16<true>(v, h1h[m], h1l[m]);
-        }
-        float part = 0.0f;
-#pragma unroll
-        for (int m = 0; m < 4; ++m) {
-            f32x16 aM = rows16(packed + OFF_BLT1, m, half), aC = zero16();
-#pragma unroll
-            for (int kb = 0; kb < 4; ++kb)
-                light_block(s_w + 4 * 2048 + (m * 4 + kb) * 4096, lane, h1h[kb], h1l[kb], aM, aC, true);
-            f32x16 v = fold16(aM, aC);
-            const f32x16 w2 = rows16(packed + OFF_WLT2, m, half);
-#pragma unroll
-            for (int r = 0; r < 16; ++r) { v[r] = fmaxf(v[r], 0.0f); part = fmaf(w2[r], v[r], part); }
-        }
-        part += __shfl_xor(part, 32);
-        const float o = part + packed[OFF_SCAL + 4];
-        const float wgt = (o > 0.0f ? o : expm1f(o)) + 1.0f;   // ELU(alpha=1) + 1
+        const float wgt = light16_weight(light16_mlp(packed, s_w, lane, in9, valid, pt, nullptr, nullptr));
         if (valid && half == 0) {
             float* c = colours + ((int64_t)g * count + slot) * 3;
             c[0] = wgt * ess[0];
@@ -2425,7 +2382,7 @@ k_light16_multi(const float* __restrict__ packed, const float* __restrict__ ligh
   }
 }
 
-void dsn_launch_light16_multi(const float* packed, const float* lights, int G, const float* n_w, const float* ray_o, const float* ray_d,
+void dsn_launch_light16_multi(const float* packed, const DsnLightEdit* lights, int G, const float* n_w, const float* ray_o, const float* ray_d,
                               const float* z_vals, const float* essence, int64_t max_count, int S, const int32_t* list,
                               const int32_t* list_count, float* colours, hipStream_t st) {
     const int64_t blocks = (max_count + 127) / 128;

@@ -91,11 +91,12 @@ __global__ void __launch_bounds__(256) k_pose_setup(const float* __restrict__ pa
         fs->bias0[t] = acc;
     }
     if (t == 0) {
-        fs->has_light = light_shift ? 1.0f : 0.0f;
-        for (int c = 0; c < 3; ++c) fs->light_shift[c] = light_shift ? light_shift[c] : 0.0f;
-        fs->has_rot = (rot && rot_center) ? 1.0f : 0.0f;
-        for (int c = 0; c < 4; ++c) fs->rot[c] = (rot && rot_center) ? rot[c] : 0.0f;
-        for (int c = 0; c < 2; ++c) fs->rot_center[c] = (rot && rot_center) ? rot_center[c] : 0.0f;
+        DsnLightEdit& e = fs->light;
+        e.has_light = light_shift ? 1.0f : 0.0f;
+        for (int c = 0; c < 3; ++c) e.light_shift[c] = light_shift ? light_shift[c] : 0.0f;
+        e.has_rot = (rot && rot_center) ? 1.0f : 0.0f;
+        for (int c = 0; c < 4; ++c) e.rot[c] = (rot && rot_center) ? rot[c] : 0.0f;
+        for (int c = 0; c < 2; ++c) e.rot_center[c] = (rot && rot_center) ? rot_center[c] : 0.0f;
     }
 }
 
@@ -821,32 +822,25 @@ __device__ __forceinline__ float dsn_row_sum_to_last(float v) {      // lane 15 
     v += dsn_row_shr(0.f, v, 8);
     return v;
 }
-template <bool WEIGHTS_ONLY, int CH>
-__global__ void __launch_bounds__(256) k_composite16(const float* __restrict__ colour, const float* __restrict__ sigma,
-                                                      const uint8_t* __restrict__ transparent,
-                                                      const float* __restrict__ z_vals, const float* __restrict__ ray_d,
-                                                      const float* __restrict__ noise, int R, float* __restrict__ rgb_map,
-                                                      float* __restrict__ disp_map, float* __restrict__ acc_map,
-                                                      float* __restrict__ weights, float* __restrict__ depth_map, int lazy_colour,
-                                                      int32_t* __restrict__ colour_max) {
-    constexpr int S = 16 * CH;
-    const int lane = threadIdx.x & 63, sub = lane & 15;
-    const int r_of_row = (blockIdx.x * 4 + (threadIdx.x >> 6)) * 4 + (lane >> 4);
-    if (r_of_row - (lane >> 4) >= R) return;              // wave-uniform
-    // a row past the last ray stays in step (the wave-wide maximum below reads every row) on a copy of the last ray and stores nothing
-    const bool ok = r_of_row < R;
-    const int r = ok ? r_of_row : R - 1;
-    const float d[3] = {ray_d[3 * r], ray_d[3 * r + 1], ray_d[3 * r + 2]};
-    const float dn = dsn_norm3(d);
-    const int64_t g0 = (int64_t)r * S + sub * CH;
-    float z[CH + 1], sg[CH];
-    uint8_t tr[CH];
+// The pieces of k_composite16 and k_composite16_multi (one copy of the arithmetic for both).  A lane holds samples g0 .. g0 + CH - 1
+// of its ray.
+// z / sigma / transparent of the lane's samples (noise added, slot map read where given); z[CH]: the first depth of the next lane
+// (row_shl:1: lane l reads lane l + 1 of its row; the ray's last sample has no successor)
+template <int CH>
+__device__ __forceinline__ void composite16_load(int64_t g0, const float* __restrict__ z_vals, const float* __restrict__ sigma,
+                                                 const uint8_t* __restrict__ transparent, const float* __restrict__ noise,
+                                                 const int32_t* __restrict__ slot_of, float (&z)[CH + 1], float (&sg)[CH],
+                                                 uint8_t (&tr)[CH], int32_t (&sl)[CH]) {
 #pragma unroll
     for (int q = 0; q < CH / 4; ++q) {
         const float4 z4 = *reinterpret_cast<const float4*>(z_vals + g0 + 4 * q);
         const float4 s4 = *reinterpret_cast<const float4*>(sigma + g0 + 4 * q);
         z[4 * q] = z4.x; z[4 * q + 1] = z4.y; z[4 * q + 2] = z4.z; z[4 * q + 3] = z4.w;
         sg[4 * q] = s4.x; sg[4 * q + 1] = s4.y; sg[4 * q + 2] = s4.z; sg[4 * q + 3] = s4.w;
+        if (slot_of) {
+            const int4 l4 = *reinterpret_cast<const int4*>(slot_of + g0 + 4 * q);
+            sl[4 * q] = l4.x; sl[4 * q + 1] = l4.y; sl[4 * q + 2] = l4.z; sl[4 * q + 3] = l4.w;
+        }
         uchar4 t4 = make_uchar4(0, 0, 0, 0);
         if (transparent) t4 = *reinterpret_cast<const uchar4*>(transparent + g0 + 4 * q);
         tr[4 * q] = t4.x; tr[4 * q + 1] = t4.y; tr[4 * q + 2] = t4.z; tr[4 * q + 3] = t4.w;
@@ -857,8 +851,14 @@ __global__ void __launch_bounds__(256) k_composite16(const float* __restrict__ c
             sg[4 * q + 2] = (tr[4 * q + 2] ? 0.f : sg[4 * q + 2]) + n4.z; sg[4 * q + 3] = (tr[4 * q + 3] ? 0.f : sg[4 * q + 3]) + n4.w;
         }
     }
-    // the first depth of the next lane (row_shl:1: lane l reads lane l + 1 of its row; the ray's last sample has no successor)
     z[CH] = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(z[0]), 0x101, 0xf, 0xf, false));
+}
+// the weights w of the lane's samples (sg: clamped to >= 0 on the way, transparent samples zeroed unless the noise did it), stored
+// where `weights` is given and the row holds a ray
+template <int CH>
+__device__ __forceinline__ void composite16_weights(const float (&z)[CH + 1], float (&sg)[CH], const uint8_t (&tr)[CH], const float* noise,
+                                                    float dn, int sub, int64_t g0, bool ok, float* __restrict__ weights, float (&w)[CH]) {
+    constexpr int S = 16 * CH;
     float alpha[CH], pre[CH];                // pre[j]: product of this lane's factors 0 .. j
     float run = 1.0f;
 #pragma unroll
@@ -879,7 +879,6 @@ __global__ void __launch_bounds__(256) k_composite16(const float* __restrict__ c
     incl = incl * dsn_row_shr(1.0f, incl, 4);
     incl = incl * dsn_row_shr(1.0f, incl, 8);
     const float before = dsn_row_shr(1.0f, incl, 1);      // transmittance entering this lane's first sample
-    float w[CH];
 #pragma unroll
     for (int j = 0; j < CH; ++j) w[j] = alpha[j] * (j == 0 ? before : before * pre[j - 1]);
     if (weights && ok) {
@@ -887,6 +886,58 @@ __global__ void __launch_bounds__(256) k_composite16(const float* __restrict__ c
         for (int q = 0; q < CH / 4; ++q)
             *reinterpret_cast<float4*>(weights + g0 + 4 * q) = make_float4(w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]);
     }
+}
+// depth / acc / disp of the ray from the row's sums (dsn_row_sum_to_last: lane 15 of the row stores where `store`)
+__device__ __forceinline__ void composite16_maps(float sdep, float sacc, bool store, int r, float* __restrict__ depth_map,
+                                                 float* __restrict__ acc_map, float* __restrict__ disp_map) {
+    if (store) {
+        depth_map[r] = sdep;
+        acc_map[r] = sacc;
+        float q = dsn_div(sdep, sacc);          // NaN when acc == 0, like the reference
+        float m = (1e-10f > q) ? 1e-10f : q;    // torch.max propagates NaN
+        if (q != q) m = q;
+        disp_map[r] = dsn_div(1.0f, m);
+    }
+}
+__device__ __forceinline__ float dsn_colour_mag(float cr, float cg, float cb) {      // max |c|, NaN -> +inf
+    const float m = fmaxf(fabsf(cr), fmaxf(fabsf(cg), fabsf(cb)));
+    return m == m ? m : INFINITY;
+}
+// the wave's largest colour magnitude into the early-stop guard word
+__device__ __forceinline__ void composite16_colour_max(float cm, int lane, int32_t* __restrict__ colour_max) {
+    cm = fmaxf(cm, dsn_row_shr(0.f, cm, 1)); cm = fmaxf(cm, dsn_row_shr(0.f, cm, 2));
+    cm = fmaxf(cm, dsn_row_shr(0.f, cm, 4)); cm = fmaxf(cm, dsn_row_shr(0.f, cm, 8));
+    // one candidate per wave, checked against a FRESH copy of the running maximum (a plain load may be served by this CU's L1 for
+    // the whole kernel, and then every row of the frame queues an atomic on the one address: that was most of this kernel's time)
+    cm = fmaxf(cm, __shfl_xor(cm, 16));
+    cm = fmaxf(cm, __shfl_xor(cm, 32));
+    if (lane == 63 && __float_as_int(cm) > __hip_atomic_load(colour_max, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+        atomicMax(colour_max, __float_as_int(cm));
+}
+
+template <bool WEIGHTS_ONLY, int CH>
+__global__ void __launch_bounds__(256) k_composite16(const float* __restrict__ colour, const float* __restrict__ sigma,
+                                                      const uint8_t* __restrict__ transparent,
+                                                      const float* __restrict__ z_vals, const float* __restrict__ ray_d,
+                                                      const float* __restrict__ noise, int R, float* __restrict__ rgb_map,
+                                                      float* __restrict__ disp_map, float* __restrict__ acc_map,
+                                                      float* __restrict__ weights, float* __restrict__ depth_map, int lazy_colour,
+                                                      int32_t* __restrict__ colour_max) {
+    constexpr int S = 16 * CH;
+    const int lane = threadIdx.x & 63, sub = lane & 15;
+    const int r_of_row = (blockIdx.x * 4 + (threadIdx.x >> 6)) * 4 + (lane >> 4);
+    if (r_of_row - (lane >> 4) >= R) return;              // wave-uniform
+    // a row past the last ray stays in step (the wave-wide maximum below reads every row) on a copy of the last ray and stores nothing
+    const bool ok = r_of_row < R;
+    const int r = ok ? r_of_row : R - 1;
+    const float d[3] = {ray_d[3 * r], ray_d[3 * r + 1], ray_d[3 * r + 2]};
+    const float dn = dsn_norm3(d);
+    const int64_t g0 = (int64_t)r * S + sub * CH;
+    float z[CH + 1], sg[CH], w[CH];
+    uint8_t tr[CH];
+    int32_t sl[CH];
+    composite16_load<CH>(g0, z_vals, sigma, transparent, noise, nullptr, z, sg, tr, sl);
+    composite16_weights<CH>(z, sg, tr, noise, dn, sub, g0, ok, weights, w);
     if (WEIGHTS_ONLY) return;
     float sr = 0.f, sgn = 0.f, sb = 0.f, sdep = 0.f, sacc = 0.f, cm = 0.f;
     float col[3 * CH];
@@ -911,42 +962,23 @@ __global__ void __launch_bounds__(256) k_composite16(const float* __restrict__ c
         sr += w[j] * cr; sgn += w[j] * cg; sb += w[j] * cb;
         sdep += w[j] * z[j];
         sacc += w[j];
-        float m = fmaxf(fabsf(cr), fmaxf(fabsf(cg), fabsf(cb)));
-        m = m == m ? m : INFINITY;
-        cm = fmaxf(cm, m);
+        cm = fmaxf(cm, dsn_colour_mag(cr, cg, cb));
     }
     sr = dsn_row_sum_to_last(sr); sgn = dsn_row_sum_to_last(sgn); sb = dsn_row_sum_to_last(sb);
     sdep = dsn_row_sum_to_last(sdep); sacc = dsn_row_sum_to_last(sacc);
-    if (colour_max) {
-        cm = fmaxf(cm, dsn_row_shr(0.f, cm, 1)); cm = fmaxf(cm, dsn_row_shr(0.f, cm, 2));
-        cm = fmaxf(cm, dsn_row_shr(0.f, cm, 4)); cm = fmaxf(cm, dsn_row_shr(0.f, cm, 8));
-        // one candidate per wave, checked against a FRESH copy of the running maximum (a plain load may be served by this CU's L1 for
-        // the whole kernel, and then every row of the frame queues an atomic on the one address: that was most of this kernel's time)
-        cm = fmaxf(cm, __shfl_xor(cm, 16));
-        cm = fmaxf(cm, __shfl_xor(cm, 32));
-        if (lane == 63 && __float_as_int(cm) > __hip_atomic_load(colour_max, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
-            atomicMax(colour_max, __float_as_int(cm));
-    }
-    if (sub == 15 && rgb_map && ok) {
-        rgb_map[3 * r] = sr; rgb_map[3 * r + 1] = sgn; rgb_map[3 * r + 2] = sb;
-        depth_map[r] = sdep;
-        acc_map[r] = sacc;
-        float q = dsn_div(sdep, sacc);          // NaN when acc == 0, like the reference
-        float m = (1e-10f > q) ? 1e-10f : q;    // torch.max propagates NaN
-        if (q != q) m = q;
-        disp_map[r] = dsn_div(1.0f, m);
-    }
+    if (colour_max) composite16_colour_max(cm, lane, colour_max);
+    const bool store = sub == 15 && rgb_map && ok;
+    if (store) { rgb_map[3 * r] = sr; rgb_map[3 * r + 1] = sgn; rgb_map[3 * r + 2] = sb; }
+    composite16_maps(sdep, sacc, store, r, depth_map, acc_map, disp_map);
 }
 
 void dsn_launch_composite(const float* colour, const float* sigma, const uint8_t* transparent, const float* z_vals,
                           const float* ray_d, const float* noise, int R, int S, float* rgb_map, float* disp_map,
                           float* acc_map, float* weights, float* depth_map, hipStream_t st, bool lazy_colour, int32_t* colour_max) {
-    // 16 lanes per ray where the ray length allows 16-byte loads per lane (S = 64 / 128) and the arrays are 16-byte aligned;
-    // DSN_COMPOSITE=wave (A/B, tests) keeps the one-wave-per-ray form
-    static const bool wave_form = [] { const char* e = getenv("DSN_COMPOSITE"); return e && e[0] == 'w'; }();
+    // 16 lanes per ray where the ray length allows 16-byte loads per lane (S = 64 / 128) and the arrays are 16-byte aligned
     const bool aligned = (((uintptr_t)z_vals | (uintptr_t)sigma | (uintptr_t)weights | (uintptr_t)noise | (uintptr_t)colour) & 15) == 0 &&
                          (((uintptr_t)transparent) & 3) == 0;
-    if (!wave_form && aligned && (S == 64 || S == 128)) {
+    if (aligned && (S == 64 || S == 128)) {
         const dim3 grid((unsigned)((R + 15) / 16)), block(256);
         const bool wo = !colour && !rgb_map;
         int32_t* cmx = colour ? colour_max : nullptr;
@@ -1003,62 +1035,17 @@ __global__ void __launch_bounds__(256) k_composite16_multi(const int32_t* __rest
     const float d[3] = {ray_d[3 * r], ray_d[3 * r + 1], ray_d[3 * r + 2]};
     const float dn = dsn_norm3(d);
     const int64_t g0 = (int64_t)r * S + sub * CH;
-    float z[CH + 1], sg[CH];
+    float z[CH + 1], sg[CH], w[CH];
     uint8_t tr[CH];
     int32_t sl[CH];
-#pragma unroll
-    for (int q = 0; q < CH / 4; ++q) {
-        const float4 z4 = *reinterpret_cast<const float4*>(z_vals + g0 + 4 * q);
-        const float4 s4 = *reinterpret_cast<const float4*>(sigma + g0 + 4 * q);
-        const int4 l4 = *reinterpret_cast<const int4*>(slot_of + g0 + 4 * q);
-        z[4 * q] = z4.x; z[4 * q + 1] = z4.y; z[4 * q + 2] = z4.z; z[4 * q + 3] = z4.w;
-        sg[4 * q] = s4.x; sg[4 * q + 1] = s4.y; sg[4 * q + 2] = s4.z; sg[4 * q + 3] = s4.w;
-        sl[4 * q] = l4.x; sl[4 * q + 1] = l4.y; sl[4 * q + 2] = l4.z; sl[4 * q + 3] = l4.w;
-        uchar4 t4 = make_uchar4(0, 0, 0, 0);
-        if (transparent) t4 = *reinterpret_cast<const uchar4*>(transparent + g0 + 4 * q);
-        tr[4 * q] = t4.x; tr[4 * q + 1] = t4.y; tr[4 * q + 2] = t4.z; tr[4 * q + 3] = t4.w;
-    }
-    z[CH] = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(z[0]), 0x101, 0xf, 0xf, false));
-    float alpha[CH], pre[CH];
-    float run = 1.0f;
-#pragma unroll
-    for (int j = 0; j < CH; ++j) {
-        float sv = sg[j];
-        if (tr[j]) sv = 0.f;
-        sv = sv > 0.f ? sv : 0.f;
-        sg[j] = sv;
-        const float dist = ((sub * CH + j + 1 < S) ? (z[j + 1] - z[j]) : 1e10f) * dn;
-        alpha[j] = 1.0f - expf(-sv * dist);
-        run = run * ((1.0f - alpha[j]) + 1e-10f);
-        pre[j] = run;
-    }
-    float incl = run;
-    incl = incl * dsn_row_shr(1.0f, incl, 1);
-    incl = incl * dsn_row_shr(1.0f, incl, 2);
-    incl = incl * dsn_row_shr(1.0f, incl, 4);
-    incl = incl * dsn_row_shr(1.0f, incl, 8);
-    const float before = dsn_row_shr(1.0f, incl, 1);
-    float w[CH];
-#pragma unroll
-    for (int j = 0; j < CH; ++j) w[j] = alpha[j] * (j == 0 ? before : before * pre[j - 1]);
-    if (weights && ok) {
-#pragma unroll
-        for (int q = 0; q < CH / 4; ++q)
-            *reinterpret_cast<float4*>(weights + g0 + 4 * q) = make_float4(w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]);
-    }
+    composite16_load<CH>(g0, z_vals, sigma, transparent, nullptr, slot_of, z, sg, tr, sl);
+    composite16_weights<CH>(z, sg, tr, nullptr, dn, sub, g0, ok, weights, w);
     if (depth_map) {      // (pointer uniform over the launch)
         float sdep = 0.f, sacc = 0.f;
 #pragma unroll
         for (int j = 0; j < CH; ++j) { sdep += w[j] * z[j]; sacc += w[j]; }
         sdep = dsn_row_sum_to_last(sdep); sacc = dsn_row_sum_to_last(sacc);
-        if (sub == 15 && ok) {
-            depth_map[r] = sdep;
-            acc_map[r] = sacc;
-            float q = dsn_div(sdep, sacc);          // NaN when acc == 0, like the reference
-            float m = (1e-10f > q) ? 1e-10f : q;    // torch.max propagates NaN
-            if (q != q) m = q;
-            disp_map[r] = dsn_div(1.0f, m);
-        }
+        composite16_maps(sdep, sacc, sub == 15 && ok, r, depth_map, acc_map, disp_map);
     }
     float cm = 0.f;
     for (int g = 0; g < G; ++g) {
@@ -1069,9 +1056,7 @@ __global__ void __launch_bounds__(256) k_composite16_multi(const int32_t* __rest
             float cr = 0.f, cg = 0.f, cb = 0.f;
             if (sg[j] > 0.f && sl[j] >= 0) { cr = cg_[3 * (int64_t)sl[j]]; cg = cg_[3 * (int64_t)sl[j] + 1]; cb = cg_[3 * (int64_t)sl[j] + 2]; }
             sr += w[j] * cr; sgn += w[j] * cg; sb += w[j] * cb;
-            float m = fmaxf(fabsf(cr), fmaxf(fabsf(cg), fabsf(cb)));
-            m = m == m ? m : INFINITY;
-            cm = fmaxf(cm, m);
+            cm = fmaxf(cm, dsn_colour_mag(cr, cg, cb));
         }
         sr = dsn_row_sum_to_last(sr); sgn = dsn_row_sum_to_last(sgn); sb = dsn_row_sum_to_last(sb);
         if (sub == 15 && ok) {
@@ -1079,14 +1064,7 @@ __global__ void __launch_bounds__(256) k_composite16_multi(const int32_t* __rest
             rgb[3 * r] = sr; rgb[3 * r + 1] = sgn; rgb[3 * r + 2] = sb;
         }
     }
-    if (colour_max) {
-        cm = fmaxf(cm, dsn_row_shr(0.f, cm, 1)); cm = fmaxf(cm, dsn_row_shr(0.f, cm, 2));
-        cm = fmaxf(cm, dsn_row_shr(0.f, cm, 4)); cm = fmaxf(cm, dsn_row_shr(0.f, cm, 8));
-        cm = fmaxf(cm, __shfl_xor(cm, 16));
-        cm = fmaxf(cm, __shfl_xor(cm, 32));
-        if (lane == 63 && __float_as_int(cm) > __hip_atomic_load(colour_max, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
-            atomicMax(colour_max, __float_as_int(cm));
-    }
+    if (colour_max) composite16_colour_max(cm, lane, colour_max);
 }
 
 bool dsn_composite_multi_supported(int S, const void* z_vals, const void* sigma, const void* weights, const void* slot_of,

@@ -96,7 +96,7 @@ void dsn_launch_light16(const float* packed, const DsnFrameState* fs, const floa
                         float* tr_hl1 = nullptr, float* tr_hl2 = nullptr, float* tr_pre = nullptr);
 // relighting sweep (dsn_render_rays_lights): lighting MLP of G light records per pass over the shading list -> colours [G][count][3]
 // by list slot; the list's slot of every sample (-1 elsewhere: the caller clears `slot`); the compositor of G lights through that map
-void dsn_launch_light16_multi(const float* packed, const float* lights, int G, const float* n_w, const float* ray_o, const float* ray_d,
+void dsn_launch_light16_multi(const float* packed, const DsnLightEdit* lights, int G, const float* n_w, const float* ray_o, const float* ray_d,
                               const float* z_vals, const float* essence, int64_t max_count, int S, const int32_t* list,
                               const int32_t* list_count, float* colours, hipStream_t st);
 void dsn_launch_slot_map(const int32_t* list, const int32_t* count, int64_t max_count, int32_t* slot, hipStream_t st);

@@ -478,13 +478,7 @@ __global__ void __launch_bounds__(T_THREADS) k_t_light_in(const float* __restric
     const float d[3] = {ray_d[3 * ray], ray_d[3 * ray + 1], ray_d[3 * ray + 2]};
     const float z = z_vals[n];
     float xw[3] = {ray_o[3 * ray] + d[0] * z, ray_o[3 * ray + 1] + d[1] * z, ray_o[3 * ray + 2] + d[2] * z};
-    if (fs->has_rot != 0.0f) {
-        const float ax = xw[0] - fs->rot_center[0], ay = xw[1] - fs->rot_center[1];
-        const float nx = (ax * fs->rot[0] + ay * fs->rot[2]) + fs->rot_center[0];
-        const float ny = (ax * fs->rot[1] + ay * fs->rot[3]) + fs->rot_center[1];
-        xw[0] = nx; xw[1] = ny;
-    }
-    if (fs->has_light != 0.0f) { xw[0] += fs->light_shift[0]; xw[1] += fs->light_shift[1]; xw[2] += fs->light_shift[2]; }
+    dsn_light_edit(fs->light, xw);
     const float vn = dsn_norm3(d);
     float* o = xl + 9 * n;
     o[0] = n_w[3 * n]; o[1] = n_w[3 * n + 1]; o[2] = n_w[3 * n + 2];

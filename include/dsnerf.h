@@ -436,7 +436,7 @@ DSN_EXPORT int dsn_render_rays_ex(const void* scene, int V, int F, const void* p
  *               reads that one count word, i.e. it SYNCHRONISES `stream` once.
  * Eval mode only: flags must hold DSN_SKIP_TRANSPARENT; jitter, noise, DSN_FIELD_FP32 and DSN_PHASE_* are rejected; S must be 64 or
  * 128 and workspace / out_weights / out_z 16-byte aligned.  The early-stop guard word (int32 word 59 of `workspace`) holds the largest
- * |colour| weighed under ANY of the lights.  (DSN_COMPOSITE=wave, an A/B switch of dsn_render_rays_ex, does not apply here.) */
+ * |colour| weighed under ANY of the lights. */
 #define DSN_LIGHT_RECORD_FLOATS 12
 /* bytes of light_scratch for n_lights lights in one group on a frame of n_shaded shaded samples (0: bad sizes) */
 DSN_EXPORT size_t dsn_render_lights_scratch_bytes(int R, int S, int n_lights, int64_t n_shaded);
