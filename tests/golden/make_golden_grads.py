@@ -3,6 +3,9 @@
 Run in the build container only (needs /root/reference, see oracle/ref_harness.py):
 
     PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_golden_grads.py
+    PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_golden_grads.py --samples 128       # full_train_grads_s128
+    PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_golden_grads.py --samples 200       # full_train_grads_s200
+    PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_golden_grads.py --samples 128 w4    # full_train_grads_w4_s128
 
 For each case the reference's Renderer.render runs in train mode (seed 233: jitter, then noise, from the CPU
 generator), the reference's own loss module (utils/loss.py, L2 + occupancy mask term) is applied, and
@@ -63,7 +66,7 @@ def grads_of(render, batch, seed, loss_fn, dtype):
     return fwd, out
 
 
-def case(name, canon, faces, xyz, poses, rays, sel, S, state, raw_noise_std, seed=233, config2=False):
+def case(name, canon, faces, xyz, poses, rays, sel, S, state, raw_noise_std, seed=233, config2=False, compact=False):
     """config2: BASELINE configs[2]'s own size (8192 rays x 64 samples).  float32 reference only (its float64 twin does not fit the
     build container's memory), and the fixture keeps what cannot be regenerated: the loss, the 33 norms / sums / sub-sampled
     gradients and the per-ray outputs - rays, body, draws and targets are functions of the seeds (tests/test_gpu_train.py rebuilds
@@ -106,6 +109,21 @@ def case(name, canon, faces, xyz, poses, rays, sel, S, state, raw_noise_std, see
         np.savez_compressed(path, **arrs)
         print(f"{name}: {os.path.getsize(path) / 1024:.0f} KiB; loss {arrs['loss']:.6f}")
         return
+    if compact:
+        # (the S > 64 cases: what cannot be regenerated - z_vals, the per-ray outputs, the loss terms, the norms / sums and the
+        #  float32 run's stored gradients.  Of the float64 run's gradients only what the tests use is kept: per tensor, the relative
+        #  L2 distance of the float32 run's stored elements from it ("spread:").  Body, rays, targets and draws are functions of the
+        #  seeds: tests/test_gpu_train.py rebuilds them and checks the draws against the sums kept here)
+        for k in [k for k in arrs if k.startswith("grad:") and not k.endswith("_f64")]:
+            a, b = arrs[k].astype(np.float64), arrs[k + "_f64"].astype(np.float64)
+            arrs["spread:" + k[5:]] = np.float64(np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-30))
+        arrs["jitter_sum"] = np.float64(arrs["jitter"].astype(np.float64).sum())
+        arrs["noise_sum"] = np.float64(arrs["noise"].astype(np.float64).sum())
+        keep = ("S", "frame", "Th", "raw_noise_std", "seed", "jitter_sum", "noise_sum", "render:z_vals", "render:color",
+                "render:acc_map", "render:depth_map")
+        arrs = {k: v for k, v in arrs.items() if k in keep or k.startswith(("loss", "norm:", "sum:", "spread:"))
+                or (k.startswith("grad:") and not k.endswith("_f64"))}
+        arrs["rays"] = np.int64(R)
     np.savez_compressed(path, **arrs)
     print(f"{name}: {os.path.getsize(path) / 1024:.0f} KiB; loss {arrs['loss']:.6f} (f64 {arrs['loss_f64']:.6f})")
     for k in ("nerf.stage1.0.weight", "nerf.stage2.4.weight", "lighting_mlp.lights_encoding.0.weight", "pose_mlp.0.weight",
@@ -153,6 +171,25 @@ def main():
         xyz = synth.pose_body(canon)
         rays = synth.make_rays(32, 32, xyz, fit_box=True)
         case("full_train_grads_" + tag, canon, faces, xyz, poses, rays, np.arange(0, 1024, 8), 64, state, raw_noise_std=1.0)
+        return
+    if "--samples" in sys.argv:                  # the full case at another S: `--samples 128` or `--samples 200 [w4]` (see below)
+        rest = [a for a in sys.argv[sys.argv.index("--samples") + 1:] if not a.startswith("-")]
+        S = int(rest[0])
+        tag = rest[1] if len(rest) > 1 else "default"
+        if tag == "default":
+            state = synth.make_state_dict()
+        else:
+            z = np.load(os.path.join(HERE, f"weights_{tag}.npz"))
+            state = {k[2:]: z[k] for k in z.files if k.startswith("w:")}
+        poses = synth.make_poses()
+        canon, faces = synth.make_body()
+        xyz = synth.pose_body(canon)
+        rays = synth.make_rays(32, 32, xyz, fit_box=True)
+        # the same 128 rays as full_train_grads at every S: S = 128 is the training adjoint's two-chunk wave form
+        # (65 <= S <= 128), S = 200 its one-thread-per-ray form (S > 128); both runs, float32 and float64, fit the container.
+        # Stored compact (see case()): about 0.3 - 0.4 MB each
+        case("full_train_grads" + ("" if tag == "default" else "_" + tag) + f"_s{S}", canon, faces, xyz, poses, rays,
+             np.arange(0, 1024, 8), S, state, raw_noise_std=1.0, compact=True)
         return
     state = synth.make_state_dict()
     poses = synth.make_poses()

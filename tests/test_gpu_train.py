@@ -9,14 +9,18 @@ import pytest
 import torch
 
 import train_oracle as TO
-from helpers import load, maxdiff, state
+from helpers import load, maxdiff, ref_tol, state
 from test_gpu_render import make_batch, make_renderer
 
 pytestmark = pytest.mark.gpu
 
 GRAD_CASES = ["small_train_grads", "small_train_grads_nonoise", "full_train_grads", "small_train_grads_w2", "full_train_grads_w2",
               "small_train_grads_w4", "full_train_grads_w4",
-              "full_train_grads_nu"]        # the SMPL-like body (dense caps at head / hands / feet): make_golden_grads.py --nonuniform
+              "full_train_grads_nu",        # the SMPL-like body (dense caps at head / hands / feet): make_golden_grads.py --nonuniform
+              # full_train_grads at S = 128 / 200 (make_golden_grads.py --samples): the compositing adjoint's two-chunk wave form
+              # k_t_composite_adjoint_w<2> (65 <= S <= 128) and its one-thread-per-ray form k_t_composite_adjoint (S > 128)
+              "full_train_grads_s128", "full_train_grads_s200", "full_train_grads_w4_s128"]
+S_CASES = ["full_train_grads_s128", "full_train_grads_s200", "full_train_grads_w4_s128"]
 from cases import FULL_LIMIT, SAMPLE, reference_loss, rel, sample_index  # noqa: E402,F401
 
 
@@ -44,10 +48,35 @@ def bar(recorded):
     return max(HEADROOM * float(recorded), FLOOR)
 
 
+def load_case(name):
+    """a gradient fixture as a dict.  The compact S > 64 cases (make_golden_grads.py --samples) keep only what cannot be regenerated:
+    their body, 128 rays of the 32 x 32 view, targets and draws are rebuilt here from the seeds as the generator made them, and the
+    draws are checked against the sums it kept"""
+    g = dict(load(name).items())
+    if "ray_o" in g:
+        return g
+    from dsnerf_amd import synth
+    R, S, seed = int(g["rays"]), int(g["S"]), int(g["seed"])
+    canon, faces = synth.make_body()
+    xyz = synth.pose_body(canon)
+    rays = synth.make_rays(32, 32, xyz, fit_box=True)
+    sel = np.arange(0, 1024, 8)[:R]
+    g.update(canonical_vertex=canon, faces=faces.astype(np.int32), xyz=xyz, poses=synth.make_poses(),
+             ray_o=rays["ray_o"][sel], ray_d=rays["ray_d"][sel], near=rays["near"][sel], far=rays["far"][sel],
+             target_rgb=synth.hash_uniform(R * 3, 91).reshape(R, 3).astype(np.float32),
+             occupancy=(synth.hash_uniform(R, 92) > 0.5).astype(np.float32))
+    torch.manual_seed(seed)                     # (the reference's draws: jitter, then noise, from the CPU generator)
+    g["jitter"] = torch.rand(1, R, S).numpy()[0]
+    g["noise"] = (torch.randn(R, S) * float(g["raw_noise_std"])).numpy()
+    assert float(g["jitter"].astype(np.float64).sum()) == float(g["jitter_sum"])
+    assert float(g["noise"].astype(np.float64).sum()) == float(g["noise_sum"])
+    return g
+
+
 def reference_case_errors(name):
     """one training forward + backward of a golden gradient case -> (loss, reference loss, {tensor: rel. L2 vs the reference's float32
     autograd on the stored elements}, {tensor: |norm - reference norm| / reference norm}, {tensor: the reference's own f32-vs-f64 spread})"""
-    g = load(name)
+    g = load_case(name)
     r = make_renderer(g, name)
     r.cfg.MODEL.raw_noise_std = float(g["raw_noise_std"])
     r.train()
@@ -62,12 +91,35 @@ def reference_case_errors(name):
         assert p.grad is not None, k
         full = p.grad.detach().cpu().numpy().reshape(-1)
         a = full if full.size <= FULL_LIMIT else full[sample_index(full.size)]
-        b32, b64 = g["grad:" + k], g["grad:" + k + "_f64"]
+        b32 = g["grad:" + k]
         err[k] = rel(a, b32)
-        spread[k] = rel(b32, b64)
+        spread[k] = rel(b32, g["grad:" + k + "_f64"]) if "grad:" + k + "_f64" in g else float(g["spread:" + k])
         nerr[k] = abs(float(np.linalg.norm(full.astype(np.float64))) - float(g["norm:" + k])) / max(float(g["norm:" + k]), 1e-30)
     assert r.range_overflow_count() == 0
     return float(loss), float(g["loss"]), err, nerr, spread
+
+
+def reference_forward_errors(name):
+    """the training forward of a golden gradient case (noise on) -> {colour / acc / depth: max |this - the reference's float32|}"""
+    g = load_case(name)
+    r = make_renderer(g, name)
+    r.cfg.MODEL.raw_noise_std = float(g["raw_noise_std"])
+    r.train()
+    torch.manual_seed(int(g["seed"]))
+    out = r.render(make_batch(g))["coarse"]
+    assert np.array_equal(out["z_vals"].cpu().numpy(), g["render:z_vals"])
+    return {k: maxdiff(out[k].detach().cpu().numpy(), g["render:" + k]) for k in ("color", "acc_map", "depth_map")}
+
+
+@pytest.mark.parametrize("name", S_CASES)
+def test_forward_matches_reference_beyond_64_samples(name):
+    """the per-ray outputs of the training forward at S = 128 (the 16-lane compositor k_composite16<false, 8>, noise added) and
+    S = 200 (the wave-per-ray k_composite) against the reference's float32 forward, at the suite's bar"""
+    g = load_case(name)
+    err = reference_forward_errors(name)
+    for k, e in err.items():
+        assert e < ref_tol(g, "render:" + k, 1e-4), (k, e, err)
+    print({k: "%.1e" % v for k, v in err.items()})
 
 
 @pytest.mark.parametrize("name", GRAD_CASES)
@@ -86,14 +138,19 @@ def test_backward_matches_reference_autograd(name):
 
 ORACLE_CASES = [("small_train_grads", None, None), ("full_train_grads", None, None), ("full_train_grads", 37, None),
                 ("full_train_grads", 37, 21), ("small_train_grads_w2", None, None), ("full_train_grads_w2", None, None),
-                ("small_train_grads_w4", None, None), ("full_train_grads_w4", None, None), ("full_train_grads_nu", None, None)]
+                ("small_train_grads_w4", None, None), ("full_train_grads_w4", None, None), ("full_train_grads_nu", None, None),
+                # either side of the compositing adjoint's variant boundaries, sliced off the S = 200 case: 65 (two chunks, 63 idle
+                # lanes in the second), 100, 128 (two full chunks), 129 (the first one-thread-per-ray S), 200; ragged ray counts
+                ("full_train_grads_s200", None, 65), ("full_train_grads_s200", None, 100), ("full_train_grads_s200", None, 128),
+                ("full_train_grads_s200", None, 129), ("full_train_grads_s200", None, None), ("full_train_grads_s200", 37, 100),
+                ("full_train_grads_s200", 37, 129)]
 
 
 def oracle_case_errors(name, nrays, nsamp):
     """dsn_render_rays_grad with cotangents on every output (colour, disp, acc, depth, weights) against autograd of the CPU oracle on
     the same inputs, full tensors -> {tensor: rel. L2}"""
     from dsnerf_amd import _lib
-    g = dict(load(name).items())
+    g = load_case(name)
     if nrays is not None:                      # a ray count that is no multiple of the 32-point wave tiles / 128-point blocks
         for k in ("ray_o", "ray_d", "near", "far", "render:z_vals", "noise", "jitter"):
             g[k] = g[k][:nrays]
