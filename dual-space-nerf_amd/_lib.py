@@ -42,7 +42,7 @@ EXPORTS = [
     "dsn_early_stop_eps_scaled", "dsn_set_early_stop_colour_scale", "dsn_nn_header_offsets", "dsn_render_workspace_bytes_for",
     "dsn_render_workspace_record_capacity", "dsn_stop_slice_len", "dsn_stop_stats_slice_len", "dsn_early_stop_colour_headroom", "dsn_render_rays_ex",
     "dsn_render_rays_grad_ex", "dsn_render_rays_train_ex", "dsn_aux_create", "dsn_aux_destroy",
-    "dsn_render_lights_scratch_bytes", "dsn_render_rays_lights",
+    "dsn_render_lights_scratch_bytes", "dsn_render_rays_lights", "dsn_image_ssim_workspace_bytes", "dsn_image_ssim",
 ]
 
 SKIP_TRANSPARENT = 1
@@ -64,6 +64,7 @@ SCREEN_MARGIN_FLOOR, SCREEN_MARGIN_CAP = 0.002, 0.15      # = F16_SCREEN_FLOOR /
 SCREEN_HEADROOM = 10.0        # = F16_SCREEN_HEADROOM: every calibration point is this factor in deviation away from a wrong drop
 SCREEN_MIN_DROPPED = 0.35     # PackedParams.calibrate_screen: below this share of dropped calibration points the screen stays off
 RAYS_ZJU, RAYS_H36M = 0, 1
+SSIM_OK, SSIM_CROP_TOO_SMALL, SSIM_EMPTY_MASK = 0, 1, 2     # dsn_image_ssim's out_status (DSN_SSIM_*)
 FRAME_FINE_ONLY = 1           # dsn_set_frame_ex: only the fine nearest-face level of the posed mesh (points beyond it: exhaustive sweep)
 FRAME_LAZY_LISTS = 2          # dsn_set_frame_ex: grid geometry only - the frame that uses the level builds the lists of the cells it visits
 LAZY_LISTS = 4096             # dsn_render_rays_ex: ... which is this flag (Scene.lazy says whether the scene's frame was set that way)
@@ -90,7 +91,7 @@ def lib():
         L.dsn_render_workspace_bytes_for.argtypes = [C.c_int, C.c_int, C.c_float]
         for n in ("dsn_packed_param_bytes", "dsn_scene_bytes", "dsn_render_workspace_bytes", "dsn_render_workspace_bytes_for", "dsn_field_record_bytes",
                   "dsn_grad_workspace_bytes", "dsn_image_workspace_bytes", "dsn_pose_state_bytes",
-                  "dsn_calibrate_workspace_bytes"):
+                  "dsn_calibrate_workspace_bytes", "dsn_image_ssim_workspace_bytes"):
             getattr(L, n).restype = C.c_size_t
         L.dsn_render_lights_scratch_bytes.restype = C.c_size_t
         L.dsn_render_lights_scratch_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int64]
@@ -1125,6 +1126,39 @@ def image_psnr(img_rgb, gt, mask_at_box=None):
     _check(lib().dsn_image_psnr(_ptr(img_rgb.contiguous(), torch.float32), _ptr(g64), _ptr(g32), _ptr(mask), H, W, _ptr(out),
                                 _ptr(ws), _stream()), "dsn_image_psnr")
     return out
+
+
+def image_ssim(img, gt, mask_at_box, clamp=False):
+    """metrics.py:23-38 ssim_metric on the device (dsn_image_ssim): img [H,W,3] or [F,H,W,3] float32, gt of the same shape
+    (float64 as the reference's batch["img"], or float32), mask_at_box [H,W] / [F,H,W] (or flattened pixels).  clamp=True
+    clamps img to [0,1] first (test.py:62-63).  Returns device tensors (ssim float64 [F], rect int32 [F,4] = {x, y, w, h},
+    status int32 [F]); no synchronisation.  A frame whose status is not SSIM_OK has no SSIM (NaN): skimage raises
+    ValueError there - ssim_status_error() says why."""
+    dev = img.device
+    if img.dim() not in (3, 4) or img.shape[-1] != 3:
+        raise ValueError(f"image_ssim: img must be [H,W,3] or [F,H,W,3], got {tuple(img.shape)}")
+    img = img.reshape(-1, *img.shape[-3:])
+    F, H, W, _ = img.shape
+    gt = gt.to(dev).reshape(F, H, W, 3).contiguous()
+    if gt.dtype not in (torch.float64, torch.float32):
+        raise TypeError(f"image_ssim: gt must be float64 or float32, got {gt.dtype}")
+    mask = mask_at_box.to(device=dev).reshape(F, H, W)
+    mask = (mask != 0).to(torch.uint8).contiguous() if mask.dtype != torch.uint8 else mask.contiguous()
+    ws = _scratch(lib().dsn_image_ssim_workspace_bytes(F, H, W), dev)
+    ssim = torch.empty(F, dtype=torch.float64, device=dev)
+    rect = torch.empty(F, 4, dtype=torch.int32, device=dev)
+    status = torch.empty(F, dtype=torch.int32, device=dev)
+    g64, g32 = (gt, None) if gt.dtype == torch.float64 else (None, gt)
+    _check(lib().dsn_image_ssim(_ptr(img.contiguous(), torch.float32), _ptr(g64), _ptr(g32), _ptr(mask), F, H, W, int(bool(clamp)),
+                                _ptr(ssim), _ptr(rect), _ptr(status), _ptr(ws), _stream()), "dsn_image_ssim")
+    return ssim, rect, status
+
+
+def ssim_status_error(status, rect):
+    """The ValueError skimage's compare_ssim raises for a crop without a whole 7 x 7 window (host values of one frame)."""
+    x, y, w, h = (int(v) for v in rect)
+    what = "the mask is empty" if int(status) == SSIM_EMPTY_MASK else f"the mask's bounding rectangle is {w} x {h}"
+    return ValueError(f"ssim: win_size exceeds image extent ({what}; SSIM needs at least 7 x 7)")
 
 
 def camera_rays(K, R, T, bounds, H, W, device=None, convention="zju"):

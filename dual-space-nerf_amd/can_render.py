@@ -986,16 +986,70 @@ class Renderer:
                 results[k] = checked
         return results
 
-    def image_metrics(self, color_img, batch, clamp=True):
+    def image_metrics(self, color_img, batch, clamp=True, ssim=False):
         """test.py:62-71 on the device: clamp to [0,1], psnr with and without mask_at_box against batch["img"].
-        Returns a dict of python floats (one 32-byte device->host copy)."""
+        ssim=True adds "ssim": test.py:73-75's metrics.py ssim_metric of the same clamped image (dsn_image_ssim); it raises
+        ValueError where skimage's compare_ssim would (a mask whose bounding rectangle is narrower or lower than 7 pixels).
+        Returns a dict of python floats (one device->host copy)."""
         img = color_img.to(self.device)
         if clamp:
             img = torch.clamp(img, min=0.0, max=1.0)
+        gt = self._metrics_gt(batch)
+        mask = self._dev(batch["mask_at_box"][0], torch.uint8)
+        m = _lib.image_psnr(img, gt, mask)
+        if ssim:
+            s, rect, status = _lib.image_ssim(img, gt, mask.reshape(img.shape[:2]))
+            m = torch.cat([m, s, status.double(), rect.reshape(-1).double()])
+        return self._metrics_dicts(m[None].cpu())[0]
+
+    def image_metrics_views(self, images, batches, clamp=True, ssim=True):
+        """image_metrics over a sequence: `images` are the [H,W,3] colour images of `batches` (e.g. the "coarse_color" tensors of
+        render_views(batches, device_output=True)).  Frames of one size go through dsn_image_ssim together; psnr is
+        dsn_image_psnr per frame; the whole sequence's numbers come back in ONE device->host copy.  Returns one dict per frame
+        with image_metrics' keys; raises ValueError (naming the frame) where image_metrics would."""
+        images, batches = list(images), list(batches)
+        if len(images) != len(batches):
+            raise ValueError(f"image_metrics_views: {len(images)} images for {len(batches)} batches")
+        if not images:
+            return []
+        imgs, gts, masks = [], [], []
+        for img, batch in zip(images, batches):
+            img = img.to(self.device)
+            imgs.append(torch.clamp(img, min=0.0, max=1.0) if clamp else img)
+            gts.append(self._metrics_gt(batch))
+            masks.append(self._dev(batch["mask_at_box"][0], torch.uint8).reshape(img.shape[:2]))
+        rows = [None] * len(imgs)
+        groups = {}
+        for k, (img, gt) in enumerate(zip(imgs, gts)):
+            groups.setdefault((tuple(img.shape), gt.dtype), []).append(k)
+        for ks in groups.values():
+            img = torch.stack([imgs[k] for k in ks]).contiguous()
+            gt = torch.stack([gts[k] for k in ks]).contiguous()
+            mask = torch.stack([masks[k] for k in ks]).contiguous()
+            if ssim:
+                s, rect, status = _lib.image_ssim(img, gt, mask)
+            for j, k in enumerate(ks):
+                m = _lib.image_psnr(img[j], gt[j], mask[j])
+                rows[k] = torch.cat([m, s[j:j + 1], status[j:j + 1].double(), rect[j].double()]) if ssim else m
+        return self._metrics_dicts(torch.stack(rows).cpu(), views=True)
+
+    def _metrics_gt(self, batch):
         gt = batch["img"][0]
-        gt = self._dev(gt, gt.dtype if gt.dtype in (torch.float32, torch.float64) else torch.float32)   # staged upload (6 MB of float64)
-        m = _lib.image_psnr(img, gt, self._dev(batch["mask_at_box"][0], torch.uint8)).cpu()
-        return {"mse": float(m[0]), "mse_wMask": float(m[1]), "psnr_woMask": float(m[2]), "psnr_wMask": float(m[3])}
+        return self._dev(gt, gt.dtype if gt.dtype in (torch.float32, torch.float64) else torch.float32)   # staged upload (6 MB of float64)
+
+    @staticmethod
+    def _metrics_dicts(rows, views=False):
+        """host rows {mse_all, mse_masked, psnr_all, psnr_masked[, ssim, status, x, y, w, h]} -> image_metrics' dicts"""
+        out = []
+        for k, r in enumerate(rows.tolist()):
+            d = {"mse": r[0], "mse_wMask": r[1], "psnr_woMask": r[2], "psnr_wMask": r[3]}
+            if len(r) > 4:
+                if int(r[5]) != _lib.SSIM_OK:
+                    e = _lib.ssim_status_error(int(r[5]), r[6:10])
+                    raise ValueError(f"frame {k}: {e}") if views else e
+                d["ssim"] = r[4]
+            out.append(d)
+        return out
 
     # ---- density query for marching cubes (reference :280-296) ----
     def query_volume(self, pts, code_idx, transparent_mask=None, batch_info={}):

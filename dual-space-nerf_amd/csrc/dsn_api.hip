@@ -308,6 +308,22 @@ int dsn_image_psnr(const float* img_rgb, const double* gt_f64, const float* gt_f
     return dsn_check_launch("dsn_image_psnr");
 }
 
+static bool dsn_ssim_sizes_ok(int F, int H, int W) {
+    return F > 0 && H > 0 && W > 0 && F <= 65535 && H <= 65535 && W <= 65535 && (int64_t)H * W < ((int64_t)1 << 31);
+}
+
+size_t dsn_image_ssim_workspace_bytes(int F, int H, int W) { return dsn_ssim_sizes_ok(F, H, W) ? dsn_image_ssim_workspace_size(F, H, W) : 0; }
+
+int dsn_image_ssim(const float* img_rgb, const double* gt_f64, const float* gt_f32, const uint8_t* mask_at_box, int F, int H, int W,
+                   int clamp_rgb, double* out_ssim, int32_t* out_rect, int32_t* out_status, void* workspace, void* stream) {
+    DSN_REQUIRE(img_rgb && mask_at_box && out_ssim && out_rect && out_status && workspace, "dsn_image_ssim: null argument");
+    DSN_REQUIRE((gt_f64 != nullptr) != (gt_f32 != nullptr), "dsn_image_ssim: exactly one ground-truth pointer");
+    DSN_REQUIRE(dsn_ssim_sizes_ok(F, H, W), "dsn_image_ssim: bad sizes");
+    dsn_launch_image_ssim(img_rgb, gt_f64, gt_f32, mask_at_box, F, H, W, clamp_rgb, out_ssim, out_rect, out_status, workspace,
+                          (hipStream_t)stream);
+    return dsn_check_launch("dsn_image_ssim");
+}
+
 int dsn_field_screen(const void* scene, int V, int F, const void* packed, const float* x_c, int64_t N, const int32_t* active_list,
                      const int32_t* active_count, float* sigma, int32_t* keep_list, int32_t* keep_count, void* stream) {
     DSN_REQUIRE(scene && packed && x_c && sigma && keep_list && keep_count, "dsn_field_screen: null argument");

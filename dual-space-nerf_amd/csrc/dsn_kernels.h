@@ -157,13 +157,16 @@ const char* dsn_train_run(const DsnSceneView& s, const float* packed, const floa
                           const float* ext_x_c = nullptr, const float* ext_d_col = nullptr, const float* ext_d_sig = nullptr,
                           const DsnTrainAux* aux = nullptr);
 
-// dsn_image.hip: image epilogue on the device (post_process scatter, clamp, mse / psnr)
+// dsn_image.hip: image epilogue on the device (post_process scatter, clamp, mse / psnr, ssim)
 size_t dsn_image_workspace_size(int H, int W);
 void dsn_launch_image_scatter(const float* rgb, const float* disp, const float* acc, const float* depth, int R,
                               const uint8_t* mask, int H, int W, int clamp_rgb, float* img_rgb, float* img_disp,
                               float* img_acc, float* img_depth, void* workspace, hipStream_t st);
 void dsn_launch_image_psnr(const float* img_rgb, const double* gt64, const float* gt32, const uint8_t* mask, int H, int W,
                            double* out4, void* workspace, hipStream_t st);
+size_t dsn_image_ssim_workspace_size(int F, int H, int W);
+void dsn_launch_image_ssim(const float* img_rgb, const double* gt64, const float* gt32, const uint8_t* mask, int F, int H, int W,
+                           int clamp_rgb, double* out_ssim, int32_t* out_rect, int32_t* out_status, void* workspace, hipStream_t st);
 // front-to-back slices with exact ray termination (dsn_geom.hip; DSN_EARLY_STOP in dsn_render_rays)
 #define DSN_STOP_MAX_SLICES 32
 // bounds[0 .. K]: slice k = samples [bounds[k], bounds[k + 1]) of every ray; its list starts at lists + R * bounds[k]

@@ -192,6 +192,22 @@ DSN_EXPORT int dsn_image_scatter(const float* rgb, const float* disp, const floa
  * (test.py:70-71).  out4 (device, float64) = {mse_all, mse_masked, psnr_all, psnr_masked}; mask may be NULL. */
 DSN_EXPORT int dsn_image_psnr(const float* img_rgb, const double* gt_f64, const float* gt_f32, const uint8_t* mask_at_box,
                    int H, int W, double* out4, void* workspace, void* stream);
+/* DSN image SSIM: metrics.py:23-38 ssim_metric (test.py:73-75), i.e. scikit-image 0.15 compare_ssim(multichannel=True) of
+ * the float64 images that are zero outside mask_at_box, cropped to cv2.boundingRect(mask_at_box): per channel a 7 x 7 uniform
+ * window, data range 2 (float64's dtype range), sample covariance (49/48), the mean of S over the crop without its 3-pixel
+ * border; the mean over the three channels.  F frames of one size: img_rgb [F,H,W,3] float32 (clamp_rgb != 0 clamps it to
+ * [0,1] first, as test.py:62-63), ground truth [F,H,W,3] (exactly one of gt_f64 / gt_f32 non-NULL), mask_at_box [F,H,W].
+ * Out (device): out_ssim [F] float64, out_rect [F,4] int32 = {x, y, w, h} of the crop, out_status [F] int32 = DSN_SSIM_*.
+ * A crop side below 7 has no SSIM (skimage raises "win_size exceeds image extent"): status != DSN_SSIM_OK and out_ssim = NaN.
+ * A frame's result is the same bits on every call and in any batch.  workspace: dsn_image_ssim_workspace_bytes(F,H,W), any
+ * contents. */
+#define DSN_SSIM_OK 0
+#define DSN_SSIM_CROP_TOO_SMALL 1   /* the bounding rectangle is narrower or lower than 7 pixels */
+#define DSN_SSIM_EMPTY_MASK 2       /* no mask pixel set (cv2.boundingRect: 0 x 0) */
+DSN_EXPORT size_t dsn_image_ssim_workspace_bytes(int F, int H, int W);
+DSN_EXPORT int dsn_image_ssim(const float* img_rgb, const double* gt_f64, const float* gt_f32, const uint8_t* mask_at_box,
+                   int F, int H, int W, int clamp_rgb, double* out_ssim, int32_t* out_rect, int32_t* out_status,
+                   void* workspace, void* stream);
 
 /* The density screen as a stage (what dsn_render_rays runs first in eval mode): for the listed points (or all N) the
  * plain-fp16 trunk; points whose fp16 density is negative by the safety margin (calibrated for the parameters: dsn_calibrate_screen) get that negative value in sigma [N] and are dropped, the
