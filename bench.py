@@ -8,9 +8,12 @@ torch.distributed.run, one rank per GPU) the SAME frame is partitioned over the 
 ray blocks), every rank renders its share, and the rendered pixels are exchanged with one RCCL all-gather
 + one index_select into ray order inside the timed region: strong scaling, value = rays of the frame x
 frames / max time (benchlib/strong.py).  --weak gives the weak line instead (every rank renders one whole
-frame of a multi-frame batch, configs[4]); the strong line carries it as a secondary object.
+frame of a multi-frame batch, configs[4]); with --full the strong line carries it as a secondary object.
 
-Prints ONE JSON line on rank 0.  Extra objects:
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the --steps steps, writes --dump-outputs and prints that line;
+everything else it can measure runs only with --full (--no-roofline / --no-cpu-baseline / --no-extras leave parts of it out).  Extra
+objects of a --full N = 1 line (the frame alone, every committed parameter set, host paths, training and the eager-GPU baseline are
+--no-extras' part of it):
   roofline     - k_field16<forward> (the dominant kernel), timed live with HIP events on the launch stream in a
                  separate stage-by-stage pass over the same frame; algorithmic FLOPs = evaluated samples
                  x 0.91776 MFLOP (2 x 458 880 MAC: trunk + heads); the reverse kernel (analytic d sigma/dx,
@@ -53,9 +56,13 @@ def parse():
     ap.add_argument("--hw", type=int, default=512, help="image side (BASELINE configs[1]: 512)")
     ap.add_argument("--samples", type=int, default=64)
     ap.add_argument("--dense", action="store_true", help="evaluate the networks on every sample (no transparent skip)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-rays", type=int, default=0, help="rays the CPU oracle is timed on (0 = sized for ~15 s)")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every secondary measurement of the mode: with N = 1 the frame alone, the other "
+                         "parameter sets, the roofline pass, the CPU and eager-GPU baselines, the host-to-host paths and the training step; "
+                         "with N > 1 the weak line beside the strong one.  Without it a run does only what its headline figure needs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: leave out the CPU and eager-GPU baselines")
+    ap.add_argument("--cpu-rays", type=int, default=0, help="--full: rays the CPU oracle is timed on (0 = sized for ~15 s)")
+    ap.add_argument("--no-roofline", action="store_true", help="--full: leave out the roofline pass")
     ap.add_argument("--fp32", action="store_true", help="exact-fp32 MFMA field kernel instead of split-fp16")
     ap.add_argument("--screen", action="store_true",
                     help="opt into the plain-fp16 density screen (Renderer.density_screen = True; off by default since round 4: its margin is "
@@ -98,7 +105,7 @@ def parse():
                          "with N > 1 runs unless --weak is given (north_star: rays partitioned across the GPUs, all-gather of pixels)")
     ap.add_argument("--weak", action="store_true",
                     help="N > 1: the weak-scaling line instead (every rank renders one whole frame of a multi-frame batch, BASELINE "
-                         "configs[4]; one all-gather of [R,6] pixels per frame).  The strong line reports it as a secondary object anyway")
+                         "configs[4]; one all-gather of [R,6] pixels per frame).  With --full the strong line reports it as a secondary object anyway")
     ap.add_argument("--big-frame", action="store_true", help="--strong: BASELINE configs[3], ONE 1024 x 1024 x 128 frame")
     ap.add_argument("--partition", default="blocks", choices=["blocks", "tiles"],
                     help="--strong: blocks = contiguous ray blocks cut for equal cost (per-ray cost from a probe frame: evaluated + shaded "
@@ -115,8 +122,8 @@ def parse():
                          "configs[4]) - the frames then differ by up to 13 %% in non-transparent samples and every step waits for the slowest "
                          "(profiles/r04_weak_emulated8.json: max / mean 1.06), a property of the data, not of the scaling")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the secondary measurements of the default N = 1 line (screen off, exact fp32, host-to-host "
-                         "render_view, eager-torch GPU baseline, torch CPU baseline)")
+                    help="--full: skip the secondary measurements of the N = 1 line (the frame alone excepted: other parameter sets, "
+                         "one pass, exact fp32, host-to-host render_view, training step, eager-torch GPU baseline) and the weak line of N > 1")
     ap.add_argument("--eager-baseline", action="store_true",
                     help="secondary mode: time the eager-PyTorch restatement of the path (oracle/train_oracle.py) on this GPU "
                          "the way the reference runs it (3072-ray chunks; 8192-ray training step), nearest-face searches "

@@ -15,9 +15,6 @@ from .common import (LAZY_LISTS, FLOP_ALL_PER_SAMPLE, FLOP_FIELD_FWD_PER_SAMPLE,
 
 def frame_bench(args, dsnerf_amd, _lib, synth, rk):
     import torch.distributed as dist
-    from .baselines import cpu_baseline, cpu_baseline_torch, eager_baseline, host_to_host, host_to_host_pipelined
-    from .roofline import roofline
-    from .train import TRAIN_DTYPE, train_measure, train_roofline
     world, rank, dev, use_dist = rk.world, rk.rank, rk.dev, rk.on
     H = W = args.hw
     S = args.samples
@@ -198,17 +195,19 @@ def frame_bench(args, dsnerf_amd, _lib, synth, rk):
     if args.dump_outputs and rank == 0:
         # (the last timed step's frame, before the frames below reuse its slot's output buffers)
         dumped = dump_outputs(args.dump_outputs, outs[(k_step - 1) % depth])
-    # latency of one frame alone (no overlap with a neighbour), for the record
-    k_step = 0
-    share_cus[0] = False
-    torch.cuda.synchronize()
-    t1 = time.perf_counter()
-    for _ in range(3):
-        step()
-        if pipe is not None:
-            pipe.flush()
+    ms_serial = None
+    if args.full:
+        # latency of one frame alone (no overlap with a neighbour), for the record
+        k_step = 0
+        share_cus[0] = False
         torch.cuda.synchronize()
-    ms_serial = 1e3 * (time.perf_counter() - t1) / 3
+        t1 = time.perf_counter()
+        for _ in range(3):
+            step()
+            if pipe is not None:
+                pipe.flush()
+            torch.cuda.synchronize()
+        ms_serial = 1e3 * (time.perf_counter() - t1) / 3
     dt, per_rank_s = rk.times(dt)          # max over ranks + every rank's own time
 
     n_active = int(ws.buf[:4].view(torch.int32)[0]) if not args.dense else R * S
@@ -259,7 +258,7 @@ def frame_bench(args, dsnerf_amd, _lib, synth, rk):
             "accurate_pass_sample_fraction": None if n_kept is None else n_kept / float(R * S),
             "early_stop": stop_info,
             "ms_per_frame": ms_step,
-            "frames_in_flight": depth, "overlap": ("none" if depth == 1 else args.overlap), "ms_per_frame_alone": ms_serial,
+            "frames_in_flight": depth, "overlap": ("none" if depth == 1 else args.overlap),
             "persistent_kernels_share_cus": bool(depth > 1 and os.environ.get("DSN_BENCH_SHARE_CUS", "1") != "0"),
             "setup_frames_per_slot": 1,      # (untimed, before the W warm-up steps: a slot's first frame carries its one-off costs)
             # every ray is fully rendered, so the dense-equivalent rate is `value`; this is the dense
@@ -279,9 +278,18 @@ def frame_bench(args, dsnerf_amd, _lib, synth, rk):
                         "forward_samples": n_fwd, "reverse_samples": n_rev, "shaded_samples": n_lit},
     }
 
+    if ms_serial is not None:
+        result["config"]["ms_per_frame_alone"] = ms_serial
     if dumped is not None:
         result["dumped_outputs"] = {"dir": os.path.abspath(args.dump_outputs), "shapes": dumped}
-    if rank == 0 and world == 1 and not args.no_extras and not (args.dense or args.fp32):
+    # --full: everything below measures something besides the headline figure (other parameter sets, the roofline pass, baselines, host
+    # paths, training) in runs of its own; a plain run ends here
+    full = args.full and rank == 0 and world == 1
+    if full:
+        from .baselines import cpu_baseline, cpu_baseline_torch, eager_baseline, host_to_host, host_to_host_pipelined
+        from .roofline import roofline
+        from .train import TRAIN_DTYPE, train_measure, train_roofline
+    if full and not args.no_extras and not (args.dense or args.fp32):
         # The frame time is a property of the CHECKPOINT as much as of the kernels: the same frame, same pipeline,
         # 5 timed frames each, for every parameter set the repo pins with reference-generated goldens.  w4 is the converged one.
         headline = cur
@@ -347,10 +355,10 @@ def frame_bench(args, dsnerf_amd, _lib, synth, rk):
                                                "trainer steps (solid, unsaturated), w3 = hash init x3.5 (dense guess), w4 = converged with "
                                                "scripts/train_w4.py: the headline.  with_density_screen: the same frames with the opt-in "
                                                "plain-fp16 screen (statistically safe: calibrated margin + audit), where its calibration lets it run")
-    if rank == 0 and world == 1 and not args.no_roofline:
+    if full and not args.no_roofline:
         scene.set_frame(packed, d_xyz, d_poses, 5, False, None, None, None)      # (the frame state of THESE parameters: by_weights has used the scene)
         result["roofline"] = roofline(_lib, scene, packed, ray_o, ray_d, near0, far0, S, t_vals, args, early=early, schedule=headline_schedule)
-    if rank == 0 and world == 1 and "roofline" in result:
+    if "roofline" in result:
         # kernel AND frame in the one block the driver parses: the dominant kernel's fraction is `frac`; the whole
         # frame's - field FLOPs executed per frame over the frame time - and the matrix pipe's busy share from the committed counters
         from .common import measured_mfma_busy
@@ -360,12 +368,12 @@ def frame_bench(args, dsnerf_amd, _lib, synth, rk):
         result["roofline"]["mfma_busy_source"] = None if busy is None else (
             f"{busy_src}: SQ_VALU_MFMA_BUSY_CYCLES / (GRBM_GUI_ACTIVE per XCD x 1024 SIMDs), committed rocprofv3 --pmc passes of this "
             f"command; not collected in this run")
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if full and not args.no_cpu_baseline:
         # north_star names "the reference's CPU PyTorch path": the torch restatement is the closer stand-in and therefore THE
         # cpu_baseline of the line; the OpenMP C port of the same algorithm - the faster CPU implementation - beside it
         result["cpu_baseline"] = cpu_baseline_torch(synth, canon, faces, xyz, poses, sd, rays, S, args)
         result["cpu_baseline_c"] = cpu_baseline(synth, canon, faces, xyz, poses, sd, rays, S, args)
-    if rank == 0 and world == 1 and not args.no_extras and not (args.dense or args.fp32):
+    if full and not args.no_extras and not (args.dense or args.fp32):
         # what else ran on this box, in the same line: the same frame without the screen and with the exact-fp32
         # kernel, the host-batch -> host-image path of the reference's render_view, and the eager-torch restatement on this GPU
         def frame_ms(reps, **kw):

@@ -272,7 +272,7 @@ def strong_bench(args, dsnerf_amd, _lib, synth, dev, world, rank, use_dist, rk):
                       "exchange": (f"all_gather_into_tensor [{slab},6] fp32 per rank (RCCL) + index_select to ray order, in the timed region"
                                    if use_dist else "none (index_select to ray order only)")},
            "ranks": rk.info(per_rank_s, args.steps)}
-    if world > 1 and not args.no_extras:
+    if world > 1 and args.full and not args.no_extras:
         # the weak-scaling line of the same run, as a secondary object (what `--weak` makes the headline): every rank renders the WHOLE
         # frame - one frame of a multi-frame batch per rank, BASELINE configs[4] - and one all-gather of [R,6] pixels per frame follows
         del share, allp, full

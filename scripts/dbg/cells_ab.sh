@@ -2,7 +2,7 @@
 cd $GRAFT_REPO_ROOT; export TMPDIR=/tmp
 for t in 0 24000 32000 52000 62000; do
   echo "== target $t"
-  DSN_NN_FINE_TARGET=$t python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-extras --no-roofline 2>/dev/null | python -c "
+  DSN_NN_FINE_TARGET=$t python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-extras --no-roofline 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.readlines()[-1]); print('  frame %.3f ms  alone %.3f' % (d['ms_per_step'], d['config'].get('ms_per_frame_alone', 0)))"
   rm -rf gpurun_out/cells_$t

@@ -4,9 +4,9 @@
 # steps (run in the order given):
 #   tests            the -m gpu suite (summary lines)            tests:EXPR      only tests matching -k EXPR
 #   smoke            __graft_entry__.smoke()
-#   bench            the driver's line: python bench.py           bench:ARGS      python bench.py ARGS (commas = spaces), e.g. bench:--weights,default,--no-extras
+#   bench            the whole line: python bench.py --full       bench:ARGS      python bench.py --full ARGS (commas = spaces), e.g. bench:--weights,default,--no-extras
 #   train            bench.py --train (default + w4 start)
-#   trace[:ARGS]     rocprofv3 --kernel-trace --stats of `bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-extras --pipeline 1 ARGS`
+#   trace[:ARGS]     rocprofv3 --kernel-trace --stats of `bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-extras --pipeline 1 ARGS`
 #   pmc[:ARGS]       the separate --pmc passes of the same command (FETCH_SIZE, WRITE_SIZE, TCC, SQ, GRBM) -> TAG_pmc*.json
 #   poison           pytest -m gpu with every scratch allocation of the binding filled with 0xFF first (DSN_POISON_SCRATCH=1)
 #   traintrace / trainpmc   the same two for `bench.py --train --steps 5 --warmup 2`
@@ -18,7 +18,7 @@
 TAG=${1:-x}; shift
 cd $GRAFT_REPO_ROOT; mkdir -p gpurun_out; export TMPDIR=/tmp
 O=gpurun_out/$TAG
-B="python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-extras --pipeline 1"
+B="python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-extras --pipeline 1"
 summ() { python - "$1" <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1])); c = d.get('config', {})
@@ -40,7 +40,7 @@ for step in "$@"; do
            else timeout 1500 python -m pytest tests -m gpu -q -p no:cacheprovider 2>&1 | grep -E "^(FAILED|ERROR)|passed|failed|^E  " | cut -c1-400 | tee ${O}_tests.txt; fi;;
     poison) DSN_POISON_SCRATCH=1 timeout 1500 python -m pytest tests -m gpu -q -p no:cacheprovider 2>&1 | grep -E "^(FAILED|ERROR)|passed|failed|^E  " | cut -c1-400 | tee ${O}_tests_poisoned.txt;;
     smoke) timeout 300 python __graft_entry__.py --smoke 2>&1 | grep -E "smoke ok|Error|error" | cut -c1-200 | tee ${O}_smoke.txt;;
-    bench) n=$(echo "bench$arg" | tr -c 'a-zA-Z0-9\n' '_'); timeout 1200 python bench.py $args > ${O}_$n.log 2> ${O}_$n.err; tail -1 ${O}_$n.log > ${O}_$n.json; summ ${O}_$n.json || tail -5 ${O}_$n.err;;
+    bench) n=$(echo "bench$arg" | tr -c 'a-zA-Z0-9\n' '_'); timeout 1200 python bench.py --full $args > ${O}_$n.log 2> ${O}_$n.err; tail -1 ${O}_$n.log > ${O}_$n.json; summ ${O}_$n.json || tail -5 ${O}_$n.err;;
     train) for w in default w4; do timeout 400 python bench.py --train --weights $w --steps 30 --warmup 5 $args 2>/dev/null | tail -1 > ${O}_train_$w.json; summ ${O}_train_$w.json; done;;
     trace) rm -rf gpurun_out/prof_$TAG; rocprofv3 --kernel-trace --stats -d gpurun_out/prof_$TAG -o r -- $B --no-roofline $args > ${O}_trace.log 2>&1
            python scripts/rocpd_sequence.py gpurun_out/prof_$TAG/r_results.db k_pose_setup > ${O}_frame_sequence.txt; python scripts/rocpd_period.py gpurun_out/prof_$TAG/r_results.db k_pose_setup > ${O}_frame_period.txt
@@ -72,7 +72,7 @@ for n, v in sorted(c['worlds'].items(), key=lambda kv: int(kv[0])):
 PY
              ;;
     weak8) timeout 900 python bench.py --emulate-world 8 --steps 8 --warmup 3 $args 2>/dev/null | tail -1 > ${O}_weak_emulated8.json; summ ${O}_weak_emulated8.json;;
-    dist1) DSN_BENCH_FORCE_DIST=1 timeout 600 python bench.py --gpus 1 --no-cpu-baseline --no-extras 2>/dev/null | tail -1 > ${O}_weak_rccl.json; summ ${O}_weak_rccl.json
+    dist1) DSN_BENCH_FORCE_DIST=1 timeout 600 python bench.py --gpus 1 --full --no-cpu-baseline --no-extras 2>/dev/null | tail -1 > ${O}_weak_rccl.json; summ ${O}_weak_rccl.json
            DSN_BENCH_FORCE_DIST=1 timeout 600 python bench.py --gpus 1 --strong --no-cpu-baseline 2>/dev/null | tail -1 > ${O}_strong_rccl.json; summ ${O}_strong_rccl.json
            DSN_BENCH_FORCE_DIST=1 timeout 600 python bench.py --gpus 1 --train --steps 10 --warmup 3 2>/dev/null | tail -1 > ${O}_train_rccl.json; summ ${O}_train_rccl.json;;
     world2) # the REAL multi-rank code paths with 2 ranks on this one GPU over gloo (RCCL refuses two ranks per device): control flow, collectives and
@@ -83,7 +83,7 @@ PY
               tail -1 ${O}_$n.log > ${O}_$n.json; summ ${O}_$n.json || tail -5 ${O}_$n.err; done;;
     ab) IFS=':' read -ra CFGS <<< "$arg"
         for rep in 1 2; do for cfg in "${CFGS[@]}"; do
-          env $cfg python bench.py --steps 8 --warmup 3 --no-cpu-baseline --no-extras --no-roofline $BENCH_ARGS 2>/dev/null | python -c "
+          env $cfg python bench.py --full --steps 8 --warmup 3 --no-cpu-baseline --no-extras --no-roofline $BENCH_ARGS 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.readlines()[-1]); print('%-44s' % '$cfg', 'frame %.3f ms' % d['ms_per_step'], 'alone %.3f' % d['config'].get('ms_per_frame_alone', 0))" | tee -a ${O}_ab.txt
         done; done;;

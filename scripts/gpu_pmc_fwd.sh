@@ -1,5 +1,5 @@
 cd $GRAFT_REPO_ROOT; mkdir -p gpurun_out; export TMPDIR=/tmp
-B="python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-roofline"
+B="python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-roofline"
 rm -rf gpurun_out/pmcw
 run() { name=$1; shift; rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d gpurun_out/pmcw/$name -o $name -- $B > gpurun_out/pmcw_$name.log 2>&1; }
 run a SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_WAIT_INST_LDS SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_MISC SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_VMEM

@@ -1,7 +1,7 @@
 # LDS / issue counters of the field kernels next to the same counters of the inner-loop micro-benchmark (scripts/ubench/field_loop.hip)
 #   /usr/local/graft/bin/gpurun --timeout 900 -- 'bash scripts/gpu_pmc_lds.sh'   -> gpurun_out/pmc_lds.json, pmc_lds_ubench.json
 cd $GRAFT_REPO_ROOT; mkdir -p gpurun_out; export TMPDIR=/tmp
-B="python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-extras --pipeline 1 --no-roofline"
+B="python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-extras --pipeline 1 --no-roofline"
 hipcc --offload-arch=gfx950 -O3 -o /tmp/fl scripts/ubench/field_loop.hip 2>/dev/null
 rm -rf gpurun_out/pmcl gpurun_out/pmclu
 run() { name=$1; shift; rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d gpurun_out/pmcl/$name -o $name -- $B > gpurun_out/pmcl_$name.log 2>&1

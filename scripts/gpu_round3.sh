@@ -6,7 +6,7 @@ cd $GRAFT_REPO_ROOT; mkdir -p gpurun_out; export TMPDIR=/tmp
 O=gpurun_out/r03_$TAG
 timeout 900 python -m pytest tests -m gpu -q -p no:cacheprovider 2>&1 | grep -E "^(FAILED|ERROR)|passed|failed|^E  " | cut -c1-300 | tee ${O}_tests.txt
 timeout 300 python __graft_entry__.py --smoke 2>&1 | grep -E "smoke ok|Error|error" | cut -c1-200 | tee ${O}_smoke.txt
-timeout 900 python bench.py > ${O}_bench.log 2> ${O}_bench.err; tail -1 ${O}_bench.log > ${O}_bench.json; python - ${O}_bench.json <<'PY'
+timeout 900 python bench.py --full > ${O}_bench.log 2> ${O}_bench.err; tail -1 ${O}_bench.log > ${O}_bench.json; python - ${O}_bench.json <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1])); c = d['config']
 print('ms_per_step', round(d['ms_per_step'], 3), 'alone', round(c['ms_per_frame_alone'], 3), 'h2h', round(c.get('host_to_host_ms', 0), 2), 'h2h caller', round(c.get('host_to_host_ms_after_a_caller_torch_cpu_op', 0), 2))
@@ -40,10 +40,10 @@ runt grbm GRBM_GUI_ACTIVE
 python scripts/pmc_summary.py gpurun_out/pmct ${O}_train_pmc.json | cut -c1-260 | head -8
 timeout 600 python bench.py --strong --no-cpu-baseline 2>/dev/null | tail -1 > ${O}_strong.json
 DSN_BENCH_FORCE_DIST=1 timeout 600 python bench.py --strong --no-cpu-baseline 2>/dev/null | tail -1 > ${O}_strong_rccl.json
-DSN_BENCH_FORCE_DIST=1 timeout 600 python bench.py --no-cpu-baseline --no-extras 2>/dev/null | tail -1 > ${O}_weak_rccl.json
+DSN_BENCH_FORCE_DIST=1 timeout 600 python bench.py --full --no-cpu-baseline --no-extras 2>/dev/null | tail -1 > ${O}_weak_rccl.json
 timeout 900 python bench.py --strong --emulate-world 8 --steps 5 --warmup 2 2>/dev/null | tail -1 > ${O}_strong_emulated8.json
 timeout 900 python bench.py --emulate-world 8 --steps 8 --warmup 3 2>/dev/null | tail -1 > ${O}_weak_emulated8.json
-for wt in w2 w3 w4; do timeout 600 python bench.py --weights $wt --no-cpu-baseline --no-extras 2>/dev/null | tail -1 > ${O}_$wt.json; done
+for wt in w2 w3 w4; do timeout 600 python bench.py --full --weights $wt --no-cpu-baseline --no-extras 2>/dev/null | tail -1 > ${O}_$wt.json; done
 for f in strong strong_rccl weak_rccl w2 w3 w4 strong_emulated8 weak_emulated8 train_bench train_bench_w4; do python -c "
 import json; d = json.load(open('${O}_$f.json')); print('$f', round(d['ms_per_step'], 2), 'ms', {k: round(v, 4) for k, v in d['config'].items() if k in ('max_over_mean', 'predicted_strong_scaling_efficiency', 'predicted_weak_scaling_efficiency')})"; done
 rm -rf gpurun_out/prof_r gpurun_out/prof_w4 gpurun_out/pmcr gpurun_out/prof_t gpurun_out/pmct

@@ -7,7 +7,7 @@ import bench, dsnerf_amd
 from dsnerf_amd import _lib
 L = _lib.lib() if callable(getattr(_lib, "lib", None)) else C.CDLL(_lib.LIB_PATH)
 L.dsn_debug_timing.argtypes = [C.POINTER(C.c_ulonglong), C.c_int]
-sys.argv = ["bench.py", "--steps", "4", "--warmup", "1", "--no-cpu-baseline", "--no-extras", "--pipeline", "1", "--no-roofline"]
+sys.argv = ["bench.py", "--full", "--steps", "4", "--warmup", "1", "--no-cpu-baseline", "--no-extras", "--pipeline", "1", "--no-roofline"]
 L.dsn_debug_timing(None, 1)
 bench.main()
 torch.cuda.synchronize()

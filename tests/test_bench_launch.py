@@ -204,3 +204,28 @@ def test_bench_dumps_the_last_timed_frame(tmp_path):
     # disp_map is NaN exactly on the rays with acc_map = 0 (like the reference): written as 0, coded 1
     code = np.load(tmp_path / "a" / "disp_map_nonfinite.npy") if "disp_map_nonfinite.npy" in files else np.zeros_like(acc)
     assert np.array_equal(code == 1, acc == 0) and not (code > 1).any()
+
+
+# ---- a plain run measures its headline figure only; --full adds the secondary measurements ----
+SECONDARY = ("roofline", "cpu_baseline", "cpu_baseline_c", "eager_gpu_baseline", "train", "train_w4", "ms_per_frame_by_weights")
+
+
+@pytest.mark.gpu
+def test_plain_run_is_lean_and_full_adds_the_secondary_measurements():
+    """without --full the line carries the headline figure and what the timed frames counted, nothing measured in runs of its own;
+    --full (here without the baselines and the extras) adds the frame alone and the roofline pass, and the headline keys stay"""
+    cmd = [sys.executable, BENCH, "--gpus", "1", "--hw", "128", "--steps", "2", "--warmup", "1"]
+    js = []
+    for extra in ([], ["--full", "--no-cpu-baseline", "--no-extras"]):
+        p = subprocess.run(cmd + extra, capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, p.stderr[-2000:]
+        js.append(_json_lines(p.stdout)[-1])
+    plain, full = js
+    for j in js:
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "whole_frame"):
+            assert k in j, k
+        assert j["steps"] == 2 and j["warmup"] == 1 and abs(j["value"] - 128 * 128 / (j["ms_per_step"] * 1e-3)) < 1e-6 * j["value"]
+    assert not [k for k in SECONDARY if k in plain], plain.keys()
+    assert "ms_per_frame_alone" not in plain["config"] and "by_weights" not in plain["config"]
+    assert full["config"]["ms_per_frame_alone"] > 0 and full["roofline"]["kernel_ms"] > 0
+    assert not [k for k in SECONDARY if k in full and k != "roofline"], full.keys()

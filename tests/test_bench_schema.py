@@ -1,5 +1,5 @@
-"""The bench line says what ran: a recorded driver line (profiles/r05_bench.json, written by `python bench.py` on the
-MI355X) carries the contract's keys, the renamed sample fractions, the whole-frame fraction and one frame time per parameter set -
+"""The bench line says what ran: a recorded driver line (profiles/r05_bench.json, written by `python bench.py --full`
+on the MI355X) carries the contract's keys, the renamed sample fractions, the whole-frame fraction and one frame time per parameter set -
 and none of the labels round 4 was faulted for."""
 import json
 import os
