@@ -43,6 +43,7 @@ EXPORTS = [
     "dsn_render_workspace_record_capacity", "dsn_stop_slice_len", "dsn_stop_stats_slice_len", "dsn_early_stop_colour_headroom", "dsn_render_rays_ex",
     "dsn_render_rays_grad_ex", "dsn_render_rays_train_ex", "dsn_aux_create", "dsn_aux_destroy",
     "dsn_render_lights_scratch_bytes", "dsn_render_rays_lights", "dsn_image_ssim_workspace_bytes", "dsn_image_ssim",
+    "dsn_density_grid_workspace_bytes", "dsn_density_grid", "dsn_mc_workspace_bytes", "dsn_mc_count", "dsn_mc_emit", "dsn_mc_table_host",
 ]
 
 SKIP_TRANSPARENT = 1
@@ -95,6 +96,16 @@ def lib():
             getattr(L, n).restype = C.c_size_t
         L.dsn_render_lights_scratch_bytes.restype = C.c_size_t
         L.dsn_render_lights_scratch_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int64]
+        L.dsn_density_grid_workspace_bytes.restype = C.c_size_t
+        L.dsn_density_grid_workspace_bytes.argtypes = [C.c_int64]
+        L.dsn_mc_workspace_bytes.restype = C.c_size_t
+        L.dsn_mc_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
+        L.dsn_mc_table_host.argtypes = [C.c_void_p, C.c_size_t]
+        L.dsn_density_grid.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                       C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p]
+        L.dsn_mc_count.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.dsn_mc_emit.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int,
+                                  C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
         if L.dsn_abi_version() != 8:
             raise RuntimeError(f"{LIB_PATH} has ABI version {L.dsn_abi_version()}, this binding needs 8 - rebuild it "
                                "(python dual-space-nerf_amd/build.py)")
@@ -555,6 +566,70 @@ def field_reverse(scene: Scene, packed: PackedParams, x_c, rec, pos, sigma, esse
                                    _ptr(pos[0]), _ptr(pos[1]), _ptr(rec), _ptr(g), _ptr(sigma, torch.float32),
                                    _ptr(essence, torch.float32), _stream()), "dsn_field_reverse")
     return g
+
+
+DENSITY_GRID_SLAB_POINTS = 1 << 25      # default slab of dsn_density_grid: 32 M points (~1 GB of scratch), whole x-planes
+
+
+def _axes_dev(axes, device):
+    out = [(a if torch.is_tensor(a) else torch.from_numpy(__import__("numpy").asarray(a))).to(device=device, dtype=torch.float32)
+           .reshape(-1).contiguous() for a in axes]
+    assert len(out) == 3, "three axis arrays (x, y, z)"
+    return out
+
+
+def density_grid(scene: Scene, packed: PackedParams, axes, slab_points=None, fp32=False, exhaustive=False):
+    """dsn_density_grid: the density volume [nx, ny, nz] (device float32) of the grid axes (x, y, z) for the scene's current frame
+    (transparent points 0).  slab_points: scratch bound in points, rounded down to whole x-planes (default
+    DENSITY_GRID_SLAB_POINTS, at least one plane)."""
+    dev = scene.device
+    x, y, z = _axes_dev(axes, dev)
+    nx, ny, nz = x.numel(), y.numel(), z.numel()
+    plane = ny * nz
+    P = int(slab_points) if slab_points is not None else max(plane, min(DENSITY_GRID_SLAB_POINTS, nx * plane))
+    vol = torch.empty(nx, ny, nz, dtype=torch.float32, device=dev)
+    nbytes = lib().dsn_density_grid_workspace_bytes(P)
+    ws = _scratch(max(nbytes, 1), dev)
+    flags = (FIELD_FP32 if fp32 else 0) | (NN_EXHAUSTIVE if exhaustive else 0)
+    _check(lib().dsn_density_grid(_ptr(scene.buf), scene.V, scene.F, _ptr(packed.buf), _ptr(x), nx, _ptr(y), ny, _ptr(z), nz, flags,
+                                  _ptr(vol), P, _ptr(ws), nbytes, _stream()), "dsn_density_grid")
+    return vol
+
+
+MC_GRADIENT = {"descent": 0, "ascent": 1}
+MC_MAX_TRI = 5               # DSN_MC_MAX_TRI
+
+
+def mc_table():
+    """the marching-cubes case table (host function): int32 [256, DSN_MC_TABLE_ROW] - count, then cube-edge triples (-1 padded)"""
+    import numpy as np
+    row = 1 + 3 * MC_MAX_TRI
+    out = np.zeros((256, row), dtype=np.int32)
+    _check(lib().dsn_mc_table_host(out.ctypes.data, out.size), "dsn_mc_table_host")
+    return out
+
+
+def marching_cubes(volume, axes, level, gradient_direction="descent"):
+    """dsn_mc_count + dsn_mc_emit on a device volume [nx, ny, nz]: (verts [V,3] float32, faces [T,3] int32) device tensors, both empty
+    where the level is not crossed.  One device->host read (the two counts)."""
+    if gradient_direction not in MC_GRADIENT:
+        raise ValueError('gradient_direction must be "descent" or "ascent"')
+    vol = volume
+    assert vol.is_cuda and vol.dtype == torch.float32 and vol.dim() == 3, "volume: device float32 [nx, ny, nz]"
+    vol = vol.contiguous()
+    dev = vol.device
+    x, y, z = _axes_dev(axes, dev)
+    nx, ny, nz = vol.shape
+    assert (x.numel(), y.numel(), z.numel()) == (nx, ny, nz), "one axis value per grid point along each axis"
+    ws = _scratch(max(lib().dsn_mc_workspace_bytes(nx, ny, nz), 1), dev)
+    counts = torch.empty(2, dtype=torch.int64, device=dev)
+    _check(lib().dsn_mc_count(_ptr(vol), nx, ny, nz, float(level), _ptr(ws), _ptr(counts), _stream()), "dsn_mc_count")
+    V, T = (int(c) for c in counts.cpu())
+    verts = torch.empty(V, 3, dtype=torch.float32, device=dev)
+    faces = torch.empty(T, 3, dtype=torch.int32, device=dev)
+    _check(lib().dsn_mc_emit(_ptr(vol), nx, ny, nz, _ptr(x), _ptr(y), _ptr(z), float(level), MC_GRADIENT[gradient_direction], _ptr(ws),
+                             V, T, _ptr(verts) if V else None, _ptr(faces) if T else None, _stream()), "dsn_mc_emit")
+    return verts, faces
 
 
 def lbs_warp(scene: Scene, pts, smpl_weights, joint_transforms, bw_type="rigid_center", exhaustive=False):

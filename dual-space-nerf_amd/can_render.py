@@ -1051,6 +1051,58 @@ class Renderer:
             out.append(d)
         return out
 
+    # ---- density grid + iso-surface on the device (utils/visualizer.py Visualizer3D, not in Renderer) ----
+    @staticmethod
+    def grid_axes(points, resolution):
+        """Visualizer3D.get_grid's axes (utils/visualizer.py:170-227, eps = 0) as float64 numpy arrays (x, y, z): `resolution` points
+        by linspace over the shortest extent of the points' bounding box, the other two by arange with that step"""
+        p = points.detach().reshape(-1, 3).float().cpu().numpy() if torch.is_tensor(points) else np.asarray(points, np.float32).reshape(-1, 3)
+        s = int(np.argmin(p.max(axis=0) - p.min(axis=0)))          # (float32 extents, as the reference's bounding_box)
+        lo, hi = p.min(axis=0).astype(np.float64), p.max(axis=0).astype(np.float64)
+        ax = [None] * 3
+        ax[s] = np.linspace(lo[s], hi[s], int(resolution))
+        step = (np.max(ax[s]) - np.min(ax[s])) / (ax[s].shape[0] - 1)
+        for a in range(3):
+            if a != s:
+                ax[a] = np.arange(lo[a], hi[a] + step, step)
+        return tuple(ax)
+
+    @staticmethod
+    def grid_axes_uniform(resolution):
+        """Visualizer3D.get_grid_uniform's axes (utils/visualizer.py:238-251): linspace(-1.2, 1.2) on all three"""
+        a = np.linspace(-1.2, 1.2, int(resolution))
+        return a, a.copy(), a.copy()
+
+    def density_grid(self, batch, resolution=None, axes=None, points=None, frame=None, fp32=False, slab_points=None):
+        """Visualizer3D.get_grid_pred_batch's density volume on the device (dsn_density_grid): the grid of `axes` (default:
+        grid_axes(points, resolution), points = batch["xyz"][0]) warped into the canonical space of batch's posed mesh, the density of
+        every non-transparent point (0 elsewhere) with the frame code `frame` (default batch["frame"]; zeroed as
+        DualSpaceNeRF.frame_args has it) and the pose of batch["poses"].  Returns (axes, volume [nx, ny, nz] device float32).
+        fp32=True: the exact-fp32 kernel, i.e. the bits of query_volume(w2l_without_lbs(points)).  Render calls that follow set their
+        own frame: their results do not change."""
+        if axes is None:
+            if resolution is None:
+                raise ValueError("density_grid: give `resolution` or `axes`")
+            axes = self.grid_axes(batch["xyz"][0] if points is None else points, resolution)
+        self._ensure_mesh(batch)
+        fi = int(torch.as_tensor(batch["frame"] if frame is None else frame).reshape(-1)[0])
+        packed = self.net.packed(self.device)
+        _lib.scene_set_pose(self.scene, packed, batch["poses"][0], fi, self.net.nerf.w is not None)
+        self._frame_src = None          # (the scene's frame state now holds this pose code: stage calls set their frame again)
+        vol = _lib.density_grid(self.scene, packed, axes, slab_points=slab_points, fp32=fp32)
+        return axes, vol
+
+    def extract_mesh(self, batch, resolution=512, level=0.5, gradient_direction="ascent", axes=None, points=None, frame=None,
+                     fp32=False, slab_points=None):
+        """Visualizer3D's mesh of the posed body on the device: density_grid + marching cubes (dsn_mc_count / dsn_mc_emit, the rule of
+        include/dsnerf.h).  Defaults are the visualizer's __main__ values.  Returns {"verts" [V,3] float32, "faces" [T,3] int32} device
+        tensors in world coordinates, or None where the level is not crossed (the reference returns None there)."""
+        axes, vol = self.density_grid(batch, resolution, axes, points, frame, fp32, slab_points)
+        verts, faces = _lib.marching_cubes(vol, axes, level, gradient_direction)
+        if faces.shape[0] == 0:
+            return None
+        return {"verts": verts, "faces": faces}
+
     # ---- density query for marching cubes (reference :280-296) ----
     def query_volume(self, pts, code_idx, transparent_mask=None, batch_info={}):
         """batch_info needs only 'poses' (the density-only branch of the reference, model/spacenet.py:223-241)."""

@@ -1051,4 +1051,89 @@ int dsn_render_rays_train(const void* scene, int V, int F, const void* packed, c
                                     out_depth, out_weights, out_z, workspace, grad_workspace, stream, nullptr, nullptr, nullptr);
 }
 
+// ---- density grid + marching cubes (utils/visualizer.py Visualizer3D) ----
+// density-grid scratch of a slab of P points: points 12 P | canonical points 12 P | active list 4 P | counters (256 B)
+static size_t dsn_grid_ws(int64_t P) { return 2 * dsn_align256(12 * (size_t)P) + dsn_align256(4 * (size_t)P) + 256; }
+
+size_t dsn_density_grid_workspace_bytes(int64_t slab_points) {
+    return slab_points > 0 && slab_points < ((int64_t)1 << 31) ? dsn_grid_ws(slab_points) : 0;
+}
+
+int dsn_density_grid(const void* scene, int V, int F, const void* packed, const float* x, int nx, const float* y, int ny, const float* z,
+                     int nz, int flags, float* volume, int64_t slab_points, void* workspace, size_t workspace_bytes, void* stream) {
+    DSN_REQUIRE(scene && packed && x && y && z && volume && workspace, "dsn_density_grid: null argument");
+    DSN_REQUIRE(V > 0 && F > 0, "dsn_density_grid: bad V/F");
+    DSN_REQUIRE(nx > 0 && ny > 0 && nz > 0, "dsn_density_grid: empty grid axis");
+    const int64_t plane = (int64_t)ny * nz, N = plane * nx;
+    DSN_REQUIRE(N < ((int64_t)1 << 31), "dsn_density_grid: more than 2^31 - 1 grid points");
+    DSN_REQUIRE(slab_points >= plane && slab_points < ((int64_t)1 << 31), "dsn_density_grid: slab_points must hold at least one x-plane (ny * nz points)");
+    DSN_REQUIRE(workspace_bytes >= dsn_grid_ws(slab_points), "dsn_density_grid: workspace smaller than dsn_density_grid_workspace_bytes(slab_points)");
+    DSN_REQUIRE((flags & ~(DSN_FIELD_FP32 | DSN_NN_EXHAUSTIVE)) == 0, "dsn_density_grid: flags other than DSN_FIELD_FP32 / DSN_NN_EXHAUSTIVE");
+    hipStream_t st = (hipStream_t)stream;
+    DsnSceneView s = dsn_scene_view((void*)scene, V, F);
+    char* p = (char*)workspace;
+    float* pts = (float*)p;                      p += dsn_align256(12 * (size_t)slab_points);
+    float* x_c = (float*)p;                      p += dsn_align256(12 * (size_t)slab_points);
+    int32_t* list = (int32_t*)p;                 p += dsn_align256(4 * (size_t)slab_points);
+    int32_t* cnt = (int32_t*)p;                  // [0] active points of the slab, [16] samples the split-fp16 kernel flagged
+    const int per = (int)(slab_points / plane);
+    for (int i0 = 0; i0 < nx; i0 += per) {
+        const int np = nx - i0 < per ? nx - i0 : per;
+        const int64_t Ns = (int64_t)np * plane;
+        float* vs = volume + (int64_t)i0 * plane;
+        if (hipMemsetAsync(cnt, 0, 256, st) != hipSuccess || hipMemsetAsync(vs, 0, sizeof(float) * (size_t)Ns, st) != hipSuccess)
+            return dsn_fail("%s", "dsn_density_grid: memset failed");
+        dsn_launch_grid_points(x, y, z, i0, ny, nz, Ns, pts, st);
+        // utils/render_utils.py w2l_without_lbs: dsn_warp's kernel (transparent points stay off the list and keep density 0)
+        dsn_launch_warp(s, pts, nullptr, nullptr, nullptr, Ns, 1, nullptr, nullptr, nullptr, nullptr, x_c, nullptr, list, cnt,
+                        (flags & DSN_NN_EXHAUSTIVE) != 0, st);
+        if (flags & DSN_FIELD_FP32)
+            dsn_launch_field((const float*)packed, s.frame, x_c, Ns, list, cnt, vs, nullptr, nullptr, st);
+        else {
+            dsn_launch_field16_den((const float*)packed, s.frame, x_c, Ns, list, cnt, vs, st, cnt + 16);
+            dsn_launch_field_fix((const float*)packed, s.frame, x_c, Ns, list, cnt, vs, nullptr, nullptr, st, cnt + 16);
+        }
+    }
+    return dsn_check_launch("dsn_density_grid");
+}
+
+static bool dsn_mc_sizes_ok(int nx, int ny, int nz) {
+    return nx >= 2 && ny >= 2 && nz >= 2 && (int64_t)nx * ny * nz < ((int64_t)1 << 31);
+}
+
+size_t dsn_mc_workspace_bytes(int nx, int ny, int nz) {
+    return dsn_mc_sizes_ok(nx, ny, nz) ? dsn_mc_workspace_size((int64_t)nx * ny * nz) : 0;
+}
+
+int dsn_mc_count(const float* volume, int nx, int ny, int nz, float level, void* workspace, int64_t* out_counts2, void* stream) {
+    DSN_REQUIRE(volume && workspace && out_counts2, "dsn_mc_count: null argument");
+    DSN_REQUIRE(dsn_mc_sizes_ok(nx, ny, nz), "dsn_mc_count: bad grid size (every axis >= 2, fewer than 2^31 points)");
+    DSN_REQUIRE(level == level, "dsn_mc_count: NaN level");
+    dsn_launch_mc_count(volume, nx, ny, nz, level, workspace, out_counts2, (hipStream_t)stream);
+    return dsn_check_launch("dsn_mc_count");
+}
+
+int dsn_mc_emit(const float* volume, int nx, int ny, int nz, const float* x, const float* y, const float* z, float level,
+                int gradient_direction, const void* workspace, int64_t n_verts, int64_t n_faces, float* verts, int32_t* faces,
+                void* stream) {
+    DSN_REQUIRE(volume && x && y && z && workspace, "dsn_mc_emit: null argument");
+    DSN_REQUIRE(dsn_mc_sizes_ok(nx, ny, nz), "dsn_mc_emit: bad grid size (every axis >= 2, fewer than 2^31 points)");
+    DSN_REQUIRE(level == level, "dsn_mc_emit: NaN level");
+    DSN_REQUIRE(gradient_direction == DSN_MC_DESCENT || gradient_direction == DSN_MC_ASCENT, "dsn_mc_emit: gradient_direction must be DSN_MC_DESCENT or DSN_MC_ASCENT");
+    DSN_REQUIRE(n_verts >= 0 && n_faces >= 0, "dsn_mc_emit: negative count");
+    DSN_REQUIRE(n_verts < ((int64_t)1 << 31), "dsn_mc_emit: 2^31 or more vertices do not fit int32 face indices");
+    DSN_REQUIRE((n_verts == 0 || verts) && (n_faces == 0 || faces), "dsn_mc_emit: null output buffer");
+    if (n_verts == 0 && n_faces == 0) return 0;
+    dsn_launch_mc_emit(volume, nx, ny, nz, x, y, z, level, gradient_direction == DSN_MC_ASCENT, workspace, verts, n_verts, faces, n_faces,
+                       (hipStream_t)stream);
+    return dsn_check_launch("dsn_mc_emit");
+}
+
+int dsn_mc_table_host(int32_t* out_host, size_t out_ints) {
+    DSN_REQUIRE(out_host, "dsn_mc_table_host: null argument");
+    DSN_REQUIRE(out_ints >= (size_t)256 * DSN_MC_TABLE_ROW, "dsn_mc_table_host: out_host holds fewer than 256 * DSN_MC_TABLE_ROW ints");
+    dsn_mc_table_copy(out_host);
+    return 0;
+}
+
 }  // extern "C"

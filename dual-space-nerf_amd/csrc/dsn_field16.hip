@@ -612,7 +612,11 @@ __device__ __forceinline__ void layer16_bwd(W16& w, int& blk, int lane, const ha
 #define F16_FWD 1
 #define F16_BWD 2
 #define F16_TRAIN 3           // FULL + every layer's activations and masked sigma-adjoints stored row-major for dsn_train.hip
+#define F16_DEN 4             // density only: the trunk and the density head of FWD (the same sigma bits), then the next tile - no colour
+                              // head, no relu records, no sigma > 0 list, no reverse pass (dsn_density_grid)
 #define F16_FIRST_BWD_BLOCK (OFF_L6T / DSN_BLK)   // 448
+#define F16_DEN_BLOCKS (F16_FIRST_BWD_BLOCK - 4 * 8)   // 416: the stream ends at rgb_net.1 (4 output blocks x 8 k-blocks)
+static_assert(F16_DEN_BLOCKS % F16_CHUNK == 0, "the density-only kernel streams whole chunks");
 template <int MODE>
 __global__ void __launch_bounds__(F16_THREADS, 1)
 k_field16(const float* __restrict__ packed, const DsnFrameState* __restrict__ fs, const float* __restrict__ x_c,
@@ -664,6 +668,7 @@ k_field16(const float* __restrict__ packed, const DsnFrameState* __restrict__ fs
     w.ring_off = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)ring;
     w.wave = wave;
     if (MODE == F16_FWD) w.nchunk = F16_FIRST_BWD_BLOCK / F16_CHUNK;
+    if (MODE == F16_DEN) w.nchunk = F16_DEN_BLOCKS / F16_CHUNK;
     if (MODE == F16_TRAIN) w.spread = false;
     // this tile's point comes from the previous tile's prefetch: list slot -> (slot on the list, sample index), then its coordinates
     auto tile_point = [&](int64_t t, bool& ok, int64_t& ls) -> int64_t {
@@ -705,7 +710,7 @@ k_field16(const float* __restrict__ packed, const DsnFrameState* __restrict__ fs
 
     // relu masks live in LDS between the forward and the reverse pass (28 VGPRs otherwise); lane-private slots,
     // so no barrier is needed around them
-#define MK_STORE(L, mk) { s_mask[L][0][tid] = mk[0]; s_mask[L][1][tid] = mk[1]; s_mask[L][2][tid] = mk[2]; s_mask[L][3][tid] = mk[3]; }
+#define MK_STORE(L, mk) { if (MODE != F16_DEN) { s_mask[L][0][tid] = mk[0]; s_mask[L][1][tid] = mk[1]; s_mask[L][2][tid] = mk[2]; s_mask[L][3][tid] = mk[3]; } }
 #define MK_LOAD(L, mk) { mk[0] = s_mask[L][0][tid]; mk[1] = s_mask[L][1][tid]; mk[2] = s_mask[L][2][tid]; mk[3] = s_mask[L][3][tid]; }
     uint32_t mk[4];
     half8 ah[8][2], al[8][2], bh[8][2], bl[8][2];
@@ -822,6 +827,7 @@ k_field16(const float* __restrict__ packed, const DsnFrameState* __restrict__ fs
     const bool flag_fwd = !(fmaxf(ovf, __shfl_xor(ovf, 32)) < F16_RANGE);
     if (valid && half == 0) sigma[pt] = flag_fwd ? dsn_nan_flag() : sg;
     if (MODE != F16_TRAIN && flag_fwd && valid && half == 0 && flag_count) atomicAdd(flag_count, 1);
+    if (MODE == F16_DEN) { __syncthreads(); continue; }      // (tile done: every wave has read its last weight block)
     bool write_rec = ST && valid;
     if (MODE == F16_FWD) {
         // samples with positive density -> the reverse-pass list (flagged samples too: the fallback behind the reverse pass
@@ -1030,6 +1036,17 @@ void dsn_launch_field16_fwd(const float* packed, const DsnFrameState* fs, const 
     hipLaunchKernelGGL(k_field16<F16_FWD>, dim3((unsigned)std::min<int64_t>(blocks, dsn_cu_count())), dim3(F16_THREADS), 0, st, packed, fs, x_c, N,
                        active_list, active_count, sigma, essence, (float*)nullptr, (uint4*)masks, pos_list, pos_count,
                        (float*)nullptr, (float*)nullptr, (float*)nullptr, (int64_t)0, rec_cap, (const int32_t*)nullptr, flag_count);
+}
+// density only (sigma of the listed samples; flagged samples get NaN and a count in flag_count for dsn_launch_field_fix)
+void dsn_launch_field16_den(const float* packed, const DsnFrameState* fs, const float* x_c, int64_t N,
+                            const int32_t* active_list, const int32_t* active_count, float* sigma, hipStream_t st,
+                            int32_t* flag_count) {
+    int64_t blocks = (N + 127) / 128;
+    if (blocks == 0) return;
+    hipLaunchKernelGGL(k_field16<F16_DEN>, dim3((unsigned)std::min<int64_t>(blocks, dsn_cu_count())), dim3(F16_THREADS), 0, st, packed, fs, x_c, N,
+                       active_list, active_count, sigma, (float*)nullptr, (float*)nullptr, (uint4*)nullptr, (int32_t*)nullptr,
+                       (int32_t*)nullptr, (float*)nullptr, (float*)nullptr, (float*)nullptr, (int64_t)0, (int64_t)0,
+                       (const int32_t*)nullptr, flag_count);
 }
 // ... reverse pass on the sigma > 0 samples only
 void dsn_launch_field16_bwd(const float* packed, const DsnFrameState* fs, const float* x_c, int64_t N,

@@ -71,6 +71,10 @@ void dsn_launch_field16_fwd(const float* packed, const DsnFrameState* fs, const 
                             const int32_t* active_list, const int32_t* active_count, float* sigma, float* essence,
                             void* masks, int32_t* pos_list, int32_t* pos_count, hipStream_t st, int64_t rec_cap,
                             int32_t* flag_count = nullptr);
+// density only: k_field16's forward trunk and density head (sigma bit-identical to dsn_launch_field16_fwd's where that does not flag)
+void dsn_launch_field16_den(const float* packed, const DsnFrameState* fs, const float* x_c, int64_t N,
+                            const int32_t* active_list, const int32_t* active_count, float* sigma, hipStream_t st,
+                            int32_t* flag_count = nullptr);
 void dsn_launch_field16_from(const float* packed, const DsnFrameState* fs, const float* x_c, int64_t N, const int32_t* list,
                              const int32_t* count, int64_t slot_base, float* sigma, float* essence, float* grad, hipStream_t st,
                              int32_t* flag_count = nullptr);
@@ -167,6 +171,13 @@ void dsn_launch_image_psnr(const float* img_rgb, const double* gt64, const float
 size_t dsn_image_ssim_workspace_size(int F, int H, int W);
 void dsn_launch_image_ssim(const float* img_rgb, const double* gt64, const float* gt32, const uint8_t* mask, int F, int H, int W,
                            int clamp_rgb, double* out_ssim, int32_t* out_rect, int32_t* out_status, void* workspace, hipStream_t st);
+// dsn_mesh.hip: density grid points and marching cubes (dsn_density_grid, dsn_mc_*)
+void dsn_launch_grid_points(const float* x, const float* y, const float* z, int i0, int ny, int nz, int64_t n, float* pts, hipStream_t st);
+size_t dsn_mc_workspace_size(int64_t N);
+void dsn_launch_mc_count(const float* vol, int nx, int ny, int nz, float level, void* workspace, int64_t* out_counts, hipStream_t st);
+void dsn_launch_mc_emit(const float* vol, int nx, int ny, int nz, const float* x, const float* y, const float* z, float level, int ascent,
+                        const void* workspace, float* verts, int64_t vcap, int32_t* faces, int64_t fcap, hipStream_t st);
+void dsn_mc_table_copy(int32_t* out_host);
 // front-to-back slices with exact ray termination (dsn_geom.hip; DSN_EARLY_STOP in dsn_render_rays)
 #define DSN_STOP_MAX_SLICES 32
 // bounds[0 .. K]: slice k = samples [bounds[k], bounds[k + 1]) of every ray; its list starts at lists + R * bounds[k]

@@ -462,6 +462,55 @@ DSN_EXPORT int dsn_render_rays_lights(const void* scene, int V, int F, const voi
                            float* out_weights, float* out_z, void* workspace, size_t workspace_bytes, void* light_scratch,
                            size_t light_scratch_bytes, const int32_t* slice_lengths_host, int n_slices, void* stream);
 
+/* ---- density grid and iso-surface (an addition within ABI 8: no existing entry point changes) -------------------------------------
+ * utils/visualizer.py:35-110 Visualizer3D.get_grid_pred_batch: the reference builds grid_pts on the host (get_grid, :170-236),
+ * warps them with Renderer.w2l_without_lbs, evaluates Renderer.query_volume in 100 000-point chunks and sets transparent points to 0.
+ * dsn_density_grid does all of it on the device for the scene's current frame (dsn_set_frame / dsn_set_pose: the frame code of the
+ * density is the frame state's), from three float32 axis arrays x [nx], y [ny], z [nz]:
+ *   volume [nx, ny, nz] float32, point n = (i ny + j) nz + k = (x[i], y[j], z[k]) (torch.meshgrid + vstack(...).T order);
+ *   transparent points 0, the others sigma of the split-fp16 density-only kernel (bit-identical to dsn_field_forward's sigma where
+ *   that does not flag; flagged points are re-evaluated by the exact-fp32 kernel).  DSN_FIELD_FP32: the exact-fp32 kernel for all,
+ *   i.e. the bits of dsn_warp + dsn_field(density only) + zeroing.  DSN_NN_EXHAUSTIVE: the nearest-face cross-check.
+ * The grid runs in slabs of whole x-planes of at most slab_points points (>= ny nz); the scratch `workspace` of
+ * dsn_density_grid_workspace_bytes(slab_points) bytes does not grow with the grid, and the result does not depend on the slab size.
+ * Grids of up to 2^31 - 1 points. */
+DSN_EXPORT size_t dsn_density_grid_workspace_bytes(int64_t slab_points);
+DSN_EXPORT int dsn_density_grid(const void* scene, int V, int F, const void* packed, const float* x, int nx, const float* y, int ny,
+                                const float* z, int nz, int flags, float* volume, int64_t slab_points, void* workspace,
+                                size_t workspace_bytes, void* stream);
+/* utils/visualizer.py:112-142 get_mesh_from_grid (skimage.measure.marching_cubes): marching cubes over volume [nx, ny, nz] at the
+ * grid's own coordinates (axes x, y, z as above; every axis >= 2 points, fewer than 2^31 points).  The rule, fixed so that a numpy
+ * restatement reproduces it bit for bit:
+ *   - inside = v > level (strict; NaN is outside);
+ *   - one vertex per sign-changing grid edge (n, d): from point n to its neighbour along axis d (0 = x, 1 = y, 2 = z), edge id 3 n + d;
+ *     t = (level - a) / (b - a) with a the value at n; the coordinate along d is ax[i] + t * (ax[i + 1] - ax[i]), the other two are the
+ *     grid's (float32, no fused multiply-add);
+ *   - vertices in ascending edge id; triangles in ascending cell index (i (ny - 1) + j) (nz - 1) + k, then in table order;
+ *     vertex numbers int32 (2^31 or more vertices: the call fails);
+ *   - DSN_MC_DESCENT (object = values above the level): each triangle's normal (v1 - v0) x (v2 - v0) points out of the object;
+ *     DSN_MC_ASCENT (the reference visualizer's setting): every triangle reversed, (v2, v1, v0).
+ * Cube numbering of the case table: corner c = dx + 2 dy + 4 dz (bit set = +1 along that axis); the case's bit c is set when corner c is
+ * inside.  Edge e = 4 d + q runs along axis d; q = b1 + 2 b2 with b1, b2 the bits of its corners along the two other axes in increasing
+ * order (d = 0: y, z; d = 1: x, z; d = 2: x, y).  Per case: on each cube face the sign-changing edges are paired (an ambiguous face -
+ * diagonal corners inside - cuts each inside corner off on its own, so the two cells sharing a face cut the same segments); the
+ * segments close into loops; each loop is fanned from its lowest-numbered edge, loops in order of that edge.
+ * Two phases (the library never allocates): dsn_mc_count writes [n_verts, n_faces] (int64) to device memory and fills `workspace`
+ * (dsn_mc_workspace_bytes, <= 8 bytes per grid point); the caller reads the counts, sizes verts [n_verts, 3] float32 and
+ * faces [n_faces, 3] int32, and dsn_mc_emit fills them from the same workspace (no atomics: every call returns the same bits).
+ * A level the volume does not cross gives 0 and 0 (the reference returns None). */
+#define DSN_MC_DESCENT 0
+#define DSN_MC_ASCENT 1
+#define DSN_MC_MAX_TRI 5                              /* triangles per case, at most */
+#define DSN_MC_TABLE_ROW (1 + 3 * DSN_MC_MAX_TRI)     /* int32 per case in dsn_mc_table_host: count, then edge triples (-1 padded) */
+DSN_EXPORT size_t dsn_mc_workspace_bytes(int nx, int ny, int nz);
+DSN_EXPORT int dsn_mc_count(const float* volume, int nx, int ny, int nz, float level, void* workspace, int64_t* out_counts2,
+                            void* stream);
+DSN_EXPORT int dsn_mc_emit(const float* volume, int nx, int ny, int nz, const float* x, const float* y, const float* z, float level,
+                           int gradient_direction, const void* workspace, int64_t n_verts, int64_t n_faces, float* verts,
+                           int32_t* faces, void* stream);
+/* the case table (host function, no device work): 256 rows of DSN_MC_TABLE_ROW int32 into a HOST array of out_ints >= 256 rows */
+DSN_EXPORT int dsn_mc_table_host(int32_t* out_host, size_t out_ints);
+
 /* diagnostics, NOT for the hot path (synchronises `stream`): {ncell, ok, total entries, capacity} of the four
  * nearest-face list levels (world fine/coarse, canonical fine/coarse) into a HOST array of 16 int32. */
 DSN_EXPORT int dsn_debug_nn_stats(const void* scene, int V, int F, int32_t* out16_host, void* stream);
