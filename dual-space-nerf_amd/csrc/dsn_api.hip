@@ -1036,7 +1036,7 @@ int dsn_render_rays_train_ex(const void* scene, int V, int F, const void* packed
     } else if (far_search) search_far();
     dsn_launch_normal(s, c.x_c, c.grad, N, c.list1, c.rowcnt, c.idx_c, c.n_w, exh, st, nn_far);
     dsn_launch_light16((const float*)packed, s.frame, c.n_w, nullptr, ray_o, ray_d, z, c.essence, N, S, c.list1, c.rowcnt, w.colour, st,
-                       c.hl1, c.hl2, c.pre);
+                       c.hl1, c.hl2, c.pre, w.count + DSN_CNT_RANGE);
     // (a colour is read only where relu(density + noise) > 0: skipped rows never are)
     dsn_launch_composite(w.colour, c.sigma, c.transparent, z, ray_d, noise, R, S, out_rgb, out_disp, out_acc, out_weights,
                          out_depth, st, true);

@@ -233,6 +233,7 @@ enum {
     OFF_SCAL = OFF_WLT2 + 128,             // [0]=density bias, [1..3]=rgb3 bias, [4]=lights_encoding.4 bias,
                                            // [5]=margin of the density screen (default / dsn_calibrate_screen, k_screen16)
                                            // [6]=colour scale of the early-stop threshold (1 / dsn_set_early_stop_colour_scale)
+                                           // [7], [8]=split-unsafe words of the trunk / lighting images (DSN_SPLIT_UNSAFE_*)
     // raw (unpacked) copies used by the per-frame setup kernel
     OFF_RAW_W0 = OFF_SCAL + 64,            // stage1.0.weight [256,87]
     OFF_RAW_B0 = OFF_RAW_W0 + 256 * 87,    // stage1.0.bias [256]
@@ -251,6 +252,12 @@ enum {
     DSN_STREAM_BLOCKS_ALL = OFF_B1 / DSN_BLK,     // 892: + lights_encoding.0 (4) and .2 (16) for k_light16
     OFF_END = OFF16_BASE + DSN_STREAM_BLOCKS_ALL * DSN_BLK
 };
+// Split-unsafe words (written by the packer, dsn_field.hip): 0, or +inf when a weight is too large for the split-fp16 images -
+// a non-finite image halfword (forward trunk / rgb head: |w| > 1023.5; transposed and lighting images: |w| >= 32 784) or a
+// density-head weight whose reverse-pass seed |w| / 64 reaches the scaled split's 32 768.  The split-fp16 kernels start their
+// range guard's running maximum at the word, so such a parameter set takes the exact-fp32 path for every sample.
+#define DSN_SPLIT_UNSAFE_FIELD (OFF_SCAL + 7)
+#define DSN_SPLIT_UNSAFE_LIGHT (OFF_SCAL + 8)
 // Position (in halfwords) of halfword hw (0..2047) of split-fp16 stream block gb.  The 872 trunk blocks are stored
 // chunk-major: a chunk = 8 consecutive blocks = 32 KB, laid out [quarter q = hw >> 9 (hi/lo of k-step 0, hi/lo of k-step 1)]
 // [block in chunk][512 halfwords], so that the 8 one-KB pieces one wave moves per chunk are contiguous - in memory AND in the

@@ -2,7 +2,7 @@
 //
 //   k_field : positional encoding -> stage1 -> stage2 -> density / colour heads AND the analytic
 //             reverse pass d sigma / d x_c (model/spacenet.py:93-148 + :301-311), one launch.
-//   k_light : LightingMLP (model/spacenet.py:174-188, :254-265).
+//   (k_light, the exact-fp32 LightingMLP, lives beside k_light16 in dsn_field16.hip: its MLP is also k_light16's range fallback)
 //
 // Formulation (CDNA4-first, not a GEMM library call): everything is computed TRANSPOSED,
 //   H_out^T [features x points] = W [features x k] * H_in^T [k x points],
@@ -138,19 +138,33 @@ __host__ __device__ inline _Float16 dsn_pack_value16(const DsnImageX& x, const f
 }
 
 __global__ void k_pack_params(DsnParamPtrs pp, float* __restrict__ packed) {
+    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) { packed[DSN_SPLIT_UNSAFE_FIELD] = 0.0f; packed[DSN_SPLIT_UNSAFE_LIGHT] = 0.0f; }
     const DsnImageX x = g_images[blockIdx.y];
     const float* src = pp.p[x.im.src];
     for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < x.im.count; e += gridDim.x * blockDim.x)
         packed[x.im.dst + e] = dsn_pack_value(x, src, e);
 }
 
-// split-fp16 stream: image i (first 15 table entries, stream order) owns blocks [dst/DSN_BLK, (dst+count)/DSN_BLK)
-__global__ void k_pack_params16(DsnParamPtrs pp, _Float16* __restrict__ dst16) {
+// the split-unsafe word an image's halfwords report to (dsn_common.h): the lighting images behind the trunk stream have their own
+__host__ __device__ inline int dsn_unsafe_word(const DsnImageX& x) { return x.im.dst >= OFF_LT0 ? DSN_SPLIT_UNSAFE_LIGHT : DSN_SPLIT_UNSAFE_FIELD; }
+// reverse-pass seed of k_field16 (density-head weight / 64, split with lo * 2^12): |w| below 2^21 keeps it inside 32 768
+__host__ __device__ inline bool dsn_seed_unsafe(float w) { return !(fabsf(w) < 2097152.0f); }
+
+// split-fp16 stream: image i (first 17 table entries, stream order) owns blocks [dst/DSN_BLK, (dst+count)/DSN_BLK).
+// Runs behind k_pack_params (same stream), which has cleared the split-unsafe words.
+__global__ void k_pack_params16(DsnParamPtrs pp, float* __restrict__ packed) {
+    _Float16* dst16 = reinterpret_cast<_Float16*>(packed + OFF16_BASE);
     const DsnImageX x = g_images[blockIdx.y];
     const float* src = pp.p[x.im.src];
     const int nblk = x.im.count / DSN_BLK, b0 = x.im.dst / DSN_BLK;
-    for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < nblk * 2048; e += gridDim.x * blockDim.x)
-        dst16[dsn_stream16_index(b0 + e / 2048, e % 2048)] = dsn_pack_value16(x, src, e / 2048, e % 2048);
+    bool unsafe = false;
+    for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < nblk * 2048; e += gridDim.x * blockDim.x) {
+        const _Float16 h = dsn_pack_value16(x, src, e / 2048, e % 2048);
+        unsafe |= !__builtin_isfinite((float)h);
+        dst16[dsn_stream16_index(b0 + e / 2048, e % 2048)] = h;
+    }
+    if (blockIdx.y == 0 && blockIdx.x == 0) unsafe |= dsn_seed_unsafe(pp.p[P_DEN_W][threadIdx.x]);      // (256 threads, 256 weights)
+    if (unsafe) packed[dsn_unsafe_word(x)] = __builtin_inff();
 }
 #define DSN_NUM_STREAM_IMAGES 17
 
@@ -162,20 +176,27 @@ void dsn_pack_params_host(const float* const* params33_host, float* packed_host)
         for (int e = 0; e < x.im.count; ++e) packed_host[x.im.dst + e] = dsn_pack_value(x, src, e);
     }
     _Float16* d16 = reinterpret_cast<_Float16*>(packed_host + OFF16_BASE);
+    packed_host[DSN_SPLIT_UNSAFE_FIELD] = 0.0f;
+    packed_host[DSN_SPLIT_UNSAFE_LIGHT] = 0.0f;
     for (int i = 0; i < DSN_NUM_STREAM_IMAGES; ++i) {
         const DsnImageX x = h_images[i];
         const float* src = params33_host[x.im.src];
         const int nblk = x.im.count / DSN_BLK, b0 = x.im.dst / DSN_BLK;
-        for (int e = 0; e < nblk * 2048; ++e) d16[dsn_stream16_index(b0 + e / 2048, e % 2048)] = dsn_pack_value16(x, src, e / 2048, e % 2048);
+        for (int e = 0; e < nblk * 2048; ++e) {
+            const _Float16 h = dsn_pack_value16(x, src, e / 2048, e % 2048);
+            if (!__builtin_isfinite((float)h)) packed_host[dsn_unsafe_word(x)] = __builtin_inff();
+            d16[dsn_stream16_index(b0 + e / 2048, e % 2048)] = h;
+        }
     }
+    for (int i = 0; i < 256; ++i)
+        if (dsn_seed_unsafe(params33_host[P_DEN_W][i])) packed_host[DSN_SPLIT_UNSAFE_FIELD] = __builtin_inff();
 }
 
 void dsn_launch_pack_params(const float* const* params33, float* packed, hipStream_t st) {
     DsnParamPtrs pp;
     for (int i = 0; i < DSN_NUM_PARAMS_INTERNAL; ++i) pp.p[i] = params33[i];
     hipLaunchKernelGGL(k_pack_params, dim3(64, DSN_NUM_IMAGES), dim3(256), 0, st, pp, packed);
-    hipLaunchKernelGGL(k_pack_params16, dim3(64, DSN_NUM_STREAM_IMAGES), dim3(256), 0, st, pp,
-                       reinterpret_cast<_Float16*>(packed + OFF16_BASE));
+    hipLaunchKernelGGL(k_pack_params16, dim3(64, DSN_NUM_STREAM_IMAGES), dim3(256), 0, st, pp, packed);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -484,95 +505,4 @@ void dsn_launch_field_fix(const float* packed, const DsnFrameState* fs, const fl
     if (blocks > dsn_cu_count_raw()) blocks = dsn_cu_count_raw();
     hipLaunchKernelGGL(k_field<true>, dim3((unsigned)blocks), dim3(FIELD_THREADS), 0, st, packed, fs, x_c, N, active_list,
                        active_count, sigma, essence, grad, flag_count);
-}
-
-// ---------------------------------------------------------------------------------------------
-// k_light : model/spacenet.py:254-265 (rotation / light-centre edits) + :174-188 LightingMLP
-// ---------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(FIELD_THREADS, 1)
-k_light(const float* __restrict__ packed, const DsnFrameState* __restrict__ fs, const float* __restrict__ n_w,
-        const float* __restrict__ x_w_pts, const float* __restrict__ ray_o, const float* __restrict__ ray_d,
-        const float* __restrict__ z_vals, const float* essence, int64_t N, int S,
-        const int32_t* __restrict__ active_list, const int32_t* __restrict__ active_count,
-        float* colour) {      // (essence and colour may be the same array: see k_light16)
-    // (round 6: the exact-fp32 twin of k_light16 was the one matrix kernel nobody had measured beside other streams'
-    //  kernels - tests/test_guard_coverage.py; it is the calibration / fallback path, so it simply takes the guard)
-    DSN_OWN_SIMD();
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int half = lane >> 5;
-    const int64_t count = active_list ? (int64_t)(*active_count) : N;
-    const int64_t slot0 = ((int64_t)blockIdx.x * 4 + wave) * 32;
-    if (slot0 >= count) return;
-    int64_t slot = slot0 + (lane & 31);
-    const bool valid = slot < count;
-    if (!valid) slot = count - 1;
-    const int64_t pt = active_list ? (int64_t)active_list[slot] : slot;
-    const int64_t ray = pt / S;
-
-    float in9[10];
-    in9[0] = n_w[3 * pt]; in9[1] = n_w[3 * pt + 1]; in9[2] = n_w[3 * pt + 2];
-    float xw[3];
-    const float d[3] = {ray_d[3 * ray], ray_d[3 * ray + 1], ray_d[3 * ray + 2]};
-    if (x_w_pts) { xw[0] = x_w_pts[3 * pt]; xw[1] = x_w_pts[3 * pt + 1]; xw[2] = x_w_pts[3 * pt + 2]; }
-    else {
-        const float z = z_vals[pt];
-        xw[0] = ray_o[3 * ray] + d[0] * z; xw[1] = ray_o[3 * ray + 1] + d[1] * z; xw[2] = ray_o[3 * ray + 2] + d[2] * z;
-    }
-    dsn_light_edit(fs->light, xw);
-    in9[3] = xw[0]; in9[4] = xw[1]; in9[5] = xw[2];
-    const float vn = dsn_norm3(d);
-    in9[6] = dsn_div(d[0], vn); in9[7] = dsn_div(d[1], vn); in9[8] = dsn_div(d[2], vn);
-    in9[9] = 0.0f;
-
-    // layer 0: 9 -> 128 (5 k-steps: low lanes feature 2s, high lanes 2s+1)
-    f32x16 h1[4], h2[4];
-#pragma unroll
-    for (int m = 0; m < 4; ++m) {
-        f32x16 acc = dsn_load_rows(packed + OFF_BLT0, m, half);
-        const float4* wp = reinterpret_cast<const float4*>(packed + OFF_LT0 + m * DSN_BLK) + lane;
-        const float4 w0 = wp[0], w1 = wp[64];
-        acc = DSN_MFMA(w0.x, half ? in9[1] : in9[0], acc);
-        acc = DSN_MFMA(w0.y, half ? in9[3] : in9[2], acc);
-        acc = DSN_MFMA(w0.z, half ? in9[5] : in9[4], acc);
-        acc = DSN_MFMA(w0.w, half ? in9[7] : in9[6], acc);
-        acc = DSN_MFMA(w1.x, half ? in9[9] : in9[8], acc);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[r] = acc[r] > 0.0f ? acc[r] : 0.0f;
-        h1[m] = acc;
-    }
-    DsnWStream ws;
-    ws.seek(packed + OFF_LT1, lane);
-#pragma unroll
-    for (int m = 0; m < 4; ++m) {
-        f32x16 acc = dsn_load_rows(packed + OFF_BLT1, m, half);
-        acc = dsn_dense<4>(ws, h1, acc);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[r] = acc[r] > 0.0f ? acc[r] : 0.0f;
-        h2[m] = acc;
-    }
-    float part = 0.0f;
-#pragma unroll
-    for (int m = 0; m < 4; ++m) {
-        const f32x16 w = dsn_load_rows(packed + OFF_WLT2, m, half);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) part = fmaf(w[r], h2[m][r], part);
-    }
-    part += __shfl_xor(part, 32);
-    const float o = part + packed[OFF_SCAL + 4];
-    const float wgt = (o > 0.0f ? o : expm1f(o)) + 1.0f;   // ELU(alpha=1) + 1
-    if (valid && half == 0) {
-        colour[3 * pt + 0] = wgt * essence[3 * pt + 0];
-        colour[3 * pt + 1] = wgt * essence[3 * pt + 1];
-        colour[3 * pt + 2] = wgt * essence[3 * pt + 2];
-    }
-}
-
-void dsn_launch_light(const float* packed, const DsnFrameState* fs, const float* n_w, const float* x_w,
-                      const float* ray_o, const float* ray_d, const float* z_vals, const float* essence, int64_t N,
-                      int S, const int32_t* active_list, const int32_t* active_count, float* colour, hipStream_t st) {
-    int64_t blocks = (N + FIELD_PTS_PER_BLOCK - 1) / FIELD_PTS_PER_BLOCK;
-    if (blocks == 0) return;
-    hipLaunchKernelGGL(k_light, dim3((unsigned)blocks), dim3(FIELD_THREADS), 0, st, packed, fs, n_w, x_w, ray_o, ray_d,
-                       z_vals, essence, N, S, active_list, active_count, colour);
 }

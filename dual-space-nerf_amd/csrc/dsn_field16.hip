@@ -8,11 +8,16 @@
 // W_lo x_lo term is 2^-24 relative - the size of one fp32 rounding.  Measured against the float64
 // reference this is as accurate as the reference's own float32 run (tests/test_gpu_stages.py::test_field;
 // sigma 8e-6 abs).  Plain bf16 / fp16 inputs miss the 1e-4 bar by 10x, bf16 2-way split by 1.4x.
-// Range: the reverse pass runs on g * 2^-6 (exact rescale at the end) so that |g| up to 4e6 stays
-// inside fp16; forward activations must stay below 65504 (they are O(10) for NeRF trunks).  Every epilogue keeps a
-// running maximum of the values it splits (one v_max3 per two elements); a sample that reaches F16_RANGE anywhere is
-// FLAGGED: its sigma is written as NaN and the exact-fp32 kernel re-evaluates it (dsn_launch_field_fix, dsn_field.hip) -
-// checkpoints whose activations or adjoints leave the fp16 range render correctly, only slower (tests/test_gpu_round2.py: test_fp16_range_fallback_*).
+// Range: the reverse pass runs on g * 2^-6 (exact rescale at the end).  Its split carries lo * 2^12, and for |v| >= 32 768
+// the residual v - hi reaches 16, so lo = 65 536 is inf in fp16: scaled splits hold |v| < F16_RANGE_SCALED = 32 768
+// (sigma-adjoints below about 2.1e6).  Forward activations (unscaled split) must stay below F16_RANGE = 65 000 (they
+// are O(10) for NeRF trunks).  Every epilogue keeps a running maximum of the values it splits (one v_max3 per two
+// elements); a sample whose forward maximum reaches F16_RANGE, or whose reverse-pass maximum reaches F16_RANGE_SCALED,
+// is FLAGGED: its sigma is written as NaN and the exact-fp32 kernel re-evaluates it (dsn_launch_field_fix, dsn_field.hip).
+// Weights: the forward images hold fp16(64 w), so |w| <= 1023.5; the packer writes +inf into packed[OFF_SCAL + 7]
+// (DSN_SPLIT_UNSAFE_FIELD) when any image halfword is not finite, and every kernel here starts its running maximum there,
+// which flags every sample.  Checkpoints whose activations, adjoints or weights leave the fp16 range render correctly,
+// only slower (tests/test_gpu_round2.py: test_fp16_range_fallback_*, tests/test_gpu_f16_range.py).
 //
 // Structure.  Same transposed formulation and register chaining as k_field (dsn_field.hip): one
 // wavefront owns 32 points, the accumulator layout of the 32x32 MFMA is re-used as the next
@@ -88,7 +93,8 @@ typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 #define F16_CHUNK 8              // blocks per ring barrier; the ring holds two chunks (fixed: the DMA immediates span one chunk)
 #define F16_RING_SLOTS (2 * F16_CHUNK)
 #define F16_NCHUNK (DSN_STREAM_BLOCKS / F16_CHUNK)   // 109
-#define F16_RANGE 65000.0f                           // |value| an epilogue may hand to the fp16 split (fp16 max 65504)
+#define F16_RANGE 65000.0f                           // |value| an epilogue may hand to the unscaled fp16 split (fp16 max 65504)
+#define F16_RANGE_SCALED 32768.0f                    // ... to the split whose lo carries 2^12 (lo of |v| >= 32 784 overflows)
 #define F16_GSCALE 0.015625f                         // reverse pass runs on g / 64
 #define F16_GUNSCALE 64.0f
 
@@ -714,7 +720,8 @@ k_field16(const float* __restrict__ packed, const DsnFrameState* __restrict__ fs
 #define MK_LOAD(L, mk) { mk[0] = s_mask[L][0][tid]; mk[1] = s_mask[L][1][tid]; mk[2] = s_mask[L][2][tid]; mk[3] = s_mask[L][3][tid]; }
     uint32_t mk[4];
     half8 ah[8][2], al[8][2], bh[8][2], bl[8][2];
-    float ovf = 0.0f;          // range guard: running max of |value| over everything this lane splits into fp16
+    float ovf = packed[DSN_SPLIT_UNSAFE_FIELD];      // range guard: running max of |value| over everything this lane splits into fp16
+                                                     // (+inf for weights the images cannot hold: every sample flagged)
     // per-sample mask record: [half][layer] uint4, 224 B contiguous per sample
     // TRAIN: indexed by sample; BWD: by the slot of the list it walks; FWD: by the slot the sample gets on the sigma > 0 list (below)
     uint4* mrec = masks ? masks + ((size_t)(MODE == F16_BWD ? lslot : pt) * 2 + half) * 7 : nullptr;
@@ -827,6 +834,9 @@ k_field16(const float* __restrict__ packed, const DsnFrameState* __restrict__ fs
     const bool flag_fwd = !(fmaxf(ovf, __shfl_xor(ovf, 32)) < F16_RANGE);
     if (valid && half == 0) sigma[pt] = flag_fwd ? dsn_nan_flag() : sg;
     if (MODE != F16_TRAIN && flag_fwd && valid && half == 0 && flag_count) atomicAdd(flag_count, 1);
+    // the reverse pass's tighter threshold applies to what IT splits: the forward maximum goes on as the flag alone (so that a
+    // forward activation in [F16_RANGE_SCALED, F16_RANGE) flags here no more than in the two-launch form)
+    ovf = flag_fwd ? __builtin_inff() : 0.0f;
     if (MODE == F16_DEN) { __syncthreads(); continue; }      // (tile done: every wave has read its last weight block)
     bool write_rec = ST && valid;
     if (MODE == F16_FWD) {
@@ -982,8 +992,8 @@ k_field16(const float* __restrict__ packed, const DsnFrameState* __restrict__ fs
             grad[3 * pt] = g[0] * F16_GUNSCALE; grad[3 * pt + 1] = g[1] * F16_GUNSCALE; grad[3 * pt + 2] = g[2] * F16_GUNSCALE;
         }
     }
-    // range guard, reverse half (ovf still holds the forward maximum in the single-launch modes)
-    const bool flagged = !(fmaxf(ovf, __shfl_xor(ovf, 32)) < F16_RANGE);
+    // range guard, reverse half (ovf started at +inf for a sample the forward half flagged, in the single-launch modes)
+    const bool flagged = !(fmaxf(ovf, __shfl_xor(ovf, 32)) < F16_RANGE_SCALED);
     if (flagged && valid && half == 0) {
         if (MODE == F16_TRAIN) { if (pos_count) atomicAdd(pos_count, 1); }    // training: counted, reported by the host mirror
         else { sigma[pt] = dsn_nan_flag(); if (flag_count) atomicAdd(flag_count, 1); }
@@ -1179,7 +1189,7 @@ k_tangent16(const float* __restrict__ packed, const float* __restrict__ x_c, con
     const float inv = sc > 0.0f ? 0.015625f / sc : 0.0f;
     for (int c = 0; c < 3; ++c) ua[c] = sc > 0.0f ? ua[c] * inv : 0.0f;
     sc *= 64.0f;                                  // what the stored outputs are multiplied back by
-    float ovf = 0.0f;                             // range guard: running max of |value| over everything this lane splits into fp16
+    float ovf = packed[DSN_SPLIT_UNSAFE_FIELD];   // range guard: running max of |value| over everything this lane splits into fp16
     if (gmax) {      // batch-wide magnitude of the outputs (bit pattern of a non-negative float orders like the float)
         float wm = valid ? sc * 0.015625f : 0.0f;
 #pragma unroll
@@ -1368,7 +1378,7 @@ k_adjoint16(const float* __restrict__ packed, int64_t N, const uint4* __restrict
     float* const ta = valid ? tr_a + pt * 256 + 4 * half : nullptr;
 #define AMK_LOAD(L, mk) { mk[0] = s_mask[L][0][tid]; mk[1] = s_mask[L][1][tid]; mk[2] = s_mask[L][2][tid]; mk[3] = s_mask[L][3][tid]; }
     uint32_t mk[4];
-    float ovf = 0.0f;          // range guard: the seed is normalised, what the six transposed layers make of it is not bounded
+    float ovf = packed[DSN_SPLIT_UNSAFE_FIELD];      // range guard: the seed is normalised, what the six transposed layers make of it is not bounded
     AMK_LOAD(5, mk) layer16_bwd<true>(w, blk, lane, ah, al, bh, bl, mk, ovf, ta ? ta + 5 * ls : nullptr, sc);
     AMK_LOAD(4, mk) layer16_bwd<true>(w, blk, lane, bh, bl, ah, al, mk, ovf, ta ? ta + 4 * ls : nullptr, sc);
     AMK_LOAD(3, mk)
@@ -1391,7 +1401,7 @@ k_adjoint16(const float* __restrict__ packed, int64_t N, const uint4* __restrict
     AMK_LOAD(1, mk) layer16_bwd<true>(w, blk, lane, ah, al, bh, bl, mk, ovf, ta ? ta + 1 * ls : nullptr, sc);
     AMK_LOAD(0, mk) layer16_bwd<true>(w, blk, lane, bh, bl, ah, al, mk, ovf, ta ? ta + 0 * ls : nullptr, sc);
 #undef AMK_LOAD
-    if (!(fmaxf(ovf, __shfl_xor(ovf, 32)) < F16_RANGE) && ta) {
+    if (!(fmaxf(ovf, __shfl_xor(ovf, 32)) < F16_RANGE_SCALED) && ta) {
         zero_train_rows(ta, ls, 6);
         if (half == 0 && range_count) atomicAdd(range_count, 1);
     }
@@ -1665,7 +1675,7 @@ k_screen16(const float* __restrict__ packed, const DsnFrameState* __restrict__ f
     // range guard: the last layer's activations are fp32 here, every earlier one went through `ovf`
     float omax = fmaxf((float)ovf[0], (float)ovf[1]);
     omax = fmaxf(omax, __shfl_xor(omax, 32));
-    const bool in_range = omax < F16_RANGE;              // false for inf (and for the NaN an inf times 0 leaves)
+    const bool in_range = fmaxf(omax, packed[DSN_SPLIT_UNSAFE_FIELD]) < F16_RANGE;   // false for inf (and for the NaN an inf times 0 leaves)
     const bool mine = valid && half == 0;
     // margin: packed[OFF_SCAL + 5] - the conservative default written by dsn_pack_params (F16_SCREEN_REL) or the value
     // dsn_calibrate_screen measured for THESE parameters (10x the largest deviation seen, +inf = never declare anything
@@ -1917,7 +1927,7 @@ k_screen16x2(const float* __restrict__ packed, const DsnFrameState* __restrict__
     // samples: an overflow in either keeps both for the accurate pass - conservative)
     float omax = fmaxf((float)ovf[0], (float)ovf[1]);
     omax = fmaxf(omax, __shfl_xor(omax, 32));
-    const bool in_range = omax < F16_RANGE;
+    const bool in_range = fmaxf(omax, packed[DSN_SPLIT_UNSAFE_FIELD]) < F16_RANGE;
     const float bd = s_vec[2560];
     const float margin = margin_override > 0.0f ? margin_override : s_vec[2560 + 5];
     bool keep[2];
@@ -2139,6 +2149,122 @@ void dsn_launch_set_packed_scalar(float* packed, int word, float v, hipStream_t 
 }
 
 // ---------------------------------------------------------------------------------------------
+// dsn_light_mlp32 : the LightingMLP (model/spacenet.py:174-188) of a wave's 32 samples in exact fp32 (v_mfma_f32_32x32x2_f32, the
+// k-ordered fma chain of dsn_field.hip): in9 = [n_w, x_w, d/|d|, 0] of this lane's sample -> the pre-activation of the output
+// (both halves of the wave hold it).  The whole of k_light's arithmetic, and k_light16's range fallback: a sample its guard flags
+// gets exactly k_light's bits.  The weight images are the fp32 ones of dsn_pack_params (OFF_LT0 / OFF_LT1: 4 KB blocks, lane l's
+// k-steps at float4 l, l + 64, l + 128, l + 192), read straight from memory: this path is the exception.
+// ---------------------------------------------------------------------------------------------
+#define DSN_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x2f32((a), (b), (c), 0, 0, 0)
+__device__ __forceinline__ float dsn_light_mlp32(const float* __restrict__ packed, int lane, const float (&in9)[10]) {
+    const int half = lane >> 5;
+    // layer 0: 9 -> 128 (5 k-steps: low lanes feature 2s, high lanes 2s+1)
+    f32x16 h1[4], h2[4];
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+        f32x16 acc = rows16(packed + OFF_BLT0, m, half);
+        const float4* wp = reinterpret_cast<const float4*>(packed + OFF_LT0 + m * DSN_BLK) + lane;
+        const float4 w0 = wp[0], w1 = wp[64];
+        acc = DSN_MFMA(w0.x, half ? in9[1] : in9[0], acc);
+        acc = DSN_MFMA(w0.y, half ? in9[3] : in9[2], acc);
+        acc = DSN_MFMA(w0.z, half ? in9[5] : in9[4], acc);
+        acc = DSN_MFMA(w0.w, half ? in9[7] : in9[6], acc);
+        acc = DSN_MFMA(w1.x, half ? in9[9] : in9[8], acc);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] = acc[r] > 0.0f ? acc[r] : 0.0f;
+        h1[m] = acc;
+    }
+    // layer 1: 128 -> 128, blocks (m, kb) in stream order, 16 k-steps each
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+        f32x16 acc = rows16(packed + OFF_BLT1, m, half);
+#pragma unroll
+        for (int kb = 0; kb < 4; ++kb) {
+            const float4* bp = reinterpret_cast<const float4*>(packed + OFF_LT1 + (m * 4 + kb) * DSN_BLK) + lane;
+            const float4 c0 = bp[0], c1 = bp[64], c2 = bp[128], c3 = bp[192];
+            acc = DSN_MFMA(c0.x, h1[kb][0], acc);  acc = DSN_MFMA(c0.y, h1[kb][1], acc);
+            acc = DSN_MFMA(c0.z, h1[kb][2], acc);  acc = DSN_MFMA(c0.w, h1[kb][3], acc);
+            acc = DSN_MFMA(c1.x, h1[kb][4], acc);  acc = DSN_MFMA(c1.y, h1[kb][5], acc);
+            acc = DSN_MFMA(c1.z, h1[kb][6], acc);  acc = DSN_MFMA(c1.w, h1[kb][7], acc);
+            acc = DSN_MFMA(c2.x, h1[kb][8], acc);  acc = DSN_MFMA(c2.y, h1[kb][9], acc);
+            acc = DSN_MFMA(c2.z, h1[kb][10], acc); acc = DSN_MFMA(c2.w, h1[kb][11], acc);
+            acc = DSN_MFMA(c3.x, h1[kb][12], acc); acc = DSN_MFMA(c3.y, h1[kb][13], acc);
+            acc = DSN_MFMA(c3.z, h1[kb][14], acc); acc = DSN_MFMA(c3.w, h1[kb][15], acc);
+        }
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] = acc[r] > 0.0f ? acc[r] : 0.0f;
+        h2[m] = acc;
+    }
+    float part = 0.0f;
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+        const f32x16 w = rows16(packed + OFF_WLT2, m, half);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) part = fmaf(w[r], h2[m][r], part);
+    }
+    part += __shfl_xor(part, 32);
+    return part + packed[OFF_SCAL + 4];
+}
+
+// ---------------------------------------------------------------------------------------------
+// k_light : model/spacenet.py:254-265 (rotation / light-centre edits) + :174-188 LightingMLP
+// ---------------------------------------------------------------------------------------------
+#define LIGHT32_THREADS 256      // k_light: 4 waves of 32 samples per workgroup (one tile, no persistent loop)
+__global__ void __launch_bounds__(LIGHT32_THREADS, 1)
+k_light(const float* __restrict__ packed, const DsnFrameState* __restrict__ fs, const float* __restrict__ n_w,
+        const float* __restrict__ x_w_pts, const float* __restrict__ ray_o, const float* __restrict__ ray_d,
+        const float* __restrict__ z_vals, const float* essence, int64_t N, int S,
+        const int32_t* __restrict__ active_list, const int32_t* __restrict__ active_count,
+        float* colour) {      // (essence and colour may be the same array: see k_light16)
+    // (round 6: the exact-fp32 twin of k_light16 was the one matrix kernel nobody had measured beside other streams'
+    //  kernels - tests/test_guard_coverage.py; it is the calibration / fallback path, so it simply takes the guard)
+    DSN_OWN_SIMD();
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int half = lane >> 5;
+    const int64_t count = active_list ? (int64_t)(*active_count) : N;
+    const int64_t slot0 = ((int64_t)blockIdx.x * 4 + wave) * 32;
+    if (slot0 >= count) return;
+    int64_t slot = slot0 + (lane & 31);
+    const bool valid = slot < count;
+    if (!valid) slot = count - 1;
+    const int64_t pt = active_list ? (int64_t)active_list[slot] : slot;
+    const int64_t ray = pt / S;
+
+    float in9[10];
+    in9[0] = n_w[3 * pt]; in9[1] = n_w[3 * pt + 1]; in9[2] = n_w[3 * pt + 2];
+    float xw[3];
+    const float d[3] = {ray_d[3 * ray], ray_d[3 * ray + 1], ray_d[3 * ray + 2]};
+    if (x_w_pts) { xw[0] = x_w_pts[3 * pt]; xw[1] = x_w_pts[3 * pt + 1]; xw[2] = x_w_pts[3 * pt + 2]; }
+    else {
+        const float z = z_vals[pt];
+        xw[0] = ray_o[3 * ray] + d[0] * z; xw[1] = ray_o[3 * ray + 1] + d[1] * z; xw[2] = ray_o[3 * ray + 2] + d[2] * z;
+    }
+    dsn_light_edit(fs->light, xw);
+    in9[3] = xw[0]; in9[4] = xw[1]; in9[5] = xw[2];
+    const float vn = dsn_norm3(d);
+    in9[6] = dsn_div(d[0], vn); in9[7] = dsn_div(d[1], vn); in9[8] = dsn_div(d[2], vn);
+    in9[9] = 0.0f;
+
+    const float o = dsn_light_mlp32(packed, lane, in9);
+    const float wgt = (o > 0.0f ? o : expm1f(o)) + 1.0f;   // ELU(alpha=1) + 1
+    if (valid && half == 0) {
+        colour[3 * pt + 0] = wgt * essence[3 * pt + 0];
+        colour[3 * pt + 1] = wgt * essence[3 * pt + 1];
+        colour[3 * pt + 2] = wgt * essence[3 * pt + 2];
+    }
+}
+
+void dsn_launch_light(const float* packed, const DsnFrameState* fs, const float* n_w, const float* x_w,
+                      const float* ray_o, const float* ray_d, const float* z_vals, const float* essence, int64_t N,
+                      int S, const int32_t* active_list, const int32_t* active_count, float* colour, hipStream_t st) {
+    int64_t blocks = (N + 127) / 128;
+    if (blocks == 0) return;
+    hipLaunchKernelGGL(k_light, dim3((unsigned)blocks), dim3(LIGHT32_THREADS), 0, st, packed, fs, n_w, x_w, ray_o, ray_d,
+                       z_vals, essence, N, S, active_list, active_count, colour);
+}
+
+// ---------------------------------------------------------------------------------------------
 // k_light16 : model/spacenet.py:254-265 + :174-188 LightingMLP with the same split-fp16 products.
 // 9 -> 128 -> 128 -> 1 per point; the 20 weight blocks (80 KB) are L1/L2-resident, so every wave reads its
 // operands straight from memory (no LDS ring: the matrix work per point is 50x smaller than the trunk's).
@@ -2204,15 +2330,23 @@ __device__ __forceinline__ void light16_fetch(int64_t p, int S, const float* __r
 }
 // The MLP of one sample: in9 = [n_w, x_w (light edit applied), d/|d|, 0] -> the pre-activation o of the output.  tr_hl1 / tr_hl2
 // (optional, training forward): the two hidden layers after their ReLU, row-major [N,128], stored for pt where valid.
+// Range guard: both split operands (the input and the first hidden layer; the second one feeds fp32 dots) carry lo * 2^12, so a
+// sample whose running maximum reaches F16_RANGE_SCALED - or any sample when the lighting images cannot hold the weights
+// (DSN_SPLIT_UNSAFE_LIGHT) - is FLAGGED and gets k_light's exact-fp32 value (dsn_light_mlp32) instead: one extra fp32 MLP per wave
+// that holds a flagged sample, nothing otherwise.  (A runtime guard and not an a-priori bound from the weights: the world point
+// of the input has no bound the weights know of.)  The stored hidden layers stay the split ones: training counts such samples.
 __device__ __forceinline__ float light16_mlp(const float* __restrict__ packed, const char* s_w, int lane, const float (&in9)[10],
-                                             bool valid, int64_t pt, float* __restrict__ tr_hl1, float* __restrict__ tr_hl2) {
+                                             bool valid, int64_t pt, float* __restrict__ tr_hl1, float* __restrict__ tr_hl2,
+                                             bool& flagged) {
     const int half = lane >> 5;
+    float ovf = packed[DSN_SPLIT_UNSAFE_LIGHT];
     // input operand: k-slot j of step 0 holds feature 2j + half (j < 5), zero beyond
     half8 xh[2], xl[2];
     {
         f32x16 v = zero16();
 #pragma unroll
         for (int j = 0; j < 5; ++j) v[j] = half ? in9[2 * j + 1] : in9[2 * j];
+        track16(ovf, v);
         split16<true>(v, xh, xl);
     }
     half8 h1h[4][2], h1l[4][2];
@@ -2224,6 +2358,7 @@ __device__ __forceinline__ float light16_mlp(const float* __restrict__ packed, c
 #pragma unroll
         for (int r = 0; r < 16; ++r) v[r] = fmaxf(v[r], 0.0f);
         if (tr_hl1 && valid) store16(tr_hl1 + pt * 128 + 4 * half + 32 * m, v, 1.0f);
+        track16(ovf, v);
         split16<true>(v, h1h[m], h1l[m]);
     }
     float part = 0.0f;
@@ -2240,7 +2375,13 @@ __device__ __forceinline__ float light16_mlp(const float* __restrict__ packed, c
         if (tr_hl2 && valid) store16(tr_hl2 + pt * 128 + 4 * half + 32 * m, v, 1.0f);
     }
     part += __shfl_xor(part, 32);
-    return part + packed[OFF_SCAL + 4];
+    float o = part + packed[OFF_SCAL + 4];
+    flagged = !(fmaxf(ovf, __shfl_xor(ovf, 32)) < F16_RANGE_SCALED);      // (inf and NaN flag too)
+    if (__ballot(flagged)) {
+        const float e = dsn_light_mlp32(packed, lane, in9);
+        if (flagged) o = e;
+    }
+    return o;
 }
 __device__ __forceinline__ float light16_weight(float o) { return (o > 0.0f ? o : expm1f(o)) + 1.0f; }   // ELU(alpha=1) + 1
 
@@ -2249,7 +2390,8 @@ k_light16(const float* __restrict__ packed, const DsnFrameState* __restrict__ fs
           const float* __restrict__ x_w_pts, const float* __restrict__ ray_o, const float* __restrict__ ray_d,
           const float* __restrict__ z_vals, const float* essence, int64_t N, int S,
           const int32_t* __restrict__ active_list, const int32_t* __restrict__ active_count,
-          float* colour, float* __restrict__ tr_hl1, float* __restrict__ tr_hl2, float* __restrict__ tr_pre) {
+          float* colour, float* __restrict__ tr_hl1, float* __restrict__ tr_hl2, float* __restrict__ tr_pre,
+          int32_t* __restrict__ range_count) {
     // (essence and colour may be the SAME array - the fused path's workspace keeps the colour where the essence was: a tile reads its
     //  samples' essences at its top and writes their colours at its end; hence no __restrict__ on the two)
     // tr_*: (training forward) light16_mlp's hidden layers, and the pre-activation of the output [N] - what the backward of the
@@ -2303,7 +2445,9 @@ k_light16(const float* __restrict__ packed, const DsnFrameState* __restrict__ fs
     in9[6] = dsn_div(d[0], vn); in9[7] = dsn_div(d[1], vn); in9[8] = dsn_div(d[2], vn);
     in9[9] = 0.0f;
 
-    const float o = light16_mlp(packed, s_w, lane, in9, valid, pt, tr_hl1, tr_hl2);
+    bool flagged;
+    const float o = light16_mlp(packed, s_w, lane, in9, valid, pt, tr_hl1, tr_hl2, flagged);
+    if (flagged && range_count && valid && half == 0) atomicAdd(range_count, 1);      // (training: its stored hidden layers are not exact)
     const float wgt = light16_weight(o);
     if (tr_pre && valid && half == 0) tr_pre[pt] = o;
     if (valid && half == 0) {
@@ -2317,12 +2461,12 @@ k_light16(const float* __restrict__ packed, const DsnFrameState* __restrict__ fs
 void dsn_launch_light16(const float* packed, const DsnFrameState* fs, const float* n_w, const float* x_w,
                         const float* ray_o, const float* ray_d, const float* z_vals, const float* essence, int64_t N,
                         int S, const int32_t* active_list, const int32_t* active_count, float* colour, hipStream_t st,
-                        float* tr_hl1, float* tr_hl2, float* tr_pre) {
+                        float* tr_hl1, float* tr_hl2, float* tr_pre, int32_t* range_count) {
     int64_t blocks = (N + 127) / 128;
     if (blocks == 0) return;
     // (one workgroup per compute unit since round 5: its waves own their SIMDs' register files, two no longer fit)
     hipLaunchKernelGGL(k_light16, dim3((unsigned)std::min<int64_t>(blocks, (int64_t)dsn_cu_count())), dim3(256), 0, st, packed, fs, n_w,
-                       x_w, ray_o, ray_d, z_vals, essence, N, S, active_list, active_count, colour, tr_hl1, tr_hl2, tr_pre);
+                       x_w, ray_o, ray_d, z_vals, essence, N, S, active_list, active_count, colour, tr_hl1, tr_hl2, tr_pre, range_count);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2388,7 +2532,8 @@ k_light16_multi(const float* __restrict__ packed, const DsnLightEdit* __restrict
         in9[3] = xw[0]; in9[4] = xw[1]; in9[5] = xw[2];
         in9[6] = vd[0]; in9[7] = vd[1]; in9[8] = vd[2];
         in9[9] = 0.0f;
-        const float wgt = light16_weight(light16_mlp(packed, s_w, lane, in9, valid, pt, nullptr, nullptr));
+        bool flagged;
+        const float wgt = light16_weight(light16_mlp(packed, s_w, lane, in9, valid, pt, nullptr, nullptr, flagged));
         if (valid && half == 0) {
             float* c = colours + ((int64_t)g * count + slot) * 3;
             c[0] = wgt * ess[0];

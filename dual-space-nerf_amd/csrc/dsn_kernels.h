@@ -97,7 +97,7 @@ void dsn_launch_set_packed_scalar(float* packed, int word, float v, hipStream_t 
 void dsn_launch_light16(const float* packed, const DsnFrameState* fs, const float* n_w, const float* x_w,
                         const float* ray_o, const float* ray_d, const float* z_vals, const float* essence, int64_t N,
                         int S, const int32_t* active_list, const int32_t* active_count, float* colour, hipStream_t st,
-                        float* tr_hl1 = nullptr, float* tr_hl2 = nullptr, float* tr_pre = nullptr);
+                        float* tr_hl1 = nullptr, float* tr_hl2 = nullptr, float* tr_pre = nullptr, int32_t* range_count = nullptr);
 // relighting sweep (dsn_render_rays_lights): lighting MLP of G light records per pass over the shading list -> colours [G][count][3]
 // by list slot; the list's slot of every sample (-1 elsewhere: the caller clears `slot`); the compositor of G lights through that map
 void dsn_launch_light16_multi(const float* packed, const DsnLightEdit* lights, int G, const float* n_w, const float* ray_o, const float* ray_d,
