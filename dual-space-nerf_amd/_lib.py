@@ -44,6 +44,7 @@ EXPORTS = [
     "dsn_render_rays_grad_ex", "dsn_render_rays_train_ex", "dsn_aux_create", "dsn_aux_destroy",
     "dsn_render_lights_scratch_bytes", "dsn_render_rays_lights", "dsn_image_ssim_workspace_bytes", "dsn_image_ssim",
     "dsn_density_grid_workspace_bytes", "dsn_density_grid", "dsn_mc_workspace_bytes", "dsn_mc_count", "dsn_mc_emit", "dsn_mc_table_host",
+    "dsn_render_maps_scratch_bytes", "dsn_render_rays_maps", "dsn_composite_maps", "dsn_shade_factor",
 ]
 
 SKIP_TRANSPARENT = 1
@@ -96,6 +97,8 @@ def lib():
             getattr(L, n).restype = C.c_size_t
         L.dsn_render_lights_scratch_bytes.restype = C.c_size_t
         L.dsn_render_lights_scratch_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int64]
+        L.dsn_render_maps_scratch_bytes.restype = C.c_size_t
+        L.dsn_render_maps_scratch_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int64]
         L.dsn_density_grid_workspace_bytes.restype = C.c_size_t
         L.dsn_density_grid_workspace_bytes.argtypes = [C.c_int64]
         L.dsn_mc_workspace_bytes.restype = C.c_size_t
@@ -666,7 +669,10 @@ def screen_debug(scene: Scene, packed: PackedParams, x_c):
     return sg, s1
 
 
-def shade(scene: Scene, packed: PackedParams, x_c, grad, x_w, ray_d, essence, S, active=None, exhaustive=False, fp32=False):
+def shade(scene: Scene, packed: PackedParams, x_c, grad, x_w, ray_d, essence, S, active=None, exhaustive=False, fp32=False,
+          want_factor=False):
+    """want_factor: the light factor ELU(lighting MLP) + 1 of every listed sample as a fourth value [N] (dsn_shade_factor; the other
+    three keep their bits)"""
     x_c = x_c.reshape(-1, 3)
     N = x_c.shape[0]
     dev = scene.device
@@ -674,6 +680,16 @@ def shade(scene: Scene, packed: PackedParams, x_c, grad, x_w, ray_d, essence, S,
     n_w = torch.zeros(N, 3, dtype=torch.float32, device=dev)
     col = torch.zeros(N, 3, dtype=torch.float32, device=dev)
     lst, cnt = (None, None) if active is None else active
+    if want_factor:
+        if fp32:
+            raise ValueError("shade: want_factor needs the split-fp16 lighting kernel (fp32=False)")
+        fac = torch.zeros(N, dtype=torch.float32, device=dev)
+        _check(lib().dsn_shade_factor(_ptr(scene.buf), scene.V, scene.F, _ptr(packed.buf), _ptr(x_c, torch.float32),
+                                      _ptr(grad.reshape(-1, 3), torch.float32), _ptr(x_w.reshape(-1, 3), torch.float32),
+                                      _ptr(ray_d, torch.float32), _ptr(essence.reshape(-1, 3), torch.float32), C.c_int64(N), S,
+                                      _ptr(lst), _ptr(cnt), _ptr(idx), _ptr(n_w), _ptr(col), _ptr(fac), NN_EXHAUSTIVE if exhaustive else 0,
+                                      _stream()), "dsn_shade_factor")
+        return idx, n_w, col, fac
     _check(lib().dsn_shade(_ptr(scene.buf), scene.V, scene.F, _ptr(packed.buf), _ptr(x_c, torch.float32),
                            _ptr(grad.reshape(-1, 3), torch.float32), _ptr(x_w.reshape(-1, 3), torch.float32),
                            _ptr(ray_d, torch.float32), _ptr(essence.reshape(-1, 3), torch.float32), C.c_int64(N), S,
@@ -694,6 +710,24 @@ def composite(colour, sigma, transparent, z_vals, ray_d, noise=None):
                                _ptr(transparent), _ptr(z_vals, torch.float32), _ptr(ray_d, torch.float32), _ptr(noise),
                                R, S, _ptr(rgb), _ptr(disp), _ptr(acc), _ptr(w), _ptr(dep), _stream()), "dsn_composite")
     return rgb, disp, acc, w, dep
+
+
+def composite_maps(essence, n_w, factor, sigma, transparent, z_vals, ray_d):
+    """Stage entry of the decomposition maps (dsn_composite_maps): dense per-sample essence [N,3], world normals [N,3] and light factor
+    [N] composited with the weights of (sigma, transparent, z_vals, ray_d).  Returns albedo [R,3], normal [R,3], shading [R], weights
+    [R,S], max2 [2] (largest |essence|, largest factor weighed).  Any S."""
+    R, S = z_vals.shape
+    dev = z_vals.device
+    alb = torch.empty(R, 3, dtype=torch.float32, device=dev)
+    nrm = torch.empty(R, 3, dtype=torch.float32, device=dev)
+    shd = torch.empty(R, dtype=torch.float32, device=dev)
+    w = torch.empty(R, S, dtype=torch.float32, device=dev)
+    mx = torch.empty(2, dtype=torch.float32, device=dev)
+    _check(lib().dsn_composite_maps(_ptr(essence.reshape(-1, 3), torch.float32), _ptr(n_w.reshape(-1, 3), torch.float32),
+                                    _ptr(factor.reshape(-1), torch.float32), _ptr(sigma.reshape(-1), torch.float32), _ptr(transparent),
+                                    _ptr(z_vals, torch.float32), _ptr(ray_d, torch.float32), R, S, _ptr(alb), _ptr(nrm), _ptr(shd),
+                                    _ptr(w), _ptr(mx), _stream()), "dsn_composite_maps")
+    return alb, nrm, shd, w, mx
 
 
 RECORD_FRACTION_DEFAULT = 0.125      # = DSN_RECORD_FRACTION_DEFAULT (csrc/dsn_api.hip)
@@ -908,6 +942,70 @@ def render_rays_lights(scene: Scene, packed: PackedParams, ws: RenderWorkspace, 
                                     _ptr(out["z_vals"]), _ptr(buf), C.c_size_t(ws.cap), _ptr(ls), C.c_size_t(min(ls.numel(), need)),
                                     sched, n_sched, _stream()),
            "dsn_render_rays_lights")
+    return out
+
+
+MAPS = ("albedo", "shading", "normal")
+
+
+def maps_bound(S: int, eps: float, scale: float) -> float:
+    """Early stop: the absolute distance of a sliced frame's map from its one-pass value, for per-sample values q with |q| <= scale on
+    the one-pass shading list: (S + 1) (eps + 2^-22) scale (include/dsnerf.h, dsn_render_rays_maps)."""
+    return (int(S) + 1) * (float(eps) + 2.0 ** -22) * float(scale)
+
+
+def render_rays_maps(scene: Scene, packed: PackedParams, ws: RenderWorkspace, ray_o, ray_d, near, far, S, t_vals, lights,
+                     maps=MAPS, want_color=True, want_max=True, skip_transparent=True, screen=False, audit=False, early_stop=False, stop_stats=False,
+                     stop_schedule=None, uniform=False, want_weights=True, scratch_budget=None, fp32=False, scratch_bytes=None):
+    """render_rays_lights that also composites the factors of the colour with the frame's weights (dsn_render_rays_maps): its dict
+    plus "albedo" [R,3], "normal" [R,3] (world space, not renormalised), "shading" [K,R] for the names in `maps`, and "maps_max" [2]
+    (device: the largest |essence| and the largest light factor that entered a sum; want_max=False: not asked for).
+    want_color=False: no "color" (out_rgb = NULL).
+    Everything else as render_rays_lights; the scratch holds 4 floats per shaded sample and light."""
+    R = ray_o.shape[0]
+    K = int(lights.shape[0])
+    dev = scene.device
+    lights = lights.to(device=dev, dtype=torch.float32).contiguous()
+    assert lights.dim() == 2 and lights.shape[1] == LIGHT_RECORD_FLOATS, "lights: [K, 12] records (light_records)"
+    maps = tuple(maps)
+    unknown = [m for m in maps if m not in MAPS]
+    if unknown:
+        raise ValueError(f"render_rays_maps: unknown maps {unknown} (albedo, shading, normal)")
+    if not skip_transparent:
+        raise ValueError("render_rays_maps: eval mode with the transparent skip only")
+    if fp32:
+        raise ValueError("render_rays_maps: the exact-fp32 field is not supported (the sweep's lighting is the split-fp16 kernel's)")
+    out = _frame_outputs(R, S, dev, want_weights, K)
+    if not want_color:
+        del out["color"]
+    if "albedo" in maps:
+        out["albedo"] = torch.empty(R, 3, dtype=torch.float32, device=dev)
+    if "normal" in maps:
+        out["normal"] = torch.empty(R, 3, dtype=torch.float32, device=dev)
+    if "shading" in maps:
+        out["shading"] = torch.empty(K, R, dtype=torch.float32, device=dev)
+    if want_max:
+        out["maps_max"] = torch.empty(2, dtype=torch.float32, device=dev)
+    flags = _frame_flags(scene, uniform=uniform, screen=screen, audit=audit, early_stop=early_stop, stop_stats=stop_stats)
+    ws.begin_frame()
+    buf = ws.get(R, S)
+    budget = LIGHT_SCRATCH_BUDGET if scratch_budget is None else int(scratch_budget)
+    L = lib()
+    need = max(min(budget, L.dsn_render_maps_scratch_bytes(R, S, K, R * S)), L.dsn_render_maps_scratch_bytes(R, S, 1, R * S))
+    if scratch_bytes is not None:
+        need = int(scratch_bytes)
+    ls = ws.light_scratch
+    if ls is None or ls.numel() < need:
+        ls = ws.light_scratch = _scratch(need, dev)
+    sched, n_sched = _slice_schedule(stop_schedule, flags)
+    _check(L.dsn_render_rays_maps(_ptr(scene.buf), scene.V, scene.F, _ptr(packed.buf), _ptr(ray_o, torch.float32),
+                                  _ptr(ray_d, torch.float32), _ptr(near, torch.float32), _ptr(far, torch.float32), R, S,
+                                  _ptr(t_vals, torch.float32), None, None, flags, _ptr(lights), K, _ptr(out.get("color")),
+                                  _ptr(out["disp_map"]), _ptr(out["acc_map"]), _ptr(out["depth_map"]), _ptr(out.get("weights")),
+                                  _ptr(out["z_vals"]), _ptr(out.get("albedo")), _ptr(out.get("normal")), _ptr(out.get("shading")),
+                                  _ptr(out.get("maps_max")), _ptr(buf), C.c_size_t(ws.cap), _ptr(ls), C.c_size_t(min(ls.numel(), need)),
+                                  sched, n_sched, _stream()),
+           "dsn_render_rays_maps")
     return out
 
 
@@ -1186,6 +1284,39 @@ def image_scatter(out: dict, mask_at_box, H, W, clamp=False):
                                    _ptr(img["coarse_disp"]), _ptr(img["coarse_acc"]), _ptr(img["coarse_depth"]), _ptr(ws),
                                    _stream()), "dsn_image_scatter")
     return img
+
+
+def image_scatter_maps(rgbs, scalars, mask_at_box, H, W):
+    """image_scatter's kernel (dsn_image_scatter, unchanged) for other per-ray arrays: `rgbs` a list of [R,3], `scalars` a list of [R]
+    device tensors -> ([H,W,3] images, [H,W,1] images), zeros outside mask_at_box.  One call carries one [R,3] and up to three [R]
+    arrays (the colour / disp / acc / depth slots)."""
+    rgbs, scalars = list(rgbs), list(scalars)
+    if not rgbs and not scalars:
+        return [], []
+    dev = (rgbs + scalars)[0].device
+    mask = mask_at_box.reshape(-1).to(device=dev, dtype=torch.uint8).contiguous()
+    R = (rgbs + scalars)[0].shape[0]
+    ws = _scratch(lib().dsn_image_workspace_bytes(H, W), dev)
+    rgb_imgs = [torch.empty(H, W, 3, dtype=torch.float32, device=dev) for _ in rgbs]
+    sc_imgs = [torch.empty(H, W, 1, dtype=torch.float32, device=dev) for _ in scalars]
+    spare_src = spare_img = None
+    i = j = 0
+    while i < len(rgbs) or j < len(scalars):
+        if i < len(rgbs):
+            src, img = rgbs[i].contiguous(), rgb_imgs[i]
+            i += 1
+        else:      # (the kernel wants a colour with every call: a zero one into an image nobody reads)
+            if spare_src is None:
+                spare_src = torch.zeros(R, 3, dtype=torch.float32, device=dev)
+                spare_img = torch.empty(H, W, 3, dtype=torch.float32, device=dev)
+            src, img = spare_src, spare_img
+        three = [(scalars[k].contiguous(), sc_imgs[k]) for k in range(j, min(j + 3, len(scalars)))]
+        j += len(three)
+        three += [(None, None)] * (3 - len(three))
+        _check(lib().dsn_image_scatter(_ptr(src, torch.float32), _ptr(three[0][0]), _ptr(three[1][0]), _ptr(three[2][0]), R, _ptr(mask),
+                                       H, W, 0, _ptr(img), _ptr(three[0][1]), _ptr(three[1][1]), _ptr(three[2][1]), _ptr(ws),
+                                       _stream()), "dsn_image_scatter")
+    return rgb_imgs, sc_imgs
 
 
 def image_psnr(img_rgb, gt, mask_at_box=None):

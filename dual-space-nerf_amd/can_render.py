@@ -567,9 +567,10 @@ class Renderer:
         return {"skip_transparent": skip, "uniform": (self.sample_points_mode == "uniform"), "screen": screen,
                 "audit": audit, "early_stop": stop, "stop_stats": stats, "stop_schedule": sched}
 
-    def _render_eval(self, scene, ws, o, d, near, far, S, jitter, noise, screen=None, plan=None, phases=0, out=None, lights=None):
+    def _render_eval(self, scene, ws, o, d, near, far, S, jitter, noise, screen=None, plan=None, phases=0, out=None, lights=None,
+                     maps=None):
         """lights: [K, 12] light records (_lib.light_records) - the frame is a relighting sweep (_lib.render_rays_lights; one call, no
-        phases), its "color" is [K, R, 3]"""
+        phases), its "color" is [K, R, 3]; maps: names of decomposition maps - the sweep also composites those (_lib.render_rays_maps)"""
         packed = self.net.packed(self.device)
         if (plan is None and screen is None and phases == 0 and noise is None and packed.screen is None and self.density_screen
                 and self.skip_transparent and not self.net.training):
@@ -596,7 +597,10 @@ class Renderer:
                                 "early_stop_bound_abs": (S + 1) * _lib.early_stop_eps(S, cs) * cs if plan["early_stop"] else 0.0}
         if lights is not None:
             self.last_frame_info["lights"] = int(lights.shape[0])
-            out = _lib.render_rays_lights(scene, packed, ws, o, d, near, far, S, self._t_vals(S), lights, **plan)
+            if maps is not None:
+                out = _lib.render_rays_maps(scene, packed, ws, o, d, near, far, S, self._t_vals(S), lights, maps=maps, **plan)
+            else:
+                out = _lib.render_rays_lights(scene, packed, ws, o, d, near, far, S, self._t_vals(S), lights, **plan)
         else:
             out = _lib.render_rays(scene, packed, ws, o, d, near, far, S, self._t_vals(S), jitter, noise, phases=phases, out=out,
                                    share_cus=getattr(self, "_frames_overlap", False), **plan)
@@ -840,7 +844,8 @@ class Renderer:
             outs.append(render_chunk(o[i:j].contiguous(), d[i:j].contiguous(), n[i:j].contiguous(), f[i:j].contiguous(), S))
         if len(outs) == 1:
             return outs[0]
-        return {k: torch.cat([x[k] for x in outs], color_axis if k == "color" else 0) for k in outs[0]}
+        # ("shading" [K, R] of a maps sweep has its rays where a sweep's "color" has them)
+        return {k: torch.cat([x[k] for x in outs], color_axis if k in ("color", "shading") else 0) for k in outs[0]}
 
     def _view_images(self, batch, chunk, scene, ws):
         coarse, _ = self.batchify_rays_view(batch["ray_o"], batch["ray_d"], batch["near"], batch["far"], batch, chunk, scene, ws)
@@ -923,6 +928,92 @@ class Renderer:
         _, H, W, _ = batch["img"].shape
         mask = self._dev(batch["mask_at_box"][0], torch.uint8)
         return [_lib.image_scatter(dict(coarse, color=coarse["color"][k]), mask, H, W) for k in range(len(lights))]
+
+    def render_view_maps(self, batch, lights=None, maps=("albedo", "shading", "normal"), chunk=None, device_output=False):
+        """The decomposition behind a view (not in the reference, whose colour is (ELU(lighting MLP) + 1) x essence per sample,
+        model/spacenet.py:174-188, and only ever composited as that product): the view's albedo, shading and normal images from the
+        frame's own pass.  With w_i the frame's compositing weights, summed over the samples of its shading list:
+            "albedo"  [H,W,3]  sum w_i essence_i        "shading" [H,W,1]  sum w_i (ELU + 1)_i
+            "normal"  [H,W,3]  sum w_i n_i   (unit world normals; NOT renormalised: the acc-weighted mean normal x coarse_acc)
+        zeros outside mask_at_box, beside render_view's four images.
+        lights=None: the net's own light (light_center / rot / rot_center as set on the net) - ONE dict, its four render_view keys
+        bit-identical to render_view(batch).  lights=[...] (render_view_lights' dicts): a list of dicts, one per light, colours
+        bit-identical to render_view_lights; "albedo" / "normal" do not depend on the light and are the same tensors in every dict.
+        maps: which of the three to produce.  Plan (early stop, density screen, audit, the second rendering in one pass when a colour
+        above the early-stop scale was weighed) and restrictions as render_view_lights.  last_frame_info["maps"] names the maps; with
+        early stop in use last_frame_info["maps_bound"] gives per map the absolute bound on its distance from the one-pass map,
+        (S + 1) (eps + 2^-22) Q: Q = 1 for the normal (exact), the largest |essence| / light factor the frame weighed for albedo /
+        shading - which bounds the samples early stop left out only as far as they are no larger than those it kept (the assumption
+        the colour threshold itself makes)."""
+        maps = (maps,) if isinstance(maps, str) else tuple(maps)
+        if not maps:
+            raise ValueError("render_view_maps: no maps asked for (albedo, shading, normal)")
+        unknown = [m for m in maps if m not in _lib.MAPS]
+        if unknown:
+            raise ValueError(f"render_view_maps: unknown maps {unknown} (albedo, shading, normal)")
+        single = lights is None
+        if not single:
+            lights = list(lights)
+            if not lights:
+                raise ValueError("render_view_maps: no lights given (None = the net's own light)")
+        if self.net.training:
+            raise RuntimeError("render_view_maps: eval mode only (Renderer.eval()); the maps have no training forward")
+        if not self.skip_transparent:
+            raise RuntimeError("render_view_maps: needs skip_transparent = True (the eval-mode path)")
+        if single:
+            net, own = self.net, {}
+            if net.light_center is not None:
+                own["light_center"] = net.light_center
+            if net.rot is not None and net.rot_center is not None:      # (DualSpaceNeRF.frame_args: one without the other is ignored)
+                own["rot"], own["rot_center"] = net.rot, net.rot_center
+            lights = [own]
+        with _HostPoolGuard(self.host_pool_limit):
+            imgs, mx = self._view_images_maps(batch, lights, maps, chunk)
+            res = self._hand_over((imgs, mx), lambda: self._view_images_maps(batch, lights, maps, chunk))
+            imgs, mx = res
+            info = dict(self.last_frame_info, lights=len(lights), maps=list(maps),
+                        rendered_again_in_one_pass=self.last_frame_info.get("rendered_again_in_one_pass", False))
+            if info.get("early_stop"):
+                S = int(self.cfg.MODEL.COARSE_RAY_SAMPLING)
+                e_max, l_max = (float(v) for v in mx.cpu())      # (synchronises; the hand-over check of a sliced frame has already)
+                scale = {"albedo": e_max, "shading": l_max, "normal": 1.0}
+                info["maps_max"] = {"essence": e_max, "light": l_max}
+                info["maps_bound"] = {m: _lib.maps_bound(S, info["early_stop_eps"], scale[m]) for m in maps}
+            self.last_frame_info = info
+            if not device_output:
+                torch.cuda.current_stream(self.device).synchronize()
+                shared = {k: imgs[0][k].cpu() for k in ("albedo", "normal") if k in imgs[0]}
+                imgs = [dict({k: v.cpu() for k, v in img.items() if k not in shared}, **shared) for img in imgs]
+            return imgs[0] if single else imgs
+
+    def _view_images_maps(self, batch, lights, maps, chunk):
+        """_view_images_lights with the decomposition maps: (one dict per light, the [2] device tensor of the largest |essence| and
+        light factor weighed)"""
+        scene, ws = self.scene, self._ws
+        frame = int(torch.as_tensor(batch["frame"]).reshape(-1)[0])
+        xyz = self._dev(batch["xyz"][0])
+        poses = batch["poses"][0].to(device=self.device, dtype=torch.float32).contiguous()
+        scene.set_frame(self.net.packed(self.device), xyz, poses, frame, self.net.nerf.w is not None, None, None, None, fine_only=True,
+                        lazy=self.lazy_lists)
+        self._frame_src = None      # (as render_view_lights leaves it: the scene's frame state lacks the net's light edit)
+        th = batch["Th"][0] if any(lt.get("light_center") is not None for lt in lights) else None
+        recs = _lib.light_records(lights, th, self.device)
+        coarse = self._render_chunks(batch["ray_o"], batch["ray_d"], batch["near"], batch["far"], chunk,
+                                     lambda o, d, n, f, S: self._render_eval(scene, ws, o, d, n, f, S, None, None, lights=recs, maps=maps),
+                                     color_axis=1)
+        _, H, W, _ = batch["img"].shape
+        mask = self._dev(batch["mask_at_box"][0], torch.uint8)
+        K = len(lights)
+        imgs = [_lib.image_scatter(dict(coarse, color=coarse["color"][k]), mask, H, W) for k in range(K)]
+        rgbs = [coarse[m] for m in ("albedo", "normal") if m in maps]
+        scal = [coarse["shading"][k] for k in range(K)] if "shading" in maps else []
+        rgb_imgs, scal_imgs = _lib.image_scatter_maps(rgbs, scal, mask, H, W)
+        for m, im in zip([m for m in ("albedo", "normal") if m in maps], rgb_imgs):
+            for img in imgs:
+                img[m] = im
+        for img, im in zip(imgs, scal_imgs):
+            img["shading"] = im
+        return imgs, coarse["maps_max"].reshape(-1, 2).max(dim=0).values      # (one pair per chunk)
 
     def render_views(self, batches, frames_in_flight=3, device_output=True, chunk=None):
         """The per-frame loop of novel_pose_vis.py:41-66 / test.py:55-64 (`for batch in loader: render.render_view(batch)`) as

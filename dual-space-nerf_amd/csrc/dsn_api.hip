@@ -275,6 +275,45 @@ int dsn_shade(const void* scene, int V, int F, const void* packed, const float* 
     return dsn_check_launch("dsn_shade");
 }
 
+int dsn_shade_factor(const void* scene, int V, int F, const void* packed, const float* x_c, const float* grad, const float* x_w,
+                     const float* ray_d, const float* essence, int64_t N, int S, const int32_t* active_list,
+                     const int32_t* active_count, int32_t* face_idx_canon, float* n_w, float* colour, float* factor, int flags,
+                     void* stream) {
+    DSN_REQUIRE(scene && packed && x_c && grad && x_w && ray_d && essence && n_w && colour && factor, "dsn_shade_factor: null argument");
+    DSN_REQUIRE(N > 0 && S > 0, "dsn_shade_factor: empty point batch");
+    DSN_REQUIRE((active_list == nullptr) == (active_count == nullptr), "dsn_shade_factor: active_list and active_count go together");
+    DSN_REQUIRE(V > 0 && F > 0, "dsn_shade_factor: bad V/F");
+    DSN_REQUIRE(!(flags & DSN_FIELD_FP32), "dsn_shade_factor: DSN_FIELD_FP32 is not supported (split-fp16 lighting only)");
+    hipStream_t st = (hipStream_t)stream;
+    DsnSceneView s = dsn_scene_view((void*)scene, V, F);
+    dsn_launch_normal(s, x_c, grad, N, active_list, active_count, face_idx_canon, n_w, (flags & DSN_NN_EXHAUSTIVE) != 0, st);
+    dsn_launch_light16((const float*)packed, s.frame, n_w, x_w, nullptr, ray_d, nullptr, essence, N, S, active_list, active_count, colour, st,
+                       nullptr, nullptr, nullptr, nullptr, factor);
+    return dsn_check_launch("dsn_shade_factor");
+}
+
+int dsn_composite_maps(const float* essence, const float* n_w, const float* factor, const float* sigma, const uint8_t* transparent,
+                       const float* z_vals, const float* ray_d, int R, int S, float* albedo_map, float* normal_map, float* shading_map,
+                       float* weights, float* out_max, void* stream) {
+    DSN_REQUIRE(sigma && z_vals && ray_d, "dsn_composite_maps: null argument");
+    DSN_REQUIRE(R > 0 && S > 0, "dsn_composite_maps: empty ray batch");
+    DSN_REQUIRE(albedo_map || normal_map || shading_map || weights || out_max, "dsn_composite_maps: no output asked for");
+    DSN_REQUIRE((!albedo_map || essence) && (!normal_map || n_w) && (!shading_map || factor),
+                "dsn_composite_maps: map requested without its source (albedo: essence, normal: n_w, shading: factor)");
+    DSN_REQUIRE(!out_max || (essence && factor), "dsn_composite_maps: out_max needs essence and factor");
+    hipStream_t st = (hipStream_t)stream;
+    if (out_max && hipMemsetAsync(out_max, 0, 2 * sizeof(float), st) != hipSuccess)
+        return dsn_fail("%s", "dsn_composite_maps: memset failed");
+    DsnMapsArgs a = {};
+    a.factors = factor; a.n_shaded = (int64_t)R * S; a.G = 1;
+    a.essence = essence; a.n_w = n_w; a.sigma = sigma; a.transparent = transparent; a.z_vals = z_vals; a.ray_d = ray_d;
+    a.R = R; a.S = S;
+    a.albedo_map = albedo_map; a.normal_map = normal_map; a.shading_maps = shading_map; a.weights = weights;
+    a.maps_max = (int32_t*)out_max;
+    dsn_launch_composite_maps(a, st);
+    return dsn_check_launch("dsn_composite_maps");
+}
+
 int dsn_composite(const float* colour, const float* sigma, const uint8_t* transparent, const float* z_vals,
                   const float* ray_d, const float* noise, int R, int S, float* rgb_map, float* disp_map,
                   float* acc_map, float* weights, float* depth_map, void* stream) {
@@ -644,8 +683,16 @@ int dsn_render_rays(const void* scene, int V, int F, const void* packed, const f
 struct DsnLightSweep {
     const DsnLightEdit* lights;      // [n_lights] (device)
     int n_lights;
-    void* scratch;            // compact colours of a group of lights: [G][n_shaded][3]
+    void* scratch;            // compact colours of a group of lights: [G][n_shaded][3] (maps: + the light factors [G][n_shaded])
     size_t scratch_bytes;
+    const struct DsnMapsOut* maps;      // dsn_render_rays_maps: the decomposition maps beside the colours (NULL: the plain sweep)
+};
+// dsn_render_rays_maps: where the maps go (each may be NULL); out_rgb may be NULL too then
+struct DsnMapsOut {
+    float* albedo;      // [R,3]
+    float* normal;      // [R,3]
+    float* shading;     // [n_lights,R]
+    float* max2;        // largest |essence|, largest light factor weighed (device)
 };
 static int dsn_render_frame(const void* scene, int V, int F, const void* packed, const float* ray_o, const float* ray_d, float* near,
                             float* far, int R, int S, const float* t_vals, const float* jitter, const float* noise,
@@ -689,7 +736,39 @@ int dsn_render_rays_lights(const void* scene, int V, int F, const void* packed, 
                 "dsn_render_rays_lights: workspace, out_weights and out_z must be 16-byte aligned");
     DSN_REQUIRE(light_scratch_bytes >= dsn_render_lights_scratch_bytes(R, S, 1, 0),
                 "dsn_render_rays_lights: light_scratch is too small (dsn_render_lights_scratch_bytes)");
-    const DsnLightSweep sweep = {reinterpret_cast<const DsnLightEdit*>(lights), n_lights, light_scratch, light_scratch_bytes};
+    const DsnLightSweep sweep = {reinterpret_cast<const DsnLightEdit*>(lights), n_lights, light_scratch, light_scratch_bytes, nullptr};
+    return dsn_render_frame(scene, V, F, packed, ray_o, ray_d, near, far, R, S, t_vals, jitter, noise, flags, out_rgb, out_disp, out_acc,
+                            out_depth, out_weights, out_z, workspace, workspace_bytes, slice_lengths_host, n_slices, stream, &sweep);
+}
+
+size_t dsn_render_maps_scratch_bytes(int R, int S, int n_lights, int64_t n_shaded) {
+    if (R <= 0 || S <= 0 || n_lights < 1 || n_shaded < 0 || n_shaded > (int64_t)R * S) return 0;
+    return dsn_align256(sizeof(float) * 4 * (size_t)n_lights * (size_t)std::max<int64_t>(n_shaded, 1));
+}
+
+int dsn_render_rays_maps(const void* scene, int V, int F, const void* packed, const float* ray_o, const float* ray_d, float* near,
+                         float* far, int R, int S, const float* t_vals, const float* jitter, const float* noise, int flags,
+                         const float* lights, int n_lights, float* out_rgb, float* out_disp, float* out_acc, float* out_depth,
+                         float* out_weights, float* out_z, float* out_albedo, float* out_normal, float* out_shading, float* out_max,
+                         void* workspace, size_t workspace_bytes, void* light_scratch, size_t light_scratch_bytes,
+                         const int32_t* slice_lengths_host, int n_slices, void* stream) {
+    DSN_REQUIRE(R > 0 && S > 0, "dsn_render_rays_maps: empty ray batch");
+    DSN_REQUIRE(scene && packed && ray_o && ray_d && near && far && t_vals && workspace && lights && light_scratch,
+                "dsn_render_rays_maps: null argument");
+    DSN_REQUIRE(out_disp && out_acc && out_depth, "dsn_render_rays_maps: null output (out_rgb and the maps may be NULL, disp / acc / depth not)");
+    DSN_REQUIRE(n_lights >= 1, "dsn_render_rays_maps: n_lights must be at least 1");
+    DSN_REQUIRE(!jitter && !noise, "dsn_render_rays_maps: eval mode only (no jitter, no noise)");
+    DSN_REQUIRE(flags & DSN_SKIP_TRANSPARENT, "dsn_render_rays_maps: eval mode only (flags must hold DSN_SKIP_TRANSPARENT)");
+    DSN_REQUIRE(!(flags & DSN_FIELD_FP32), "dsn_render_rays_maps: DSN_FIELD_FP32 is not supported (split-fp16 lighting only)");
+    DSN_REQUIRE(!(flags & (DSN_PHASE_GEOMETRY | DSN_PHASE_FIELD | DSN_PHASE_SHADE)),
+                "dsn_render_rays_maps: DSN_PHASE_* bits are not supported (one call renders the whole sweep)");
+    DSN_REQUIRE(S == 64 || S == 128, "dsn_render_rays_maps: S must be 64 or 128 (the 16-lane compositor)");
+    DSN_REQUIRE((((uintptr_t)workspace | (uintptr_t)out_weights | (uintptr_t)out_z) & 15) == 0,
+                "dsn_render_rays_maps: workspace, out_weights and out_z must be 16-byte aligned");
+    DSN_REQUIRE(light_scratch_bytes >= dsn_render_maps_scratch_bytes(R, S, 1, 0),
+                "dsn_render_rays_maps: light_scratch is too small (dsn_render_maps_scratch_bytes)");
+    const DsnMapsOut maps = {out_albedo, out_normal, out_shading, out_max};
+    const DsnLightSweep sweep = {reinterpret_cast<const DsnLightEdit*>(lights), n_lights, light_scratch, light_scratch_bytes, &maps};
     return dsn_render_frame(scene, V, F, packed, ray_o, ray_d, near, far, R, S, t_vals, jitter, noise, flags, out_rgb, out_disp, out_acc,
                             out_depth, out_weights, out_z, workspace, workspace_bytes, slice_lengths_host, n_slices, stream, &sweep);
 }
@@ -721,7 +800,7 @@ static int dsn_render_frame(const void* scene, int V, int F, const void* packed,
     }
     const bool custom_schedule = slice_lengths_host && n_slices > 0;
     DSN_REQUIRE(scene && packed && ray_o && ray_d && near && far && t_vals && workspace, "dsn_render_rays: null argument");
-    DSN_REQUIRE(out_rgb && out_disp && out_acc && out_depth, "dsn_render_rays: null output");
+    DSN_REQUIRE((out_rgb || (sweep && sweep->maps)) && out_disp && out_acc && out_depth, "dsn_render_rays: null output");
     DSN_REQUIRE(V > 0 && F > 0, "dsn_render_rays: bad V/F");
     const bool skip = (flags & DSN_SKIP_TRANSPARENT) != 0;
     DSN_REQUIRE(!(skip && noise), "dsn_render_rays: DSN_SKIP_TRANSPARENT is only exact without noise (eval mode)");
@@ -905,11 +984,16 @@ static int dsn_render_frame(const void* scene, int V, int F, const void* packed,
     int32_t n_sh = 0;
     if (hipMemcpyAsync(&n_sh, cnt, sizeof(int32_t), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
         return dsn_fail("%s", "dsn_render_rays_lights: reading the shading list's length failed");
-    const size_t per_light = sizeof(float) * 3 * (size_t)n_sh;
+    // (maps: the light factors [G][n_shaded] behind the group's colours - 4 floats per shaded sample and light)
+    const DsnMapsOut* const maps = sweep->maps;
+    const char* const who = maps ? "dsn_render_rays_maps" : "dsn_render_rays_lights";
+    const size_t per_light = sizeof(float) * (maps ? 4 : 3) * (size_t)n_sh;
     const int G = per_light == 0 ? sweep->n_lights : (int)std::min<size_t>((size_t)sweep->n_lights, sweep->scratch_bytes / per_light);
     if (G < 1)
-        return dsn_fail("dsn_render_rays_lights: light_scratch is too small%s: one light's colours need %lld bytes "
-                        "(dsn_render_lights_scratch_bytes)", "", (long long)per_light);
+        return maps ? dsn_fail("dsn_render_rays_maps: light_scratch is too small%s: one light's colours and factors need %lld bytes "
+                               "(dsn_render_maps_scratch_bytes)", "", (long long)per_light)
+                    : dsn_fail("dsn_render_rays_lights: light_scratch is too small%s: one light's colours need %lld bytes "
+                               "(dsn_render_lights_scratch_bytes)", "", (long long)per_light);
     // the slot map takes the slice-filter list's buffer: dead after the field phase on both eval paths (early stop: its last
     // reader is the reverse pass's selection; one pass: never used)
     int32_t* slot = w.alive;
@@ -920,9 +1004,35 @@ static int dsn_render_frame(const void* scene, int V, int F, const void* packed,
         return dsn_fail("%s", "dsn_render_rays_lights: memset failed");
     dsn_launch_slot_map(list, cnt, n_sh, slot, st);
     float* colours = (float*)sweep->scratch;
+    // Decomposition maps: the sweep's passes as they are - the lighting kernel also keeps its factor by slot, and the compositor
+    // (k_composite16_maps: k_composite16_multi's sums, same bits) weighs the essence, the normal and the factors too.  The essence
+    // array is still intact here (the sweep's colours live in the caller's scratch; on the one-light path the colour overwrites it).
+    // Albedo, normal and the two maxima are written by the first group only, like disp / acc / depth / weights.
+    if (maps && maps->max2 && hipMemsetAsync(maps->max2, 0, 2 * sizeof(float), st) != hipSuccess)
+        return dsn_fail("%s", "dsn_render_rays_maps: memset failed");
     for (int g0 = 0; g0 < sweep->n_lights; g0 += G) {
         const int Gc = std::min(G, sweep->n_lights - g0);
         const bool first = g0 == 0;      // (the per-ray outputs that do not depend on the light: written once)
+        if (maps) {
+            float* factors = colours + (size_t)G * 3 * (size_t)n_sh;
+            dsn_launch_light16_multi((const float*)packed, sweep->lights + g0, Gc, w.n_w, ray_o, ray_d, z,
+                                     w.essence, n_sh, S, list, cnt, colours, st, factors);
+            DsnMapsArgs a = {};
+            a.slot_of = slot; a.colours = colours; a.factors = factors; a.n_shaded = n_sh; a.G = Gc;
+            a.essence = w.essence; a.n_w = w.n_w; a.sigma = w.sigma; a.transparent = w.transparent; a.z_vals = z; a.ray_d = ray_d;
+            a.R = R; a.S = S;
+            a.rgb_maps = out_rgb ? out_rgb + (size_t)g0 * 3 * R : nullptr;
+            a.shading_maps = maps->shading ? maps->shading + (size_t)g0 * R : nullptr;
+            if (first) {
+                a.albedo_map = maps->albedo; a.normal_map = maps->normal;
+                a.disp_map = out_disp; a.acc_map = out_acc; a.weights = out_weights; a.depth_map = out_depth;
+            }
+            // (the largest factor is a maximum over every group; the largest |essence| is the same in all of them)
+            a.maps_max = (int32_t*)maps->max2;
+            a.colour_max = w.count + DSN_CNT_STOP + 3;
+            dsn_launch_composite_maps(a, st);
+            continue;
+        }
         dsn_launch_light16_multi((const float*)packed, sweep->lights + g0, Gc, w.n_w, ray_o, ray_d, z,
                                  w.essence, n_sh, S, list, cnt, colours, st);
         dsn_launch_composite_multi(slot, colours, n_sh, Gc, w.sigma, w.transparent, z, ray_d, R, S, out_rgb + (size_t)g0 * 3 * R,
@@ -932,7 +1042,7 @@ static int dsn_render_frame(const void* scene, int V, int F, const void* packed,
     if (flags & DSN_STOP_STATS)
         dsn_launch_stop_stats(w.sigma, w.transparent, z, ray_d, R, S, dsn_stats_slice_len(R, S), (const float*)packed + OFF_SCAL,
                               w.count + DSN_CNT_STOP + 2, st, w.count + DSN_CNT_HIST, w.count + DSN_CNT_STOP + 3, dsn_slice_len(R, S));
-    return dsn_check_launch("dsn_render_rays_lights");
+    return dsn_check_launch(who);
     }
     if (do_shade) {
     dsn_launch_normal(s, w.x_c, w.grad, N, list, cnt, nullptr, w.n_w, exh, st);

@@ -2385,13 +2385,15 @@ __device__ __forceinline__ float light16_mlp(const float* __restrict__ packed, c
 }
 __device__ __forceinline__ float light16_weight(float o) { return (o > 0.0f ? o : expm1f(o)) + 1.0f; }   // ELU(alpha=1) + 1
 
+// FACTOR (dsn_shade_factor): the light factor ELU + 1 of every sample goes to factor[N] as well; the colours keep their bits
+template <bool FACTOR>
 __global__ void __launch_bounds__(256, 1)
 k_light16(const float* __restrict__ packed, const DsnFrameState* __restrict__ fs, const float* __restrict__ n_w,
           const float* __restrict__ x_w_pts, const float* __restrict__ ray_o, const float* __restrict__ ray_d,
           const float* __restrict__ z_vals, const float* essence, int64_t N, int S,
           const int32_t* __restrict__ active_list, const int32_t* __restrict__ active_count,
           float* colour, float* __restrict__ tr_hl1, float* __restrict__ tr_hl2, float* __restrict__ tr_pre,
-          int32_t* __restrict__ range_count) {
+          int32_t* __restrict__ range_count, float* __restrict__ factor) {
     // (essence and colour may be the SAME array - the fused path's workspace keeps the colour where the essence was: a tile reads its
     //  samples' essences at its top and writes their colours at its end; hence no __restrict__ on the two)
     // tr_*: (training forward) light16_mlp's hidden layers, and the pre-activation of the output [N] - what the backward of the
@@ -2454,6 +2456,7 @@ k_light16(const float* __restrict__ packed, const DsnFrameState* __restrict__ fs
         colour[3 * pt + 0] = wgt * ess[0];
         colour[3 * pt + 1] = wgt * ess[1];
         colour[3 * pt + 2] = wgt * ess[2];
+        if (FACTOR) factor[pt] = wgt;
     }
   }
 }
@@ -2461,12 +2464,17 @@ k_light16(const float* __restrict__ packed, const DsnFrameState* __restrict__ fs
 void dsn_launch_light16(const float* packed, const DsnFrameState* fs, const float* n_w, const float* x_w,
                         const float* ray_o, const float* ray_d, const float* z_vals, const float* essence, int64_t N,
                         int S, const int32_t* active_list, const int32_t* active_count, float* colour, hipStream_t st,
-                        float* tr_hl1, float* tr_hl2, float* tr_pre, int32_t* range_count) {
+                        float* tr_hl1, float* tr_hl2, float* tr_pre, int32_t* range_count, float* factor) {
     int64_t blocks = (N + 127) / 128;
     if (blocks == 0) return;
     // (one workgroup per compute unit since round 5: its waves own their SIMDs' register files, two no longer fit)
-    hipLaunchKernelGGL(k_light16, dim3((unsigned)std::min<int64_t>(blocks, (int64_t)dsn_cu_count())), dim3(256), 0, st, packed, fs, n_w,
-                       x_w, ray_o, ray_d, z_vals, essence, N, S, active_list, active_count, colour, tr_hl1, tr_hl2, tr_pre, range_count);
+    const dim3 grid((unsigned)std::min<int64_t>(blocks, (int64_t)dsn_cu_count()));
+    if (factor)
+        hipLaunchKernelGGL(k_light16<true>, grid, dim3(256), 0, st, packed, fs, n_w, x_w, ray_o, ray_d, z_vals, essence, N, S, active_list,
+                           active_count, colour, tr_hl1, tr_hl2, tr_pre, range_count, factor);
+    else
+        hipLaunchKernelGGL(k_light16<false>, grid, dim3(256), 0, st, packed, fs, n_w, x_w, ray_o, ray_d, z_vals, essence, N, S, active_list,
+                           active_count, colour, tr_hl1, tr_hl2, tr_pre, range_count, factor);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2477,12 +2485,15 @@ void dsn_launch_light16(const float* packed, const DsnFrameState* fs, const floa
 // dsn_light_edit.
 // lights: G light records (DsnLightEdit).
 // colours: [G][count][3], indexed by the sample's slot on the list (not by the sample: a dense [N,3] per light would not fit).
+// FACTOR (dsn_render_rays_maps): the light factor wgt = ELU + 1 of every (light, slot) goes to factors [G][count] as well - the
+// "shading" of the decomposition colour = factor x essence (model/spacenet.py:174-188); the colours keep their bits.
 // ---------------------------------------------------------------------------------------------
+template <bool FACTOR>
 __global__ void __launch_bounds__(256, 1)
 k_light16_multi(const float* __restrict__ packed, const DsnLightEdit* __restrict__ lights, int G, const float* __restrict__ n_w,
                 const float* __restrict__ ray_o, const float* __restrict__ ray_d, const float* __restrict__ z_vals,
                 const float* __restrict__ essence, int S, const int32_t* __restrict__ list, const int32_t* __restrict__ list_count,
-                float* __restrict__ colours) {
+                float* __restrict__ colours, float* __restrict__ factors) {
     __shared__ __attribute__((aligned(16))) char s_w[LIGHT_LDS_BYTES];
 #ifndef F16_SHARE_SIMD
     DSN_OWN_SIMD();
@@ -2539,6 +2550,7 @@ k_light16_multi(const float* __restrict__ packed, const DsnLightEdit* __restrict
             c[0] = wgt * ess[0];
             c[1] = wgt * ess[1];
             c[2] = wgt * ess[2];
+            if (FACTOR) factors[(int64_t)g * count + slot] = wgt;
         }
     }
   }
@@ -2546,9 +2558,14 @@ k_light16_multi(const float* __restrict__ packed, const DsnLightEdit* __restrict
 
 void dsn_launch_light16_multi(const float* packed, const DsnLightEdit* lights, int G, const float* n_w, const float* ray_o, const float* ray_d,
                               const float* z_vals, const float* essence, int64_t max_count, int S, const int32_t* list,
-                              const int32_t* list_count, float* colours, hipStream_t st) {
+                              const int32_t* list_count, float* colours, hipStream_t st, float* factors) {
     const int64_t blocks = (max_count + 127) / 128;
     if (blocks == 0 || G < 1) return;
-    hipLaunchKernelGGL(k_light16_multi, dim3((unsigned)std::min<int64_t>(blocks, (int64_t)dsn_cu_count())), dim3(256), 0, st, packed,
-                       lights, G, n_w, ray_o, ray_d, z_vals, essence, S, list, list_count, colours);
+    const dim3 grid((unsigned)std::min<int64_t>(blocks, (int64_t)dsn_cu_count()));
+    if (factors)
+        hipLaunchKernelGGL(k_light16_multi<true>, grid, dim3(256), 0, st, packed, lights, G, n_w, ray_o, ray_d, z_vals, essence, S, list,
+                           list_count, colours, factors);
+    else
+        hipLaunchKernelGGL(k_light16_multi<false>, grid, dim3(256), 0, st, packed, lights, G, n_w, ray_o, ray_d, z_vals, essence, S, list,
+                           list_count, colours, factors);
 }

@@ -1085,6 +1085,200 @@ void dsn_launch_composite_multi(const int32_t* slot_of, const float* colours, in
 }
 
 // ---------------------------------------------------------------------------------------------
+// Decomposition maps (dsn_render_rays_maps, dsn_composite_maps): the factors of colour = (ELU(lighting MLP) + 1) x essence
+// (model/spacenet.py:174-188) composited one by one with the frame's own weights w_i (utils/nerf_net_utils.py:18-51):
+//   albedo[r] = sum w_i e_i,  normal[r] = sum w_i n_i (world space, not renormalised),  shading[g][r] = sum w_i L_{g,i},
+//   rgb[g][r] = sum w_i L_{g,i} e_i - over the samples on the shading list with sigma > 0; every other sample adds 0 to every map,
+// as it adds colour 0 to the frame.
+// k_composite16_maps<CH>: k_composite16_multi's load, weights, depth / acc / disp and per-light rgb sums, expression for expression
+// (same bits), plus the essence and the normal read from the frame's dense [N,3] arrays BY SAMPLE for listed samples only (the
+// arrays hold rubbish elsewhere: never let it into a product, cf. k_composite16's lazy colour) and the light factors through the slot
+// map.  All sums in the compositor's order: the per-lane j loop, then dsn_row_sum_to_last.  maps_max[0] / [1]: the largest |e| and the
+// largest L weighed (float bits; composite16_colour_max's one candidate per wave against a fresh copy).
+// slot_of == NULL (the stage entry): dense colours / factors, slot = sample, listed = sigma > 0 and not transparent.
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ float dsn_nan_to_inf(float v) { return v == v ? v : INFINITY; }
+
+template <int CH>
+__global__ void __launch_bounds__(256) k_composite16_maps(const DsnMapsArgs a) {
+    constexpr int S = 16 * CH;
+    const int lane = threadIdx.x & 63, sub = lane & 15;
+    const int r_of_row = (blockIdx.x * 4 + (threadIdx.x >> 6)) * 4 + (lane >> 4);
+    if (r_of_row - (lane >> 4) >= a.R) return;              // wave-uniform
+    const bool ok = r_of_row < a.R;
+    const int r = ok ? r_of_row : a.R - 1;
+    const float d[3] = {a.ray_d[3 * r], a.ray_d[3 * r + 1], a.ray_d[3 * r + 2]};
+    const float dn = dsn_norm3(d);
+    const int64_t g0 = (int64_t)r * S + sub * CH;
+    float z[CH + 1], sg[CH], w[CH];
+    uint8_t tr[CH];
+    int32_t sl[CH];
+    composite16_load<CH>(g0, a.z_vals, a.sigma, a.transparent, nullptr, a.slot_of, z, sg, tr, sl);
+    composite16_weights<CH>(z, sg, tr, nullptr, dn, sub, g0, ok, a.weights, w);
+    const bool last = sub == 15 && ok;
+    if (a.depth_map) {      // (every pointer is uniform over the launch)
+        float sdep = 0.f, sacc = 0.f;
+#pragma unroll
+        for (int j = 0; j < CH; ++j) { sdep += w[j] * z[j]; sacc += w[j]; }
+        sdep = dsn_row_sum_to_last(sdep); sacc = dsn_row_sum_to_last(sacc);
+        composite16_maps(sdep, sacc, last, r, a.depth_map, a.acc_map, a.disp_map);
+    }
+    // where a listed sample's per-light values live (-1: not listed - contributes 0 to every map)
+    int64_t at[CH];
+#pragma unroll
+    for (int j = 0; j < CH; ++j) at[j] = !(sg[j] > 0.f) ? -1 : a.slot_of ? (int64_t)sl[j] : g0 + j;
+    float em = 0.f, lm = 0.f, cm = 0.f;
+    if (a.albedo_map || a.maps_max) {
+        float sr = 0.f, sgn = 0.f, sb = 0.f;
+#pragma unroll
+        for (int j = 0; j < CH; ++j) {
+            float er = 0.f, eg = 0.f, eb = 0.f;
+            if (at[j] >= 0) { er = a.essence[3 * (g0 + j)]; eg = a.essence[3 * (g0 + j) + 1]; eb = a.essence[3 * (g0 + j) + 2]; }
+            sr += w[j] * er; sgn += w[j] * eg; sb += w[j] * eb;
+            em = fmaxf(em, dsn_colour_mag(er, eg, eb));
+        }
+        sr = dsn_row_sum_to_last(sr); sgn = dsn_row_sum_to_last(sgn); sb = dsn_row_sum_to_last(sb);
+        if (last && a.albedo_map) { a.albedo_map[3 * r] = sr; a.albedo_map[3 * r + 1] = sgn; a.albedo_map[3 * r + 2] = sb; }
+    }
+    if (a.normal_map) {
+        float sx = 0.f, sy = 0.f, sz = 0.f;
+#pragma unroll
+        for (int j = 0; j < CH; ++j) {
+            float nx = 0.f, ny = 0.f, nz = 0.f;
+            if (at[j] >= 0) { nx = a.n_w[3 * (g0 + j)]; ny = a.n_w[3 * (g0 + j) + 1]; nz = a.n_w[3 * (g0 + j) + 2]; }
+            sx += w[j] * nx; sy += w[j] * ny; sz += w[j] * nz;
+        }
+        sx = dsn_row_sum_to_last(sx); sy = dsn_row_sum_to_last(sy); sz = dsn_row_sum_to_last(sz);
+        if (last) { a.normal_map[3 * r] = sx; a.normal_map[3 * r + 1] = sy; a.normal_map[3 * r + 2] = sz; }
+    }
+    for (int g = 0; g < a.G; ++g) {
+        if (a.colours) {      // k_composite16_multi's light loop
+            const float* cg_ = a.colours + (int64_t)g * a.n_shaded * 3;
+            float sr = 0.f, sgn = 0.f, sb = 0.f;
+#pragma unroll
+            for (int j = 0; j < CH; ++j) {
+                float cr = 0.f, cg = 0.f, cb = 0.f;
+                if (at[j] >= 0) { cr = cg_[3 * at[j]]; cg = cg_[3 * at[j] + 1]; cb = cg_[3 * at[j] + 2]; }
+                sr += w[j] * cr; sgn += w[j] * cg; sb += w[j] * cb;
+                cm = fmaxf(cm, dsn_colour_mag(cr, cg, cb));
+            }
+            sr = dsn_row_sum_to_last(sr); sgn = dsn_row_sum_to_last(sgn); sb = dsn_row_sum_to_last(sb);
+            if (last && a.rgb_maps) {
+                float* rgb = a.rgb_maps + (int64_t)g * a.R * 3;
+                rgb[3 * r] = sr; rgb[3 * r + 1] = sgn; rgb[3 * r + 2] = sb;
+            }
+        }
+        if (a.factors && (a.shading_maps || a.maps_max)) {
+            const float* fg = a.factors + (int64_t)g * a.n_shaded;
+            float ss = 0.f;
+#pragma unroll
+            for (int j = 0; j < CH; ++j) {
+                float f = 0.f;
+                if (at[j] >= 0) f = fg[at[j]];
+                ss += w[j] * f;
+                lm = fmaxf(lm, dsn_nan_to_inf(f));
+            }
+            ss = dsn_row_sum_to_last(ss);
+            if (last && a.shading_maps) a.shading_maps[(int64_t)g * a.R + r] = ss;
+        }
+    }
+    if (a.colour_max && a.colours) composite16_colour_max(cm, lane, a.colour_max);
+    if (a.maps_max) {
+        composite16_colour_max(em, lane, a.maps_max);
+        composite16_colour_max(lm, lane, a.maps_max + 1);
+    }
+}
+
+// any S, any alignment (the stage entry dsn_composite_maps): one wave per ray in chunks of 64 samples, k_composite's scan and
+// butterfly sums.  Dense arrays only (slot = sample), no per-light colours; a light's sum is carried across the chunks in its
+// output word (written and read back by lane 0 alone).
+__global__ void __launch_bounds__(256) k_composite_maps(const DsnMapsArgs a) {
+    const int lane = threadIdx.x & 63;
+    const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int S = a.S;
+    if (r >= a.R) return;   // wave-uniform
+    float d[3] = {a.ray_d[3 * r], a.ray_d[3 * r + 1], a.ray_d[3 * r + 2]};
+    const float dn = dsn_norm3(d);
+    float carry = 1.0f;
+    float alb[3] = {0.f, 0.f, 0.f}, nrm[3] = {0.f, 0.f, 0.f}, sdep = 0.f, sacc = 0.f, em = 0.f, lm = 0.f;
+    for (int base = 0; base < S; base += 64) {
+        const int i = base + lane;
+        const bool in = i < S;
+        const int64_t g = (int64_t)r * S + i;
+        float z = in ? a.z_vals[g] : 0.f;
+        float zn = __shfl_down(z, 1);
+        if (lane == 63 && i + 1 < S) zn = a.z_vals[g + 1];
+        float dist = (i + 1 < S) ? (zn - z) : 1e10f;
+        dist = dist * dn;
+        float s = 0.f;
+        if (in) {
+            s = a.sigma[g];
+            if (a.transparent && a.transparent[g]) s = 0.f;
+            s = s > 0.f ? s : 0.f;
+        }
+        const float alpha = in ? (1.0f - expf(-s * dist)) : 0.f;
+        const float fac = in ? ((1.0f - alpha) + 1e-10f) : 1.0f;
+        float incl = fac;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            float t = __shfl_up(incl, off);
+            if (lane >= off) incl = incl * t;
+        }
+        float excl = __shfl_up(incl, 1);
+        if (lane == 0) excl = 1.0f;
+        const float T = carry * excl;
+        carry = carry * __shfl(incl, 63);
+        const float w = alpha * T;
+        if (in && a.weights) a.weights[g] = w;
+        const bool listed = in && s > 0.f;
+        float e[3] = {0.f, 0.f, 0.f}, n[3] = {0.f, 0.f, 0.f};
+        if (listed && a.essence) { e[0] = a.essence[3 * g]; e[1] = a.essence[3 * g + 1]; e[2] = a.essence[3 * g + 2]; }
+        if (listed && a.n_w) { n[0] = a.n_w[3 * g]; n[1] = a.n_w[3 * g + 1]; n[2] = a.n_w[3 * g + 2]; }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) { alb[c] += dsn_wave_sum(w * e[c]); nrm[c] += dsn_wave_sum(w * n[c]); }
+        sdep += dsn_wave_sum(w * z);
+        sacc += dsn_wave_sum(w);
+        em = fmaxf(em, dsn_colour_mag(e[0], e[1], e[2]));
+        if (a.factors) {
+            for (int k = 0; k < a.G; ++k) {
+                const float f = listed ? a.factors[(int64_t)k * a.n_shaded + g] : 0.f;
+                const float ss = dsn_wave_sum(w * f);
+                lm = fmaxf(lm, dsn_nan_to_inf(f));
+                if (lane == 0 && a.shading_maps) {
+                    float* o = a.shading_maps + (int64_t)k * a.R + r;
+                    *o = base == 0 ? ss : *o + ss;
+                }
+            }
+        }
+    }
+    if (a.maps_max) {
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) { em = fmaxf(em, __shfl_xor(em, off)); lm = fmaxf(lm, __shfl_xor(lm, off)); }
+        if (lane == 0) {
+            if (__float_as_int(em) > __hip_atomic_load(a.maps_max, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(a.maps_max, __float_as_int(em));
+            if (__float_as_int(lm) > __hip_atomic_load(a.maps_max + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(a.maps_max + 1, __float_as_int(lm));
+        }
+    }
+    if (lane == 0) {
+        if (a.albedo_map) { a.albedo_map[3 * r] = alb[0]; a.albedo_map[3 * r + 1] = alb[1]; a.albedo_map[3 * r + 2] = alb[2]; }
+        if (a.normal_map) { a.normal_map[3 * r] = nrm[0]; a.normal_map[3 * r + 1] = nrm[1]; a.normal_map[3 * r + 2] = nrm[2]; }
+        composite16_maps(sdep, sacc, a.depth_map != nullptr, r, a.depth_map, a.acc_map, a.disp_map);
+    }
+}
+
+void dsn_launch_composite_maps(const DsnMapsArgs& a, hipStream_t st) {
+    const bool aligned = dsn_composite_multi_supported(a.S, a.z_vals, a.sigma, a.weights, a.slot_of, a.transparent);
+    if (aligned) {
+        const dim3 grid((unsigned)((a.R + 15) / 16)), block(256);
+        if (a.S == 64) hipLaunchKernelGGL(k_composite16_maps<4>, grid, block, 0, st, a);
+        else hipLaunchKernelGGL(k_composite16_maps<8>, grid, block, 0, st, a);
+        return;
+    }
+    // (the frame entry refuses what the 16-lane form cannot take before it gets here: dense arrays, no per-light colours)
+    hipLaunchKernelGGL(k_composite_maps, dim3((unsigned)((a.R + 3) / 4)), dim3(256), 0, st, a);
+}
+
+// ---------------------------------------------------------------------------------------------
 // Front-to-back evaluation with exact ray termination (DSN_EARLY_STOP, eval mode).
 // utils/nerf_net_utils.py:24-39: weight_i = alpha_i * T_i with T_i = prod_{j<i}(1 - alpha_j + 1e-10) non-increasing along the ray, so
 // once T < eps every later sample has weight < eps and all of them together add less than eps to acc_map (eps * colour to the

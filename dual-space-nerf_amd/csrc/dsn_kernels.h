@@ -97,18 +97,32 @@ void dsn_launch_set_packed_scalar(float* packed, int word, float v, hipStream_t 
 void dsn_launch_light16(const float* packed, const DsnFrameState* fs, const float* n_w, const float* x_w,
                         const float* ray_o, const float* ray_d, const float* z_vals, const float* essence, int64_t N,
                         int S, const int32_t* active_list, const int32_t* active_count, float* colour, hipStream_t st,
-                        float* tr_hl1 = nullptr, float* tr_hl2 = nullptr, float* tr_pre = nullptr, int32_t* range_count = nullptr);
+                        float* tr_hl1 = nullptr, float* tr_hl2 = nullptr, float* tr_pre = nullptr, int32_t* range_count = nullptr,
+                        float* factor = nullptr);      // factor [N] (dsn_shade_factor): the light factor ELU + 1 beside the colour
 // relighting sweep (dsn_render_rays_lights): lighting MLP of G light records per pass over the shading list -> colours [G][count][3]
 // by list slot; the list's slot of every sample (-1 elsewhere: the caller clears `slot`); the compositor of G lights through that map
 void dsn_launch_light16_multi(const float* packed, const DsnLightEdit* lights, int G, const float* n_w, const float* ray_o, const float* ray_d,
                               const float* z_vals, const float* essence, int64_t max_count, int S, const int32_t* list,
-                              const int32_t* list_count, float* colours, hipStream_t st);
+                              const int32_t* list_count, float* colours, hipStream_t st,
+                              float* factors = nullptr);      // factors [G][count] (dsn_render_rays_maps): ELU + 1 by list slot
 void dsn_launch_slot_map(const int32_t* list, const int32_t* count, int64_t max_count, int32_t* slot, hipStream_t st);
 bool dsn_composite_multi_supported(int S, const void* z_vals, const void* sigma, const void* weights, const void* slot_of,
                                    const void* transparent);
 void dsn_launch_composite_multi(const int32_t* slot_of, const float* colours, int64_t n_shaded, int G, const float* sigma,
                                 const uint8_t* transparent, const float* z_vals, const float* ray_d, int R, int S, float* rgb_maps,
                                 float* disp_map, float* acc_map, float* weights, float* depth_map, int32_t* colour_max, hipStream_t st);
+// decomposition maps (dsn_render_rays_maps, dsn_composite_maps): the compositor's weights over the essence, the world normal and the
+// light factors of G lights.  slot_of == NULL: `factors` / `colours` are dense ([G][N], [G][N][3]) and every sample with sigma > 0
+// counts as listed.  Every output pointer may be NULL; maps_max (2 words, float bits, cleared by the caller): largest |essence| and
+// largest factor weighed.  Any S (one wave per ray where S is not 64 / 128 or an array is not 16-byte aligned).
+struct DsnMapsArgs {
+    const int32_t* slot_of; const float* colours; const float* factors; int64_t n_shaded; int G;
+    const float* essence; const float* n_w; const float* sigma; const uint8_t* transparent; const float* z_vals; const float* ray_d;
+    int R, S;
+    float *rgb_maps, *albedo_map, *normal_map, *shading_maps, *disp_map, *acc_map, *weights, *depth_map;
+    int32_t *colour_max, *maps_max;
+};
+void dsn_launch_composite_maps(const DsnMapsArgs& a, hipStream_t st);
 void dsn_launch_camera_rays(const double* K, const double* R, const double* T, const double* bounds, int H, int W,
                             float* ray_o, float* ray_d, float* near, float* far, uint8_t* mask, hipStream_t st, int h36m = 0);
 // dsn_field.hip

@@ -462,6 +462,50 @@ DSN_EXPORT int dsn_render_rays_lights(const void* scene, int V, int F, const voi
                            float* out_weights, float* out_z, void* workspace, size_t workspace_bytes, void* light_scratch,
                            size_t light_scratch_bytes, const int32_t* slice_lengths_host, int n_slices, void* stream);
 
+/* ---- decomposition maps (an addition within ABI 8: no existing entry point changes) ------------------------------------------------
+ * The model is a decomposition: a sample's colour is (ELU(lighting MLP) + 1) x essence (model/spacenet.py:174-188), the lighting MLP fed
+ * by the world normal of normal_local2world (:278-298).  dsn_render_rays_maps is dsn_render_rays_lights that also composites the
+ * factors one by one with the frame's own weights w_i (utils/nerf_net_utils.py:18-51; the bits of out_weights).  With e_i the essence
+ * (SpaceNet.forward's rgbs, model/spacenet.py:141-147), n_i the unit world normal, L_{k,i} = ELU + 1 under light k (after the light
+ * edit of :254-265), summed over the samples i of the frame's SHADING LIST (not transparent, sigma > 0 and - with DSN_EARLY_STOP - not
+ * left out by ray termination or the weight cull):
+ *   out_albedo  [R,3]           sum w_i e_i
+ *   out_normal  [R,3]           sum w_i n_i      world space, NOT renormalised: the acc-weighted mean normal x acc
+ *   out_shading [n_lights,R]    sum w_i L_{k,i}
+ *   out_rgb     [n_lights,R,3]  sum w_i L_{k,i} e_i      dsn_render_rays_lights' out_rgb, bit for bit
+ *   out_max     device, >= 2 floats: the largest |e| (any channel) and the largest L that entered a sum (NaN counts as +inf).
+ * A sample off the list adds 0 to every map, as it adds colour 0 to the frame; in one pass (no DSN_EARLY_STOP) that is exact, since
+ * such a sample has alpha = 0.  With DSN_EARLY_STOP a map with |q| <= Q on the one-pass list is within (S + 1) (eps + 2^-22) Q of its
+ * one-pass value, eps = dsn_early_stop_eps_scaled(S, colour scale): at most S culled samples of weight < eps each and a terminated
+ * tail of total weight < eps (1 + S 2^-23), plus the rounding of two float sums of S terms.  Q = 1 for the normal.  The sums run in
+ * the compositor's order, whatever the grouping of the lights: every map is deterministic and independent of light_scratch_bytes.
+ * Each of out_rgb / out_albedo / out_normal / out_shading / out_max may be NULL.  light_scratch holds 4 floats per shaded sample and
+ * light (the colours and the factors of a group).  Restrictions, the single synchronisation, early stop, the density screen, its
+ * audit and the slice schedule as for dsn_render_rays_lights; albedo, normal, disp, acc, depth and weights are written with the first
+ * group of lights. */
+DSN_EXPORT size_t dsn_render_maps_scratch_bytes(int R, int S, int n_lights, int64_t n_shaded);
+DSN_EXPORT int dsn_render_rays_maps(const void* scene, int V, int F, const void* packed, const float* ray_o, const float* ray_d,
+                         float* near, float* far, int R, int S, const float* t_vals, const float* jitter, const float* noise, int flags,
+                         const float* lights, int n_lights, float* out_rgb, float* out_disp, float* out_acc, float* out_depth,
+                         float* out_weights, float* out_z, float* out_albedo, float* out_normal, float* out_shading, float* out_max,
+                         void* workspace, size_t workspace_bytes, void* light_scratch, size_t light_scratch_bytes,
+                         const int32_t* slice_lengths_host, int n_slices, void* stream);
+/* Stage entry (per-stage parity, like dsn_composite): the three maps of ONE light from dense per-sample arrays - essence [R S,3],
+ * n_w [R S,3], factor [R S] (dsn_shade_factor), sigma [R S], transparent (optional, uint8 [R S]), z_vals [R,S], ray_d [R,3].  A sample
+ * counts where it is not transparent and sigma > 0; the arrays are not read elsewhere.  Any S (S = 64 / 128 with 16-byte aligned
+ * arrays: the 16-lane form of dsn_render_rays_maps; otherwise one wave per ray).  Outputs: albedo_map [R,3], normal_map [R,3],
+ * shading_map [R], weights [R,S], out_max (device, 2 floats) - each may be NULL (a map needs its source array, out_max needs essence
+ * and factor), not all of them. */
+DSN_EXPORT int dsn_composite_maps(const float* essence, const float* n_w, const float* factor, const float* sigma, const uint8_t* transparent,
+                       const float* z_vals, const float* ray_d, int R, int S, float* albedo_map, float* normal_map, float* shading_map,
+                       float* weights, float* out_max, void* stream);
+/* dsn_shade (normal_local2world + the split-fp16 lighting MLP) that also stores the light factor ELU + 1 of every listed sample in
+ * factor [N]; n_w and colour have dsn_shade's bits.  DSN_FIELD_FP32 is rejected. */
+DSN_EXPORT int dsn_shade_factor(const void* scene, int V, int F, const void* packed, const float* x_c, const float* grad, const float* x_w,
+                     const float* ray_d, const float* essence, int64_t N, int S, const int32_t* active_list,
+                     const int32_t* active_count, int32_t* face_idx_canon, float* n_w, float* colour, float* factor, int flags,
+                     void* stream);
+
 /* ---- density grid and iso-surface (an addition within ABI 8: no existing entry point changes) -------------------------------------
  * utils/visualizer.py:35-110 Visualizer3D.get_grid_pred_batch: the reference builds grid_pts on the host (get_grid, :170-236),
  * warps them with Renderer.w2l_without_lbs, evaluates Renderer.query_volume in 100 000-point chunks and sets transparent points to 0.
