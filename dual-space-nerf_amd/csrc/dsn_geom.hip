@@ -392,24 +392,34 @@ void dsn_launch_sample_gg(const float* xyz, int V, const float* ray_o, const flo
 #define NN_TILE 2048
 __device__ __forceinline__ int dsn_nearest_bruteforce(const float4* __restrict__ cent, int F, float px, float py,
                                                       float pz, float4* s_tile) {
-    float best = INFINITY;
-    int bi = 0;
+    // the winner is resolved per block of DSN_NN_BLOCK consecutive indices (DsnBlk, dsn_nn.h: the index of the per-candidate
+    // 'd < best' rule); tiles are whole blocks, so a block's position is the index of its first centroid
+    static_assert(NN_TILE % DSN_NN_BLOCK == 0 && DSN_NN_BLOCK == 8, "tiles of whole blocks");
+    DsnBlk bs;
     for (int base = 0; base < F; base += NN_TILE) {
         int n = min(NN_TILE, F - base);
         __syncthreads();
         for (int j = threadIdx.x; j < n; j += blockDim.x) s_tile[j] = cent[base + j];
         __syncthreads();
-#pragma unroll 8
-        for (int j = 0; j < n; ++j) {
-            float4 c = s_tile[j];
-            float dx = px - c.x, dy = py - c.y, dz = pz - c.z;
-            float d = dx * dx;
-            d = fmaf(dy, dy, d);
-            d = fmaf(dz, dz, d);
-            if (d < best) { best = d; bi = base + j; }
+        int j = 0;
+        for (; j + DSN_NN_BLOCK <= n; j += DSN_NN_BLOCK) {
+            float d[DSN_NN_BLOCK];
+#pragma unroll
+            for (int u = 0; u < DSN_NN_BLOCK; ++u) d[u] = dsn_d2(px, py, pz, s_tile[j + u]);
+            bs.fold8(d[0], d[1], d[2], d[3], d[4], d[5], d[6], d[7]);
+            bs.close(base + j);
+        }
+        if (j < n) {                                 // the table's last, short block
+            const int pos = base + j;
+            for (; j < n; ++j) bs.fold(dsn_d2(px, py, pz, s_tile[j]));
+            bs.close(pos);
         }
     }
-    return bi;
+    return dsn_blk_resolve(px, py, pz, bs.blk, 0, [&](int p) {
+        float4 a = p < F ? cent[p] : dsn_blk_pad();
+        a.w = __int_as_float(p);
+        return a;
+    });
 }
 
 // can_render.py:333-379 w2l_without_lbs.  One thread per sample point.

@@ -109,6 +109,52 @@ __device__ __forceinline__ float dsn_d2(float px, float py, float pz, const floa
     return d;
 }
 
+// Block-deferred winner of a nearest-centroid scan (the scans whose candidates are wave-uniform: k_nns_search, k_nns_search_far,
+// dsn_nearest_bruteforce).  The serial rule is "d < best: best = d, index = this entry" after EVERY candidate - a compare and two
+// selects per candidate and sample, for an index that changes a handful of times over a list.  Here the candidates are taken in
+// blocks of DSN_NN_BLOCK consecutive list entries.  Pass 1 keeps, per sample, the running minimum `run` of all distances so far
+// (v_min3_f32: the minimum IS one of its operands bit for bit; a NaN operand is ignored as '<' ignores it) and, when a block closes,
+// blk = this block's position if run fell strictly below `best`, the minimum at the previous close.  Pass 2 (dsn_blk_resolve, once per
+// lane) re-reads that one block and repeats the serial strict '<' scan over it from +inf.
+// Why the index is the serial scan's: blk is the first block, in list order, whose minimum is strictly below everything in front of it -
+// the first block that attains the list's minimum; the strict scan inside it finds the first entry that attains that minimum.  That is
+// the entry the serial 'd < best' scan stops at, ties included.  A sample no candidate of which is below +inf (NaN coordinates)
+// keeps blk = -1 and its index as it was.  Distances are the same dsn_d2 values in both passes.
+#define DSN_NN_BLOCK 8
+__device__ __forceinline__ float dsn_min3(float a, float b, float c) {
+    float r;      // (asm: a fminf chain is re-associated and gets canonicalising v_max in front - see track16, dsn_field16.hip)
+    asm("v_min3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
+    return r;
+}
+struct DsnBlk {
+    float run = INFINITY, best = INFINITY;      // minimum of every distance folded so far / at the last close()
+    int blk = -1;                               // position of the first entry of the winning block (-1: none yet)
+    __device__ __forceinline__ void fold(float d) { run = dsn_min3(run, d, d); }
+    __device__ __forceinline__ void fold4(float d0, float d1, float d2, float d3) { run = dsn_min3(dsn_min3(d0, d1, d2), d3, run); }
+    __device__ __forceinline__ void fold8(float d0, float d1, float d2, float d3, float d4, float d5, float d6, float d7) {
+        run = dsn_min3(dsn_min3(d0, d1, d2), dsn_min3(d3, d4, d5), dsn_min3(d6, d7, run));
+    }
+    __device__ __forceinline__ void close(int pos) {
+        blk = run < best ? pos : blk;
+        best = run;
+    }
+};
+// pass 2: fetch(p) = entry p of the list the block positions refer to (.w = its face index bits; beyond the list: dsn_blk_pad())
+__device__ __forceinline__ float4 dsn_blk_pad() { return make_float4(INFINITY, INFINITY, INFINITY, 0.f); }      // d = +inf or NaN: never '<'
+template <class Fetch>
+__device__ __forceinline__ int dsn_blk_resolve(float px, float py, float pz, int blk, int keep, Fetch fetch) {
+    if (blk < 0) return keep;
+    float b = INFINITY;
+    int id = keep;
+#pragma unroll 2      // (runs once per lane: kept small, the scans around it live on their registers)
+    for (int j = 0; j < DSN_NN_BLOCK; ++j) {
+        const float4 a = fetch(blk + j);
+        const float d = dsn_d2(px, py, pz, a);
+        if (d < b) { b = d; id = __float_as_int(a.w); }
+    }
+    return id;
+}
+
 // cell index of p in grid g by its geometry alone, or -1 when p is outside the grid
 __device__ __forceinline__ int dsn_grid_cell_geom(const DsnGrid& g, float px, float py, float pz) {
     float fx = (px - g.lo[0]) * g.inv_cell, fy = (py - g.lo[1]) * g.inv_cell, fz = (pz - g.lo[2]) * g.inv_cell;

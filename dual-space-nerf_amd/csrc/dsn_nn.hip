@@ -675,8 +675,9 @@ struct NnsWarp {
     const DsnFaceRec* face_world; const DsnFaceRec* face_canon; uint8_t* transparent; float* x_c; int32_t* active_list;
     int32_t* active_count; int lazy_canon;
 };
+// (amdgpu_waves_per_eu(8): the register budget of eight waves per SIMD, 64 - what the 20 KB of LDS per workgroup allow as well)
 template <bool WARP>
-__global__ void __launch_bounds__(NNS_THREADS) k_nns_search(const int32_t* __restrict__ off_f, const float4* __restrict__ list_f,
+__global__ void __launch_bounds__(NNS_THREADS) __attribute__((amdgpu_waves_per_eu(8))) k_nns_search(const int32_t* __restrict__ off_f, const float4* __restrict__ list_f,
                                                             const int32_t* __restrict__ wave_cell, const int32_t* __restrict__ wave_offs,
                                                             const int32_t* __restrict__ totals, const int32_t* __restrict__ offs,
                                                             const int32_t* __restrict__ counts, const float4* __restrict__ sorted,
@@ -699,7 +700,8 @@ __global__ void __launch_bounds__(NNS_THREADS) k_nns_search(const int32_t* __res
     const int c = __builtin_amdgcn_readfirstlane(wave_cell[wave_on ? w : 0]);
     // TWO samples per lane (slots lane and lane + 64 of the wave's 128): the distance arithmetic runs on packed fp32
     // (v_pk_add / v_pk_mul / v_pk_fma_f32 with the candidate broadcast from SGPRs: 6 instructions per candidate and PAIR of samples
-    // instead of 12 - the same IEEE operations per component, so the same distances bit for bit); compare + select stay per sample
+    // instead of 12 - the same IEEE operations per component, so the same distances bit for bit); the minimum is kept per sample, the
+    // index per block of candidates (below)
     const int slot = (w - __builtin_amdgcn_readfirstlane(wave_offs[c])) * NNS_PER + lane;
     const int cnt_c = __builtin_amdgcn_readfirstlane(counts[c]);
     const bool valid[2] = {wave_on && slot < cnt_c, wave_on && slot + 64 < cnt_c};
@@ -712,34 +714,52 @@ __global__ void __launch_bounds__(NNS_THREADS) k_nns_search(const int32_t* __res
     const int o = __builtin_amdgcn_readfirstlane(off_f[c]);
     const int n = wave_on ? __builtin_amdgcn_readfirstlane(off_f[c + 1]) - o : 0;
     const float4* __restrict__ e = list_f + o;
-    float best[2] = {INFINITY, INFINITY};
+    // The winner is resolved per block of DSN_NN_BLOCK consecutive list entries (DsnBlk, dsn_nn.h: same distances, same index as the
+    // per-candidate 'd < best' rule): bs[h] = the block state of the lane's sample h, bi[h] = its face index once resolved.
+    DsnBlk bs[2];
     int bi[2] = {0, 0};
     // squared distance exactly as dsn_d2: dx * dx, then fma(dy, dy, .), then fma(dz, dz, .) - per component of the pair
-    auto step = [&](const float4 a) {
+    auto dist = [&](const float4 a) {
         const f32x2 cx = {a.x, a.x}, cy = {a.y, a.y}, cz = {a.z, a.z};
         const f32x2 dx = px - cx, dy = py - cy, dz = pz - cz;
         f32x2 d = dx * dx;
         d = __builtin_elementwise_fma(dy, dy, d);
         d = __builtin_elementwise_fma(dz, dz, d);
-        const int id = __float_as_int(a.w);
-        if (d.x < best[0]) { best[0] = d.x; bi[0] = id; }
-        if (d.y < best[1]) { best[1] = d.y; bi[1] = id; }
+        return d;
     };
+    auto block8 = [&](const float4 (&a)[DSN_NN_BLOCK], int pos) {      // one whole block: entries pos .. pos + 7 of the list being walked
+        static_assert(DSN_NN_BLOCK == 8, "fold8");
+        f32x2 d[DSN_NN_BLOCK];
+#pragma unroll
+        for (int u = 0; u < DSN_NN_BLOCK; ++u) d[u] = dist(a[u]);
+        bs[0].fold8(d[0].x, d[1].x, d[2].x, d[3].x, d[4].x, d[5].x, d[6].x, d[7].x);
+        bs[1].fold8(d[0].y, d[1].y, d[2].y, d[3].y, d[4].y, d[5].y, d[6].y, d[7].y);
+        bs[0].close(pos);
+        bs[1].close(pos);
+    };
+    auto batch4 = [&](const float4 (&a)[4]) {                          // half a block (the paths that fetch in batches of 4)
+        f32x2 d[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) d[u] = dist(a[u]);
+        bs[0].fold4(d[0].x, d[1].x, d[2].x, d[3].x);
+        bs[1].fold4(d[0].y, d[1].y, d[2].y, d[3].y);
+    };
+    auto close2 = [&](int pos) { bs[0].close(pos); bs[1].close(pos); };
+#if !defined(DSN_NN_NO_PRUNE)
+    __shared__ __attribute__((aligned(16))) float4 s_surv[NNS_THREADS / 64][NNS_SURVIVORS];
+    float4* const surv = s_surv[__builtin_amdgcn_readfirstlane(threadIdx.x >> 6)];
+#endif
     int k = 0;
     if (!WARP && cent) {
         const int32_t* __restrict__ ids = reinterpret_cast<const int32_t*>(list_f) + o;
         auto at = [&](int f) { float4 a = cent[f]; a.w = __int_as_float(f); return a; };
+        auto entry = [&](int p) { return p < n ? at(ids[p]) : dsn_blk_pad(); };      // pass 2: a lane's own read of list entry p
         // (far points are few per coarse cell - a wave with at most 64 of them leaves the second slot of every lane empty: one
         //  sample per lane, the plain fma chain of dsn_d2)
         const bool single = cnt_c - (w - __builtin_amdgcn_readfirstlane(wave_offs[c])) * NNS_PER <= 64;      // wave-uniform
         if (single) {
-            float b0 = INFINITY;
-            int i0 = 0;
+            DsnBlk b1;
             const float qx = q[0].x, qy = q[0].y, qz = q[0].z;
-            auto step1 = [&](const float4 a) {
-                const float d = dsn_d2(qx, qy, qz, a);
-                if (d < b0) { b0 = d; i0 = __float_as_int(a.w); }
-            };
             constexpr int NB1 = 4;
             const int nb1 = n / NB1;
             int g1[NB1], g2[NB1];
@@ -758,14 +778,16 @@ __global__ void __launch_bounds__(NNS_THREADS) k_nns_search(const int32_t* __res
                     }
 #pragma unroll
                     for (int j = 0; j < NB1; ++j) g2[j] = ids[NB1 * (b + 2 < nb1 ? b + 2 : 0) + j];
-#pragma unroll
-                    for (int j = 0; j < NB1; ++j) step1(c0[j]);
+                    b1.fold4(dsn_d2(qx, qy, qz, c0[0]), dsn_d2(qx, qy, qz, c0[1]), dsn_d2(qx, qy, qz, c0[2]), dsn_d2(qx, qy, qz, c0[3]));
+                    if (b & 1) b1.close(NB1 * (b - 1));      // (wave-uniform: two batches are one block)
 #pragma unroll
                     for (int j = 0; j < NB1; ++j) { c0[j] = c1[j]; g1[j] = g2[j]; }
                 }
             }
-            for (int kk = NB1 * nb1; kk < n; ++kk) step1(at(ids[kk]));
-            if (valid[0]) nn[__float_as_int(q[0].w)] = i0;
+            // the tail (< 4 entries) belongs to the block of entry 4 nb1: the open one when nb1 is odd, else a new, short one
+            for (int kk = NB1 * nb1; kk < n; ++kk) b1.fold(dsn_d2(qx, qy, qz, at(ids[kk])));
+            b1.close((n - 1) & ~(DSN_NN_BLOCK - 1));         // (nothing open: run = best, nothing changes)
+            if (valid[0]) nn[__float_as_int(q[0].w)] = dsn_blk_resolve(qx, qy, qz, b1.blk, 0, entry);
             return;
         }
         // Two dependent scalar loads per candidate (index, then centroid), and scalar loads return out of order - the only wait is
@@ -790,13 +812,17 @@ __global__ void __launch_bounds__(NNS_THREADS) k_nns_search(const int32_t* __res
             for (int b = 0; b < nb; ++b) {
                 if (b + 1 < nb) load_cent(f1, a1);  // centroids of batch b + 1
                 load_ids(b + 2, f2);                // indices of batch b + 2
-#pragma unroll
-                for (int j = 0; j < NB; ++j) step(a0[j]);
+                batch4(a0);
+                if (b & 1) close2(NB * (b - 1));    // (wave-uniform: two batches are one block)
 #pragma unroll
                 for (int j = 0; j < NB; ++j) { a0[j] = a1[j]; f1[j] = f2[j]; }
             }
         }
-        for (k = NB * nb; k < n; ++k) step(at(ids[k]));
+        // the tail (< 4 entries) belongs to the block of entry 4 nb: the open one when nb is odd, else a new, short one
+        for (k = NB * nb; k < n; ++k) { const f32x2 d = dist(at(ids[k])); bs[0].fold(d.x); bs[1].fold(d.y); }
+        close2((n - 1) & ~(DSN_NN_BLOCK - 1));      // (nothing open: run = best, nothing changes)
+#pragma unroll
+        for (int h2 = 0; h2 < 2; ++h2) bi[h2] = dsn_blk_resolve(px[h2], py[h2], pz[h2], bs[h2].blk, 0, entry);
     } else {
     // Per-wave pruning of the cell's candidate list (round 6).  The list holds every face that can be nearest to SOME point of the cell;
     // the wave's 128 samples fill a part of it.  With B = the bounding box of
@@ -813,8 +839,6 @@ __global__ void __launch_bounds__(NNS_THREADS) k_nns_search(const int32_t* __res
     bool pruned = false;
     int ns = 0;
 #if !defined(DSN_NN_NO_PRUNE)
-    __shared__ __attribute__((aligned(16))) float4 s_surv[NNS_THREADS / 64][NNS_SURVIVORS];
-    float4* const surv = s_surv[threadIdx.x >> 6];
     if (n >= 96) {                                   // wave-uniform
         const float INF = INFINITY;
         float lo[3] = {fminf(valid[0] ? q[0].x : INF, valid[1] ? q[1].x : INF), fminf(valid[0] ? q[0].y : INF, valid[1] ? q[1].y : INF),
@@ -839,28 +863,58 @@ __global__ void __launch_bounds__(NNS_THREADS) k_nns_search(const int32_t* __res
         }
 #pragma unroll
         for (int m = 32; m >= 1; m >>= 1) t = fminf(t, __shfl_xor(t, m));
-        t = t * 1.0001f;
+        // (every lane holds the same bounds now: kept in scalar registers, out of the way of the scan)
+        auto uni = [](float x) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(x))); };
+        t = uni(t * 1.0001f);
+#pragma unroll
+        for (int a = 0; a < 3; ++a) { lo[a] = uni(lo[a]); hi[a] = uni(hi[a]); }
         if (t < INF) {                               // (wave-uniform; an unbounded box or a non-finite bound: the whole list)
             pruned = true;
             // the survivors collected so far, in list order (a list that leaves more than the wave's LDS holds is drained in rounds)
+            // Blocks are counted within the round (the next round overwrites the array): a lane whose winning block lies in this
+            // round resolves its index before the round ends; the others keep the index of an earlier round.  The round's last,
+            // short block is padded with candidates at +inf, which no sample is strictly nearer to than to anything.
+            static_assert(NNS_SURVIVORS % DSN_NN_BLOCK == 0, "the padded last block fits the array");
             auto drain = [&]() {
+                if (lane < ((-ns) & (DSN_NN_BLOCK - 1))) surv[ns + lane] = dsn_blk_pad();
                 __builtin_amdgcn_wave_barrier();
+                bs[0].blk = bs[1].blk = -1;
+                // One block of eight, read and evaluated as two halves (the scheduler does not move the second half's reads in front of the
+                // first half's arithmetic): 16 registers of entries in flight instead of 32 - with them the kernel fits 64, eight waves to a
+                // SIMD.  The reads stay whole 16-byte ones (the empty asm keeps .w in use): z is then broadcast to the packed arithmetic
+                // from the aligned register pair (z, w); narrowed to 12 bytes the read costs a move per candidate.
+                auto block_at = [&](int j) {
+                    f32x2 d[DSN_NN_BLOCK];
+#pragma unroll
+                    for (int half = 0; half < 2; ++half) {
+                        float4 a[4];
+#pragma unroll
+                        for (int u = 0; u < 4; ++u) a[u] = surv[j + 4 * half + u];
+#pragma unroll
+                        for (int u = 0; u < 4; ++u) { d[4 * half + u] = dist(a[u]); asm volatile("" ::"v"(a[u].w)); }
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                    bs[0].fold8(d[0].x, d[1].x, d[2].x, d[3].x, d[4].x, d[5].x, d[6].x, d[7].x);
+                    bs[1].fold8(d[0].y, d[1].y, d[2].y, d[3].y, d[4].y, d[5].y, d[6].y, d[7].y);
+                    close2(j);
+                };
+                // (two blocks per trip: the minimum at the previous close and the running one swap registers instead of being copied)
                 int j = 0;
-                for (; j + 8 <= ns; j += 8) {
-                    float4 a[8];
+                for (; j + 2 * DSN_NN_BLOCK <= ns; j += 2 * DSN_NN_BLOCK) { block_at(j); block_at(j + DSN_NN_BLOCK); }
+                for (; j < ns; j += DSN_NN_BLOCK) block_at(j);
 #pragma unroll
-                    for (int u = 0; u < 8; ++u) a[u] = surv[j + u];
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) step(a[u]);
-                }
-                for (; j < ns; ++j) step(surv[j]);
+                for (int h2 = 0; h2 < 2; ++h2)
+                    bi[h2] = dsn_blk_resolve(px[h2], py[h2], pz[h2], bs[h2].blk, bi[h2], [&](int p) { return surv[p]; });
                 __builtin_amdgcn_wave_barrier();
                 ns = 0;
             };
-            for (int k0 = 0; k0 < n; k0 += 64) {
+            // (ONE call site of the drain - the kernel's register count is that of one copy of its loop, with nothing of the sweep live
+            //  across it: the round that would overflow the array is evaluated again after the drain, against the empty array)
+            for (int k0 = 0;;) {
+                const bool last = k0 >= n;                           // (wave-uniform: the sweep is over, drain what is left)
                 bool keep = false;
                 float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (k0 + lane < n) {
+                if (!last && k0 + lane < n) {
                     a = e[k0 + lane];
                     const float gx = fmaxf(fmaxf(lo[0] - a.x, a.x - hi[0]), 0.0f), gy = fmaxf(fmaxf(lo[1] - a.y, a.y - hi[1]), 0.0f),
                                 gz = fmaxf(fmaxf(lo[2] - a.z, a.z - hi[2]), 0.0f);
@@ -868,23 +922,33 @@ __global__ void __launch_bounds__(NNS_THREADS) k_nns_search(const int32_t* __res
                 }
                 const unsigned long long mk = __ballot(keep);
                 const int add = __popcll(mk);
-                if (ns + add > NNS_SURVIVORS) drain();               // (wave-uniform)
-                if (keep) surv[ns + __popcll(mk & ((1ull << lane) - 1ull))] = a;
+                if (last || ns + add > NNS_SURVIVORS) {              // (wave-uniform)
+                    drain();
+                    if (last) break;
+                    continue;
+                }
+                // (mbcnt: the kept entries in the lanes below)
+                if (keep) surv[ns + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mk >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mk, 0u))] = a;
                 ns += add;
+                k0 += 64;
             }
-            drain();
         }
     }
     if (!pruned) {
 #endif
-    for (; k + 8 <= n; k += 8) {                     // wave-uniform addresses: 128 B of candidates per scalar-load batch
-        float4 a[8];
+    for (; k + DSN_NN_BLOCK <= n; k += DSN_NN_BLOCK) {      // wave-uniform addresses: 128 B of candidates per scalar-load batch
+        float4 a[DSN_NN_BLOCK];
 #pragma unroll
-        for (int j = 0; j < 8; ++j) a[j] = e[k + j];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) step(a[j]);
+        for (int j = 0; j < DSN_NN_BLOCK; ++j) a[j] = e[k + j];
+        block8(a, k);
     }
-    for (; k < n; ++k) step(e[k]);
+    if (k < n) {                                     // the tail: a short block
+        for (int j = k; j < n; ++j) { const f32x2 d = dist(e[j]); bs[0].fold(d.x); bs[1].fold(d.y); }
+        close2(k);
+    }
+#pragma unroll
+    for (int h2 = 0; h2 < 2; ++h2)                   // (a lane's own read of list entry p)
+        bi[h2] = dsn_blk_resolve(px[h2], py[h2], pz[h2], bs[h2].blk, 0, [&](int p) { return p < n ? e[p] : dsn_blk_pad(); });
 #if !defined(DSN_NN_NO_PRUNE)
     }
 #endif
@@ -900,7 +964,7 @@ __global__ void __launch_bounds__(NNS_THREADS) k_nns_search(const int32_t* __res
     for (int h2 = 0; h2 < 2; ++h2) {
         idx[h2] = (int64_t)__float_as_int(q[h2].w);
         if (valid[h2]) {
-            const float p[3] = {q[h2].x, q[h2].y, q[h2].z};
+            const float p[3] = {px[h2], py[h2], pz[h2]};
             const DsnFaceRec fw = dsn_load_face(wp.face_world, bi[h2]);
             float u, v, h, xc[3] = {0.f, 0.f, 0.f};
             dsn_project(p, fw, u, v, h);
@@ -916,22 +980,31 @@ __global__ void __launch_bounds__(NNS_THREADS) k_nns_search(const int32_t* __res
         }
     }
     if (wp.active_list) {      // workgroup-aggregated append, as in k_warp: one atomic per 512 samples
-        __shared__ int s_cnt[NNS_THREADS / 64][2];
-        __shared__ int s_base;
         const unsigned long long m0 = __ballot(active[0]), m1 = __ballot(active[1]);
         const int wave = threadIdx.x >> 6;
-        if (lane == 0) { s_cnt[wave][0] = __popcll(m0); s_cnt[wave][1] = __popcll(m1); }
+#if !defined(DSN_NN_NO_PRUNE)
+        // the counts live in the survivor arrays, which are done with: a wave's own two in front of ITS array (the other waves may still
+        // be scanning theirs until the barrier), the base behind wave 0's two - the workgroup's LDS stays at 20 KB, eight to a compute unit
+        static_assert(NNS_SURVIVORS >= 3, "room for the counts");
+        auto s_cnt = [&](int wv2, int h) -> int& { return reinterpret_cast<int*>(s_surv[wv2])[h]; };
+        int& s_base = reinterpret_cast<int*>(s_surv[0])[2];
+#else
+        __shared__ int s_cnt_[NNS_THREADS / 64][2];
+        __shared__ int s_base;
+        auto s_cnt = [&](int wv2, int h) -> int& { return s_cnt_[wv2][h]; };
+#endif
+        if (lane == 0) { s_cnt(wave, 0) = __popcll(m0); s_cnt(wave, 1) = __popcll(m1); }
         __syncthreads();
         if (threadIdx.x == 0) {
             int tot = 0;
-            for (int kk = 0; kk < NNS_THREADS / 64; ++kk) tot += s_cnt[kk][0] + s_cnt[kk][1];
+            for (int kk = 0; kk < NNS_THREADS / 64; ++kk) tot += s_cnt(kk, 0) + s_cnt(kk, 1);
             s_base = tot ? atomicAdd(wp.active_count, tot) : 0;
         }
         __syncthreads();
         int off = s_base;
-        for (int kk = 0; kk < wave; ++kk) off += s_cnt[kk][0] + s_cnt[kk][1];
+        for (int kk = 0; kk < wave; ++kk) off += s_cnt(kk, 0) + s_cnt(kk, 1);
         if (active[0]) wp.active_list[off + __popcll(m0 & ((1ull << lane) - 1ull))] = (int32_t)idx[0];
-        if (active[1]) wp.active_list[off + s_cnt[wave][0] + __popcll(m1 & ((1ull << lane) - 1ull))] = (int32_t)idx[1];
+        if (active[1]) wp.active_list[off + s_cnt(wave, 0) + __popcll(m1 & ((1ull << lane) - 1ull))] = (int32_t)idx[1];
     }
 }
 
@@ -1068,17 +1141,14 @@ __global__ void __launch_bounds__(NNS_THREADS) k_nns_search_far(const int32_t* _
     const int32_t* __restrict__ ids = list_c + o + (len > seg ? k0 : 0);
     typedef float f32x2 __attribute__((ext_vector_type(2)));
     const f32x2 px = {q[0].x, q[1].x}, py = {q[0].y, q[1].y}, pz = {q[0].z, q[1].z};
-    float best[2] = {INFINITY, INFINITY};
-    int bi[2] = {0x7fffffff, 0x7fffffff};
-    auto step = [&](const float4 a) {      // exactly dsn_d2 per component of the pair
+    DsnBlk bs[2];                          // the segment's winner, resolved per block of its entries (DsnBlk, dsn_nn.h)
+    auto dist = [&](const float4 a) {      // exactly dsn_d2 per component of the pair
         const f32x2 cx = {a.x, a.x}, cy = {a.y, a.y}, cz = {a.z, a.z};
         const f32x2 dx = px - cx, dy = py - cy, dz = pz - cz;
         f32x2 d = dx * dx;
         d = __builtin_elementwise_fma(dy, dy, d);
         d = __builtin_elementwise_fma(dz, dz, d);
-        const int id = __float_as_int(a.w);
-        if (d.x < best[0]) { best[0] = d.x; bi[0] = id; }
-        if (d.y < best[1]) { best[1] = d.y; bi[1] = id; }
+        return d;
     };
     auto at = [&](int f) { float4 a = cent[f]; a.w = __int_as_float(f); return a; };
     constexpr int NB = 4;      // one batch ahead on the indices, one on the centroids (see k_nns_search)
@@ -1099,17 +1169,29 @@ __global__ void __launch_bounds__(NNS_THREADS) k_nns_search_far(const int32_t* _
             }
 #pragma unroll
             for (int j = 0; j < NB; ++j) f2[j] = ids[NB * (b + 2 < nb ? b + 2 : 0) + j];
+            {
+                f32x2 d[NB];
 #pragma unroll
-            for (int j = 0; j < NB; ++j) step(a0[j]);
+                for (int j = 0; j < NB; ++j) d[j] = dist(a0[j]);
+                bs[0].fold4(d[0].x, d[1].x, d[2].x, d[3].x);
+                bs[1].fold4(d[0].y, d[1].y, d[2].y, d[3].y);
+            }
+            if (b & 1) { bs[0].close(NB * (b - 1)); bs[1].close(NB * (b - 1)); }      // (wave-uniform: two batches are one block)
 #pragma unroll
             for (int j = 0; j < NB; ++j) { a0[j] = a1[j]; f1[j] = f2[j]; }
         }
     }
-    for (int k = NB * nb; k < n; ++k) step(at(ids[k]));
+    // the tail (< 4 entries) belongs to the block of entry 4 nb: the open one when nb is odd, else a new, short one
+    for (int k = NB * nb; k < n; ++k) { const f32x2 d = dist(at(ids[k])); bs[0].fold(d.x); bs[1].fold(d.y); }
+    bs[0].close((n - 1) & ~(DSN_NN_BLOCK - 1));
+    bs[1].close((n - 1) & ~(DSN_NN_BLOCK - 1));
 #pragma unroll
     for (int h2 = 0; h2 < 2; ++h2)
-        if (valid[h2] && best[h2] < INFINITY)
-            atomicMin(keys + __float_as_int(q[h2].w), ((unsigned long long)__float_as_uint(best[h2]) << 32) | (unsigned)bi[h2]);
+        if (valid[h2] && bs[h2].best < INFINITY) {      // (then a block won: blk >= 0)
+            const int id = dsn_blk_resolve(q[h2].x, q[h2].y, q[h2].z, bs[h2].blk, 0x7fffffff,
+                                           [&](int p) { return p < n ? at(ids[p]) : dsn_blk_pad(); });
+            atomicMin(keys + __float_as_int(q[h2].w), ((unsigned long long)__float_as_uint(bs[h2].best) << 32) | (unsigned)id);
+        }
 }
 __global__ void __launch_bounds__(NNS_THREADS) k_nns_far_finish(const int32_t* __restrict__ cell_of, const unsigned long long* __restrict__ keys,
                                                                 int64_t N, int32_t* __restrict__ nn) {
