@@ -48,13 +48,19 @@ typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 #define F16_FENCE 0           // sched_barrier after every block
 #endif
 #ifndef F16_SGB
-#define F16_SGB 1             // sched_group_barrier interleave (1 MFMA : 4 VALU) inside every block + fence per block
+#define F16_SGB 1             // sched_group_barrier interleave (1 MFMA : F16_SGB_VALU VALU) inside every block + fence per block
 #endif
 #ifndef F16_SGB_VALU
-#define F16_SGB_VALU 4        // VALU instructions per MFMA in that pattern
+#define F16_SGB_VALU 2        // VALU instructions per MFMA in that pattern.  An epilogue slice is 12 instructions per block of 6 MFMAs (the
+                              // accumulators are VGPRs, read in place: build.py FILE_FLAGS): 8 (forward) / 6 (reverse) the compiler sees +
+                              // 4 / 6 inline-asm statements, which no group holds and which settle beside their operands.  Groups of 2
+                              // spread the slice over the block (forward: 3 other issues in most gaps, inside the 5 a gap hides; reverse:
+                              // a fifth of the gaps still hold 6 or more); groups of 4 put the whole slice behind the first
+                              // two or three MFMAs and leave the last gaps empty (profiles/field16_vgpr_ab.txt, scripts/isa_budget.py)
 #endif
 #ifndef F16_SGB_DS
-#define F16_SGB_DS 0          // 1: pin one operand ds_read behind each of the first four MFMAs of a block
+#define F16_SGB_DS 1          // 1: pin one operand ds_read of the next block behind each of the first four MFMAs of a block (0: they fall where
+                              // the scheduler likes, two or three to a gap; reverse kernel -2 % with 1)
 #endif
 #ifndef F16_MIX
 #define F16_MIX 1             // hi / lo split of the pipelined epilogues with v_cvt_pk_f16_f32 + v_fma_mix{lo,hi}_f16 (inline asm)
@@ -267,15 +273,12 @@ __device__ __forceinline__ void dense16(W16& w, int& blk, int lane, const half8 
 #endif
         ++blk;
 #if F16_SGB
-        // pin the issue order inside this block: MFMA, 4 VALU (epilogue slice of the previous output block), MFMA, ...
+        // pin the issue order inside this block: MFMA, ds_read, 2 VALU (epilogue slice of the previous output block), MFMA, ...
         // (hipcc otherwise clusters all MFMAs of a chunk and leaves the VALU work as an unoverlapped tail)
-#if F16_SGB_DS == 2
-        __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);   // the next block's four operand reads first: a full block (6 MFMAs) of lead
-#endif
 #pragma unroll
         for (int i = 0; i < 6; ++i) {
             __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-#if F16_SGB_DS == 1
+#if F16_SGB_DS
             if (i < 4) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);   // one operand ds_read behind each of 4 MFMAs
 #endif
             __builtin_amdgcn_sched_group_barrier(0x002, F16_SGB_VALU, 0);

@@ -1,14 +1,19 @@
 #!/usr/bin/env python3
 """Register / spill / LDS table of the kernels of one .hip file (hipcc -Rpass-analysis=kernel-resource-usage).
     python scripts/kres.py dual-space-nerf_amd/csrc/dsn_field16.hip [-DFOO=1 ...]"""
+import importlib.util
+import os
 import re
 import subprocess
 import sys
 
 src = sys.argv[1]
 extra = sys.argv[2:]
-cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-Wno-inline-asm",
-       "-Wno-unused-result", "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage", "-c", src, "-o", "/tmp/kres.o"] + extra
+# compiled with the product's own flags for this file (build.py FLAGS + FILE_FLAGS)
+_spec = importlib.util.spec_from_file_location("dsn_build", os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "dual-space-nerf_amd", "build.py"))
+_build = importlib.util.module_from_spec(_spec)
+_spec.loader.exec_module(_build)
+cmd = ["/opt/rocm/bin/hipcc"] + _build.flags_for(src) + ["--cuda-device-only", "-Rpass-analysis=kernel-resource-usage", "-c", src, "-o", "/tmp/kres.o"] + extra
 out = subprocess.run(cmd, capture_output=True, text=True).stderr
 rows, cur = [], None
 for line in out.splitlines():
