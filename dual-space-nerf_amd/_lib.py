@@ -6,6 +6,7 @@ eager / CPU fallback: if the library is missing or a call fails, a RuntimeError 
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 
 import torch
@@ -45,6 +46,7 @@ EXPORTS = [
     "dsn_render_lights_scratch_bytes", "dsn_render_rays_lights", "dsn_image_ssim_workspace_bytes", "dsn_image_ssim",
     "dsn_density_grid_workspace_bytes", "dsn_density_grid", "dsn_mc_workspace_bytes", "dsn_mc_count", "dsn_mc_emit", "dsn_mc_table_host",
     "dsn_render_maps_scratch_bytes", "dsn_render_rays_maps", "dsn_composite_maps", "dsn_shade_factor",
+    "dsn_raster_workspace_bytes", "dsn_raster_mesh", "dsn_raster_mesh_ex",
 ]
 
 SKIP_TRANSPARENT = 1
@@ -109,6 +111,12 @@ def lib():
         L.dsn_mc_count.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
         L.dsn_mc_emit.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int,
                                   C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.dsn_raster_workspace_bytes.restype = C.c_size_t
+        L.dsn_raster_workspace_bytes.argtypes = [C.c_int64, C.c_int64, C.c_int, C.c_int]
+        raster = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_int, C.c_int,
+                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
+        L.dsn_raster_mesh.argtypes = raster + [C.c_void_p]
+        L.dsn_raster_mesh_ex.argtypes = raster + [C.c_int, C.c_int, C.c_void_p]
         if L.dsn_abi_version() != 8:
             raise RuntimeError(f"{LIB_PATH} has ABI version {L.dsn_abi_version()}, this binding needs 8 - rebuild it "
                                "(python dual-space-nerf_amd/build.py)")
@@ -633,6 +641,60 @@ def marching_cubes(volume, axes, level, gradient_direction="descent"):
     _check(lib().dsn_mc_emit(_ptr(vol), nx, ny, nz, _ptr(x), _ptr(y), _ptr(z), float(level), MC_GRADIENT[gradient_direction], _ptr(ws),
                              V, T, _ptr(verts) if V else None, _ptr(faces) if T else None, _stream()), "dsn_mc_emit")
     return verts, faces
+
+
+RM_CLEAR, RM_PROJECT, RM_RASTER, RM_RASTER_BIG, RM_SHADE = 1, 2, 4, 8, 16      # DSN_RM_*: the kernels of dsn_raster_mesh_ex
+RM_BIG_PIXELS = 16           # DSN_RM_BIG_PIXELS
+
+
+def raster_camera(camera_pose, yfov, height, width):
+    """(pose [3, 4] float32 numpy, fx, fy) of dsn_raster_mesh: the reference's camera pose (utils/visualizer.py:150-157) where none is
+    given, and the NDC scales of pyrender's PerspectiveCamera(yfov, aspectRatio = width / height) rounded to float32"""
+    import numpy as np
+    if camera_pose is None:
+        camera_pose = np.array([[1.0, 0.0, 0.0, 0.0], [0.0, 1.0, 0.0, 0.0], [0.0, 0.0, 1.0, 2.5], [0.0, 0.0, 0.0, 1.0]])
+    if torch.is_tensor(camera_pose):
+        camera_pose = camera_pose.detach().cpu().numpy()
+    pose = np.ascontiguousarray(np.asarray(camera_pose, dtype=np.float64).reshape(4, 4)[:3], dtype=np.float32)
+    fy = 1.0 / math.tan(0.5 * float(yfov))
+    fx = fy * float(height) / float(width)
+    return pose, float(np.float32(fx)), float(np.float32(fy))
+
+
+def raster_mesh(verts, faces, camera_pose=None, yfov=math.pi / 3, height=1024, width=None, znear=0.05, intensity=30.0,
+                inner=math.pi / 16, outer=math.pi / 6, base=0.3, fx=None, fy=None, phases=0, big_pixels=0, out=None):
+    """dsn_raster_mesh (utils/visualizer.py:144-168 render_mesh, the rule of include/dsnerf.h): the mesh (verts [V, 3] float32,
+    faces [T, 3] int32, device tensors) seen by a pinhole camera at the camera-to-world pose `camera_pose` (4 x 4; default the
+    reference's: the identity at (0, 0, 2.5)) under a spotlight riding with the camera.  Returns {"color" [H, W, 3] uint8 (255 where
+    empty), "depth" [H, W] float32 (0 where empty), "face" [H, W] int32 (-1 where empty)} device tensors.  fx / fy: the NDC scales
+    themselves instead of yfov and the aspect width / height.  phases / big_pixels / out: dsn_raster_mesh_ex's measurement switches
+    (scripts/bench_render_mesh.py; `out` = a dict of an earlier call whose tensors and workspace are used again)."""
+    import numpy as np
+    require_gpu()
+    width = height if width is None else width
+    H, W = int(height), int(width)
+    assert verts.is_cuda and faces.is_cuda, "verts and faces: device tensors"
+    dev = verts.device
+    verts = verts.reshape(-1, 3).to(torch.float32).contiguous()
+    faces = faces.reshape(-1, 3).to(torch.int32).contiguous()
+    V, T = verts.shape[0], faces.shape[0]
+    nbytes = lib().dsn_raster_workspace_bytes(V, T, H, W)
+    if nbytes == 0:
+        raise RuntimeError("dsn_raster_mesh: height and width must be 1 ... 16384 and the mesh below 2^31 vertices and faces")
+    pose, fx0, fy0 = raster_camera(camera_pose, yfov, H, W)
+    fx, fy = (fx0 if fx is None else float(fx)), (fy0 if fy is None else float(fy))
+    light = np.array([intensity, math.cos(inner), math.cos(outer), base], dtype=np.float32)
+    if out is None:
+        out = {"color": torch.empty(H, W, 3, dtype=torch.uint8, device=dev), "depth": torch.empty(H, W, dtype=torch.float32, device=dev),
+               "face": torch.empty(H, W, dtype=torch.int32, device=dev), "_ws": _scratch(nbytes, dev)}
+    ws = out["_ws"]
+    assert ws.numel() >= nbytes and out["face"].shape == (H, W)
+    _check(lib().dsn_raster_mesh_ex(_ptr(verts) if V else None, V, _ptr(faces) if T else None, T, pose.ctypes.data, fx, fy, float(znear),
+                                    light.ctypes.data, H, W, _ptr(out["face"]), _ptr(out["depth"]), _ptr(out["color"]), _ptr(ws), nbytes,
+                                    int(phases), int(big_pixels), _stream()), "dsn_raster_mesh")
+    if phases or big_pixels:
+        return out
+    return {k: out[k] for k in ("color", "depth", "face")}
 
 
 def lbs_warp(scene: Scene, pts, smpl_weights, joint_transforms, bw_type="rigid_center", exhaustive=False):

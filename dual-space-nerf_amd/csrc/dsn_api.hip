@@ -4,6 +4,7 @@
 #include "../../include/dsnerf.h"
 #include "dsn_common.h"
 #include "dsn_kernels.h"
+#include <cmath>
 #include <cstdlib>
 
 #include <stdio.h>
@@ -1244,6 +1245,43 @@ int dsn_mc_table_host(int32_t* out_host, size_t out_ints) {
     DSN_REQUIRE(out_ints >= (size_t)256 * DSN_MC_TABLE_ROW, "dsn_mc_table_host: out_host holds fewer than 256 * DSN_MC_TABLE_ROW ints");
     dsn_mc_table_copy(out_host);
     return 0;
+}
+
+static bool dsn_raster_sizes_ok(int64_t V, int64_t T, int H, int W) {
+    return V >= 0 && T >= 0 && V < ((int64_t)1 << 31) && T < ((int64_t)1 << 31) && H >= 1 && H <= 16384 && W >= 1 && W <= 16384;
+}
+
+size_t dsn_raster_workspace_bytes(int64_t n_verts, int64_t n_faces, int H, int W) {
+    return dsn_raster_sizes_ok(n_verts, n_faces, H, W) ? dsn_raster_workspace_size(n_verts, n_faces, H, W) : 0;
+}
+
+int dsn_raster_mesh_ex(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, const float* cam_pose_host, float fx,
+                       float fy, float znear, const float* light_host, int H, int W, int32_t* out_face, float* out_depth,
+                       uint8_t* out_color, void* workspace, size_t workspace_bytes, int phases, int big_pixels, void* stream) {
+    DSN_REQUIRE(n_verts >= 0 && n_faces >= 0, "dsn_raster_mesh: negative count");
+    DSN_REQUIRE(H >= 1 && H <= 16384 && W >= 1 && W <= 16384, "dsn_raster_mesh: H and W must be 1 ... 16384");
+    DSN_REQUIRE(dsn_raster_sizes_ok(n_verts, n_faces, H, W), "dsn_raster_mesh: 2^31 or more vertices or faces");
+    DSN_REQUIRE(cam_pose_host && light_host && workspace, "dsn_raster_mesh: null argument");
+    DSN_REQUIRE((n_verts == 0 || verts) && (n_faces == 0 || faces), "dsn_raster_mesh: null mesh");
+    DSN_REQUIRE(out_face || out_depth || out_color, "dsn_raster_mesh: no output (out_face, out_depth and out_color are all null)");
+    DSN_REQUIRE(workspace_bytes >= dsn_raster_workspace_size(n_verts, n_faces, H, W), "dsn_raster_mesh: workspace_bytes too small (dsn_raster_workspace_bytes)");
+    DSN_REQUIRE(((uintptr_t)workspace & 15) == 0, "dsn_raster_mesh: workspace must be 16-byte aligned");
+    DSN_REQUIRE(std::isfinite(fx) && std::isfinite(fy) && std::isfinite(znear), "dsn_raster_mesh: fx, fy and znear must be finite");
+    DSN_REQUIRE(znear > 0.0f, "dsn_raster_mesh: znear must be positive");
+    for (int i = 0; i < 12; ++i) DSN_REQUIRE(std::isfinite(cam_pose_host[i]), "dsn_raster_mesh: cam_pose_host is not finite");
+    for (int i = 0; i < 4; ++i) DSN_REQUIRE(std::isfinite(light_host[i]), "dsn_raster_mesh: light_host is not finite");
+    DSN_REQUIRE(light_host[1] > light_host[2], "dsn_raster_mesh: light_host needs cos_inner > cos_outer");
+    DSN_REQUIRE(phases >= 0 && phases < 32 && big_pixels >= 0, "dsn_raster_mesh_ex: bad phases or big_pixels");
+    dsn_launch_raster_mesh(verts, n_verts, faces, n_faces, cam_pose_host, fx, fy, znear, light_host, H, W, out_face, out_depth, out_color,
+                           workspace, phases ? phases : 31, big_pixels ? big_pixels : DSN_RM_BIG_PIXELS, (hipStream_t)stream);
+    return dsn_check_launch("dsn_raster_mesh");
+}
+
+int dsn_raster_mesh(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, const float* cam_pose_host, float fx,
+                    float fy, float znear, const float* light_host, int H, int W, int32_t* out_face, float* out_depth, uint8_t* out_color,
+                    void* workspace, size_t workspace_bytes, void* stream) {
+    return dsn_raster_mesh_ex(verts, n_verts, faces, n_faces, cam_pose_host, fx, fy, znear, light_host, H, W, out_face, out_depth,
+                              out_color, workspace, workspace_bytes, 0, 0, stream);
 }
 
 }  // extern "C"

@@ -1,7 +1,8 @@
 """utils/visualizer.py Visualizer3D with its device-bound methods on gfx950 kernels: the density grid of get_grid_pred_batch
 (Renderer.density_grid, dsn_density_grid) and the marching cubes of get_mesh_from_grid (dsn_mc_count / dsn_mc_emit, the rule of
-include/dsnerf.h).  No skimage, trimesh or pyrender: meshes are returned as numpy (verts, faces); connected=True (trimesh's
-component split) and render_mesh (pyrender) are not provided."""
+include/dsnerf.h), and the preview image of render_mesh (dsn_raster_mesh: a deterministic rasteriser with the reference's camera and
+spotlight, not a pixel copy of pyrender's GL output).  No skimage, trimesh or pyrender: meshes are returned as numpy (verts, faces);
+connected=True (trimesh's component split) is not provided."""
 import numpy as np
 import torch
 
@@ -79,3 +80,22 @@ class Visualizer3D(object):
         if faces.shape[0] == 0:
             return None
         return verts.cpu().numpy(), faces.cpu().numpy()
+
+    @torch.no_grad()
+    def render_mesh(self, mesh, camera_pose=None):
+        """numpy uint8 [resolution_render, resolution_render, 3], as pyrender's `color` (utils/visualizer.py:144-168): the mesh under
+        the reference's camera (yfov pi/3, aspect 1) and spotlight (intensity 30, cones pi/16 and pi/6) on a white background, by
+        dsn_raster_mesh.  mesh: the (verts, faces) pair of get_mesh_from_grid or the {"verts", "faces"} dict of
+        Renderer.extract_mesh, numpy or device.  camera_pose: a 4 x 4 camera-to-world matrix (default the reference's: 2.5 in front
+        of the origin, looking down -z) - a real body is not at the origin; the light rides with the camera, as the reference adds
+        both with one pose."""
+        if mesh is None:
+            raise ValueError("render_mesh: no mesh (get_mesh_from_grid returns None where the level is not crossed)")
+        verts, faces = (mesh["verts"], mesh["faces"]) if isinstance(mesh, dict) else mesh
+
+        def dev(a, dtype):
+            a = a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))
+            return a.to(device="cuda", dtype=dtype)
+        out = _lib.raster_mesh(dev(verts, torch.float32), dev(faces, torch.int32), camera_pose=camera_pose,
+                               height=self.resolution_render, width=self.resolution_render)
+        return out["color"].cpu().numpy()

@@ -555,6 +555,61 @@ DSN_EXPORT int dsn_mc_emit(const float* volume, int nx, int ny, int nz, const fl
 /* the case table (host function, no device work): 256 rows of DSN_MC_TABLE_ROW int32 into a HOST array of out_ints >= 256 rows */
 DSN_EXPORT int dsn_mc_table_host(int32_t* out_host, size_t out_ints);
 
+/* ---- mesh preview (an addition within ABI 8: no existing entry point changes) -------------------------------------------------------
+ * utils/visualizer.py:144-168 Visualizer3D.render_mesh (pyrender: PerspectiveCamera(yfov = pi/3, aspect 1), a SpotLight of intensity 30
+ * with cone angles pi/16 and pi/6 at the camera's pose, white background, no ambient light): a deterministic triangle rasteriser with
+ * that camera and light.  It is NOT a pixel copy of pyrender (GL rasterisation and its PBR shader cannot be pinned); camera, light
+ * geometry, image orientation (row 0 is the top, +x to the right), dtypes and background are pyrender's, and the rule below is fixed
+ * so that a numpy restatement (tests/raster_restate.py) reproduces face and depth bit for bit.  All float32, no fused multiply-add,
+ * `/` and sqrt correctly rounded; parentheses give the order of operations.
+ *   verts [n_verts, 3] float32, faces [n_faces, 3] int32 (device); cam_pose_host: 12 floats in HOST memory, the rows of the
+ *   camera-to-world pose [R | t] (camera looking down -z, y up); fx, fy: the NDC scales 1 / (aspect tan(yfov / 2)) and
+ *   1 / tan(yfov / 2); light_host: 4 floats in HOST memory {intensity, cos_inner, cos_outer, base}.  Both host arrays are read
+ *   before the call returns.
+ * Vertex:   d = v - t;  c_k = (d0 R0k + d1 R1k) + d2 R2k;  w = -c_2;  xn = (fx c_0) / w, yn = (fy c_1) / w;
+ *           px = (xn + 1) (W / 2), py = (1 - yn) (H / 2);  X = rint(px 256), Y = rint(py 256) (round-half-even, 1/256 px);
+ *           valid when w > znear, px and py are finite and |X|, |Y| <= 2^24;  iw = 1 / w.
+ * Triangle: dropped when a vertex index is outside [0, n_verts) (checked on the device), a vertex is invalid, or its signed integer
+ *           area (X1 - X0)(Y2 - Y0) - (Y1 - Y0)(X2 - X0) is 0.  Two-sided: with a negative area vertices 1 and 2 are swapped (P = (v0, v2,
+ *           v1)) and the area negated.  There is NO near-plane clipping: a triangle with a vertex at or behind znear is dropped whole.
+ * Coverage: E_k(p) = (bx - ax)(py - ay) - (by - ay)(px - ax) in int64 with (a, b) = (P[k+1], P[k+2]) (indices mod 3), the edge opposite
+ *           P[k].  The pixel centre p = (256 x + 128, 256 y + 128) is covered when every E_k > 0, or E_k = 0 on a top-left edge
+ *           (by - ay < 0, or by = ay and bx > ax): a pixel on an edge two triangles share belongs to exactly one of them.
+ * Depth:    l_k = float(E_k) / float(area);  q = (l_0 iw_0 + l_1 iw_1) + l_2 iw_2 (iw of P[k]);  z = 1 / q, the camera-space distance along
+ *           -z.  Per pixel the smallest (z bits, face index) wins: nearest fragment, and on equal depth the lowest face index, whatever
+ *           the order the triangles arrive in.  Every call returns the same bits.
+ * Shade:    flat, two-sided, the diffuse term of a glTF punctual spotlight at the camera pointing down -z.
+ *           xn = float(2 x + 1) / W - 1, yn = 1 - float(2 y + 1) / H;  p = ((xn z) / fx, (yn z) / fy, -z);
+ *           r2 = (px px + py py) + z z, r = sqrt(r2);  s = clamp((z / r - cos_outer) / (cos_inner - cos_outer), 0, 1)^2;
+ *           n = (c1 - c0) x (c2 - c0) from the camera coordinates of the face's vertices in the order given, each component
+ *           a b - c d;  nn = sqrt((n0 n0 + n1 n1) + n2 n2);  ndl = |(n0 px + n1 py) - n2 z| / (nn r), or 0 when nn = 0;
+ *           col = ((k s) ndl) / r2 with k = (base intensity) / float(pi);  level = floor(min(col, 1) 255 + 0.5) in all three channels.
+ * Outputs (device; each may be NULL, not all): out_face [H, W] int32 (-1 empty), out_depth [H, W] float32 z (0 where empty, as
+ * pyrender's depth), out_color [H, W, 3] uint8 (255 where empty).  A mesh with 0 faces gives the empty image.
+ * Rejected: null required pointers, H or W outside 1 ... 16384, negative counts or 2^31 and more, a workspace smaller than
+ * dsn_raster_workspace_bytes(n_verts, n_faces, H, W) (0 for bad sizes) or not 16-byte aligned, fx / fy / znear not finite, znear <= 0
+ * (depth must be positive: its bits are ordered as integers), light values not finite or cos_inner <= cos_outer.
+ * Kernels: a 64-bit visibility buffer (depth bits << 32 | face) cleared by the call, one thread per vertex, one thread per triangle
+ * with one 64-bit unsigned atomic minimum per covered pixel; a triangle whose pixel bounding box holds more than
+ * DSN_RM_BIG_PIXELS pixels is rasterised by a whole wave instead.  No allocation, no synchronisation, all on `stream`. */
+#define DSN_RM_BIG_PIXELS 16      /* measured: scripts/bench_render_mesh.py, profiles/render_mesh_bench.json */
+DSN_EXPORT size_t dsn_raster_workspace_bytes(int64_t n_verts, int64_t n_faces, int H, int W);
+DSN_EXPORT int dsn_raster_mesh(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, const float* cam_pose_host,
+                               float fx, float fy, float znear, const float* light_host, int H, int W, int32_t* out_face,
+                               float* out_depth, uint8_t* out_color, void* workspace, size_t workspace_bytes, void* stream);
+/* measurement (scripts/bench_render_mesh.py): enqueue only these kernels (0 = all; one mesh and one workspace through the phases of a
+ * frame, in order), and the box size above which a triangle takes the wave form (0 = DSN_RM_BIG_PIXELS).  The image does not depend on
+ * big_pixels. */
+#define DSN_RM_CLEAR 1
+#define DSN_RM_PROJECT 2
+#define DSN_RM_RASTER 4
+#define DSN_RM_RASTER_BIG 8
+#define DSN_RM_SHADE 16
+DSN_EXPORT int dsn_raster_mesh_ex(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, const float* cam_pose_host,
+                                  float fx, float fy, float znear, const float* light_host, int H, int W, int32_t* out_face,
+                                  float* out_depth, uint8_t* out_color, void* workspace, size_t workspace_bytes, int phases,
+                                  int big_pixels, void* stream);
+
 /* diagnostics, NOT for the hot path (synchronises `stream`): {ncell, ok, total entries, capacity} of the four
  * nearest-face list levels (world fine/coarse, canonical fine/coarse) into a HOST array of 16 int32. */
 DSN_EXPORT int dsn_debug_nn_stats(const void* scene, int V, int F, int32_t* out16_host, void* stream);

@@ -9,7 +9,7 @@ while [ $# -gt 1 ]; do
   ( /opt/rocm/bin/hipcc $CF $flags \
       -c $P/csrc/dsn_field16.hip -o $P/variants/$name.o 2> $P/variants/$name.log && \
     /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC $P/build/dsn_api.o $P/build/dsn_geom.o $P/build/dsn_nn.o $P/build/dsn_field.o \
-      $P/variants/$name.o $P/build/dsn_train.o $P/build/dsn_image.o $P/build/dsn_mesh.o -o $P/variants/$name.so && echo "built $name" ) &
+      $P/variants/$name.o $P/build/dsn_train.o $P/build/dsn_image.o $P/build/dsn_mesh.o $P/build/dsn_raster.o -o $P/variants/$name.so && echo "built $name" ) &
 done
 wait
 rm -f $P/variants/*.o

@@ -11,7 +11,7 @@ while [ $# -gt 1 ]; do
   ( /opt/rocm/bin/hipcc $CF16 $flags -c $P/csrc/dsn_field16.hip -o $P/variants/$name.f16.o 2> $P/variants/$name.log && \
     /opt/rocm/bin/hipcc $CF $flags -c $P/csrc/dsn_train.hip -o $P/variants/$name.train.o 2>> $P/variants/$name.log && \
     /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC $P/build/dsn_api.o $P/build/dsn_geom.o $P/build/dsn_nn.o $P/build/dsn_field.o \
-      $P/variants/$name.f16.o $P/variants/$name.train.o $P/build/dsn_image.o $P/build/dsn_mesh.o -o $P/variants/$name.so && echo "built $name" ) &
+      $P/variants/$name.f16.o $P/variants/$name.train.o $P/build/dsn_image.o $P/build/dsn_mesh.o $P/build/dsn_raster.o -o $P/variants/$name.so && echo "built $name" ) &
 done
 wait
 rm -f $P/variants/*.o
