@@ -46,7 +46,7 @@ EXPORTS = [
     "dsn_render_lights_scratch_bytes", "dsn_render_rays_lights", "dsn_image_ssim_workspace_bytes", "dsn_image_ssim",
     "dsn_density_grid_workspace_bytes", "dsn_density_grid", "dsn_mc_workspace_bytes", "dsn_mc_count", "dsn_mc_emit", "dsn_mc_table_host",
     "dsn_render_maps_scratch_bytes", "dsn_render_rays_maps", "dsn_composite_maps", "dsn_shade_factor",
-    "dsn_raster_workspace_bytes", "dsn_raster_mesh", "dsn_raster_mesh_ex",
+    "dsn_raster_workspace_bytes", "dsn_raster_mesh", "dsn_raster_mesh_ex", "dsn_mc_normals", "dsn_raster_mesh_attr",
 ]
 
 SKIP_TRANSPARENT = 1
@@ -111,12 +111,15 @@ def lib():
         L.dsn_mc_count.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
         L.dsn_mc_emit.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int,
                                   C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.dsn_mc_normals.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int,
+                                     C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
         L.dsn_raster_workspace_bytes.restype = C.c_size_t
         L.dsn_raster_workspace_bytes.argtypes = [C.c_int64, C.c_int64, C.c_int, C.c_int]
         raster = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_int, C.c_int,
                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
         L.dsn_raster_mesh.argtypes = raster + [C.c_void_p]
         L.dsn_raster_mesh_ex.argtypes = raster + [C.c_int, C.c_int, C.c_void_p]
+        L.dsn_raster_mesh_attr.argtypes = raster + [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         if L.dsn_abi_version() != 8:
             raise RuntimeError(f"{LIB_PATH} has ABI version {L.dsn_abi_version()}, this binding needs 8 - rebuild it "
                                "(python dual-space-nerf_amd/build.py)")
@@ -620,9 +623,10 @@ def mc_table():
     return out
 
 
-def marching_cubes(volume, axes, level, gradient_direction="descent"):
+def marching_cubes(volume, axes, level, gradient_direction="descent", want_normals=False):
     """dsn_mc_count + dsn_mc_emit on a device volume [nx, ny, nz]: (verts [V,3] float32, faces [T,3] int32) device tensors, both empty
-    where the level is not crossed.  One device->host read (the two counts)."""
+    where the level is not crossed.  One device->host read (the two counts).  want_normals: a third tensor, the unit vertex normals
+    [V,3] float32 of dsn_mc_normals (verts and faces keep their bits)."""
     if gradient_direction not in MC_GRADIENT:
         raise ValueError('gradient_direction must be "descent" or "ascent"')
     vol = volume
@@ -640,11 +644,17 @@ def marching_cubes(volume, axes, level, gradient_direction="descent"):
     faces = torch.empty(T, 3, dtype=torch.int32, device=dev)
     _check(lib().dsn_mc_emit(_ptr(vol), nx, ny, nz, _ptr(x), _ptr(y), _ptr(z), float(level), MC_GRADIENT[gradient_direction], _ptr(ws),
                              V, T, _ptr(verts) if V else None, _ptr(faces) if T else None, _stream()), "dsn_mc_emit")
-    return verts, faces
+    if not want_normals:
+        return verts, faces
+    normals = torch.empty(V, 3, dtype=torch.float32, device=dev)
+    _check(lib().dsn_mc_normals(_ptr(vol), nx, ny, nz, _ptr(x), _ptr(y), _ptr(z), float(level), MC_GRADIENT[gradient_direction], _ptr(ws),
+                                V, _ptr(normals) if V else None, _stream()), "dsn_mc_normals")
+    return verts, faces, normals
 
 
 RM_CLEAR, RM_PROJECT, RM_RASTER, RM_RASTER_BIG, RM_SHADE = 1, 2, 4, 8, 16      # DSN_RM_*: the kernels of dsn_raster_mesh_ex
 RM_BIG_PIXELS = 16           # DSN_RM_BIG_PIXELS
+RM_SMOOTH, RM_UNLIT = 1, 2   # DSN_RM_*: the mode word of dsn_raster_mesh_attr
 
 
 def raster_camera(camera_pose, yfov, height, width):
@@ -662,13 +672,19 @@ def raster_camera(camera_pose, yfov, height, width):
 
 
 def raster_mesh(verts, faces, camera_pose=None, yfov=math.pi / 3, height=1024, width=None, znear=0.05, intensity=30.0,
-                inner=math.pi / 16, outer=math.pi / 6, base=0.3, fx=None, fy=None, phases=0, big_pixels=0, out=None):
+                inner=math.pi / 16, outer=math.pi / 6, base=0.3, fx=None, fy=None, phases=0, big_pixels=0, out=None,
+                vertex_normals=None, vertex_colors=None, smooth=False, lit=True):
     """dsn_raster_mesh (utils/visualizer.py:144-168 render_mesh, the rule of include/dsnerf.h): the mesh (verts [V, 3] float32,
     faces [T, 3] int32, device tensors) seen by a pinhole camera at the camera-to-world pose `camera_pose` (4 x 4; default the
     reference's: the identity at (0, 0, 2.5)) under a spotlight riding with the camera.  Returns {"color" [H, W, 3] uint8 (255 where
     empty), "depth" [H, W] float32 (0 where empty), "face" [H, W] int32 (-1 where empty)} device tensors.  fx / fy: the NDC scales
     themselves instead of yfov and the aspect width / height.  phases / big_pixels / out: dsn_raster_mesh_ex's measurement switches
-    (scripts/bench_render_mesh.py; `out` = a dict of an earlier call whose tensors and workspace are used again)."""
+    (scripts/bench_render_mesh.py; `out` = a dict of an earlier call whose tensors and workspace are used again).
+    vertex_normals / vertex_colors [V, 3] float32, smooth, lit=False: dsn_raster_mesh_attr - world-space vertex normals (shaded smooth
+    with smooth=True) and vertex colours interpolated over every triangle; the colours take the grey base's place under the spotlight
+    (lit) or are painted as they are (lit=False).  The dict then also holds "normal" [H, W, 3] float32 (the unit world normal of every
+    pixel) and, with colours, "attr" [H, W, 3] float32 (the interpolated colour, not clamped), both 0 where empty.  Without any of
+    the four the call is dsn_raster_mesh_ex's, bit for bit."""
     import numpy as np
     require_gpu()
     width = height if width is None else width
@@ -684,17 +700,38 @@ def raster_mesh(verts, faces, camera_pose=None, yfov=math.pi / 3, height=1024, w
     pose, fx0, fy0 = raster_camera(camera_pose, yfov, H, W)
     fx, fy = (fx0 if fx is None else float(fx)), (fy0 if fy is None else float(fy))
     light = np.array([intensity, math.cos(inner), math.cos(outer), base], dtype=np.float32)
+    attr = vertex_normals is not None or vertex_colors is not None or smooth or not lit
+    if smooth and vertex_normals is None:
+        raise ValueError("raster_mesh: smooth=True needs vertex_normals")
+
+    def per_vertex(a, what):
+        if a is None:
+            return None
+        a = a.to(device=dev, dtype=torch.float32).reshape(-1, 3).contiguous()
+        if a.shape[0] != V:
+            raise ValueError(f"raster_mesh: {what} has {a.shape[0]} rows for {V} vertices")
+        return a
+    vn, vc = per_vertex(vertex_normals, "vertex_normals"), per_vertex(vertex_colors, "vertex_colors")
     if out is None:
         out = {"color": torch.empty(H, W, 3, dtype=torch.uint8, device=dev), "depth": torch.empty(H, W, dtype=torch.float32, device=dev),
                "face": torch.empty(H, W, dtype=torch.int32, device=dev), "_ws": _scratch(nbytes, dev)}
+    if attr and "normal" not in out:
+        out["normal"] = torch.empty(H, W, 3, dtype=torch.float32, device=dev)
+    if vc is not None and "attr" not in out:
+        out["attr"] = torch.empty(H, W, 3, dtype=torch.float32, device=dev)
     ws = out["_ws"]
     assert ws.numel() >= nbytes and out["face"].shape == (H, W)
-    _check(lib().dsn_raster_mesh_ex(_ptr(verts) if V else None, V, _ptr(faces) if T else None, T, pose.ctypes.data, fx, fy, float(znear),
-                                    light.ctypes.data, H, W, _ptr(out["face"]), _ptr(out["depth"]), _ptr(out["color"]), _ptr(ws), nbytes,
-                                    int(phases), int(big_pixels), _stream()), "dsn_raster_mesh")
+    head = (_ptr(verts) if V else None, V, _ptr(faces) if T else None, T, pose.ctypes.data, fx, fy, float(znear), light.ctypes.data, H, W,
+            _ptr(out["face"]), _ptr(out["depth"]), _ptr(out["color"]), _ptr(ws), nbytes, int(phases), int(big_pixels))
+    if attr:
+        mode = (RM_SMOOTH if smooth else 0) | (0 if lit else RM_UNLIT)
+        _check(lib().dsn_raster_mesh_attr(*head, _ptr(vn) if V else None, _ptr(vc) if V else None, mode, _ptr(out["normal"]),
+                                          _ptr(out["attr"]) if vc is not None else None, _stream()), "dsn_raster_mesh_attr")
+    else:
+        _check(lib().dsn_raster_mesh_ex(*head, _stream()), "dsn_raster_mesh")
     if phases or big_pixels:
         return out
-    return {k: out[k] for k in ("color", "depth", "face")}
+    return {k: out[k] for k in ("color", "depth", "face", "normal", "attr") if k in out and (attr or k in ("color", "depth", "face"))}
 
 
 def lbs_warp(scene: Scene, pts, smpl_weights, joint_transforms, bw_type="rigid_center", exhaustive=False):

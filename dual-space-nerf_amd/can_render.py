@@ -1184,15 +1184,88 @@ class Renderer:
         return axes, vol
 
     def extract_mesh(self, batch, resolution=512, level=0.5, gradient_direction="ascent", axes=None, points=None, frame=None,
-                     fp32=False, slab_points=None):
+                     fp32=False, slab_points=None, normals=False, attributes=None):
         """Visualizer3D's mesh of the posed body on the device: density_grid + marching cubes (dsn_mc_count / dsn_mc_emit, the rule of
         include/dsnerf.h).  Defaults are the visualizer's __main__ values.  Returns {"verts" [V,3] float32, "faces" [T,3] int32} device
-        tensors in world coordinates, or None where the level is not crossed (the reference returns None there)."""
+        tensors in world coordinates, or None where the level is not crossed (the reference returns None there).
+        normals=True adds "normals" [V,3] float32, the unit vertex normals of dsn_mc_normals (along the density's gradient: out of the
+        body with gradient_direction="descent", into it with "ascent", as the triangles of that mode are oriented); attributes: a tuple of mesh_attributes' names ("albedo", "normal", "colour", "sigma", "valid"), evaluated at the
+        vertices with mesh_attributes' defaults and added under those names.  verts and faces do not depend on either."""
+        names = tuple(attributes) if attributes else ()
+        unknown = set(names) - set(self.MESH_ATTRIBUTES)
+        if unknown:
+            raise ValueError(f"extract_mesh: unknown attributes {sorted(unknown)} {self.MESH_ATTRIBUTES}")
         axes, vol = self.density_grid(batch, resolution, axes, points, frame, fp32, slab_points)
-        verts, faces = _lib.marching_cubes(vol, axes, level, gradient_direction)
-        if faces.shape[0] == 0:
+        out = _lib.marching_cubes(vol, axes, level, gradient_direction, want_normals=bool(normals))
+        if out[1].shape[0] == 0:
             return None
-        return {"verts": verts, "faces": faces}
+        mesh = {"verts": out[0], "faces": out[1]}
+        if normals:
+            mesh["normals"] = out[2]
+        if names:
+            a = self.mesh_attributes(batch, out[0], frame=frame)
+            mesh.update({k: a[k] for k in names})
+        return mesh
+
+    MESH_ATTRIBUTES = ("albedo", "normal", "colour", "sigma", "valid")
+    MESH_VIEW_ORIGIN = (0.0, 0.0, 2.5)      # the translation of the mesh preview's default camera pose (_lib.raster_camera)
+
+    @torch.no_grad()
+    def mesh_attributes(self, batch, verts, view_origin=None, view_dirs=None, lights=None, frame=None, slab=1 << 22):
+        """The field at the vertices of a mesh of batch's posed body (world coordinates, e.g. extract_mesh's): per slab of at most
+        `slab` vertices dsn_warp (one sample per ray: per-vertex directions, an active list), dsn_field (essence and gradient of the
+        listed vertices) and dsn_shade - the stage kernels as they are, so every value has the bits of those three calls, whatever
+        the slab size.  The viewing direction of a vertex is verts - view_origin (default MESH_VIEW_ORIGIN), or view_dirs [V,3].
+        Returns device tensors: "albedo" [V,3] (the essence), "normal" [V,3] (dsn_shade's unit world normal), "colour" [V,3]
+        ((ELU + 1) x essence, the lit colour; with lights = [...] in render_view_lights' form [K,V,3]: dsn_shade once per light, the
+        warp and the field once), "sigma" [V], "valid" [V] bool - False where the warp calls the vertex transparent; everything
+        else is 0 there.  Frame, pose and code as density_grid takes them (no light edit of the net's applies without `lights`);
+        the scene is left as density_grid leaves it, and render calls that follow set their own frame."""
+        self._ensure_mesh(batch)
+        fi = int(torch.as_tensor(batch["frame"] if frame is None else frame).reshape(-1)[0])
+        packed = self.net.packed(self.device)
+        poses, zero = batch["poses"][0], self.net.nerf.w is not None
+        _lib.scene_set_pose(self.scene, packed, poses, fi, zero)
+        self._frame_src = None          # (as density_grid: stage calls set their frame again)
+        dev = self.device
+        verts = torch.as_tensor(verts).to(device=dev, dtype=torch.float32).reshape(-1, 3).contiguous()
+        V = verts.shape[0]
+        if view_dirs is not None:
+            dirs = torch.as_tensor(view_dirs).to(device=dev, dtype=torch.float32).reshape(-1, 3).contiguous()
+            if dirs.shape[0] != V:
+                raise ValueError(f"mesh_attributes: view_dirs has {dirs.shape[0]} rows for {V} vertices")
+        else:
+            o = torch.as_tensor(self.MESH_VIEW_ORIGIN if view_origin is None else view_origin)
+            dirs = verts - o.to(device=dev, dtype=torch.float32).reshape(1, 3)
+        recs = None
+        if lights is not None:
+            lights = list(lights)
+            th = batch["Th"][0] if any(lt.get("light_center") is not None for lt in lights) else None
+            recs = _lib.light_records(lights, th, "cpu")
+        K = None if recs is None else recs.shape[0]
+        out = {"albedo": torch.zeros(V, 3, device=dev), "normal": torch.zeros(V, 3, device=dev),
+               "colour": torch.zeros((V, 3) if K is None else (K, V, 3), device=dev), "sigma": torch.zeros(V, device=dev),
+               "valid": torch.zeros(V, dtype=torch.bool, device=dev)}
+        slab = max(int(slab), 1)
+        for s0 in range(0, V, slab):
+            sl = slice(s0, min(s0 + slab, V))
+            x_w, d = verts[sl].contiguous(), dirs[sl].contiguous()
+            w = _lib.warp(self.scene, x_w, d, 1, want_dir=True, want_active=True)
+            act = (w["active_list"], w["active_count"])
+            sigma, ess, grad = _lib.field(self.scene, packed, w["x_c"], active=act)
+            out["valid"][sl] = w["transparent"] == 0
+            out["sigma"][sl], out["albedo"][sl] = sigma, ess
+            if recs is None:
+                _, out["normal"][sl], out["colour"][sl] = _lib.shade(self.scene, packed, w["x_c"], grad, x_w, d, ess, 1, active=act)
+                continue
+            for k in range(K):
+                r = recs[k]
+                _lib.scene_set_pose(self.scene, packed, poses, fi, zero, r[1:4] if r[0] else None, r[5:9] if r[4] else None,
+                                    r[9:11] if r[4] else None)
+                _, out["normal"][sl], out["colour"][k, sl] = _lib.shade(self.scene, packed, w["x_c"], grad, x_w, d, ess, 1, active=act)
+        if recs is not None:
+            _lib.scene_set_pose(self.scene, packed, poses, fi, zero)
+        return out
 
     # ---- density query for marching cubes (reference :280-296) ----
     def query_volume(self, pts, code_idx, transparent_mask=None, batch_info={}):

@@ -1240,6 +1240,20 @@ int dsn_mc_emit(const float* volume, int nx, int ny, int nz, const float* x, con
     return dsn_check_launch("dsn_mc_emit");
 }
 
+int dsn_mc_normals(const float* volume, int nx, int ny, int nz, const float* x, const float* y, const float* z, float level,
+                   int gradient_direction, const void* workspace, int64_t n_verts, float* normals, void* stream) {
+    DSN_REQUIRE(volume && x && y && z && workspace, "dsn_mc_normals: null argument");
+    DSN_REQUIRE(dsn_mc_sizes_ok(nx, ny, nz), "dsn_mc_normals: bad grid size (every axis >= 2, fewer than 2^31 points)");
+    DSN_REQUIRE(level == level, "dsn_mc_normals: NaN level");
+    DSN_REQUIRE(gradient_direction == DSN_MC_DESCENT || gradient_direction == DSN_MC_ASCENT, "dsn_mc_normals: gradient_direction must be DSN_MC_DESCENT or DSN_MC_ASCENT");
+    DSN_REQUIRE(n_verts >= 0, "dsn_mc_normals: negative count");
+    DSN_REQUIRE(n_verts == 0 || normals, "dsn_mc_normals: null output buffer");
+    if (n_verts == 0) return 0;
+    dsn_launch_mc_normals(volume, nx, ny, nz, x, y, z, level, gradient_direction == DSN_MC_ASCENT, workspace, normals, n_verts,
+                          (hipStream_t)stream);
+    return dsn_check_launch("dsn_mc_normals");
+}
+
 int dsn_mc_table_host(int32_t* out_host, size_t out_ints) {
     DSN_REQUIRE(out_host, "dsn_mc_table_host: null argument");
     DSN_REQUIRE(out_ints >= (size_t)256 * DSN_MC_TABLE_ROW, "dsn_mc_table_host: out_host holds fewer than 256 * DSN_MC_TABLE_ROW ints");
@@ -1255,15 +1269,18 @@ size_t dsn_raster_workspace_bytes(int64_t n_verts, int64_t n_faces, int H, int W
     return dsn_raster_sizes_ok(n_verts, n_faces, H, W) ? dsn_raster_workspace_size(n_verts, n_faces, H, W) : 0;
 }
 
-int dsn_raster_mesh_ex(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, const float* cam_pose_host, float fx,
-                       float fy, float znear, const float* light_host, int H, int W, int32_t* out_face, float* out_depth,
-                       uint8_t* out_color, void* workspace, size_t workspace_bytes, int phases, int big_pixels, void* stream) {
+// the checks and the launch of dsn_raster_mesh_ex and dsn_raster_mesh_attr (extra: the latter's two further outputs count as outputs)
+static int dsn_raster_mesh_any(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, const float* cam_pose_host, float fx,
+                               float fy, float znear, const float* light_host, int H, int W, int32_t* out_face, float* out_depth,
+                               uint8_t* out_color, void* workspace, size_t workspace_bytes, int phases, int big_pixels,
+                               const float* vertex_normals, const float* vertex_colors, int mode, float* out_normal, float* out_attr,
+                               void* stream) {
     DSN_REQUIRE(n_verts >= 0 && n_faces >= 0, "dsn_raster_mesh: negative count");
     DSN_REQUIRE(H >= 1 && H <= 16384 && W >= 1 && W <= 16384, "dsn_raster_mesh: H and W must be 1 ... 16384");
     DSN_REQUIRE(dsn_raster_sizes_ok(n_verts, n_faces, H, W), "dsn_raster_mesh: 2^31 or more vertices or faces");
     DSN_REQUIRE(cam_pose_host && light_host && workspace, "dsn_raster_mesh: null argument");
     DSN_REQUIRE((n_verts == 0 || verts) && (n_faces == 0 || faces), "dsn_raster_mesh: null mesh");
-    DSN_REQUIRE(out_face || out_depth || out_color, "dsn_raster_mesh: no output (out_face, out_depth and out_color are all null)");
+    DSN_REQUIRE(out_face || out_depth || out_color || out_normal || out_attr, "dsn_raster_mesh: no output (out_face, out_depth and out_color are all null)");
     DSN_REQUIRE(workspace_bytes >= dsn_raster_workspace_size(n_verts, n_faces, H, W), "dsn_raster_mesh: workspace_bytes too small (dsn_raster_workspace_bytes)");
     DSN_REQUIRE(((uintptr_t)workspace & 15) == 0, "dsn_raster_mesh: workspace must be 16-byte aligned");
     DSN_REQUIRE(std::isfinite(fx) && std::isfinite(fy) && std::isfinite(znear), "dsn_raster_mesh: fx, fy and znear must be finite");
@@ -1272,9 +1289,30 @@ int dsn_raster_mesh_ex(const float* verts, int64_t n_verts, const int32_t* faces
     for (int i = 0; i < 4; ++i) DSN_REQUIRE(std::isfinite(light_host[i]), "dsn_raster_mesh: light_host is not finite");
     DSN_REQUIRE(light_host[1] > light_host[2], "dsn_raster_mesh: light_host needs cos_inner > cos_outer");
     DSN_REQUIRE(phases >= 0 && phases < 32 && big_pixels >= 0, "dsn_raster_mesh_ex: bad phases or big_pixels");
-    dsn_launch_raster_mesh(verts, n_verts, faces, n_faces, cam_pose_host, fx, fy, znear, light_host, H, W, out_face, out_depth, out_color,
-                           workspace, phases ? phases : 31, big_pixels ? big_pixels : DSN_RM_BIG_PIXELS, (hipStream_t)stream);
+    DSN_REQUIRE(mode >= 0 && mode <= (DSN_RM_SMOOTH | DSN_RM_UNLIT), "dsn_raster_mesh_attr: mode must be a combination of DSN_RM_SMOOTH and DSN_RM_UNLIT");
+    DSN_REQUIRE(!(mode & DSN_RM_SMOOTH) || vertex_normals || n_verts == 0, "dsn_raster_mesh_attr: DSN_RM_SMOOTH needs vertex_normals (null)");
+    DSN_REQUIRE(!out_attr || vertex_colors || n_verts == 0, "dsn_raster_mesh_attr: out_attr needs vertex_colors (null)");
+    dsn_launch_raster_mesh_attr(verts, n_verts, faces, n_faces, cam_pose_host, fx, fy, znear, light_host, H, W, out_face, out_depth,
+                                out_color, workspace, phases ? phases : 31, big_pixels ? big_pixels : DSN_RM_BIG_PIXELS, vertex_normals,
+                                vertex_colors, mode, out_normal, out_attr, (hipStream_t)stream);
     return dsn_check_launch("dsn_raster_mesh");
+}
+
+int dsn_raster_mesh_ex(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, const float* cam_pose_host, float fx,
+                       float fy, float znear, const float* light_host, int H, int W, int32_t* out_face, float* out_depth,
+                       uint8_t* out_color, void* workspace, size_t workspace_bytes, int phases, int big_pixels, void* stream) {
+    return dsn_raster_mesh_any(verts, n_verts, faces, n_faces, cam_pose_host, fx, fy, znear, light_host, H, W, out_face, out_depth, out_color,
+                               workspace, workspace_bytes, phases, big_pixels, nullptr, nullptr, 0, nullptr, nullptr, stream);
+}
+
+int dsn_raster_mesh_attr(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, const float* cam_pose_host, float fx,
+                         float fy, float znear, const float* light_host, int H, int W, int32_t* out_face, float* out_depth,
+                         uint8_t* out_color, void* workspace, size_t workspace_bytes, int phases, int big_pixels,
+                         const float* vertex_normals, const float* vertex_colors, int mode, float* out_normal, float* out_attr,
+                         void* stream) {
+    return dsn_raster_mesh_any(verts, n_verts, faces, n_faces, cam_pose_host, fx, fy, znear, light_host, H, W, out_face, out_depth, out_color,
+                               workspace, workspace_bytes, phases, big_pixels, vertex_normals, vertex_colors, mode, out_normal, out_attr,
+                               stream);
 }
 
 int dsn_raster_mesh(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, const float* cam_pose_host, float fx,

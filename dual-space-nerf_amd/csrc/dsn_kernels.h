@@ -191,12 +191,19 @@ size_t dsn_mc_workspace_size(int64_t N);
 void dsn_launch_mc_count(const float* vol, int nx, int ny, int nz, float level, void* workspace, int64_t* out_counts, hipStream_t st);
 void dsn_launch_mc_emit(const float* vol, int nx, int ny, int nz, const float* x, const float* y, const float* z, float level, int ascent,
                         const void* workspace, float* verts, int64_t vcap, int32_t* faces, int64_t fcap, hipStream_t st);
+void dsn_launch_mc_normals(const float* vol, int nx, int ny, int nz, const float* x, const float* y, const float* z, float level, int ascent,
+                           const void* workspace, float* normals, int64_t vcap, hipStream_t st);
 void dsn_mc_table_copy(int32_t* out_host);
 // dsn_raster.hip: the mesh preview (dsn_raster_mesh)
 size_t dsn_raster_workspace_size(int64_t V, int64_t T, int H, int W);
 void dsn_launch_raster_mesh(const float* verts, int64_t V, const int32_t* faces, int64_t T, const float* pose12, float fx, float fy,
                             float znear, const float* light4, int H, int W, int32_t* out_face, float* out_depth, uint8_t* out_color,
                             void* workspace, int phases, int big_pixels, hipStream_t st);
+// (all four null and mode 0: dsn_launch_raster_mesh)
+void dsn_launch_raster_mesh_attr(const float* verts, int64_t V, const int32_t* faces, int64_t T, const float* pose12, float fx, float fy,
+                                 float znear, const float* light4, int H, int W, int32_t* out_face, float* out_depth, uint8_t* out_color,
+                                 void* workspace, int phases, int big_pixels, const float* vertex_normals, const float* vertex_colors,
+                                 int mode, float* out_normal, float* out_attr, hipStream_t st);
 // front-to-back slices with exact ray termination (dsn_geom.hip; DSN_EARLY_STOP in dsn_render_rays)
 #define DSN_STOP_MAX_SLICES 32
 // bounds[0 .. K]: slice k = samples [bounds[k], bounds[k + 1]) of every ray; its list starts at lists + R * bounds[k]

@@ -353,6 +353,47 @@ __global__ void __launch_bounds__(MC_THREADS) k_mc_emit(const float* __restrict_
     }
 }
 
+// vertex normals (dsn_mc_normals, the rule of include/dsnerf.h): one thread per grid point, from the words of the count pass.  The
+// gradient of the volume at a grid point is a difference quotient over the grid's own coordinates (central inside, one-sided on the
+// grid's outer faces); a vertex takes the gradients of its edge's two points, mixed with the t of its position.
+__device__ __forceinline__ float mc_grad1(const float* __restrict__ vol, int64_t n, int64_t s, const float* __restrict__ A, int i, int nd) {
+    const int lo = i > 0 ? i - 1 : 0, hi = i + 1 < nd ? i + 1 : nd - 1;      // (nd >= 2: lo < hi)
+    return (vol[n + (int64_t)(hi - i) * s] - vol[n - (int64_t)(i - lo) * s]) / (A[hi] - A[lo]);
+}
+
+__global__ void __launch_bounds__(MC_THREADS) k_mc_normals(const float* __restrict__ vol, int nx, int ny, int nz, const float* __restrict__ ax,
+                                                           const float* __restrict__ ay, const float* __restrict__ az, float level, float sign,
+                                                           const int32_t* __restrict__ words, const int64_t* __restrict__ tv,
+                                                           float* __restrict__ normals, int64_t vcap) {
+    const int64_t N = (int64_t)nx * ny * nz;
+    const int64_t n = (int64_t)blockIdx.x * MC_THREADS + threadIdx.x;
+    if (n >= N) return;
+    const int w = words[n];
+    const int bits = w & 7;
+    if (!bits) return;
+    const int64_t sx = (int64_t)ny * nz, sy = nz;
+    const McPoint p = mc_ijk(n, ny, nz);
+    const float a = vol[n];
+    const float ga[3] = {mc_grad1(vol, n, sx, ax, p.i, nx), mc_grad1(vol, n, sy, ay, p.j, ny), mc_grad1(vol, n, 1, az, p.k, nz)};
+    int64_t vo = tv[n / MC_TILE] + (w >> 3);
+    for (int d = 0; d < 3; ++d) {
+        if (!((bits >> d) & 1)) continue;          // (a set bit: the neighbour along d exists)
+        const int64_t m = n + (d == 0 ? sx : (d == 1 ? sy : 1));
+        const float gb[3] = {mc_grad1(vol, m, sx, ax, p.i + (d == 0), nx), mc_grad1(vol, m, sy, ay, p.j + (d == 1), ny),
+                             mc_grad1(vol, m, 1, az, p.k + (d == 2), nz)};
+        const float t = (level - a) / (vol[m] - a);
+        const float g0 = ga[0] + t * (gb[0] - ga[0]), g1 = ga[1] + t * (gb[1] - ga[1]), g2 = ga[2] + t * (gb[2] - ga[2]);
+        const float nn = sqrtf((g0 * g0 + g1 * g1) + g2 * g2);
+        const bool ok = nn > 0.0f && nn < __builtin_inff();      // (NaN fails both; a finite norm: finite components)
+        if (vo < vcap) {
+            normals[3 * vo] = ok ? (sign * g0) / nn : 0.0f;
+            normals[3 * vo + 1] = ok ? (sign * g1) / nn : 0.0f;
+            normals[3 * vo + 2] = ok ? (sign * g2) / nn : 0.0f;
+        }
+        ++vo;
+    }
+}
+
 void dsn_launch_mc_count(const float* vol, int nx, int ny, int nz, float level, void* workspace, int64_t* out_counts, hipStream_t st) {
     const int64_t N = (int64_t)nx * ny * nz, tiles = mc_tiles(N);
     McWs w = mc_ws(workspace, N);
@@ -366,4 +407,12 @@ void dsn_launch_mc_emit(const float* vol, int nx, int ny, int nz, const float* x
     McWs w = mc_ws((void*)workspace, N);
     hipLaunchKernelGGL(k_mc_emit, dim3((unsigned)tiles), dim3(MC_THREADS), 0, st, vol, nx, ny, nz, x, y, z, level, ascent, w.words, w.tv,
                        w.tf, verts, vcap, faces, fcap);
+}
+
+void dsn_launch_mc_normals(const float* vol, int nx, int ny, int nz, const float* x, const float* y, const float* z, float level, int ascent,
+                           const void* workspace, float* normals, int64_t vcap, hipStream_t st) {
+    const int64_t N = (int64_t)nx * ny * nz;
+    McWs w = mc_ws((void*)workspace, N);
+    hipLaunchKernelGGL(k_mc_normals, dim3((unsigned)((N + MC_THREADS - 1) / MC_THREADS)), dim3(MC_THREADS), 0, st, vol, nx, ny, nz, x, y, z,
+                       level, ascent ? 1.0f : -1.0f, w.words, w.tv, normals, vcap);
 }

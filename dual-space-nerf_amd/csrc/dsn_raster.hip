@@ -13,6 +13,8 @@
 //   k_rm_raster_big  ... and one wave rasterises each listed triangle, lanes striding over the box: a low-resolution mesh or a close
 //                  camera never puts a long pixel loop on one lane
 //   k_rm_shade     one thread per pixel: unpacks the winner, writes face / depth / colour
+//   k_rm_shade_attr  dsn_raster_mesh_attr's shade step in k_rm_shade's place (the passes before it are the same kernels): the winner's
+//                  perspective-correct weights from its edge functions again, vertex normals and colours interpolated with them
 // No float atomics, no MFMA, no allocation, no synchronisation; everything on the caller's stream.
 #include "dsn_common.h"
 #include "dsn_kernels.h"
@@ -226,13 +228,130 @@ __global__ void __launch_bounds__(RM_THREADS) k_rm_shade(const unsigned long lon
     out_color[3 * i] = u; out_color[3 * i + 1] = u; out_color[3 * i + 2] = u;
 }
 
+// dsn_raster_mesh_attr's shade step (the rule of include/dsnerf.h).  face and depth as k_rm_shade writes them; the winner's triangle is
+// set up again from the projected vertices (the same integers: the same E_k, area and 1/w as the raster pass saw).
+__global__ void __launch_bounds__(RM_THREADS) k_rm_shade_attr(const unsigned long long* __restrict__ vis, const int4* __restrict__ pv,
+                                                              const float* __restrict__ verts, int64_t V, const int32_t* __restrict__ faces,
+                                                              int64_t T, RmCam cam, float intensity, float base,
+                                                              const float* __restrict__ vnorm, const float* __restrict__ vcol, int mode,
+                                                              int32_t* __restrict__ out_face, float* __restrict__ out_depth,
+                                                              uint8_t* __restrict__ out_color, float* __restrict__ out_normal,
+                                                              float* __restrict__ out_attr) {
+    const int64_t i = (int64_t)blockIdx.x * RM_THREADS + threadIdx.x;
+    if (i >= (int64_t)cam.H * cam.W) return;
+    const unsigned long long key = vis[i];
+    bool hit = key != RM_EMPTY;
+    int64_t vi[3] = {0, 0, 0};
+    if (hit) {
+        const int64_t g = (int64_t)(key & 0xFFFFFFFFull);
+        hit = g < T;
+        if (hit) {
+            vi[0] = faces[3 * g]; vi[1] = faces[3 * g + 1]; vi[2] = faces[3 * g + 2];
+            hit = vi[0] >= 0 && vi[1] >= 0 && vi[2] >= 0 && vi[0] < V && vi[1] < V && vi[2] < V;      // (nothing is gathered through a bad index)
+        }
+    }
+    const int32_t f = hit ? (int32_t)(key & 0xFFFFFFFFull) : -1;
+    const float z = hit ? __uint_as_float((uint32_t)(key >> 32)) : 0.0f;
+    if (out_face) out_face[i] = f;
+    if (out_depth) out_depth[i] = z;
+    if (!out_color && !out_normal && !out_attr) return;
+    float level[3] = {255.0f, 255.0f, 255.0f};
+    float nw[3] = {0.0f, 0.0f, 0.0f}, at[3] = {0.0f, 0.0f, 0.0f};
+    RmTri t;
+    if (hit && rm_setup(pv, faces, f, V, cam.H, cam.W, t)) {
+        const int y = (int)(i / cam.W), x = (int)(i % cam.W);
+        // weights b_k = (l_k iw_k) z of P[k]; P = (v0, v2, v1) where the integer area was negative
+        const int4 a = pv[vi[0]], b = pv[vi[1]], c = pv[vi[2]];
+        if ((int64_t)(b.x - a.x) * (c.y - a.y) - (int64_t)(b.y - a.y) * (c.x - a.x) < 0) { const int64_t s = vi[1]; vi[1] = vi[2]; vi[2] = s; }
+        const int64_t cx = 256 * (int64_t)x + 128, cy = 256 * (int64_t)y + 128;
+        float bk[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const float l = (float)(t.A[k] * cx + t.B[k] * cy + t.C[k]) / t.area;
+            bk[k] = (l * t.iw[k]) * z;
+        }
+        const float xn = (float)(2 * x + 1) / cam.fw - 1.0f, yn = 1.0f - (float)(2 * y + 1) / cam.fh;
+        const float px = (xn * z) / cam.fx, py = (yn * z) / cam.fy;
+        const float r2 = (px * px + py * py) + z * z;
+        const float r = sqrtf(r2);
+        float s = (z / r - cam.cos_outer) / (cam.cos_inner - cam.cos_outer);
+        s = s > 0.0f ? s : 0.0f;
+        s = s < 1.0f ? s : 1.0f;
+        s = s * s;
+        // the normal in camera space (n, of length nn) and in world space (nw, unit)
+        float n0 = 0.0f, n1 = 0.0f, n2 = 0.0f, nn = 0.0f;
+        bool smooth = (mode & DSN_RM_SMOOTH) != 0;
+        if (smooth) {
+            float m[3][3];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                m[k][0] = vnorm[3 * vi[k]]; m[k][1] = vnorm[3 * vi[k] + 1]; m[k][2] = vnorm[3 * vi[k] + 2];
+                const float q = (fabsf(m[k][0]) + fabsf(m[k][1])) + fabsf(m[k][2]);
+                smooth = smooth && q > 0.0f && q < __builtin_inff();      // (NaN fails; all three zero fails)
+            }
+            if (smooth) {
+                float u[3];
+#pragma unroll
+                for (int e = 0; e < 3; ++e) u[e] = (bk[0] * m[0][e] + bk[1] * m[1][e]) + bk[2] * m[2][e];
+                const float len = sqrtf((u[0] * u[0] + u[1] * u[1]) + u[2] * u[2]);
+                smooth = len > 0.0f && len < __builtin_inff();
+                if (smooth) {
+                    nw[0] = u[0] / len; nw[1] = u[1] / len; nw[2] = u[2] / len;
+                    n0 = (nw[0] * cam.R[0] + nw[1] * cam.R[3]) + nw[2] * cam.R[6];
+                    n1 = (nw[0] * cam.R[1] + nw[1] * cam.R[4]) + nw[2] * cam.R[7];
+                    n2 = (nw[0] * cam.R[2] + nw[1] * cam.R[5]) + nw[2] * cam.R[8];
+                    nn = sqrtf((n0 * n0 + n1 * n1) + n2 * n2);
+                }
+            }
+        }
+        if (!smooth) {      // the flat rule, from the face's vertices in the order given
+            const int64_t g = f;
+            float c0[3], c1[3], c2[3];
+            rm_camera(cam, verts + 3 * (int64_t)faces[3 * g], c0);
+            rm_camera(cam, verts + 3 * (int64_t)faces[3 * g + 1], c1);
+            rm_camera(cam, verts + 3 * (int64_t)faces[3 * g + 2], c2);
+            const float a0 = c1[0] - c0[0], a1 = c1[1] - c0[1], a2 = c1[2] - c0[2];
+            const float b0 = c2[0] - c0[0], b1 = c2[1] - c0[1], b2 = c2[2] - c0[2];
+            n0 = a1 * b2 - a2 * b1; n1 = a2 * b0 - a0 * b2; n2 = a0 * b1 - a1 * b0;
+            nn = sqrtf((n0 * n0 + n1 * n1) + n2 * n2);
+            if (nn > 0.0f && nn < __builtin_inff()) {
+#pragma unroll
+                for (int e = 0; e < 3; ++e) nw[e] = ((cam.R[3 * e] * n0 + cam.R[3 * e + 1] * n1) + cam.R[3 * e + 2] * n2) / nn;
+            }
+        }
+        const float ndl = nn == 0.0f ? 0.0f : fabsf((n0 * px + n1 * py) - n2 * z) / (nn * r);
+        float col[3] = {base, base, base};
+        if (vcol) {
+#pragma unroll
+            for (int e = 0; e < 3; ++e) {
+                at[e] = (bk[0] * vcol[3 * vi[0] + e] + bk[1] * vcol[3 * vi[1] + e]) + bk[2] * vcol[3 * vi[2] + e];
+                float q = at[e] > 0.0f ? at[e] : 0.0f;          // (NaN: 0)
+                col[e] = q < 1.0f ? q : 1.0f;
+            }
+        }
+#pragma unroll
+        for (int e = 0; e < 3; ++e) {
+            float v = col[e];
+            if (!(mode & DSN_RM_UNLIT)) {
+                v = ((((col[e] * intensity) / 3.14159265358979323846f) * s) * ndl) / r2;
+                v = v < 1.0f ? v : 1.0f;
+            }
+            level[e] = floorf(v * 255.0f + 0.5f);
+        }
+    }
+    if (out_color) { out_color[3 * i] = (uint8_t)level[0]; out_color[3 * i + 1] = (uint8_t)level[1]; out_color[3 * i + 2] = (uint8_t)level[2]; }
+    if (out_normal) { out_normal[3 * i] = nw[0]; out_normal[3 * i + 1] = nw[1]; out_normal[3 * i + 2] = nw[2]; }
+    if (out_attr) { out_attr[3 * i] = at[0]; out_attr[3 * i + 1] = at[1]; out_attr[3 * i + 2] = at[2]; }
+}
+
 size_t dsn_raster_workspace_size(int64_t V, int64_t T, int H, int W) {
     return 16 * (size_t)V + 8 * (size_t)H * W + 8 + 4 * (size_t)T;
 }
 
-void dsn_launch_raster_mesh(const float* verts, int64_t V, const int32_t* faces, int64_t T, const float* pose12, float fx, float fy,
-                            float znear, const float* light4, int H, int W, int32_t* out_face, float* out_depth, uint8_t* out_color,
-                            void* workspace, int phases, int big_pixels, hipStream_t st) {
+void dsn_launch_raster_mesh_attr(const float* verts, int64_t V, const int32_t* faces, int64_t T, const float* pose12, float fx, float fy,
+                                 float znear, const float* light4, int H, int W, int32_t* out_face, float* out_depth, uint8_t* out_color,
+                                 void* workspace, int phases, int big_pixels, const float* vertex_normals, const float* vertex_colors,
+                                 int mode, float* out_normal, float* out_attr, hipStream_t st) {
     RmCam cam;
     for (int i = 0; i < 3; ++i) {
         for (int k = 0; k < 3; ++k) cam.R[3 * i + k] = pose12[4 * i + k];
@@ -256,6 +375,17 @@ void dsn_launch_raster_mesh(const float* verts, int64_t V, const int32_t* faces,
         hipLaunchKernelGGL(k_rm_raster_big, dim3((unsigned)(nb < RM_BIG_BLOCKS ? nb : RM_BIG_BLOCKS)), dim3(RM_THREADS), 0, st, w.pv, V,
                            faces, T, H, W, w.vis, w.count, w.list);
     }
-    if (phases & DSN_RM_SHADE)
+    if (!(phases & DSN_RM_SHADE)) return;
+    if (!vertex_normals && !vertex_colors && !mode && !out_normal && !out_attr)
         hipLaunchKernelGGL(k_rm_shade, blocks(P), dim3(RM_THREADS), 0, st, w.vis, verts, V, faces, T, cam, out_face, out_depth, out_color);
+    else
+        hipLaunchKernelGGL(k_rm_shade_attr, blocks(P), dim3(RM_THREADS), 0, st, w.vis, w.pv, verts, V, faces, T, cam, light4[0], light4[3],
+                           vertex_normals, vertex_colors, mode, out_face, out_depth, out_color, out_normal, out_attr);
+}
+
+void dsn_launch_raster_mesh(const float* verts, int64_t V, const int32_t* faces, int64_t T, const float* pose12, float fx, float fy,
+                            float znear, const float* light4, int H, int W, int32_t* out_face, float* out_depth, uint8_t* out_color,
+                            void* workspace, int phases, int big_pixels, hipStream_t st) {
+    dsn_launch_raster_mesh_attr(verts, V, faces, T, pose12, fx, fy, znear, light4, H, W, out_face, out_depth, out_color, workspace, phases,
+                                big_pixels, nullptr, nullptr, 0, nullptr, nullptr, st);
 }

@@ -1,8 +1,10 @@
 """utils/visualizer.py Visualizer3D with its device-bound methods on gfx950 kernels: the density grid of get_grid_pred_batch
 (Renderer.density_grid, dsn_density_grid) and the marching cubes of get_mesh_from_grid (dsn_mc_count / dsn_mc_emit, the rule of
 include/dsnerf.h), and the preview image of render_mesh (dsn_raster_mesh: a deterministic rasteriser with the reference's camera and
-spotlight, not a pixel copy of pyrender's GL output).  No skimage, trimesh or pyrender: meshes are returned as numpy (verts, faces);
-connected=True (trimesh's component split) is not provided."""
+spotlight, not a pixel copy of pyrender's GL output).  No skimage, trimesh or pyrender: meshes are numpy (verts, faces) pairs or the
+dicts of Renderer.extract_mesh, which may carry vertex normals (dsn_mc_normals, skimage's third output) and the field's albedo, normal
+and lit colour at the vertices (Renderer.mesh_attributes); render_mesh shades them smooth and in colour (dsn_raster_mesh_attr) and
+save_ply writes them to a file.  connected=True (trimesh's component split) is not provided."""
 import numpy as np
 import torch
 
@@ -65,9 +67,10 @@ class Visualizer3D(object):
         grid_pts = grid["grid_pts"].reshape(B, X, Y, Z, 3).numpy()
         return grid_pts, grid_pred
 
-    def get_mesh_from_grid(self, grid_pts, grid_pred):
+    def get_mesh_from_grid(self, grid_pts, grid_pred, return_normals=False):
         """(verts [V,3] float32, faces [T,3] int32) numpy arrays of the iso-surface at mc_value in the grid's coordinates, or None
-        where the level is not crossed.  grid_pts / grid_pred: [X,Y,Z,3] / [X,Y,Z,1] (or with the leading B = 1)."""
+        where the level is not crossed.  grid_pts / grid_pred: [X,Y,Z,3] / [X,Y,Z,1] (or with the leading B = 1).
+        return_normals=True: a third array, the unit vertex normals [V,3] float32 (skimage's vertex_normals, by dsn_mc_normals)."""
         if self.connected:
             raise NotImplementedError("Visualizer3D(connected=True): the largest-component split (trimesh) is not provided")
         grid_pts = np.asarray(grid_pts)
@@ -76,26 +79,90 @@ class Visualizer3D(object):
             grid_pts, grid_pred = grid_pts[0], grid_pred[0]
         axes = (grid_pts[:, 0, 0, 0], grid_pts[0, :, 0, 1], grid_pts[0, 0, :, 2])
         vol = torch.from_numpy(np.ascontiguousarray(grid_pred.reshape(grid_pts.shape[:3]), dtype=np.float32)).cuda()
-        verts, faces = _lib.marching_cubes(vol, axes, self.mc_value, self.gradient_direction)
-        if faces.shape[0] == 0:
+        out = _lib.marching_cubes(vol, axes, self.mc_value, self.gradient_direction, want_normals=bool(return_normals))
+        if out[1].shape[0] == 0:
             return None
-        return verts.cpu().numpy(), faces.cpu().numpy()
+        return tuple(a.cpu().numpy() for a in out)
 
     @torch.no_grad()
-    def render_mesh(self, mesh, camera_pose=None):
+    def render_mesh(self, mesh, camera_pose=None, smooth=None, colors=None, lit=True):
         """numpy uint8 [resolution_render, resolution_render, 3], as pyrender's `color` (utils/visualizer.py:144-168): the mesh under
         the reference's camera (yfov pi/3, aspect 1) and spotlight (intensity 30, cones pi/16 and pi/6) on a white background, by
         dsn_raster_mesh.  mesh: the (verts, faces) pair of get_mesh_from_grid or the {"verts", "faces"} dict of
         Renderer.extract_mesh, numpy or device.  camera_pose: a 4 x 4 camera-to-world matrix (default the reference's: 2.5 in front
         of the origin, looking down -z) - a real body is not at the origin; the light rides with the camera, as the reference adds
-        both with one pose."""
+        both with one pose.
+        A (verts, faces, normals) triple or a dict with "normals" is shaded smooth (smooth=None: when normals are there; False: flat).
+        colors: per-vertex colours [V,3] in [0, 1], or the key of the mesh dict that holds them ("albedo", "colour"); they take the
+        grey's place under the spotlight, or with lit=False are painted as they are (dsn_raster_mesh_attr).  A plain (verts, faces)
+        pair renders as it always did."""
         if mesh is None:
             raise ValueError("render_mesh: no mesh (get_mesh_from_grid returns None where the level is not crossed)")
-        verts, faces = (mesh["verts"], mesh["faces"]) if isinstance(mesh, dict) else mesh
+        if isinstance(mesh, dict):
+            verts, faces, normals = mesh["verts"], mesh["faces"], mesh.get("normals")
+        else:
+            verts, faces, normals = (tuple(mesh) + (None,))[:3]
+        if isinstance(colors, str):
+            if not isinstance(mesh, dict) or colors not in mesh:
+                raise ValueError(f"render_mesh: the mesh has no {colors!r}")
+            colors = mesh[colors]
+        if smooth and normals is None:
+            raise ValueError("render_mesh: smooth=True needs a mesh with normals")
+        smooth = normals is not None if smooth is None else bool(smooth)
 
         def dev(a, dtype):
             a = a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))
             return a.to(device="cuda", dtype=dtype)
+        kw = {}
+        if smooth or colors is not None or not lit:
+            kw = dict(vertex_normals=dev(normals, torch.float32) if smooth else None,
+                      vertex_colors=None if colors is None else dev(colors, torch.float32), smooth=smooth, lit=bool(lit))
         out = _lib.raster_mesh(dev(verts, torch.float32), dev(faces, torch.int32), camera_pose=camera_pose,
-                               height=self.resolution_render, width=self.resolution_render)
+                               height=self.resolution_render, width=self.resolution_render, **kw)
         return out["color"].cpu().numpy()
+
+
+def save_ply(path, mesh, colors=None):
+    """Write a mesh as binary little-endian PLY (numpy only): float x y z per vertex, float nx ny nz where the mesh has normals, uchar
+    red green blue where colours are given, and the faces as `uchar 3` + three int32.  mesh: a (verts, faces[, normals]) tuple or the
+    dict of Renderer.extract_mesh, numpy or device; colors: [V,3] floats (clamped to [0, 1], NaN as 0, level floor(c 255 + 0.5)) or the
+    key of the mesh dict that holds them ("albedo", "colour")."""
+    def host(a, dtype):
+        a = a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+        return np.ascontiguousarray(a, dtype=dtype)
+    if isinstance(mesh, dict):
+        verts, faces, normals = mesh["verts"], mesh["faces"], mesh.get("normals")
+    else:
+        verts, faces, normals = (tuple(mesh) + (None,))[:3]
+    if isinstance(colors, str):
+        if not isinstance(mesh, dict) or colors not in mesh:
+            raise ValueError(f"save_ply: the mesh has no {colors!r}")
+        colors = mesh[colors]
+    verts, faces = host(verts, "<f4").reshape(-1, 3), host(faces, "<i4").reshape(-1, 3)
+    V, T = verts.shape[0], faces.shape[0]
+    fields, cols = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")], [verts]
+    if normals is not None:
+        normals = host(normals, "<f4").reshape(-1, 3)
+        fields += [("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")]
+        cols.append(normals)
+    if colors is not None:
+        c = host(colors, np.float64).reshape(-1, 3)
+        c = np.where(c > 0, c, 0.0)                    # (NaN: 0)
+        colors = np.floor(np.where(c < 1, c, 1.0) * 255.0 + 0.5).astype(np.uint8)
+        fields += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
+        cols.append(colors)
+    if any(a.shape != (V, 3) for a in cols):
+        raise ValueError("save_ply: normals and colours need one row per vertex")
+    vrec = np.empty(V, dtype=fields)
+    for k, (name, _) in enumerate(fields):
+        vrec[name] = cols[k // 3][:, k % 3]
+    frec = np.empty(T, dtype=[("n", "u1"), ("v", "<i4", (3,))])
+    frec["n"], frec["v"] = 3, faces
+    ply_type = {"<f4": "float", "u1": "uchar"}
+    header = ["ply", "format binary_little_endian 1.0", f"element vertex {V}"]
+    header += [f"property {ply_type[t]} {name}" for name, t in fields]
+    header += [f"element face {T}", "property list uchar int vertex_indices", "end_header"]
+    with open(path, "wb") as f:
+        f.write(("\n".join(header) + "\n").encode("ascii"))
+        f.write(vrec.tobytes())
+        f.write(frec.tobytes())

@@ -552,6 +552,21 @@ DSN_EXPORT int dsn_mc_count(const float* volume, int nx, int ny, int nz, float l
 DSN_EXPORT int dsn_mc_emit(const float* volume, int nx, int ny, int nz, const float* x, const float* y, const float* z, float level,
                            int gradient_direction, const void* workspace, int64_t n_verts, int64_t n_faces, float* verts,
                            int32_t* faces, void* stream);
+/* Vertex normals of the same mesh (skimage.measure.marching_cubes' third output; the reference's get_mesh_from_grid carries them to
+ * trimesh.Trimesh(vertex_normals=...)): normals [n_verts, 3] float32 in dsn_mc_emit's vertex order, from the workspace dsn_mc_count
+ * left (dsn_mc_emit may run before or after: neither writes it).  The rule, float32 throughout, no fused multiply-add, `/` and sqrt
+ * correctly rounded, so that numpy reproduces it bit for bit (tests/mc_normals_restate.py):
+ *   - gradient of the volume at a grid point along axis d, at index i of nd with coordinates ax: inside
+ *     (v[i + 1] - v[i - 1]) / (ax[i + 1] - ax[i - 1]); at i = 0 (v[1] - v[0]) / (ax[1] - ax[0]); at i = nd - 1
+ *     (v[nd - 1] - v[nd - 2]) / (ax[nd - 1] - ax[nd - 2]);
+ *   - vertex of edge (n, d) between the points a = n and b = its neighbour along d: g = g_a + t (g_b - g_a) per component, with
+ *     dsn_mc_emit's t = (level - v_a) / (v_b - v_a);
+ *   - nn = sqrt((g0 g0 + g1 g1) + g2 g2); normal = (s g) / nn with s = -1 for DSN_MC_DESCENT (the object is where the values are
+ *     higher: the normal points out of it, with that mode's (v1 - v0) x (v2 - v0)) and s = +1 for DSN_MC_ASCENT;
+ *   - (0, 0, 0) unless 0 < nn < infinity (a zero gradient, NaN or infinite values among the neighbours).
+ * skimage's fourth output (`values`) is not provided. */
+DSN_EXPORT int dsn_mc_normals(const float* volume, int nx, int ny, int nz, const float* x, const float* y, const float* z, float level,
+                              int gradient_direction, const void* workspace, int64_t n_verts, float* normals, void* stream);
 /* the case table (host function, no device work): 256 rows of DSN_MC_TABLE_ROW int32 into a HOST array of out_ints >= 256 rows */
 DSN_EXPORT int dsn_mc_table_host(int32_t* out_host, size_t out_ints);
 
@@ -609,6 +624,34 @@ DSN_EXPORT int dsn_raster_mesh_ex(const float* verts, int64_t n_verts, const int
                                   float fx, float fy, float znear, const float* light_host, int H, int W, int32_t* out_face,
                                   float* out_depth, uint8_t* out_color, void* workspace, size_t workspace_bytes, int phases,
                                   int big_pixels, void* stream);
+/* The preview with per-vertex attributes: dsn_raster_mesh_ex's arguments, then
+ *   vertex_normals [n_verts, 3] float32, world space (NULL: none; required by DSN_RM_SMOOTH), e.g. dsn_mc_normals';
+ *   vertex_colors  [n_verts, 3] float32 (NULL: none; required by out_attr), e.g. an albedo or a lit colour of the field;
+ *   mode: DSN_RM_SMOOTH | DSN_RM_UNLIT (0: flat normals, lit);
+ *   out_normal [H, W, 3] float32: the unit world normal the pixel was shaded with; out_attr [H, W, 3] float32: the interpolated
+ *   colour, not clamped.  Both 0 where the pixel is empty; each may be NULL (one of the five outputs must not be).
+ * Visibility is dsn_raster_mesh's own pass (the same kernels): face and depth have its bits.  Only the shade step differs; with P, l_k,
+ * iw_k and z as defined for the depth:
+ *   weights   b_k = (l_k iw_k) z (perspective-correct: they reproduce an affine function of the world position at the fragment);
+ *   attribute a = (b_0 a_0 + b_1 a_1) + b_2 a_2 per component, a_k the value at P[k];
+ *   normal    DSN_RM_SMOOTH: u = the attribute rule on the vertex normals, len = sqrt((u0 u0 + u1 u1) + u2 u2), world normal u / len,
+ *             camera-space n_k = (m0 R0k + m1 R1k) + m2 R2k of m = u / len (as a vertex offset is rotated), nn = sqrt((n0 n0 + n1 n1) +
+ *             n2 n2).  Falls back to the flat rule where (|m0| + |m1|) + |m2| of one of the three vertex normals is 0 or not finite, or
+ *             len is 0 or not finite.  Flat: n and nn of dsn_raster_mesh's rule; world normal ((R_e0 n0 + R_e1 n1) + R_e2 n2) / nn, or 0
+ *             unless 0 < nn < infinity.  Either way ndl = |(n0 px + n1 py) - n2 z| / (nn r), or 0 when nn = 0 (two-sided);
+ *   colour    c_ch = the interpolated colour clamped to [0, 1] (c > 0 ? c : 0, then c < 1 ? c : 1: NaN is 0), or `base` in every channel
+ *             without vertex_colors.  Lit: col_ch = min(((((c_ch intensity) / float(pi)) s) ndl) / r2, 1); DSN_RM_UNLIT: col_ch = c_ch
+ *             (the colours as they are: e.g. the model's own lit colour painted on the mesh);  level = floor(col_ch 255 + 0.5).
+ * Without attributes, mode 0: dsn_raster_mesh's image (and with out_normal and out_attr NULL too, its shade kernel).
+ * The workspace is dsn_raster_workspace_bytes'.  Rejected: what dsn_raster_mesh_ex rejects, a mode outside 0 ... 3, DSN_RM_SMOOTH
+ * without vertex_normals, out_attr without vertex_colors. */
+#define DSN_RM_SMOOTH 1
+#define DSN_RM_UNLIT 2
+DSN_EXPORT int dsn_raster_mesh_attr(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, const float* cam_pose_host,
+                                    float fx, float fy, float znear, const float* light_host, int H, int W, int32_t* out_face,
+                                    float* out_depth, uint8_t* out_color, void* workspace, size_t workspace_bytes, int phases,
+                                    int big_pixels, const float* vertex_normals, const float* vertex_colors, int mode, float* out_normal,
+                                    float* out_attr, void* stream);
 
 /* diagnostics, NOT for the hot path (synchronises `stream`): {ncell, ok, total entries, capacity} of the four
  * nearest-face list levels (world fine/coarse, canonical fine/coarse) into a HOST array of 16 int32. */
