@@ -47,6 +47,7 @@ EXPORTS = [
     "dsn_density_grid_workspace_bytes", "dsn_density_grid", "dsn_mc_workspace_bytes", "dsn_mc_count", "dsn_mc_emit", "dsn_mc_table_host",
     "dsn_render_maps_scratch_bytes", "dsn_render_rays_maps", "dsn_composite_maps", "dsn_shade_factor",
     "dsn_raster_workspace_bytes", "dsn_raster_mesh", "dsn_raster_mesh_ex", "dsn_mc_normals", "dsn_raster_mesh_attr",
+    "dsn_mesh_cc_workspace_bytes", "dsn_mesh_cc_label", "dsn_mesh_cc_emit", "dsn_mesh_cc_label_ex", "dsn_mesh_cc_emit_ex",
 ]
 
 SKIP_TRANSPARENT = 1
@@ -120,6 +121,14 @@ def lib():
         L.dsn_raster_mesh.argtypes = raster + [C.c_void_p]
         L.dsn_raster_mesh_ex.argtypes = raster + [C.c_int, C.c_int, C.c_void_p]
         L.dsn_raster_mesh_attr.argtypes = raster + [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.dsn_mesh_cc_workspace_bytes.restype = C.c_size_t
+        L.dsn_mesh_cc_workspace_bytes.argtypes = [C.c_int64, C.c_int64]
+        cc_label = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        cc_emit = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_size_t, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.dsn_mesh_cc_label.argtypes = cc_label + [C.c_void_p]
+        L.dsn_mesh_cc_label_ex.argtypes = cc_label + [C.c_int, C.c_void_p]
+        L.dsn_mesh_cc_emit.argtypes = cc_emit + [C.c_void_p]
+        L.dsn_mesh_cc_emit_ex.argtypes = cc_emit + [C.c_int, C.c_void_p]
         if L.dsn_abi_version() != 8:
             raise RuntimeError(f"{LIB_PATH} has ABI version {L.dsn_abi_version()}, this binding needs 8 - rebuild it "
                                "(python dual-space-nerf_amd/build.py)")
@@ -650,6 +659,90 @@ def marching_cubes(volume, axes, level, gradient_direction="descent", want_norma
     _check(lib().dsn_mc_normals(_ptr(vol), nx, ny, nz, _ptr(x), _ptr(y), _ptr(z), float(level), MC_GRADIENT[gradient_direction], _ptr(ws),
                                 V, _ptr(normals) if V else None, _stream()), "dsn_mc_normals")
     return verts, faces, normals
+
+
+MESH_CC_TILE = 1024          # DSN_MESH_CC_TILE: vertices / faces per tile of the compaction scans
+CC_INIT, CC_UNITE, CC_FLATTEN, CC_SUMS, CC_SELECT, CC_COUNT, CC_EMIT_VERTS, CC_EMIT_FACES = 1, 2, 4, 8, 16, 32, 64, 128      # DSN_CC_*
+
+
+def mesh_area_shift(lo, hi, n_faces):
+    """area_shift of dsn_mesh_cc_label (the rule of include/dsnerf.h) from the bounding box lo [3], hi [3] of the vertices whose
+    coordinates are all finite (None: there is none): 61 - bit_length(T) - e, clamped to +-60, e the frexp exponent of float32 D2"""
+    import numpy as np
+    e = 0
+    if lo is not None:
+        with np.errstate(over="ignore", invalid="ignore"):
+            d = np.asarray(hi, np.float32) - np.asarray(lo, np.float32)
+            d2 = np.float32(np.float32(d[0] * d[0] + d[1] * d[1]) + d[2] * d[2])
+        e = int(np.frexp(d2)[1]) if np.isfinite(d2) else 128
+    return max(-60, min(60, 61 - int(n_faces).bit_length() - e))
+
+
+def _mesh_cc_inputs(verts, faces):
+    assert verts.is_cuda and faces.is_cuda, "verts and faces: device tensors"
+    verts = verts.reshape(-1, 3).to(torch.float32).contiguous()
+    faces = faces.reshape(-1, 3).to(torch.int32).contiguous()
+    V, T = verts.shape[0], faces.shape[0]
+    lo = hi = None
+    if V:
+        fin = torch.isfinite(verts).all(dim=1, keepdim=True)
+        inf = torch.tensor(float("inf"), device=verts.device)
+        box = torch.cat([torch.where(fin, verts, inf).amin(dim=0), torch.where(fin, verts, -inf).amax(dim=0)]).cpu().numpy()
+        if box[0] <= box[3]:                       # (no finite vertex: +inf > -inf)
+            lo, hi = box[:3], box[3:]
+    return verts, faces, V, T, mesh_area_shift(lo, hi, T)
+
+
+def _mesh_cc_label(verts, faces, V, T, shift, want_labels, phases=0, state=None):
+    dev = verts.device
+    nbytes = lib().dsn_mesh_cc_workspace_bytes(V, T)
+    if nbytes == 0:
+        raise RuntimeError("dsn_mesh_cc_label: the mesh must stay below 2^31 vertices and faces")
+    if state is None:
+        state = {"ws": _scratch(nbytes, dev), "counts": torch.empty(6, dtype=torch.int64, device=dev),
+                 "labels": torch.empty(V, dtype=torch.int32, device=dev) if want_labels else None}
+    labels = state["labels"]
+    _check(lib().dsn_mesh_cc_label_ex(_ptr(verts) if V else None, _ptr(faces) if T else None, V, T, shift, _ptr(state["ws"]), nbytes,
+                                      _ptr(labels) if labels is not None and V else None, _ptr(state["counts"]), int(phases), _stream()),
+           "dsn_mesh_cc_label")
+    return state, nbytes
+
+
+def mesh_components(verts, faces):
+    """dsn_mesh_cc_label (the rule of include/dsnerf.h) on a device mesh (verts [V,3] float32, faces [T,3] int32): the connected
+    components under the shared-vertex-index rule.  Returns {"labels" [V] int32 on the device (a component's label is its smallest vertex
+    index; -1: the vertex is in no valid face), "n_components", "winner" (the label of the component with the largest area, -1: none),
+    "area" (the winner's, float), "faces_in_winner", "n_verts" / "n_faces" (of the winner), "area_shift", "area_sum" (the integer the
+    area comes from)}.  One device->host read of the six counts behind one of the bounding box (six floats: the shift is a host
+    argument of the call)."""
+    require_gpu()
+    verts, faces, V, T, shift = _mesh_cc_inputs(verts, faces)
+    st, _ = _mesh_cc_label(verts, faces, V, T, shift, True)
+    n, winner, nv, nf, s, fw = (int(c) for c in st["counts"].cpu())
+    return {"labels": st["labels"], "n_components": n, "winner": winner, "area": math.ldexp(float(s), -shift - 1), "faces_in_winner": fw,
+            "n_verts": nv, "n_faces": nf, "area_shift": shift, "area_sum": s}
+
+
+def largest_component(verts, faces, want_source=True, info=None):
+    """dsn_mesh_cc_label + dsn_mesh_cc_emit: the component of the mesh with the largest area (ties: the smaller label) as a mesh of its
+    own - (verts' [V',3] float32, faces' [T',3] int32, source_vertex [V'] int32 or None) device tensors; vertices and faces keep their
+    order and winding, source_vertex holds each kept vertex's old index (per-vertex arrays follow by a[source_vertex.long()]).  A mesh
+    without a valid face gives three empty tensors.  One device->host read of the six counts, behind one of the bounding box.  info: a
+    dict that receives n_components, winner, area, faces_in_winner and area_shift."""
+    require_gpu()
+    verts, faces, V, T, shift = _mesh_cc_inputs(verts, faces)
+    dev = verts.device
+    st, nbytes = _mesh_cc_label(verts, faces, V, T, shift, False)
+    n, winner, nv, nf, s, fw = (int(c) for c in st["counts"].cpu())
+    out_v = torch.empty(nv, 3, dtype=torch.float32, device=dev)
+    out_f = torch.empty(nf, 3, dtype=torch.int32, device=dev)
+    src = torch.empty(nv, dtype=torch.int32, device=dev) if want_source else None
+    _check(lib().dsn_mesh_cc_emit(_ptr(verts) if V else None, _ptr(faces) if T else None, V, T, _ptr(st["ws"]), nbytes, nv, nf,
+                                  _ptr(out_v) if nv else None, _ptr(out_f) if nf else None, _ptr(src) if want_source and nv else None,
+                                  _stream()), "dsn_mesh_cc_emit")
+    if info is not None:
+        info.update(n_components=n, winner=winner, area=math.ldexp(float(s), -shift - 1), faces_in_winner=fw, area_shift=shift)
+    return out_v, out_f, src
 
 
 RM_CLEAR, RM_PROJECT, RM_RASTER, RM_RASTER_BIG, RM_SHADE = 1, 2, 4, 8, 16      # DSN_RM_*: the kernels of dsn_raster_mesh_ex

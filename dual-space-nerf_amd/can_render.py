@@ -1184,13 +1184,18 @@ class Renderer:
         return axes, vol
 
     def extract_mesh(self, batch, resolution=512, level=0.5, gradient_direction="ascent", axes=None, points=None, frame=None,
-                     fp32=False, slab_points=None, normals=False, attributes=None):
+                     fp32=False, slab_points=None, normals=False, attributes=None, largest_component=False):
         """Visualizer3D's mesh of the posed body on the device: density_grid + marching cubes (dsn_mc_count / dsn_mc_emit, the rule of
         include/dsnerf.h).  Defaults are the visualizer's __main__ values.  Returns {"verts" [V,3] float32, "faces" [T,3] int32} device
         tensors in world coordinates, or None where the level is not crossed (the reference returns None there).
         normals=True adds "normals" [V,3] float32, the unit vertex normals of dsn_mc_normals (along the density's gradient: out of the
         body with gradient_direction="descent", into it with "ascent", as the triangles of that mode are oriented); attributes: a tuple of mesh_attributes' names ("albedo", "normal", "colour", "sigma", "valid"), evaluated at the
-        vertices with mesh_attributes' defaults and added under those names.  verts and faces do not depend on either."""
+        vertices with mesh_attributes' defaults and added under those names.  verts and faces do not depend on either.
+        largest_component=True: only the connected component of the surface with the largest area (the reference visualizer's
+        connected=True; dsn_mesh_cc_label / dsn_mesh_cc_emit, the rule of include/dsnerf.h) - floaters and inner shells go.  The
+        filter runs right after marching cubes: the normals are gathered through "source_vertex" [V'] int32 (each kept vertex's index
+        in the unfiltered mesh), the attributes are evaluated at the kept vertices only (per vertex and independent: the rows of
+        the unfiltered call, bit for bit), and "n_components" says how many pieces the surface had."""
         names = tuple(attributes) if attributes else ()
         unknown = set(names) - set(self.MESH_ATTRIBUTES)
         if unknown:
@@ -1202,6 +1207,13 @@ class Renderer:
         mesh = {"verts": out[0], "faces": out[1]}
         if normals:
             mesh["normals"] = out[2]
+        if largest_component:
+            info = {}
+            v, f, src = _lib.largest_component(out[0], out[1], info=info)
+            mesh.update(verts=v, faces=f, source_vertex=src, n_components=info["n_components"])
+            if normals:
+                mesh["normals"] = out[2][src.long()]
+            out = (v, f)
         if names:
             a = self.mesh_attributes(batch, out[0], frame=frame)
             mesh.update({k: a[k] for k in names})

@@ -1261,6 +1261,56 @@ int dsn_mc_table_host(int32_t* out_host, size_t out_ints) {
     return 0;
 }
 
+static bool dsn_mesh_cc_sizes_ok(int64_t V, int64_t T) { return V >= 0 && T >= 0 && V < ((int64_t)1 << 31) && T < ((int64_t)1 << 31); }
+
+size_t dsn_mesh_cc_workspace_bytes(int64_t n_verts, int64_t n_faces) {
+    return dsn_mesh_cc_sizes_ok(n_verts, n_faces) ? dsn_mesh_cc_workspace_size(n_verts, n_faces) : 0;
+}
+
+int dsn_mesh_cc_label_ex(const float* verts, const int32_t* faces, int64_t n_verts, int64_t n_faces, int area_shift, void* workspace,
+                         size_t workspace_bytes, int32_t* labels_v, int64_t* out_counts6, int phases, void* stream) {
+    DSN_REQUIRE(n_verts >= 0 && n_faces >= 0, "dsn_mesh_cc_label: negative count");
+    DSN_REQUIRE(dsn_mesh_cc_sizes_ok(n_verts, n_faces), "dsn_mesh_cc_label: 2^31 or more vertices or faces");
+    DSN_REQUIRE((n_verts == 0 || verts) && (n_faces == 0 || faces), "dsn_mesh_cc_label: null mesh");
+    DSN_REQUIRE(workspace && out_counts6, "dsn_mesh_cc_label: null argument");
+    DSN_REQUIRE(workspace_bytes >= dsn_mesh_cc_workspace_size(n_verts, n_faces), "dsn_mesh_cc_label: workspace_bytes too small (dsn_mesh_cc_workspace_bytes)");
+    DSN_REQUIRE(((uintptr_t)workspace & 15) == 0, "dsn_mesh_cc_label: workspace must be 16-byte aligned");
+    DSN_REQUIRE(area_shift >= -60 && area_shift <= 60, "dsn_mesh_cc_label: area_shift must be -60 ... 60");
+    DSN_REQUIRE(phases >= 0 && phases < 256, "dsn_mesh_cc_label_ex: bad phases");
+    dsn_launch_mesh_cc_label(verts, faces, n_verts, n_faces, std::ldexp(1.0, area_shift), workspace, labels_v, out_counts6,
+                             phases ? phases : 255, (hipStream_t)stream);
+    return dsn_check_launch("dsn_mesh_cc_label");
+}
+
+int dsn_mesh_cc_label(const float* verts, const int32_t* faces, int64_t n_verts, int64_t n_faces, int area_shift, void* workspace,
+                      size_t workspace_bytes, int32_t* labels_v, int64_t* out_counts6, void* stream) {
+    return dsn_mesh_cc_label_ex(verts, faces, n_verts, n_faces, area_shift, workspace, workspace_bytes, labels_v, out_counts6, 0, stream);
+}
+
+int dsn_mesh_cc_emit_ex(const float* verts, const int32_t* faces, int64_t n_verts, int64_t n_faces, void* workspace, size_t workspace_bytes,
+                        int64_t out_n_verts, int64_t out_n_faces, float* out_verts, int32_t* out_faces, int32_t* source_vertex, int phases,
+                        void* stream) {
+    DSN_REQUIRE(n_verts >= 0 && n_faces >= 0 && out_n_verts >= 0 && out_n_faces >= 0, "dsn_mesh_cc_emit: negative count");
+    DSN_REQUIRE(dsn_mesh_cc_sizes_ok(n_verts, n_faces), "dsn_mesh_cc_emit: 2^31 or more vertices or faces");
+    DSN_REQUIRE(out_n_verts <= n_verts && out_n_faces <= n_faces, "dsn_mesh_cc_emit: more kept vertices or faces than the mesh has");
+    DSN_REQUIRE((n_verts == 0 || verts) && (n_faces == 0 || faces), "dsn_mesh_cc_emit: null mesh");
+    DSN_REQUIRE(workspace, "dsn_mesh_cc_emit: null argument");
+    DSN_REQUIRE((out_n_verts == 0 || out_verts) && (out_n_faces == 0 || out_faces), "dsn_mesh_cc_emit: null output buffer");
+    DSN_REQUIRE(workspace_bytes >= dsn_mesh_cc_workspace_size(n_verts, n_faces), "dsn_mesh_cc_emit: workspace_bytes too small (dsn_mesh_cc_workspace_bytes)");
+    DSN_REQUIRE(((uintptr_t)workspace & 15) == 0, "dsn_mesh_cc_emit: workspace must be 16-byte aligned");
+    DSN_REQUIRE(phases >= 0 && phases < 256, "dsn_mesh_cc_emit_ex: bad phases");
+    if (out_n_verts == 0 && out_n_faces == 0) return 0;
+    dsn_launch_mesh_cc_emit(verts, faces, n_verts, n_faces, workspace, out_verts, out_n_verts, out_faces, out_n_faces, source_vertex,
+                            phases ? phases : 255, (hipStream_t)stream);
+    return dsn_check_launch("dsn_mesh_cc_emit");
+}
+
+int dsn_mesh_cc_emit(const float* verts, const int32_t* faces, int64_t n_verts, int64_t n_faces, void* workspace, size_t workspace_bytes,
+                     int64_t out_n_verts, int64_t out_n_faces, float* out_verts, int32_t* out_faces, int32_t* source_vertex, void* stream) {
+    return dsn_mesh_cc_emit_ex(verts, faces, n_verts, n_faces, workspace, workspace_bytes, out_n_verts, out_n_faces, out_verts, out_faces,
+                               source_vertex, 0, stream);
+}
+
 static bool dsn_raster_sizes_ok(int64_t V, int64_t T, int H, int W) {
     return V >= 0 && T >= 0 && V < ((int64_t)1 << 31) && T < ((int64_t)1 << 31) && H >= 1 && H <= 16384 && W >= 1 && W <= 16384;
 }

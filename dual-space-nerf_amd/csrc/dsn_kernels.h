@@ -194,6 +194,12 @@ void dsn_launch_mc_emit(const float* vol, int nx, int ny, int nz, const float* x
 void dsn_launch_mc_normals(const float* vol, int nx, int ny, int nz, const float* x, const float* y, const float* z, float level, int ascent,
                            const void* workspace, float* normals, int64_t vcap, hipStream_t st);
 void dsn_mc_table_copy(int32_t* out_host);
+// dsn_mesh.hip: connected components and the largest piece of an indexed mesh (dsn_mesh_cc_*; scale = 2^area_shift; phases: DSN_CC_*)
+size_t dsn_mesh_cc_workspace_size(int64_t V, int64_t T);
+void dsn_launch_mesh_cc_label(const float* verts, const int32_t* faces, int64_t V, int64_t T, double scale, void* workspace, int32_t* labels_v,
+                              int64_t* out_counts, int phases, hipStream_t st);
+void dsn_launch_mesh_cc_emit(const float* verts, const int32_t* faces, int64_t V, int64_t T, void* workspace, float* out_verts, int64_t vcap,
+                             int32_t* out_faces, int64_t fcap, int32_t* source_vertex, int phases, hipStream_t st);
 // dsn_raster.hip: the mesh preview (dsn_raster_mesh)
 size_t dsn_raster_workspace_size(int64_t V, int64_t T, int H, int W);
 void dsn_launch_raster_mesh(const float* verts, int64_t V, const int32_t* faces, int64_t T, const float* pose12, float fx, float fy,

@@ -416,3 +416,306 @@ void dsn_launch_mc_normals(const float* vol, int nx, int ny, int nz, const float
     hipLaunchKernelGGL(k_mc_normals, dim3((unsigned)((N + MC_THREADS - 1) / MC_THREADS)), dim3(MC_THREADS), 0, st, vol, nx, ny, nz, x, y, z,
                        level, ascent ? 1.0f : -1.0f, w.words, w.tv, normals, vcap);
 }
+
+// ---------------------------------------------------------------------------------------------
+// connected components of an indexed mesh and its largest piece (dsn_mesh_cc_label / dsn_mesh_cc_emit, the rule of include/dsnerf.h)
+//   label : init -> unite (lock-free union-find over the vertex array, one thread per face) -> flatten (every vertex to its root, unused
+//           vertices -1) -> sums (per face 64-bit integer adds to its root's slots, aggregated per wave) -> select (the arg-max over the
+//           roots, per tile and then over the tiles: no atomics, the same winner every call) -> count + scan (kept vertices and faces per
+//           tile of CC_TILE, k_mc_scan over the tiles' totals);
+//   emit  : vertices (the workgroup scan again: new index, source_vertex, the vertex map), then faces renumbered through the map.
+// ---------------------------------------------------------------------------------------------
+#define CC_PER 4                               // consecutive vertices / faces per thread
+#define CC_TILE (MC_THREADS * CC_PER)
+static_assert(CC_TILE == DSN_MESH_CC_TILE, "compaction tile");
+
+static int64_t cc_tiles(int64_t n) { return (n + CC_TILE - 1) / CC_TILE; }
+static size_t cc_up(size_t b) { return (b + 15) / 16 * 16; }
+// header 64 B (int32 word 0: the winner) | label int32 [V] | vmap int32 [V] | sum uint64 [V] | cnt uint64 [V] | used uint8 [V] |
+// tile vertex offsets int64 [tiles + 1] | tile face offsets int64 [tiles + 1] | tile best sum uint64 [tilesV] | tile best label
+// int32 [tilesV] | tile component count int32 [tilesV]            (tiles = max(tilesV, tilesT); every part 16-byte aligned)
+struct CcWs {
+    int32_t* head; int32_t* label; int32_t* vmap; unsigned long long* sum; unsigned long long* cnt; uint8_t* used;
+    int64_t* tv; int64_t* tf; unsigned long long* bsum; int32_t* blab; int32_t* bcomp; size_t bytes;
+};
+static CcWs cc_ws(void* w, int64_t V, int64_t T) {
+    const int64_t tilesV = cc_tiles(V), tilesT = cc_tiles(T), tiles = tilesV > tilesT ? tilesV : tilesT;
+    char* p = (char*)w;
+    size_t o = 0;
+    CcWs r;
+    r.head = (int32_t*)(p + o); o += 64;
+    r.label = (int32_t*)(p + o); o += cc_up((size_t)4 * V);
+    r.vmap = (int32_t*)(p + o); o += cc_up((size_t)4 * V);
+    r.sum = (unsigned long long*)(p + o); o += cc_up((size_t)8 * V);
+    r.cnt = (unsigned long long*)(p + o); o += cc_up((size_t)8 * V);
+    r.used = (uint8_t*)(p + o); o += cc_up((size_t)V);
+    r.tv = (int64_t*)(p + o); o += cc_up((size_t)8 * (tiles + 1));
+    r.tf = (int64_t*)(p + o); o += cc_up((size_t)8 * (tiles + 1));
+    r.bsum = (unsigned long long*)(p + o); o += cc_up((size_t)8 * tilesV);
+    r.blab = (int32_t*)(p + o); o += cc_up((size_t)4 * tilesV);
+    r.bcomp = (int32_t*)(p + o); o += cc_up((size_t)4 * tilesV);
+    r.bytes = o;
+    return r;
+}
+size_t dsn_mesh_cc_workspace_size(int64_t V, int64_t T) { return cc_ws(nullptr, V, T).bytes; }
+
+__global__ void __launch_bounds__(MC_THREADS) k_cc_init(int32_t* __restrict__ parent, unsigned long long* __restrict__ sum,
+                                                        unsigned long long* __restrict__ cnt, uint8_t* __restrict__ used, int V) {
+    const int64_t v = (int64_t)blockIdx.x * MC_THREADS + threadIdx.x;
+    if (v >= V) return;
+    parent[v] = (int32_t)v; sum[v] = 0; cnt[v] = 0; used[v] = 0;
+}
+
+// The union-find of k_cc_unite.  Invariant: parent[x] <= x, always - a root is only ever hooked under a smaller root (compare-and-swap)
+// and a shortcut only ever lowers an entry to one of its ancestors (atomic minimum).  Every access is a relaxed agent-scope atomic: the
+// eight L2s are not coherent for plain loads of lines another compute unit's atomics rewrote.  Whatever value a load returns - a stale
+// one included - is an ancestor <= x, so cc_find walks strictly downward and ends; no thread ever waits for another's write.
+// The walks compare unsigned and follow an entry only while it is below its index: whatever bytes the array holds (the measurement
+// entries can run a phase on a workspace the phases before it never wrote), no index leaves [0, x].
+__device__ __forceinline__ int32_t cc_load(int32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ int32_t cc_find(int32_t* __restrict__ parent, int32_t x) {
+    int32_t p = cc_load(parent + x);
+    while ((uint32_t)p < (uint32_t)x) {            // (a root: p == x)
+        const int32_t g = cc_load(parent + p);     // g <= p
+        if ((uint32_t)g < (uint32_t)p) __hip_atomic_fetch_min(parent + x, g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // path halving
+        x = p; p = g;
+    }
+    return x;
+}
+__device__ __forceinline__ void cc_unite(int32_t* __restrict__ parent, int32_t a, int32_t b) {
+    for (;;) {
+        a = cc_find(parent, a); b = cc_find(parent, b);
+        if (a == b) return;
+        const int32_t hi = a > b ? a : b, lo = a > b ? b : a;
+        int32_t seen = hi;
+        if (__hip_atomic_compare_exchange_strong(parent + hi, &seen, lo, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;
+        if ((uint32_t)seen >= (uint32_t)hi) return;
+        a = seen; b = lo;                          // hi was hooked meanwhile: go on from what the atomic returned (an ancestor of hi)
+    }
+}
+__device__ __forceinline__ bool cc_face(const int32_t* __restrict__ faces, int64_t t, int V, int32_t& i0, int32_t& i1, int32_t& i2) {
+    i0 = faces[3 * t]; i1 = faces[3 * t + 1]; i2 = faces[3 * t + 2];
+    return (uint32_t)i0 < (uint32_t)V && (uint32_t)i1 < (uint32_t)V && (uint32_t)i2 < (uint32_t)V;
+}
+
+__global__ void __launch_bounds__(MC_THREADS) k_cc_unite(const int32_t* __restrict__ faces, int V, int64_t T, int32_t* __restrict__ parent,
+                                                         uint8_t* __restrict__ used) {
+    const int64_t t = (int64_t)blockIdx.x * MC_THREADS + threadIdx.x;
+    if (t >= T) return;
+    int32_t i0, i1, i2;
+    if (!cc_face(faces, t, V, i0, i1, i2)) return;
+    used[i0] = 1; used[i1] = 1; used[i2] = 1;      // (every writer stores the same byte; read by the next launch)
+    cc_unite(parent, i0, i1);
+    cc_unite(parent, i0, i2);
+}
+
+// every vertex to its root, in place (a walk meets entries of before this launch or roots already written: ancestors either way);
+// a vertex no valid face uses: -1 (a singleton, no other walk passes through it)
+__global__ void __launch_bounds__(MC_THREADS) k_cc_flatten(int32_t* __restrict__ parent, const uint8_t* __restrict__ used, int V,
+                                                           int32_t* __restrict__ labels_out) {
+    const int64_t v = (int64_t)blockIdx.x * MC_THREADS + threadIdx.x;
+    if (v >= V) return;
+    int32_t r = -1;
+    if (used[v]) {
+        r = (int32_t)v;
+        for (int32_t p = parent[r]; (uint32_t)p < (uint32_t)r; p = parent[r]) r = p;
+    }
+    parent[v] = r;
+    if (labels_out) labels_out[v] = r;
+}
+
+// doubled area of a face in float32 (dsnerf.h), as the integer floor(d 2^k): scale = 2^k
+__device__ __forceinline__ unsigned long long cc_area_q(const float* __restrict__ verts, int32_t i0, int32_t i1, int32_t i2, double scale) {
+    const float* a = verts + 3 * (int64_t)i0; const float* b = verts + 3 * (int64_t)i1; const float* c = verts + 3 * (int64_t)i2;
+    const float e1x = b[0] - a[0], e1y = b[1] - a[1], e1z = b[2] - a[2];
+    const float e2x = c[0] - a[0], e2y = c[1] - a[1], e2z = c[2] - a[2];
+    const float nx = e1y * e2z - e1z * e2y, ny = e1z * e2x - e1x * e2z, nz = e1x * e2y - e1y * e2x;
+    float d = sqrtf((nx * nx + ny * ny) + nz * nz);
+    if (!(d < __builtin_inff())) d = 0.0f;         // (NaN and infinity)
+    const double x = floor((double)d * scale);     // exact: a power of two times a float
+    return x < 9223372036854775808.0 ? (unsigned long long)x : 9223372036854775808ull;      // (2^63: only a shift the host rule never gives)
+}
+
+__global__ void __launch_bounds__(MC_THREADS) k_cc_sums(const float* __restrict__ verts, const int32_t* __restrict__ faces, int V, int64_t T,
+                                                        const int32_t* __restrict__ label, double scale,
+                                                        unsigned long long* __restrict__ sum, unsigned long long* __restrict__ cnt) {
+    const int64_t t = (int64_t)blockIdx.x * MC_THREADS + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    int32_t i0 = 0, i1 = 0, i2 = 0, root = -1;
+    unsigned long long q = 0;
+    bool todo = t < T && cc_face(faces, t, V, i0, i1, i2);
+    if (todo) { root = label[i0]; q = cc_area_q(verts, i0, i1, i2, scale); }
+    todo = todo && (uint32_t)root < (uint32_t)V;   // (always, after k_cc_flatten)
+    // per wave: the lanes that share the first pending lane's root add up among themselves, one lane issues the two atomics
+    for (;;) {
+        const unsigned long long pending = __ballot(todo);
+        if (!pending) break;
+        const int leader = __ffsll((long long)pending) - 1;
+        const int32_t r0 = __shfl(root, leader);
+        const bool mine = todo && root == r0;
+        unsigned long long qs = mine ? q : 0ull;
+        int n = mine ? 1 : 0;
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) { qs += __shfl_xor(qs, off); n += __shfl_xor(n, off); }
+        if (lane == leader) { atomicAdd(sum + r0, qs); atomicAdd(cnt + r0, (unsigned long long)n); }
+        todo = todo && !mine;
+    }
+}
+
+// (sum, label) a beats b: the larger sum, on equal sums the smaller label; label -1 = none
+__device__ __forceinline__ bool cc_better(unsigned long long sa, int32_t la, unsigned long long sb, int32_t lb) {
+    if (la < 0) return false;
+    if (lb < 0) return true;
+    return sa > sb || (sa == sb && la < lb);
+}
+template <int THREADS>
+__device__ __forceinline__ void cc_block_best(unsigned long long& s, int32_t& l, int& n) {
+    __shared__ unsigned long long ss[THREADS];
+    __shared__ int32_t sl[THREADS];
+    __shared__ int sn[THREADS];
+    const int t = threadIdx.x;
+    ss[t] = s; sl[t] = l; sn[t] = n;
+    __syncthreads();
+    for (int off = THREADS / 2; off >= 1; off >>= 1) {
+        if (t < off) {
+            if (cc_better(ss[t + off], sl[t + off], ss[t], sl[t])) { ss[t] = ss[t + off]; sl[t] = sl[t + off]; }
+            sn[t] += sn[t + off];
+        }
+        __syncthreads();
+    }
+    s = ss[0]; l = sl[0]; n = sn[0];
+}
+
+__global__ void __launch_bounds__(MC_THREADS) k_cc_select_tiles(const int32_t* __restrict__ label, const unsigned long long* __restrict__ sum,
+                                                                const unsigned long long* __restrict__ cnt, int V,
+                                                                unsigned long long* __restrict__ bsum, int32_t* __restrict__ blab,
+                                                                int32_t* __restrict__ bcomp) {
+    const int64_t v0 = (int64_t)blockIdx.x * CC_TILE + (int64_t)threadIdx.x * CC_PER;
+    unsigned long long s = 0; int32_t l = -1; int n = 0;
+    for (int q = 0; q < CC_PER && v0 + q < V; ++q) {
+        const int32_t v = (int32_t)(v0 + q);
+        if (label[v] != v || cnt[v] == 0) continue;      // (a root with at least one face)
+        ++n;
+        if (cc_better(sum[v], v, s, l)) { s = sum[v]; l = v; }
+    }
+    cc_block_best<MC_THREADS>(s, l, n);
+    if (threadIdx.x == 0) { bsum[blockIdx.x] = s; blab[blockIdx.x] = l; bcomp[blockIdx.x] = n; }
+}
+
+// one workgroup over the tiles: out[0] components, out[1] winner, out[4] its sum, out[5] its faces; head[0] = winner
+__global__ void __launch_bounds__(MC_SCAN_THREADS) k_cc_select_final(const unsigned long long* __restrict__ bsum, const int32_t* __restrict__ blab,
+                                                                     const int32_t* __restrict__ bcomp, int64_t tilesV,
+                                                                     const unsigned long long* __restrict__ cnt, int V,
+                                                                     int32_t* __restrict__ head, int64_t* __restrict__ out) {
+    unsigned long long s = 0; int32_t l = -1; int n = 0;
+    for (int64_t k = threadIdx.x; k < tilesV; k += MC_SCAN_THREADS) {
+        n += bcomp[k];
+        if (cc_better(bsum[k], blab[k], s, l)) { s = bsum[k]; l = blab[k]; }
+    }
+    cc_block_best<MC_SCAN_THREADS>(s, l, n);
+    if (threadIdx.x == 0) {
+        head[0] = l;
+        out[0] = n; out[1] = l; out[4] = (int64_t)s; out[5] = (uint32_t)l < (uint32_t)V ? (int64_t)cnt[l] : 0;
+    }
+}
+
+__device__ __forceinline__ bool cc_keep_face(const int32_t* __restrict__ faces, int64_t t, int V, const int32_t* __restrict__ label,
+                                             int32_t winner, int32_t& i0, int32_t& i1, int32_t& i2) {
+    return cc_face(faces, t, V, i0, i1, i2) && label[i0] == winner;
+}
+
+// kept vertices and faces of tile blockIdx.x (either may lie beyond the mesh: 0)
+__global__ void __launch_bounds__(MC_THREADS) k_cc_count(const int32_t* __restrict__ faces, int V, int64_t T, const int32_t* __restrict__ label,
+                                                         const int32_t* __restrict__ head, int64_t* __restrict__ tv, int64_t* __restrict__ tf) {
+    const int32_t winner = head[0];
+    const int64_t n0 = (int64_t)blockIdx.x * CC_TILE + (int64_t)threadIdx.x * CC_PER;
+    int nv = 0, nf = 0;
+    if (winner >= 0)
+        for (int q = 0; q < CC_PER; ++q) {
+            int32_t i0, i1, i2;
+            if (n0 + q < V && label[n0 + q] == winner) ++nv;
+            if (n0 + q < T && cc_keep_face(faces, n0 + q, V, label, winner, i0, i1, i2)) ++nf;
+        }
+    int tot_v, tot_f;
+    mc_block_scan(nv, nf, tot_v, tot_f);
+    if (threadIdx.x == 0) { tv[blockIdx.x] = tot_v; tf[blockIdx.x] = tot_f; }
+}
+
+__global__ void __launch_bounds__(MC_THREADS) k_cc_emit_verts(const float* __restrict__ verts, int V, const int32_t* __restrict__ label,
+                                                              const int32_t* __restrict__ head, const int64_t* __restrict__ tv,
+                                                              int32_t* __restrict__ vmap, float* __restrict__ out_verts, int64_t vcap,
+                                                              int32_t* __restrict__ source) {
+    const int32_t winner = head[0];
+    const int64_t n0 = (int64_t)blockIdx.x * CC_TILE + (int64_t)threadIdx.x * CC_PER;
+    int keep = 0, nv = 0, none = 0, tot_v, tot_n;
+    if (winner >= 0)
+        for (int q = 0; q < CC_PER; ++q)
+            if (n0 + q < V && label[n0 + q] == winner) { keep |= 1 << q; ++nv; }
+    mc_block_scan(nv, none, tot_v, tot_n);
+    int64_t o = tv[blockIdx.x] + nv;
+    for (int q = 0; q < CC_PER && n0 + q < V; ++q) {
+        const int64_t v = n0 + q;
+        if (!((keep >> q) & 1)) { vmap[v] = -1; continue; }
+        vmap[v] = (int32_t)o;
+        if ((uint64_t)o < (uint64_t)vcap) {
+            out_verts[3 * o] = verts[3 * v]; out_verts[3 * o + 1] = verts[3 * v + 1]; out_verts[3 * o + 2] = verts[3 * v + 2];
+            if (source) source[o] = (int32_t)v;
+        }
+        ++o;
+    }
+}
+
+__global__ void __launch_bounds__(MC_THREADS) k_cc_emit_faces(const int32_t* __restrict__ faces, int V, int64_t T, const int32_t* __restrict__ label,
+                                                              const int32_t* __restrict__ head, const int64_t* __restrict__ tf,
+                                                              const int32_t* __restrict__ vmap, int32_t* __restrict__ out_faces, int64_t fcap) {
+    const int32_t winner = head[0];
+    const int64_t n0 = (int64_t)blockIdx.x * CC_TILE + (int64_t)threadIdx.x * CC_PER;
+    int32_t idx[CC_PER][3];
+    int keep = 0, nf = 0, none = 0, tot_f, tot_n;
+    if (winner >= 0)
+#pragma unroll
+        for (int q = 0; q < CC_PER; ++q)
+            if (n0 + q < T && cc_keep_face(faces, n0 + q, V, label, winner, idx[q][0], idx[q][1], idx[q][2])) { keep |= 1 << q; ++nf; }
+    mc_block_scan(nf, none, tot_f, tot_n);
+    int64_t o = tf[blockIdx.x] + nf;
+#pragma unroll
+    for (int q = 0; q < CC_PER; ++q) {
+        if (!((keep >> q) & 1)) continue;
+        if ((uint64_t)o < (uint64_t)fcap) { out_faces[3 * o] = vmap[idx[q][0]]; out_faces[3 * o + 1] = vmap[idx[q][1]]; out_faces[3 * o + 2] = vmap[idx[q][2]]; }
+        ++o;
+    }
+}
+
+void dsn_launch_mesh_cc_label(const float* verts, const int32_t* faces, int64_t V, int64_t T, double scale, void* workspace, int32_t* labels_v,
+                              int64_t* out_counts, int phases, hipStream_t st) {
+    CcWs w = cc_ws(workspace, V, T);
+    const int64_t tilesV = cc_tiles(V), tilesT = cc_tiles(T), tiles = tilesV > tilesT ? tilesV : tilesT;
+    const unsigned gV = (unsigned)((V + MC_THREADS - 1) / MC_THREADS), gT = (unsigned)((T + MC_THREADS - 1) / MC_THREADS);
+    if ((phases & DSN_CC_INIT) && gV) hipLaunchKernelGGL(k_cc_init, dim3(gV), dim3(MC_THREADS), 0, st, w.label, w.sum, w.cnt, w.used, (int)V);
+    if ((phases & DSN_CC_UNITE) && gT && gV) hipLaunchKernelGGL(k_cc_unite, dim3(gT), dim3(MC_THREADS), 0, st, faces, (int)V, T, w.label, w.used);
+    if ((phases & DSN_CC_FLATTEN) && gV) hipLaunchKernelGGL(k_cc_flatten, dim3(gV), dim3(MC_THREADS), 0, st, w.label, w.used, (int)V, labels_v);
+    if ((phases & DSN_CC_SUMS) && gT && gV)
+        hipLaunchKernelGGL(k_cc_sums, dim3(gT), dim3(MC_THREADS), 0, st, verts, faces, (int)V, T, w.label, scale, w.sum, w.cnt);
+    if (phases & DSN_CC_SELECT) {
+        if (tilesV)
+            hipLaunchKernelGGL(k_cc_select_tiles, dim3((unsigned)tilesV), dim3(MC_THREADS), 0, st, w.label, w.sum, w.cnt, (int)V, w.bsum, w.blab, w.bcomp);
+        hipLaunchKernelGGL(k_cc_select_final, dim3(1), dim3(MC_SCAN_THREADS), 0, st, w.bsum, w.blab, w.bcomp, tilesV, w.cnt, (int)V, w.head,
+                           out_counts);
+    }
+    if (phases & DSN_CC_COUNT) {
+        if (tiles) hipLaunchKernelGGL(k_cc_count, dim3((unsigned)tiles), dim3(MC_THREADS), 0, st, faces, (int)V, T, w.label, w.head, w.tv, w.tf);
+        hipLaunchKernelGGL(k_mc_scan, dim3(1), dim3(MC_SCAN_THREADS), 0, st, w.tv, w.tf, tiles, out_counts + 2);
+    }
+}
+
+void dsn_launch_mesh_cc_emit(const float* verts, const int32_t* faces, int64_t V, int64_t T, void* workspace, float* out_verts, int64_t vcap,
+                             int32_t* out_faces, int64_t fcap, int32_t* source_vertex, int phases, hipStream_t st) {
+    CcWs w = cc_ws(workspace, V, T);
+    const int64_t tilesV = cc_tiles(V), tilesT = cc_tiles(T);
+    if ((phases & DSN_CC_EMIT_VERTS) && tilesV)
+        hipLaunchKernelGGL(k_cc_emit_verts, dim3((unsigned)tilesV), dim3(MC_THREADS), 0, st, verts, (int)V, w.label, w.head, w.tv, w.vmap, out_verts,
+                           vcap, source_vertex);
+    if ((phases & DSN_CC_EMIT_FACES) && tilesT && tilesV && fcap > 0)
+        hipLaunchKernelGGL(k_cc_emit_faces, dim3((unsigned)tilesT), dim3(MC_THREADS), 0, st, faces, (int)V, T, w.label, w.head, w.tf, w.vmap,
+                           out_faces, fcap);
+}

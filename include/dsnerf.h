@@ -570,6 +570,70 @@ DSN_EXPORT int dsn_mc_normals(const float* volume, int nx, int ny, int nz, const
 /* the case table (host function, no device work): 256 rows of DSN_MC_TABLE_ROW int32 into a HOST array of out_ints >= 256 rows */
 DSN_EXPORT int dsn_mc_table_host(int32_t* out_host, size_t out_ints);
 
+/* ---- mesh components (an addition within ABI 8: no existing entry point changes) ----------------------------------------------------
+ * utils/visualizer.py:129-138, Visualizer3D(connected=True): the reference splits the mesh with trimesh and keeps the component with the
+ * largest area.  Here: the connected components of an indexed mesh (verts [V, 3] float32, faces [T, 3] int32, device) and its largest
+ * piece as a compacted mesh, by a rule fixed so that a numpy restatement (tests/mesh_cc_restate.py) reproduces every output bit for bit.
+ *   Valid faces:  a face is valid when its three indices lie in [0, V).  Invalid faces belong to no component and are never emitted.  A
+ *                 face with a repeated index is valid: it has area 0 and still connects.
+ *   Connectivity: two valid faces are connected when they share a vertex INDEX (coincident positions under different indices do not
+ *                 connect); a component is a class of the transitive closure.  trimesh's split joins faces that share an EDGE: on the
+ *                 output of dsn_mc_emit the two rules give the same partition (every vertex's triangles form one edge-connected fan;
+ *                 tests/test_mesh_cc_host.py), on arbitrary meshes they differ at pinch vertices - two pieces touching in one vertex
+ *                 are ONE component here.
+ *   Label:        a component's label is the smallest vertex index it contains, whatever the face order or the scheduling; a vertex used
+ *                 by no valid face has label -1.
+ *   Area:         per valid face (a, b, c), float32, no fused multiply-add: e1 = b - a, e2 = c - a; n = e1 x e2, each component two
+ *                 rounded products and one subtraction (n0 = e1_1 e2_2 - e1_2 e2_1, ...); s = (n0 n0 + n1 n1) + n2 n2; d = sqrt(s), the
+ *                 doubled area; a d that is not finite counts as 0.  The face adds q = floor(d 2^area_shift), formed exactly in double,
+ *                 to its component's unsigned 64-bit sum: integer sums do not depend on the order the faces arrive in.  The caller
+ *                 chooses the shift: area_shift = 61 - bit_length(T) - e, clamped to +-60, with e the frexp exponent of float32
+ *                 D2 = (dx dx + dy dy) + dz dz over the extents of the bounding box of the vertices whose coordinates are all finite
+ *                 (128 where D2 is not finite, 0 without such a vertex); no triangle with finite vertices has a doubled area above D2,
+ *                 so the sums stay below 2^61.  (A q of 2^63 or more - no shift of this rule gives one - counts as 2^63.)  The area
+ *                 of a component is sum 2^(-area_shift - 1).
+ *   Winner:       the component with the largest sum; on equal sums the smaller label (the reference keeps the first component whose
+ *                 area is strictly greater, in trimesh's unpinned component order).
+ *   Filtered mesh: the winner's vertices in their original order; the winner's valid faces in their original order and winding, their
+ *                 indices renumbered through the vertex map; source_vertex [V'] int32 = each kept vertex's old index (per-vertex arrays
+ *                 follow by one gather).  A mesh that is one component without unused vertices comes back bit for bit.
+ * Two phases, as dsn_mc_count / dsn_mc_emit (the library never allocates): dsn_mesh_cc_label fills `workspace`
+ * (dsn_mesh_cc_workspace_bytes(V, T), 16-byte aligned; its earlier contents are not read), writes labels_v [V] int32 (may be NULL) and
+ * out_counts: 6 int64 in device memory {components, winner label (-1: none), V', T', the winner's sum, the winner's face count}.  The caller
+ * reads them, sizes out_verts [V', 3], out_faces [T', 3] and source_vertex [V'] (may be NULL), and dsn_mesh_cc_emit fills them from the
+ * same workspace (rows beyond n_verts / n_faces are not written).  V = 0 or T = 0 is a valid call: all counts 0, the winner -1.
+ * Kernels: a lock-free union-find over the vertex array, one thread per face (a root is only ever hooked under a smaller root by a
+ * compare-and-swap, so parent[x] <= x always holds, every walk goes strictly downward and ends whatever value it reads, and no thread waits
+ * for another; every access of that kernel is a relaxed agent-scope atomic), a launch that flattens every vertex to its root, 64-bit
+ * integer atomic adds of the faces' areas aggregated per wave, a deterministic arg-max over the roots, and two scans over tiles of
+ * DSN_MESH_CC_TILE vertices / faces that decide the output order (no atomics there).  Every call returns the same bits.  No allocation,
+ * no synchronisation, all on `stream`.
+ * Rejected: null verts with V > 0, null faces with T > 0, a null workspace or out_counts, negative sizes or 2^31 and more, a workspace
+ * that is not 16-byte aligned or smaller than dsn_mesh_cc_workspace_bytes (0 for bad sizes), a shift outside +-60; by dsn_mesh_cc_emit
+ * also null outputs with non-zero counts and counts above V / T. */
+#define DSN_MESH_CC_TILE 1024
+DSN_EXPORT size_t dsn_mesh_cc_workspace_bytes(int64_t n_verts, int64_t n_faces);
+DSN_EXPORT int dsn_mesh_cc_label(const float* verts, const int32_t* faces, int64_t n_verts, int64_t n_faces, int area_shift, void* workspace,
+                                 size_t workspace_bytes, int32_t* labels_v, int64_t* out_counts6, void* stream);
+DSN_EXPORT int dsn_mesh_cc_emit(const float* verts, const int32_t* faces, int64_t n_verts, int64_t n_faces, void* workspace,
+                                size_t workspace_bytes, int64_t out_n_verts, int64_t out_n_faces, float* out_verts, int32_t* out_faces,
+                                int32_t* source_vertex, void* stream);
+/* measurement (scripts/bench_mesh_cc.py): enqueue only these kernels (0 = all; one mesh and one workspace through the phases in order) */
+#define DSN_CC_INIT 1
+#define DSN_CC_UNITE 2
+#define DSN_CC_FLATTEN 4
+#define DSN_CC_SUMS 8
+#define DSN_CC_SELECT 16
+#define DSN_CC_COUNT 32
+#define DSN_CC_EMIT_VERTS 64
+#define DSN_CC_EMIT_FACES 128
+DSN_EXPORT int dsn_mesh_cc_label_ex(const float* verts, const int32_t* faces, int64_t n_verts, int64_t n_faces, int area_shift,
+                                    void* workspace, size_t workspace_bytes, int32_t* labels_v, int64_t* out_counts6, int phases,
+                                    void* stream);
+DSN_EXPORT int dsn_mesh_cc_emit_ex(const float* verts, const int32_t* faces, int64_t n_verts, int64_t n_faces, void* workspace,
+                                   size_t workspace_bytes, int64_t out_n_verts, int64_t out_n_faces, float* out_verts, int32_t* out_faces,
+                                   int32_t* source_vertex, int phases, void* stream);
+
 /* ---- mesh preview (an addition within ABI 8: no existing entry point changes) -------------------------------------------------------
  * utils/visualizer.py:144-168 Visualizer3D.render_mesh (pyrender: PerspectiveCamera(yfov = pi/3, aspect 1), a SpotLight of intensity 30
  * with cone angles pi/16 and pi/6 at the camera's pose, white background, no ambient light): a deterministic triangle rasteriser with
