@@ -48,6 +48,7 @@ EXPORTS = [
     "dsn_render_maps_scratch_bytes", "dsn_render_rays_maps", "dsn_composite_maps", "dsn_shade_factor",
     "dsn_raster_workspace_bytes", "dsn_raster_mesh", "dsn_raster_mesh_ex", "dsn_mc_normals", "dsn_raster_mesh_attr",
     "dsn_mesh_cc_workspace_bytes", "dsn_mesh_cc_label", "dsn_mesh_cc_emit", "dsn_mesh_cc_label_ex", "dsn_mesh_cc_emit_ex",
+    "dsn_bound_mask", "dsn_train_rays_workspace_bytes", "dsn_train_rays",
 ]
 
 SKIP_TRANSPARENT = 1
@@ -69,6 +70,8 @@ SCREEN_MARGIN_FLOOR, SCREEN_MARGIN_CAP = 0.002, 0.15      # = F16_SCREEN_FLOOR /
 SCREEN_HEADROOM = 10.0        # = F16_SCREEN_HEADROOM: every calibration point is this factor in deviation away from a wrong drop
 SCREEN_MIN_DROPPED = 0.35     # PackedParams.calibrate_screen: below this share of dropped calibration points the screen stays off
 RAYS_ZJU, RAYS_H36M = 0, 1
+TRAIN_RAYS_OK, TRAIN_RAYS_EMPTY_CLASS, TRAIN_RAYS_SHORT, TRAIN_RAYS_BAD_CAMERA = 0, 1, 2, 3     # dsn_train_rays' status (DSN_TRAIN_RAYS_*)
+TRAIN_RAYS_MAX_ROUNDS, TRAIN_RAYS_MAX_RAYS = 64, 65536
 SSIM_OK, SSIM_CROP_TOO_SMALL, SSIM_EMPTY_MASK = 0, 1, 2     # dsn_image_ssim's out_status (DSN_SSIM_*)
 FRAME_FINE_ONLY = 1           # dsn_set_frame_ex: only the fine nearest-face level of the posed mesh (points beyond it: exhaustive sweep)
 FRAME_LAZY_LISTS = 2          # dsn_set_frame_ex: grid geometry only - the frame that uses the level builds the lists of the cells it visits
@@ -129,6 +132,11 @@ def lib():
         L.dsn_mesh_cc_label_ex.argtypes = cc_label + [C.c_int, C.c_void_p]
         L.dsn_mesh_cc_emit.argtypes = cc_emit + [C.c_void_p]
         L.dsn_mesh_cc_emit_ex.argtypes = cc_emit + [C.c_int, C.c_void_p]
+        L.dsn_bound_mask.argtypes = [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        L.dsn_train_rays_workspace_bytes.restype = C.c_size_t
+        L.dsn_train_rays_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
+        L.dsn_train_rays.argtypes = ([C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 6 + [C.c_int, C.c_uint32]
+                                     + [C.c_void_p] * 12 + [C.c_size_t, C.c_void_p])
         if L.dsn_abi_version() != 8:
             raise RuntimeError(f"{LIB_PATH} has ABI version {L.dsn_abi_version()}, this binding needs 8 - rebuild it "
                                "(python dual-space-nerf_amd/build.py)")
@@ -1580,3 +1588,78 @@ def camera_rays(K, R, T, bounds, H, W, device=None, convention="zju"):
     _check(lib().dsn_camera_rays(_ptr(K), _ptr(R), _ptr(T), _ptr(bounds), H, W, RAYS_H36M if convention == "h36m" else RAYS_ZJU,
                                  _ptr(ray_o), _ptr(ray_d), _ptr(near), _ptr(far), _ptr(mask), _stream()), "dsn_camera_rays")
     return ray_o, ray_d, near, far, mask.bool()
+
+
+def _camera_f64(K, R, T, bounds, dev):
+    f64 = lambda a: torch.as_tensor(a, dtype=torch.float64).reshape(-1).to(dev).contiguous()
+    K, R, T, bounds = f64(K), f64(R), f64(T), f64(bounds)
+    if (K.numel(), R.numel(), T.numel(), bounds.numel()) != (9, 9, 3, 6):
+        raise ValueError("K, R must be [3,3], T [3] or [3,1], bounds [2,3]")
+    return K, R, T, bounds
+
+
+def bound_mask(K, R, T, bounds, H, W, device=None):
+    """get_bound_2d_mask (utils/rays_utils.py:49-60) on the device by the rule of include/dsnerf.h: the union of the reference's six
+    corner loops, exact integers - cv2.fillPoly's result without the outline pixels its line drawing adds.  Returns uint8 [H,W]
+    (all zero for a camera with a box corner behind it)."""
+    require_gpu()
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    K, R, T, bounds = _camera_f64(K, R, T, bounds, dev)
+    out = torch.empty(int(H), int(W), dtype=torch.uint8, device=dev)
+    _check(lib().dsn_bound_mask(_ptr(K), _ptr(R), _ptr(T), _ptr(bounds), int(H), int(W), _ptr(out), _stream()), "dsn_bound_mask")
+    return out
+
+
+def train_rays(img, K, R, T, bounds, mask_a, nrays, seed, convention="zju", mask_b=None, occupancy_src=None, bound_mask_in=None,
+               workspace=None):
+    """A training batch drawn on the device (dsn_train_rays; my_sample_ray / sample_ray_h36m by the rule of include/dsnerf.h).
+    img [H,W,3] float64 or float32, mask_a (zju: msk_cihp; h36m: msk) and the optional mask_b (h36m: msk_cihp), occupancy_src,
+    bound_mask_in [H,W] uint8: device tensors (anything else is copied over).  Returns a dict of device tensors - ray_o, ray_d, rgb
+    [n,3], near, far [n], coord [n,2] int64, mask_at_box [n] bool, occupancy [n] uint8 (None without occupancy_src), bound_mask [H,W]
+    uint8, status and rounds (int32 scalars) - without synchronising: the caller reads status (TRAIN_RAYS_*) when it wants to know."""
+    require_gpu()
+    if convention not in ("zju", "h36m"):
+        raise ValueError("convention must be 'zju' or 'h36m'")
+    if not 0 <= int(seed) < 2 ** 32:
+        raise ValueError("seed must be 0 ... 2^32 - 1")
+    dev = img.device if isinstance(img, torch.Tensor) and img.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    img = torch.as_tensor(img).to(dev)
+    if img.dim() != 3 or img.shape[2] != 3:
+        raise ValueError(f"img must be [H,W,3], got {tuple(img.shape)}")
+    if img.dtype not in (torch.float64, torch.float32):
+        raise TypeError(f"img must be float64 or float32, got {img.dtype}")
+    img = img.contiguous()
+    H, W = int(img.shape[0]), int(img.shape[1])
+
+    def u8(m, what):
+        if m is None:
+            return None
+        m = torch.as_tensor(m).to(dev)
+        if tuple(m.shape) != (H, W):
+            raise ValueError(f"{what} must be [{H},{W}], got {tuple(m.shape)}")
+        return (m if m.dtype == torch.uint8 else m.to(torch.uint8)).contiguous()
+
+    mask_a, mask_b = u8(mask_a, "mask"), u8(mask_b, "mask_b")
+    occupancy_src, bound_mask_in = u8(occupancy_src, "occupancy_src"), u8(bound_mask_in, "bound_mask")
+    if mask_a is None or (convention == "h36m" and mask_b is None):
+        raise ValueError("mask is required (h36m: mask_b = msk_cihp too)")
+    n = int(nrays)
+    K, R, T, bounds = _camera_f64(K, R, T, bounds, dev)
+    nbytes = lib().dsn_train_rays_workspace_bytes(H, W, n)
+    if nbytes == 0:
+        raise ValueError(f"train_rays: nrays must be 1 ... {TRAIN_RAYS_MAX_RAYS} and H * W below 2^31 (got nrays = {n}, {H} x {W})")
+    ws = workspace if workspace is not None and workspace.numel() >= nbytes else _scratch(nbytes, dev)
+    e = lambda *shape, dtype=torch.float32: torch.empty(*shape, dtype=dtype, device=dev)
+    out = {"ray_o": e(n, 3), "ray_d": e(n, 3), "near": e(n), "far": e(n), "coord": e(n, 2, dtype=torch.int64), "rgb": e(n, 3),
+           "occupancy": None if occupancy_src is None else e(n, dtype=torch.uint8), "mask_at_box": e(n, dtype=torch.uint8),
+           "bound_mask": e(H, W, dtype=torch.uint8), "status": e((), dtype=torch.int32), "rounds": e((), dtype=torch.int32)}
+    g64, g32 = (img, None) if img.dtype == torch.float64 else (None, img)
+    _check(lib().dsn_train_rays(_ptr(K), _ptr(R), _ptr(T), _ptr(bounds), H, W, RAYS_H36M if convention == "h36m" else RAYS_ZJU,
+                                _ptr(g64), _ptr(g32), _ptr(mask_a), _ptr(mask_b), _ptr(bound_mask_in), _ptr(occupancy_src), n,
+                                int(seed), _ptr(out["ray_o"]), _ptr(out["ray_d"]), _ptr(out["near"]), _ptr(out["far"]),
+                                _ptr(out["coord"]), _ptr(out["rgb"]), _ptr(out["occupancy"]), _ptr(out["mask_at_box"]),
+                                _ptr(out["bound_mask"]), _ptr(out["status"]), _ptr(out["rounds"]), _ptr(ws), ws.numel(), _stream()),
+           "dsn_train_rays")
+    out["mask_at_box"] = out["mask_at_box"].bool()
+    out["workspace"] = ws
+    return out

@@ -499,6 +499,42 @@ class Renderer:
         return self.render_rays(pts, rays, z_vals, frame_idx, net=net,
                                 transparent_mask=batch_info["transparent_mask"], batch_info=batch_info)
 
+    # ---- the datasets' ray sampler (utils/rays_utils.py:104-172, utils/h36m_utils.py:78-146) on the device ----
+    def sample_batch(self, img, K, R, T, bounds, mask, nrays, seed, convention="zju", mask_b=None, occupancy_from=None,
+                     bound_mask=None, check=True):
+        """A training batch drawn on the device (_lib.train_rays, the rule of include/dsnerf.h) from an image, its masks and the
+        camera: what the datasets' my_sample_ray (convention "zju", mask = msk_cihp) / sample_ray_h36m ("h36m", mask = msk,
+        mask_b = msk_cihp) call builds on the host.  img [H,W,3] float64 or float32; mask, mask_b, occupancy_from (the map
+        `occupancy` is gathered from: msk_fg; omitted -> no "occupancy" key) and bound_mask (a box mask of the caller's, e.g. cv2's;
+        omitted -> computed) [H,W]; device tensors are used as they are.  The same arguments give the same batch, bit for bit.
+        Returns the datasets' keys on the device with the loader's leading 1 - rgb, ray_o, ray_d [1,n,3], near, far [1,n], coord
+        [1,n,2] int64, mask_at_box [1,n] bool, occupancy [1,n] uint8, mybound_mask [1,H,W] uint8 - plus "rounds"; render() takes it
+        once xyz, poses and frame are added.  check=True reads the status word (one synchronisation): ValueError for an empty body
+        or random class or an unusable camera (the reference: ValueError from np.random.randint), RuntimeError for a batch still
+        short after _lib.TRAIN_RAYS_MAX_ROUNDS rounds (the reference loops for ever).  check=False leaves the device status word
+        in the dict ("status") for the caller to read when it likes."""
+        b = _lib.train_rays(img if isinstance(img, torch.Tensor) else torch.as_tensor(img), K, R, T, bounds, mask, nrays, seed,
+                            convention=convention, mask_b=mask_b, occupancy_src=occupancy_from, bound_mask_in=bound_mask,
+                            workspace=getattr(self, "_sample_ws", None))
+        self._sample_ws = b.pop("workspace")
+        status = b.pop("status")
+        batch = {k: b[k][None] for k in ("rgb", "ray_o", "ray_d", "near", "far", "coord", "mask_at_box")}
+        if b["occupancy"] is not None:
+            batch["occupancy"] = b["occupancy"][None]
+        batch["mybound_mask"] = b["bound_mask"][None]
+        batch["rounds"] = b["rounds"]
+        if not check:
+            batch["status"] = status
+            return batch
+        s = int(status)
+        if s == _lib.TRAIN_RAYS_EMPTY_CLASS:
+            raise ValueError("sample_batch: the body class or the box mask is empty (np.random.randint: low >= high)")
+        if s == _lib.TRAIN_RAYS_BAD_CAMERA:
+            raise ValueError("sample_batch: a corner of the bounds lies behind the camera or projects to nothing finite")
+        if s == _lib.TRAIN_RAYS_SHORT:
+            raise RuntimeError(f"sample_batch: fewer than {int(nrays)} rays passed the box test in {_lib.TRAIN_RAYS_MAX_ROUNDS} rounds")
+        return batch
+
     # ---- the trainer's call (reference :137-168) ----
     def render(self, batch):
         o, d = self._dev(batch["ray_o"][0]), self._dev(batch["ray_d"][0])

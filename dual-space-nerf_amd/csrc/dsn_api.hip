@@ -501,6 +501,52 @@ int dsn_camera_rays(const double* K3x3, const double* R3x3, const double* T3, co
     return dsn_check_launch("dsn_camera_rays");
 }
 
+// a training batch drawn on the device (utils/rays_utils.py:104-172, utils/h36m_utils.py:78-146; the rule is in dsnerf.h)
+static bool dsn_image_size_ok(int H, int W) { return H > 0 && W > 0 && (int64_t)H * W < ((int64_t)1 << 31); }
+
+int dsn_bound_mask(const double* K3x3, const double* R3x3, const double* T3, const double* bounds2x3, int H, int W, uint8_t* mask_out,
+                   void* stream) {
+    DSN_REQUIRE(K3x3 && R3x3 && T3 && bounds2x3 && mask_out, "dsn_bound_mask: null argument");
+    DSN_REQUIRE(H > 0 && W > 0, "dsn_bound_mask: empty image");
+    DSN_REQUIRE(dsn_image_size_ok(H, W), "dsn_bound_mask: 2^31 or more pixels");
+    dsn_launch_bound_mask(K3x3, R3x3, T3, bounds2x3, H, W, mask_out, (hipStream_t)stream);
+    return dsn_check_launch("dsn_bound_mask");
+}
+
+size_t dsn_train_rays_workspace_bytes(int H, int W, int nrays) {
+    if (!dsn_image_size_ok(H, W) || nrays < 1 || nrays > DSN_TRAIN_RAYS_MAX_RAYS) return 0;
+    return dsn_train_rays_workspace_size((int64_t)H * W, nrays);
+}
+
+int dsn_train_rays(const double* K3x3, const double* R3x3, const double* T3, const double* bounds2x3, int H, int W, int convention,
+                   const double* img_f64, const float* img_f32, const uint8_t* mask_a, const uint8_t* mask_b, const uint8_t* bound_mask_in,
+                   const uint8_t* occupancy_src, int nrays, uint32_t seed, float* ray_o, float* ray_d, float* near, float* far,
+                   int64_t* coord, float* rgb, uint8_t* occupancy, uint8_t* mask_at_box, uint8_t* bound_mask_out, int32_t* status,
+                   int32_t* rounds, void* workspace, size_t workspace_bytes, void* stream) {
+    DSN_REQUIRE(K3x3 && R3x3 && T3 && bounds2x3 && mask_a && ray_o && ray_d && near && far && coord && rgb && mask_at_box &&
+                bound_mask_out && status && rounds && workspace, "dsn_train_rays: null argument");
+    DSN_REQUIRE(H > 0 && W > 0, "dsn_train_rays: empty image");
+    DSN_REQUIRE(dsn_image_size_ok(H, W), "dsn_train_rays: 2^31 or more pixels");
+    DSN_REQUIRE(nrays >= 1 && nrays <= DSN_TRAIN_RAYS_MAX_RAYS, "dsn_train_rays: nrays must be 1 ... 65536");
+    DSN_REQUIRE(convention == DSN_RAYS_ZJU || convention == DSN_RAYS_H36M, "dsn_train_rays: unknown convention");
+    DSN_REQUIRE((img_f64 != nullptr) != (img_f32 != nullptr), "dsn_train_rays: exactly one of img_f64 / img_f32");
+    DSN_REQUIRE(convention != DSN_RAYS_H36M || mask_b, "dsn_train_rays: DSN_RAYS_H36M needs mask_b (msk_cihp)");
+    DSN_REQUIRE((occupancy != nullptr) == (occupancy_src != nullptr), "dsn_train_rays: occupancy and occupancy_src go together");
+    DSN_REQUIRE(workspace_bytes >= dsn_train_rays_workspace_size((int64_t)H * W, nrays),
+                "dsn_train_rays: workspace_bytes too small (dsn_train_rays_workspace_bytes)");
+    DSN_REQUIRE(((uintptr_t)workspace & 15) == 0, "dsn_train_rays: workspace must be 16-byte aligned");
+    DsnTrainRaysArgs a;
+    a.K = K3x3; a.R = R3x3; a.T = T3; a.bounds = bounds2x3;
+    a.H = H; a.W = W; a.convention = convention; a.nrays = nrays; a.seed = seed;
+    a.img64 = img_f64; a.img32 = img_f32;
+    a.mask_a = mask_a; a.mask_b = convention == DSN_RAYS_H36M ? mask_b : nullptr; a.bound_in = bound_mask_in; a.occ_src = occupancy_src;
+    a.ray_o = ray_o; a.ray_d = ray_d; a.near = near; a.far = far; a.rgb = rgb; a.coord = coord;
+    a.occupancy = occupancy; a.mask_at_box = mask_at_box; a.bound_out = bound_mask_out;
+    a.status = status; a.rounds = rounds; a.workspace = workspace;
+    dsn_launch_train_rays(a, (hipStream_t)stream);
+    return dsn_check_launch("dsn_train_rays");
+}
+
 // workspace carve for the fused path
 #define DSN_CELLMAJOR_MIN (1 << 20)   // below ~1 M samples the five extra launches cost more than they save (measured:
                                       // -0.12 ms at 128x128x32, +0.42 ms at 256x256x64)

@@ -125,6 +125,23 @@ struct DsnMapsArgs {
 void dsn_launch_composite_maps(const DsnMapsArgs& a, hipStream_t st);
 void dsn_launch_camera_rays(const double* K, const double* R, const double* T, const double* bounds, int H, int W,
                             float* ray_o, float* ray_d, float* near, float* far, uint8_t* mask, hipStream_t st, int h36m = 0);
+// dsn_sample.hip: a training batch drawn on the device (dsn_train_rays / dsn_bound_mask, the rule of include/dsnerf.h)
+struct DsnTrainRaysArgs {
+    const double *K, *R, *T, *bounds;
+    int H, W, convention, nrays;
+    uint32_t seed;
+    const double* img64; const float* img32;
+    const uint8_t *mask_a, *mask_b, *bound_in, *occ_src;
+    float *ray_o, *ray_d, *near, *far, *rgb;
+    int64_t* coord;
+    uint8_t *occupancy, *mask_at_box, *bound_out;
+    int32_t *status, *rounds;
+    void* workspace;
+};
+size_t dsn_train_rays_workspace_size(int64_t hw, int nrays);
+void dsn_launch_bound_mask(const double* K, const double* R, const double* T, const double* bounds, int H, int W, uint8_t* mask_out,
+                           hipStream_t st);
+void dsn_launch_train_rays(const DsnTrainRaysArgs& a, hipStream_t st);
 // dsn_field.hip
 void dsn_pack_params_host(const float* const* params33_host, float* packed_host);
 void dsn_launch_pack_params(const float* const* params33_dev_array, float* packed, hipStream_t st);

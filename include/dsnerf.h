@@ -178,6 +178,63 @@ DSN_EXPORT int dsn_composite(const float* colour, const float* sigma, const uint
 DSN_EXPORT int dsn_camera_rays(const double* K3x3, const double* R3x3, const double* T3, const double* bounds2x3, int H, int W,
                     int convention, float* ray_o, float* ray_d, float* near, float* far, uint8_t* mask_at_box, void* stream);
 
+/* ---- a training batch drawn on the device: utils/rays_utils.py:104-172 my_sample_ray (DSN_RAYS_ZJU) and
+ * utils/h36m_utils.py:78-146 sample_ray_h36m (DSN_RAYS_H36M) from an image, its masks and the camera in device memory.
+ * Not numpy's random stream and not cv2.fillPoly's outline pixels: the rule below, which tests/train_rays_restate.py restates in
+ * numpy and tests/golden/train_rays.npz pins to the reference's own two functions (run with that fill and those draws).
+ *
+ * Box mask (get_bound_2d_mask): the eight corners of `bounds` in get_bound_corners' order (corner t: x = max where t & 4, y = max
+ *   where t & 2, z = max where t & 1), cam = ((x R[c][0] + y R[c][1]) + z R[c][2]) + T[c], pix = (cam0 K[c][0] + cam1 K[c][1]) +
+ *   cam2 K[c][2], (u, v) = round-half-even(pix0 / pix2, pix1 / pix2), all float64.  The mask is the union of the six loops as the
+ *   reference writes them - {0,1,3,2} {4,5,7,6,5} {0,1,5,4} {2,3,7,6} {0,2,6,4} {1,3,7,5}, each closed from its last vertex to its
+ *   first; the second keeps the reference's closing typo and is the triangle 5-7-6 plus the segment 4-5.  Pixel (x, y) belongs to a
+ *   loop if it lies on one of its segments (cross product 0, inside the segment's box) or its winding number is non-zero (edge a->b
+ *   counts +1 when ay <= y < by and cross > 0, -1 when by <= y < ay and cross < 0, cross = (bx-ax)(y-ay) - (by-ay)(x-ax)); exact
+ *   64-bit integers.  NOT the convex hull of the rounded corners: corners round independently and the two differ by a few pixels.
+ *   A corner with camera z <= 0, pix2 <= 0, a non-finite projection or |u|, |v| >= 2^29 is an argument error; K, R, T live on the
+ *   device, so it is reported as status DSN_TRAIN_RAYS_BAD_CAMERA (dsn_bound_mask: an all-zero mask).  cv2.fillPoly additionally
+ *   paints the outline pixels of its line drawing; a caller who needs those passes its own mask as bound_mask_in (values 0 / 1).
+ * Classes, each listed in row-major pixel order (np.argwhere), b = (bound == 1):
+ *   DSN_RAYS_ZJU  (mask_a = msk_cihp):                 body mask_a != 0;  face mask_a == 2;  random b;  rgb = img[coord]
+ *   DSN_RAYS_H36M (mask_a = msk, mask_b = msk_cihp):   body b && mask_a == 1;  face mask_b == 2 (not cut by the box);
+ *                                                      random b && mask_a != 100;  rgb = b ? img[coord] : 0 (h36m_utils.py:85-88)
+ * Rounds, the reference's while loop: with rem rays missing, n_body = floor(rem 6 / 10), n_face = floor(rem 5 / 100) (= Python's
+ *   int(rem * 0.6), int(rem * 0.05) for every rem <= 70000), n_rand = rem - n_body - n_face; the face draws are left out of the round
+ *   when the face class is empty.  The drawn coordinates are body, face, random in slot order; each gets its ray and the
+ *   convention's box test (dsn_camera_rays' per-pixel rule, bit for bit), the accepted ones are appended in order; the loop ends at
+ *   rem == 0.  An empty body or random class: DSN_TRAIN_RAYS_EMPTY_CLASS (the reference raises ValueError, low >= high).  rem > 0
+ *   after DSN_TRAIN_RAYS_MAX_ROUNDS rounds: DSN_TRAIN_RAYS_SHORT (the reference would loop for ever).
+ * Draws: slot k (0-based, within its class) of class c (0 body, 1 face, 2 random) in round r (0-based) picks list entry
+ *   (h(seed, r, c, k) * count_c) >> 32 (64-bit product), with the 32-bit counter hash
+ *     mix(x): x ^= x >> 16; x *= 0x7FEB352D; x ^= x >> 15; x *= 0x846CA68B; x ^= x >> 16
+ *     h = mix(mix(seed + 0x9E3779B9 * (3 r + c)) ^ k)            (all modulo 2^32)
+ *   a pure function of its arguments: the same call gives the same batch, bit for bit.
+ * Outputs (device, n = nrays): ray_o, ray_d [n,3], near, far [n] float32 with the bits dsn_camera_rays writes for the pixel;
+ *   coord [n,2] int64 (row, col); rgb [n,3] float32 from img_f64 or img_f32 ([H,W,3]; exactly one non-NULL); occupancy [n] uint8 =
+ *   occupancy_src[coord] (both NULL or both given); mask_at_box [n] = 1; bound_mask_out [H,W] uint8 = the box mask (a copy of
+ *   bound_mask_in when given) - the batch's mybound_mask; status (int32) and rounds (int32, rounds run).  With a status other than
+ *   DSN_TRAIN_RAYS_OK the rows behind the accepted rays are zero (mask_at_box 0).
+ * mask_b is required by DSN_RAYS_H36M and ignored by DSN_RAYS_ZJU.  Rejected by the return value: null arguments, H or W <= 0,
+ * H W >= 2^31, nrays outside 1 ... DSN_TRAIN_RAYS_MAX_RAYS, an unknown convention, both or neither image pointer, occupancy
+ * without occupancy_src (or the reverse), a workspace smaller than dsn_train_rays_workspace_bytes(H, W, nrays) (0 for bad sizes) or
+ * not 16-byte aligned.  The workspace may hold anything on entry.  Kernels only: no allocation, no copy to the host, no
+ * synchronisation; no atomics. */
+#define DSN_TRAIN_RAYS_OK 0
+#define DSN_TRAIN_RAYS_EMPTY_CLASS 1
+#define DSN_TRAIN_RAYS_SHORT 2
+#define DSN_TRAIN_RAYS_BAD_CAMERA 3
+#define DSN_TRAIN_RAYS_MAX_ROUNDS 64
+#define DSN_TRAIN_RAYS_MAX_RAYS 65536
+DSN_EXPORT int dsn_bound_mask(const double* K3x3, const double* R3x3, const double* T3, const double* bounds2x3, int H, int W,
+                              uint8_t* mask_out, void* stream);
+DSN_EXPORT size_t dsn_train_rays_workspace_bytes(int H, int W, int nrays);
+DSN_EXPORT int dsn_train_rays(const double* K3x3, const double* R3x3, const double* T3, const double* bounds2x3, int H, int W,
+                              int convention, const double* img_f64, const float* img_f32, const uint8_t* mask_a, const uint8_t* mask_b,
+                              const uint8_t* bound_mask_in, const uint8_t* occupancy_src, int nrays, uint32_t seed, float* ray_o,
+                              float* ray_d, float* near, float* far, int64_t* coord, float* rgb, uint8_t* occupancy,
+                              uint8_t* mask_at_box, uint8_t* bound_mask_out, int32_t* status, int32_t* rounds, void* workspace,
+                              size_t workspace_bytes, void* stream);
+
 /* ---- image epilogue on the device ----------------------------------------------------------
  * utils/render_utils.py:466-472 post_process: row k of the compacted per-ray outputs (rgb [R,3], disp/acc/depth [R],
  * the rays of the pixels where mask_at_box is set, in pixel order) goes to the k-th masked pixel of the [H,W] images;
