@@ -879,6 +879,7 @@ static int dsn_render_frame(const void* scene, int V, int F, const void* packed,
     const bool cellmajor = !exh && N >= (int64_t)cellmajor_min;
     const bool fused_nn = cellmajor && !getenv("DSN_NN_UNFUSED");
     const bool lazy = (flags & DSN_LAZY_LISTS) != 0;
+    const bool clear_cells = fused_nn && dsn_clear_cells_on(lazy, skip);      // (read once: the list build and the search below agree)
     // a lazily set frame (DSN_FRAME_LAZY_LISTS) outside the fused cell-major path: every cell's lists, here, before anything reads them
     // (small ray batches, DSN_NN_UNFUSED, the exhaustive cross-check) - ONCE per frame: the device header says whether the level is
     // still lazy, the chunks after the first find it complete (round 5 rebuilt everything per call)
@@ -890,7 +891,8 @@ static int dsn_render_frame(const void* scene, int V, int F, const void* packed,
         dsn_launch_sample_gg(s.xyz, (flags & DSN_SAMPLE_UNIFORM) ? 0 : V, ray_o, ray_d, near, far, R, S, t_vals, jitter, z, nullptr, st,
                              s.nn_world.fine.g, (int32_t*)w.grad, counts, outside0, (int32_t*)w.grad + N);      // (+ N: every sample's rank in its cell)
         // ... and a lazily set frame gets the lists of the cells that classification found samples in (counts > 0)
-        if (lazy) dsn_launch_build_nn_visited(s.cent_world, F, s.nn_world, counts, st);
+        // (eval mode, `skip`: the search below runs with lazy_canon - cells all of whose samples are transparent get no list and no scan)
+        if (lazy) dsn_launch_build_nn_visited(s.cent_world, F, s.nn_world, counts, st, s.face_world, clear_cells);
     } else
         dsn_launch_sample_gg(s.xyz, (flags & DSN_SAMPLE_UNIFORM) ? 0 : V, ray_o, ray_d, near, far, R, S, t_vals, jitter, z, nullptr, st);
     if (skip) {
@@ -910,7 +912,7 @@ static int dsn_render_frame(const void* scene, int V, int F, const void* packed,
         } else {
             int32_t* outside = nullptr;
             dsn_launch_nn_cellmajor_warp(s.nn_world, ray_o, ray_d, z, N, S, g3, w.sort_scratch, w.nn_small, s.face_world, s.face_canon,
-                                         w.transparent, w.x_c, list, cnt, skip, &outside, st, true, lazy);
+                                         w.transparent, w.x_c, list, cnt, skip, &outside, st, true, lazy, clear_cells);
             dsn_launch_warp(s, nullptr, ray_o, ray_d, z, N, S, nullptr, nullptr, nullptr, w.transparent, w.x_c, nullptr, list, cnt, exh, st,
                             nullptr, skip, g3, outside);
         }

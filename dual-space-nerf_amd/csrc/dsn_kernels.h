@@ -50,7 +50,8 @@ void dsn_launch_nn_cellmajor(const DsnNNView& v, const float* pts, const float* 
 void dsn_launch_nn_cellmajor_warp(const DsnNNView& v, const float* ray_o, const float* ray_d, const float* z_vals, int64_t N, int S,
                                   int32_t* cell_of, void* sorted, void* small, const DsnFaceRec* face_world, const DsnFaceRec* face_canon,
                                   uint8_t* transparent, float* x_c, int32_t* active_list, int32_t* active_count, bool lazy_canon,
-                                  int32_t** outside, hipStream_t st, bool classified = false, bool lazy_call = false);
+                                  int32_t** outside, hipStream_t st, bool classified = false, bool lazy_call = false,
+                                  bool clear_cells = false);
 void dsn_launch_lbs_warp(const DsnSceneView& s, const float* pts, int64_t N, const float* smpl_w, const float* A, int bw_type,
                          int32_t* face_idx, float* weights, uint8_t* transparent, float* pts_zero, bool exhaustive, hipStream_t st);
 void dsn_launch_normal(const DsnSceneView& s, const float* x_c, const float* grad, int64_t N,
@@ -60,7 +61,9 @@ void dsn_launch_normal(const DsnSceneView& s, const float* x_c, const float* gra
 void dsn_launch_build_nn(const float4* cent, int F, const DsnNNView& nn, float pad_fine, float pad_coarse, hipStream_t st,
                          bool fine_only = false, bool dense_fine = false, bool lazy = false);
 // the lists of a lazy fine level for the cells with visited[cell] > 0 (no-op on a level that holds every cell's lists)
-void dsn_launch_build_nn_visited(const float4* cent, int F, const DsnNNView& nn, const int32_t* visited, hipStream_t st);
+void dsn_launch_build_nn_visited(const float4* cent, int F, const DsnNNView& nn, const int32_t* visited, hipStream_t st,
+                                 const DsnFaceRec* face_world = nullptr, bool clear_cells = false);
+bool dsn_clear_cells_on(bool lazy_call, bool lazy_canon);      // the clear-cell flags of a lazily built level: written and read by this call?
 // a lazily set fine level completed for every cell - decided on the device: no-op sweeps once the level is complete
 void dsn_launch_build_nn_complete(const float4* cent, int F, const DsnNNView& nn, hipStream_t st);
 void dsn_launch_composite(const float* colour, const float* sigma, const uint8_t* transparent, const float* z_vals,

@@ -59,6 +59,9 @@ struct DsnGridView {        // one level
     float4* super_list;     // [maxsuper][DSN_SUPER_CAP] supersets, ascending face order
     unsigned long long* member;   // [maxcell][DSN_SUPER_CAP / 64] (fine level only): which entries of its super-cell's superset a cell's list
                                   // holds, one bit per entry - k_grid_count leaves them for k_grid_fill (no third sweep of the superset)
+    uint8_t* clear;         // [maxcell] (fine level only, 64 KB): 1 = every point of the cell's guarded box is transparent whichever member of
+                            // L(B) is its nearest face - written by the lazy build of a fused eval frame (k_grid_count, dsn_face_clears_box);
+                            // such a cell has an empty list and k_nns_search<true> does not scan for its samples
 };
 __host__ __device__ inline int dsn_grid_maxsuper(int maxcell) { return maxcell / 32; }   // grids with more super-cells (very thin ones) build unaccelerated
 struct DsnNNView { DsnGridView fine, coarse; };
@@ -69,7 +72,7 @@ __host__ __device__ inline size_t dsn_grid_bytes(int maxcell, int cap, int entry
     if (entry_bytes == 16)
         b += dsn_align256(sizeof(int32_t) * (size_t)maxcell) +
              dsn_align256(sizeof(float) * 4 * (size_t)dsn_grid_maxsuper(maxcell) * DSN_SUPER_CAP) +
-             dsn_align256(8 * (size_t)(DSN_SUPER_CAP / 64) * (size_t)maxcell);
+             dsn_align256(8 * (size_t)(DSN_SUPER_CAP / 64) * (size_t)maxcell) + dsn_align256((size_t)maxcell);
     return b;
 }
 __host__ __device__ inline DsnGridView dsn_grid_view(char*& p, int maxcell, int cap, int entry_bytes) {
@@ -81,10 +84,12 @@ __host__ __device__ inline DsnGridView dsn_grid_view(char*& p, int maxcell, int 
     v.super_cnt = nullptr;
     v.super_list = nullptr;
     v.member = nullptr;
+    v.clear = nullptr;
     if (entry_bytes == 16) {
         v.super_cnt = (int32_t*)p;  p += dsn_align256(sizeof(int32_t) * (size_t)maxcell);
         v.super_list = (float4*)p;  p += dsn_align256(sizeof(float) * 4 * (size_t)dsn_grid_maxsuper(maxcell) * DSN_SUPER_CAP);
         v.member = (unsigned long long*)p;  p += dsn_align256(8 * (size_t)(DSN_SUPER_CAP / 64) * (size_t)maxcell);
+        v.clear = (uint8_t*)p;      p += dsn_align256((size_t)maxcell);
     }
     return v;
 }

@@ -167,24 +167,96 @@ __device__ __forceinline__ const float4* dsn_cell_source(const DsnGrid& g, int c
     return super_list + (size_t)sb * DSN_SUPER_CAP;
 }
 
+// Clear cells.  The fused eval search (k_nns_search<true> with lazy_canon) writes transparent = 1, x_c = 0 and no list entry
+// for a sample whose nearest face f has  |h| > 0.1  or  u outside [-4, 5]  or  v outside [-4, 5]  (dsn_project): which face it was does
+// not reach the result.  The nearest face of every point of a cell's guarded box B is a member of L(B), so if EVERY member puts ALL
+// of B outside one of the three ranges, every sample of the cell is transparent and its scan is work nobody reads.
+// dsn_project is affine in p.  With the face's stored record (no orthogonality of n, v10, v20 is assumed - only the stored numbers):
+//     h(p) = n . t,                      t = p - m0
+//     w    = t - n (n . t)               (q - m0 of dsn_project)
+//     u(p) = inv (d11 v20 - d01 v10) . w = gu . t,     gu = inv (d11 a - d01 b),   a = v20 - (v20 . n) n,  b = v10 - (v10 . n) n
+//     v(p) = inv (d00 v10 - d01 v20) . w = gv . t,     gv = inv (d00 b - d01 a)
+// so over B = centre c +- half each of them lies in  value(c) +- sum_i |g_i| half_i.  value(c) is dsn_project's own float32 result.
+// Margins.  eps = 2^-24; with P_i = |c_i| + half_i + |m0_i| >= |p_i| + |m0_i| >= |t_i| and  H = sum_i |n_i| P_i >= |n . t|,  dsn_project's float32 steps give
+//     |fl(h) - h| <= 4 eps H                              (t_i rounded once; three products, two sums)
+//     |fl(w_i) - w_i| <= 8 eps W_i,  W_i = P_i + |n_i| H >= |w_i|              (n_i sd, q_i, w_i: one rounding each, + 4 eps H |n_i| from sd)
+//     |fl(d02) - d02| <= 11 eps E20, E20 = sum_i |v20_i| W_i >= |d02|;   the same for d12 with E10 = sum_i |v10_i| W_i
+//     |fl(u) - u| <= 15 eps |inv| (|d11| E20 + |d01| E10),   |fl(v) - v| <= 15 eps |inv| (|d00| E10 + |d01| E20)
+// for the sample's evaluation, the same again for value(c) here, and a few eps of the radius (its terms are bounded by the same sums):
+// under 40 eps in all.  The margins below are 128 eps = 2^-17 of those magnitudes (for h: 2^-17 H against 8 eps H), more than three times that.
+// A record that is not finite makes a margin or a value NaN / inf and every comparison below false for u and v; dsn_project then
+// answers NaN u / v as well and the kernel's own test reduces to |h| > 0.1, which is what is left here.  A face whose inv exceeds
+// 1e12 (area^2 below 1e-12 m^4: the products in front of it may underflow, which the bound above does not cover) passes through |h| only.
+#define DSN_CLEAR_MARGIN 7.62939453125e-6f      // 2^-17
+#define DSN_CLEAR_INV_MAX 1e12f
+// Cells whose U(B)^2 is below this do not start the walk (they stay unflagged, which is always right).  The face g that attains U(B) is a
+// member, and its centroid lies within U(B) of every point of B: it clears B through |h| only if U(B) > 0.1.  Below that a cell could
+// still pass through u / v of EVERY member (lateral distances of 4-5 edge lengths to all of them); on the bench frame none does - the
+// smallest U(B)^2 of a flagged cell is 0.031 (both bodies; 0.030 with twinned faces), while 5 300 of the 25 043 visited cells lie below
+// 0.01 and would each walk one round for nothing (profiles/nns_transparent_fraction.txt).
+#ifndef DSN_CLEAR_MIN_U2
+#define DSN_CLEAR_MIN_U2 0.01f
+#endif
+__device__ __forceinline__ bool dsn_face_clears_box(const DsnFaceRec& f, const float* c, const float* half) {
+    float u, v, h;
+    dsn_project(c, f, u, v, h);
+    float P[3], W[3], a[3], b[3];
+    const float an = dsn_dot3(f.v20, f.n), bn = dsn_dot3(f.v10, f.n);
+    float H = 0.f, rh = 0.f;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        P[i] = fabsf(c[i]) + half[i] + fabsf(f.m0[i]);
+        H += fabsf(f.n[i]) * P[i];
+        rh += fabsf(f.n[i]) * half[i];
+        a[i] = f.v20[i] - an * f.n[i];
+        b[i] = f.v10[i] - bn * f.n[i];
+    }
+    if (fabsf(h) - rh - DSN_CLEAR_MARGIN * H > 0.1f) return true;                  // (NaN: false)
+    if (!(fabsf(f.inv) <= DSN_CLEAR_INV_MAX)) return false;
+    float E20 = 0.f, E10 = 0.f, ru = 0.f, rv = 0.f;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        W[i] = P[i] + fabsf(f.n[i]) * H;
+        E20 += fabsf(f.v20[i]) * W[i];
+        E10 += fabsf(f.v10[i]) * W[i];
+        ru += fabsf(f.d11 * a[i] - f.d01 * b[i]) * half[i];
+        rv += fabsf(f.d00 * b[i] - f.d01 * a[i]) * half[i];
+    }
+    const float ai = fabsf(f.inv);
+    const float mu = DSN_CLEAR_MARGIN * ai * (fabsf(f.d11) * E20 + fabsf(f.d01) * E10) + ai * ru;
+    const float mv = DSN_CLEAR_MARGIN * ai * (fabsf(f.d00) * E10 + fabsf(f.d01) * E20) + ai * rv;
+    return (u - mu > 5.f) || (u + mu < -4.f) || (v - mv > 5.f) || (v + mv < -4.f);      // (NaN / inf margins: false)
+}
+
 #ifndef DSN_GRID_U
 #define DSN_GRID_U 4
 #endif
 // pass 1+2: U(B)^2 and the list length of every cell (one wavefront per cell)
-__global__ void __launch_bounds__(256) k_grid_count(const float4* __restrict__ cent_all, int F_all, const DsnGrid* __restrict__ gp,
+// CLEAR = true (the lazy build of a fused eval frame only, dsn_launch_build_nn_visited): the clear-cell pass behind the second sweep;
+// every other build launches CLEAR = false, the kernel as it was.
+// (amdgpu_waves_per_eu(8): the sweeps are latency-bound and live on eight waves per SIMD - the clear-cell walk fits their 64 registers;
+//  CLEAR = false needs 34)
+template <bool CLEAR>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) k_grid_count(const float4* __restrict__ cent_all, int F_all, const DsnGrid* __restrict__ gp,
                                                      float* __restrict__ u2, int32_t* __restrict__ offsets, int maxsuper,
                                                      const int32_t* __restrict__ super_cnt, const float4* __restrict__ super_list,
                                                      const int32_t* __restrict__ visited, int lazy_build,
-                                                     unsigned long long* __restrict__ member) {
+                                                     unsigned long long* __restrict__ member,
+                                                     uint8_t* __restrict__ clear, const DsnFaceRec* __restrict__ face) {
     // member (optional): the membership bits of the second sweep, 64 entries of the superset per word - k_grid_fill places the entries
     // from them instead of sweeping the superset a third time (cells that sweep the whole table have no words: they are swept again)
+    // clear / face (CLEAR only): the clear-cell flag of every cell of the level is written here - a flagged cell's count is 0
+    // (k_grid_fill writes nothing for it)
     const DsnGrid g = *gp;
-    if (lazy_build && !g.lazy) return;
     const int lane = threadIdx.x & 63;
     const int cell = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (lazy_build && !g.lazy) {              // (the level holds every cell's lists already: no cell is skipped by the search)
+        if (CLEAR && lane == 0 && cell < g.ncell) clear[cell] = 0;
+        return;
+    }
     if (cell >= g.ncell) return;
     if (visited && visited[cell] <= 0) {      // (lazy build: a cell no sample of the frame lies in gets an empty list)
-        if (lane == 0) offsets[cell + 1] = 0;
+        if (lane == 0) { offsets[cell + 1] = 0; if (CLEAR) clear[cell] = 0; }
         return;
     }
     float blo[3], bhi[3];
@@ -207,6 +279,12 @@ __global__ void __launch_bounds__(256) k_grid_count(const float4* __restrict__ c
     for (int o = 32; o >= 1; o >>= 1) m = fminf(m, __shfl_xor(m, o));
     int cnt = 0;
     unsigned long long* __restrict__ mw = (member && cent != cent_all) ? member + (size_t)cell * (DSN_SUPER_CAP / 64) : nullptr;
+    // clear-cell pass: lane j keeps word j of the second sweep's membership bits in a register (a superset has at most DSN_SUPER_CAP =
+    // 64 x 64 entries), so that the walk below reads members only - a handful of rounds of 64 instead of the ~31 of the superset, with
+    // neither LDS nor a pass over memory.  A cell that sweeps the whole table (no usable superset) stays unflagged.
+    static_assert(DSN_SUPER_CAP == 64 * 64, "one membership word per lane");
+    unsigned long long mine = 0ull;
+    const bool want_clear = CLEAR && m >= DSN_CLEAR_MIN_U2 && F <= DSN_SUPER_CAP;      // (wave-uniform; a NaN bound: no walk)
     for (int f0 = 0; f0 < F; f0 += 64 * GRID_U) {
         float4 c[GRID_U];
 #pragma unroll
@@ -216,9 +294,48 @@ __global__ void __launch_bounds__(256) k_grid_count(const float4* __restrict__ c
             const int fb = f0 + 64 * u;                  // (wave-uniform)
             const bool in = fb + lane < F && dsn_in_list(dsn_box_dmin2(c[u], blo, bhi), m);
             const unsigned long long mk = __ballot(in);
+            if (CLEAR && want_clear && lane == (fb >> 6)) mine = mk;
             cnt += __popcll(mk);
             if (mw && lane == 0 && fb < F) mw[fb >> 6] = mk;
         }
+    }
+    if (CLEAR) {
+        // the members, 64 per round: lane l of a round takes member k = k0 + l of the list - the word that holds it (the largest w whose
+        // members in front, front[w], are <= k: binary lifting over the lanes' values) and its bit in that word (rank select by halves).
+        // The first member that does not clear the box ends the walk (cells near the body leave in the first round).
+        bool is_clear = want_clear && cnt > 0;
+        if (is_clear) {
+            float cc[3], half[3];
+#pragma unroll
+            for (int i = 0; i < 3; ++i) { cc[i] = 0.5f * (blo[i] + bhi[i]); half[i] = 0.5f * (bhi[i] - blo[i]) + 2.4e-7f * (fabsf(blo[i]) + fabsf(bhi[i])); }   // (+ 4 eps: the rounding of the two)
+            const int pc = __popcll(mine);
+            int inc = pc;
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) { const int x = __shfl_up(inc, o); if (lane >= o) inc += x; }
+            const int front = inc - pc;                  // (lane 63's inc = cnt: every word of the sweep is some lane's)
+            for (int k0 = 0; k0 < cnt; k0 += 64) {
+                const bool on = k0 + lane < cnt;
+                const int k = on ? k0 + lane : cnt - 1;  // (every lane takes part in the shuffles)
+                int w = 0;
+#pragma unroll
+                for (int s = 32; s >= 1; s >>= 1) { const int fv = __shfl(front, w + s); if (fv <= k) w += s; }
+                unsigned long long x = __shfl(mine, w);
+                int r = k - __shfl(front, w), bit = 0;   // 0 <= r < popcount(x)
+#pragma unroll
+                for (int sh = 32; sh >= 1; sh >>= 1) {
+                    const int below = __popcll(x & ((1ull << sh) - 1ull));
+                    if (r >= below) { r -= below; x >>= sh; bit += sh; }
+                }
+                bool bad = false;
+                if (on) {
+                    const int fi = __float_as_int(cent[(w << 6) + bit].w);      // ((w << 6) + bit < F: a set bit of the sweep)
+                    bad = !((unsigned)fi < (unsigned)F_all) || !dsn_face_clears_box(dsn_load_face(face, fi), cc, half);
+                }
+                if (__ballot(bad)) { is_clear = false; break; }
+            }
+        }
+        if (lane == 0) clear[cell] = is_clear ? 1 : 0;
+        if (is_clear) cnt = 0;
     }
     if (lane == 0) { u2[cell] = m; offsets[cell + 1] = cnt; }
 }
@@ -294,13 +411,15 @@ __global__ void __launch_bounds__(256) k_grid_fill(const float4* __restrict__ ce
                                                     const float* __restrict__ u2, const int32_t* __restrict__ offsets,
                                                     void* __restrict__ list, int maxsuper, const int32_t* __restrict__ super_cnt,
                                                     const float4* __restrict__ super_list, const int32_t* __restrict__ visited, int lazy_build,
-                                                    const unsigned long long* __restrict__ member) {
+                                                    const unsigned long long* __restrict__ member,
+                                                    const uint8_t* __restrict__ clear = nullptr) {
     const DsnGrid g = *gp;
     if (lazy_build ? g.lazy != (lazy_build == 2 ? 3 : 2) : !g.ok) return;
     const int lane = threadIdx.x & 63;
     const int cell = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (cell >= g.ncell) return;
     if (visited && visited[cell] <= 0) return;
+    if (clear && clear[cell]) return;         // (a clear cell's list is empty: k_grid_count, its membership words notwithstanding)
     int F;
     const float4* __restrict__ cent = dsn_cell_source(g, cell, cent_all, F_all, maxsuper, super_cnt, super_list, F);
     int base = offsets[cell];
@@ -380,8 +499,8 @@ static void dsn_build_level(const float4* cent, int F, const DsnGridView& v, flo
     const int32_t* none = nullptr;
     if (vv.super_cnt)
         hipLaunchKernelGGL(k_grid_super, dim3(maxsuper), dim3(256), 0, st, cent, F, v.g, maxsuper, vv.super_cnt, vv.super_list, none, 0);
-    hipLaunchKernelGGL(k_grid_count, dim3((maxcell + 3) / 4), dim3(256), 0, st, cent, F, v.g, v.u2, v.offsets, maxsuper,
-                       (const int32_t*)vv.super_cnt, (const float4*)vv.super_list, none, 0, dsn_member_words(vv));
+    hipLaunchKernelGGL(k_grid_count<false>, dim3((maxcell + 3) / 4), dim3(256), 0, st, cent, F, v.g, v.u2, v.offsets, maxsuper,
+                       (const int32_t*)vv.super_cnt, (const float4*)vv.super_list, none, 0, dsn_member_words(vv), (uint8_t*)nullptr, (const DsnFaceRec*)nullptr);
     dsn_launch_grid_scan(v, maxcell, 0, st);
     if (inline_entries)
         hipLaunchKernelGGL(k_grid_fill<true>, dim3((maxcell + 3) / 4), dim3(256), 0, st, cent, F, v.g, v.u2, v.offsets, v.list,
@@ -396,19 +515,31 @@ static void dsn_build_level(const float4* cent, int F, const DsnGridView& v, flo
 // same sweeps, same lists entry for entry as the full build - for fewer cells: a 512 x 512 frame's samples visit 48 % of the posed
 // mesh's fine cells, an eighth of its rays (a rank's block of a partitioned frame) a tenth.  No-ops on a level that holds every
 // cell's lists (lazy = 0).
-void dsn_launch_build_nn_visited(const float4* cent, int F, const DsnNNView& nn, const int32_t* visited, hipStream_t st) {
+// clear_cells: the call is the fused eval path with lazy_canon (dsn_clear_cells_on) - k_grid_count also decides which visited cells are
+// clear (dsn_face_clears_box over their members, face_world); those get an empty list and k_nns_search<true> no scan.
+// DSN_NN_NO_CLEAR_CELLS=1 (cross-check / A-B switch): no flags, every visited cell's list, every sample scanned.
+bool dsn_clear_cells_on(bool lazy_call, bool lazy_canon) { return lazy_call && lazy_canon && getenv("DSN_NN_NO_CLEAR_CELLS") == nullptr; }
+void dsn_launch_build_nn_visited(const float4* cent, int F, const DsnNNView& nn, const int32_t* visited, hipStream_t st,
+                                 const DsnFaceRec* face_world, bool clear_cells) {
     const DsnGridView& v = nn.fine;
+    uint8_t* const clear = (clear_cells && face_world) ? v.clear : nullptr;
     const int maxcell = DSN_NN_FINE_MAXCELL, maxsuper = dsn_grid_maxsuper(maxcell);
     DsnGridView vv = v;
     if (getenv("DSN_NN_NO_SUPER")) vv.super_cnt = nullptr;
     if (getenv("DSN_LAZY_ALL_CELLS")) visited = nullptr;      // (cross-check switch: the lazy build for every cell)
     if (vv.super_cnt)
         hipLaunchKernelGGL(k_grid_super, dim3(maxsuper), dim3(256), 0, st, cent, F, v.g, maxsuper, vv.super_cnt, vv.super_list, visited, 1);
-    hipLaunchKernelGGL(k_grid_count, dim3((maxcell + 3) / 4), dim3(256), 0, st, cent, F, v.g, v.u2, v.offsets, maxsuper,
-                       (const int32_t*)vv.super_cnt, (const float4*)vv.super_list, visited, 1, dsn_member_words(vv));
+    if (clear)
+        hipLaunchKernelGGL(k_grid_count<true>, dim3((maxcell + 3) / 4), dim3(256), 0, st, cent, F, v.g, v.u2, v.offsets, maxsuper,
+                           (const int32_t*)vv.super_cnt, (const float4*)vv.super_list, visited, 1, dsn_member_words(vv), clear, face_world);
+    else
+        hipLaunchKernelGGL(k_grid_count<false>, dim3((maxcell + 3) / 4), dim3(256), 0, st, cent, F, v.g, v.u2, v.offsets, maxsuper,
+                           (const int32_t*)vv.super_cnt, (const float4*)vv.super_list, visited, 1, dsn_member_words(vv), (uint8_t*)nullptr,
+                           (const DsnFaceRec*)nullptr);
     dsn_launch_grid_scan(v, maxcell, 1, st);
     hipLaunchKernelGGL(k_grid_fill<true>, dim3((maxcell + 3) / 4), dim3(256), 0, st, cent, F, v.g, v.u2, v.offsets, v.list,
-                       maxsuper, (const int32_t*)vv.super_cnt, (const float4*)vv.super_list, visited, 1, (const unsigned long long*)dsn_member_words(vv));
+                       maxsuper, (const int32_t*)vv.super_cnt, (const float4*)vv.super_list, visited, 1, (const unsigned long long*)dsn_member_words(vv),
+                       (const uint8_t*)clear);
 }
 
 // A lazily set level completed for EVERY cell (a lazily set frame rendered outside the fused cell-major path: small ray batches,
@@ -426,8 +557,8 @@ void dsn_launch_build_nn_complete(const float4* cent, int F, const DsnNNView& nn
     const int32_t* none = nullptr;
     if (vv.super_cnt)
         hipLaunchKernelGGL(k_grid_super, dim3(maxsuper), dim3(256), 0, st, cent, F, v.g, maxsuper, vv.super_cnt, vv.super_list, none, 2);
-    hipLaunchKernelGGL(k_grid_count, dim3((maxcell + 3) / 4), dim3(256), 0, st, cent, F, v.g, v.u2, v.offsets, maxsuper,
-                       (const int32_t*)vv.super_cnt, (const float4*)vv.super_list, none, 2, dsn_member_words(vv));
+    hipLaunchKernelGGL(k_grid_count<false>, dim3((maxcell + 3) / 4), dim3(256), 0, st, cent, F, v.g, v.u2, v.offsets, maxsuper,
+                       (const int32_t*)vv.super_cnt, (const float4*)vv.super_list, none, 2, dsn_member_words(vv), (uint8_t*)nullptr, (const DsnFaceRec*)nullptr);
     dsn_launch_grid_scan(v, maxcell, 2, st);
     hipLaunchKernelGGL(k_grid_fill<true>, dim3((maxcell + 3) / 4), dim3(256), 0, st, cent, F, v.g, v.u2, v.offsets, v.list,
                        maxsuper, (const int32_t*)vv.super_cnt, (const float4*)vv.super_list, none, 2, (const unsigned long long*)dsn_member_words(vv));
@@ -674,6 +805,7 @@ __global__ void __launch_bounds__(NNS_THREADS) k_nns_scatter_ranked(int32_t* __r
 struct NnsWarp {
     const DsnFaceRec* face_world; const DsnFaceRec* face_canon; uint8_t* transparent; float* x_c; int32_t* active_list;
     int32_t* active_count; int lazy_canon;
+    const uint8_t* clear;      // (optional) the clear-cell flags THIS call's lazy list build wrote (DsnGridView::clear): no scan for their samples
 };
 // (amdgpu_waves_per_eu(8): the register budget of eight waves per SIMD, 64 - what the 20 KB of LDS per workgroup allow as well)
 template <bool WARP>
@@ -698,6 +830,10 @@ __global__ void __launch_bounds__(NNS_THREADS) __attribute__((amdgpu_waves_per_e
     if (WARP ? (int)(vb * (NNS_THREADS / 64)) >= nwaves : w >= nwaves) return;      // (WARP: block-uniform - the append below has barriers)
     const bool wave_on = w < nwaves;
     const int c = __builtin_amdgcn_readfirstlane(wave_cell[wave_on ? w : 0]);
+    // a wave of a clear cell (WARP with lazy_canon only; wave-uniform): no pruning, no scan, no face record - its samples get below
+    // what the scan would have ended in for every member of the (empty) list, transparent = 1 and x_c = 0
+    bool clear_cell = false;
+    if (WARP) clear_cell = wp.clear && wave_on && __builtin_amdgcn_readfirstlane((int)wp.clear[c]) != 0;
     // TWO samples per lane (slots lane and lane + 64 of the wave's 128): the distance arithmetic runs on packed fp32
     // (v_pk_add / v_pk_mul / v_pk_fma_f32 with the candidate broadcast from SGPRs: 6 instructions per candidate and PAIR of samples
     // instead of 12 - the same IEEE operations per component, so the same distances bit for bit); the minimum is kept per sample, the
@@ -750,7 +886,8 @@ __global__ void __launch_bounds__(NNS_THREADS) __attribute__((amdgpu_waves_per_e
     float4* const surv = s_surv[__builtin_amdgcn_readfirstlane(threadIdx.x >> 6)];
 #endif
     int k = 0;
-    if (!WARP && cent) {
+    if (clear_cell) {
+    } else if (!WARP && cent) {
         const int32_t* __restrict__ ids = reinterpret_cast<const int32_t*>(list_f) + o;
         auto at = [&](int f) { float4 a = cent[f]; a.w = __int_as_float(f); return a; };
         auto entry = [&](int p) { return p < n ? at(ids[p]) : dsn_blk_pad(); };      // pass 2: a lane's own read of list entry p
@@ -964,14 +1101,18 @@ __global__ void __launch_bounds__(NNS_THREADS) __attribute__((amdgpu_waves_per_e
     for (int h2 = 0; h2 < 2; ++h2) {
         idx[h2] = (int64_t)__float_as_int(q[h2].w);
         if (valid[h2]) {
-            const float p[3] = {px[h2], py[h2], pz[h2]};
-            const DsnFaceRec fw = dsn_load_face(wp.face_world, bi[h2]);
-            float u, v, h, xc[3] = {0.f, 0.f, 0.f};
-            dsn_project(p, fw, u, v, h);
-            const bool tr = (u > 5.f) || (u < -4.f) || (v > 5.f) || (v < -4.f) || (fabsf(h) > 0.1f);
-            if (!(tr && wp.lazy_canon)) {
-                const DsnFaceRec fc = dsn_load_face(wp.face_canon, bi[h2]);
-                dsn_map2face(u, v, h, fc, xc);
+            float xc[3] = {0.f, 0.f, 0.f};
+            bool tr = true;
+            if (!clear_cell) {                     // (wave-uniform)
+                const float p[3] = {px[h2], py[h2], pz[h2]};
+                const DsnFaceRec fw = dsn_load_face(wp.face_world, bi[h2]);
+                float u, v, h;
+                dsn_project(p, fw, u, v, h);
+                tr = (u > 5.f) || (u < -4.f) || (v > 5.f) || (v < -4.f) || (fabsf(h) > 0.1f);
+                if (!(tr && wp.lazy_canon)) {
+                    const DsnFaceRec fc = dsn_load_face(wp.face_canon, bi[h2]);
+                    dsn_map2face(u, v, h, fc, xc);
+                }
             }
             const int64_t i = idx[h2];
             wp.transparent[i] = tr ? 1 : 0;
@@ -1013,7 +1154,7 @@ __global__ void __launch_bounds__(NNS_THREADS) __attribute__((amdgpu_waves_per_e
 void dsn_launch_nn_cellmajor_warp(const DsnNNView& v, const float* ray_o, const float* ray_d, const float* z_vals, int64_t N, int S,
                                   int32_t* cell_of, void* sorted, void* small, const DsnFaceRec* face_world, const DsnFaceRec* face_canon,
                                   uint8_t* transparent, float* x_c, int32_t* active_list, int32_t* active_count, bool lazy_canon,
-                                  int32_t** outside, hipStream_t st, bool classified, bool lazy_call) {
+                                  int32_t** outside, hipStream_t st, bool classified, bool lazy_call, bool clear_cells) {
     // classified: the sampler has filled cell_of / counts / the outside counter already (dsn_nn_cellmajor_begin + dsn_launch_sample_gg)
     char* q = (char*)small;
     int32_t* counts = (int32_t*)q;     q += dsn_align256(4 * (size_t)(DSN_NN_FINE_MAXCELL + 1));
@@ -1047,7 +1188,9 @@ void dsn_launch_nn_cellmajor_warp(const DsnNNView& v, const float* ray_o, const 
         hipLaunchKernelGGL(k_nns_scatter, gN, b, 0, st, cell_of, (const float*)nullptr, ray_o, ray_d, z_vals, N, S, offs, counts, (float4*)sorted,
                            (const DsnGrid*)v.fine.g, cell_of, totals + 2, lc);
     const int64_t max_waves = N / NNS_PER + DSN_NN_FINE_MAXCELL + 1;
-    const NnsWarp wp = {face_world, face_canon, transparent, x_c, active_list, active_count, lazy_canon ? 1 : 0};
+    // clear_cells: THIS call's lazy list build wrote the clear-cell flags (the caller read dsn_clear_cells_on once, for both launches)
+    const NnsWarp wp = {face_world, face_canon, transparent, x_c, active_list, active_count, lazy_canon ? 1 : 0,
+                        (clear_cells && lazy_call && lazy_canon) ? (const uint8_t*)v.fine.clear : (const uint8_t*)nullptr};
     hipLaunchKernelGGL(k_nns_search<true>, dim3((unsigned)((max_waves + 3) / 4)), b, 0, st, v.fine.offsets, (const float4*)v.fine.list,
                        wave_cell, wave_offs, totals, offs, counts, (const float4*)sorted, (int32_t*)nullptr, wp, (const float4*)nullptr);
 }
