@@ -49,6 +49,7 @@ EXPORTS = [
     "dsn_raster_workspace_bytes", "dsn_raster_mesh", "dsn_raster_mesh_ex", "dsn_mc_normals", "dsn_raster_mesh_attr",
     "dsn_mesh_cc_workspace_bytes", "dsn_mesh_cc_label", "dsn_mesh_cc_emit", "dsn_mesh_cc_label_ex", "dsn_mesh_cc_emit_ex",
     "dsn_bound_mask", "dsn_train_rays_workspace_bytes", "dsn_train_rays",
+    "dsn_mesh_bind_normals", "dsn_mesh_pose_workspace_bytes", "dsn_mesh_pose", "dsn_mesh_stretch",
 ]
 
 SKIP_TRANSPARENT = 1
@@ -137,6 +138,11 @@ def lib():
         L.dsn_train_rays_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
         L.dsn_train_rays.argtypes = ([C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 6 + [C.c_int, C.c_uint32]
                                      + [C.c_void_p] * 12 + [C.c_size_t, C.c_void_p])
+        L.dsn_mesh_bind_normals.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+        L.dsn_mesh_pose_workspace_bytes.restype = C.c_size_t
+        L.dsn_mesh_pose_workspace_bytes.argtypes = [C.c_int, C.c_int]
+        L.dsn_mesh_pose.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_int64] + [C.c_void_p] * 5
+        L.dsn_mesh_stretch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
         if L.dsn_abi_version() != 8:
             raise RuntimeError(f"{LIB_PATH} has ABI version {L.dsn_abi_version()}, this binding needs 8 - rebuild it "
                                "(python dual-space-nerf_amd/build.py)")
@@ -751,6 +757,88 @@ def largest_component(verts, faces, want_source=True, info=None):
     if info is not None:
         info.update(n_components=n, winner=winner, area=math.ldexp(float(s), -shift - 1), faces_in_winner=fw, area_shift=shift)
     return out_v, out_f, src
+
+
+MESH_POSE_BAD_BINDING = 1    # DSN_MESH_POSE_BAD_BINDING: dsn_mesh_pose's status bit
+
+
+def _body_faces(body_faces, device):
+    return body_faces.to(device=device, dtype=torch.int32).reshape(-1, 3).contiguous()
+
+
+def mesh_bind_normals(body_xyz, body_faces, face_idx, normals):
+    """dsn_mesh_bind_normals (the rule of include/dsnerf.h): the covectors cov [N,3] of normals [N,3] at mesh vertices bound to faces
+    face_idx [N] of the posed body (body_xyz [Vb,3], body_faces [Fb,3]) - what dsn_mesh_pose carries to another pose.  Device
+    tensors in, a device tensor out."""
+    require_gpu()
+    dev = normals.device
+    body_xyz = _f32(body_xyz, dev).reshape(-1, 3)
+    body_faces = _body_faces(body_faces, dev)
+    face_idx = face_idx.to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
+    normals = _f32(normals, dev).reshape(-1, 3)
+    N = face_idx.shape[0]
+    if normals.shape[0] != N:
+        raise ValueError(f"mesh_bind_normals: {normals.shape[0]} normals for {N} bound vertices")
+    cov = torch.empty(N, 3, dtype=torch.float32, device=dev)
+    _check(lib().dsn_mesh_bind_normals(_ptr(body_xyz), body_xyz.shape[0], _ptr(body_faces), body_faces.shape[0],
+                                       _ptr(face_idx) if N else None, _ptr(normals) if N else None, N, _ptr(cov) if N else None, _stream()),
+           "dsn_mesh_bind_normals")
+    return cov
+
+
+def mesh_pose(binding, body_faces, target_xyz):
+    """dsn_mesh_pose (the rule of include/dsnerf.h): the bound vertices of `binding` ({"face_idx" [N] int32, "uv" [N,2], "h" [N],
+    "cov" [N,3] or None / absent}: dsn_warp's record per vertex, mesh_bind_normals' covectors) under the bodies target_xyz [P,Vb,3] of
+    the topology body_faces [Fb,3].  Returns {"verts" [P,N,3], "normals" [P,N,3] (None without cov),
+    "status": an int32 device tensor whose word 0 has MESH_POSE_BAD_BINDING set when a face_idx lay outside [0, Fb) (NaN rows there;
+    not read back here)}."""
+    require_gpu()
+    dev = binding["face_idx"].device
+    target_xyz = _f32(target_xyz, dev)
+    if target_xyz.dim() != 3 or target_xyz.shape[2] != 3:
+        raise ValueError(f"mesh_pose: target_xyz must be [P,Vb,3], got {tuple(target_xyz.shape)}")
+    P, Vb = target_xyz.shape[0], target_xyz.shape[1]
+    body_faces = _body_faces(body_faces, dev)
+    Fb = body_faces.shape[0]
+    face_idx = binding["face_idx"].to(dtype=torch.int32).reshape(-1).contiguous()
+    N = face_idx.shape[0]
+    uv, h = _f32(binding["uv"], dev).reshape(-1, 2), _f32(binding["h"], dev).reshape(-1)
+    cov = binding.get("cov")
+    cov = None if cov is None else _f32(cov, dev).reshape(-1, 3)
+    if uv.shape[0] != N or h.shape[0] != N or (cov is not None and cov.shape[0] != N):
+        raise ValueError(f"mesh_pose: the binding's uv / h / cov do not have {N} rows")
+    nbytes = lib().dsn_mesh_pose_workspace_bytes(P, Fb)
+    if nbytes == 0:
+        raise RuntimeError(f"dsn_mesh_pose: bad sizes (P = {P} poses of {Fb} body faces)")
+    ws = _scratch(nbytes, dev)
+    verts = torch.empty(P, N, 3, dtype=torch.float32, device=dev)
+    normals = torch.empty(P, N, 3, dtype=torch.float32, device=dev) if cov is not None else None
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    n = bool(N)
+    _check(lib().dsn_mesh_pose(_ptr(target_xyz), P, Vb, _ptr(body_faces), Fb, _ptr(face_idx) if n else None, _ptr(uv) if n else None,
+                               _ptr(h) if n else None, _ptr(cov) if n else None, N, _ptr(verts) if n else None,
+                               _ptr(normals) if n else None, _ptr(status), _ptr(ws), _stream()), "dsn_mesh_pose")
+    return {"verts": verts, "normals": normals, "status": status}
+
+
+def mesh_stretch(bind_verts, posed_verts, faces):
+    """dsn_mesh_stretch (the rule of include/dsnerf.h): per pose and mesh face the largest ratio of a posed edge to the same edge of the
+    mesh as it was bound - bind_verts [N,3], posed_verts [P,N,3], faces [T,3] int32 -> [P,T] float32 (device tensors); +inf for a face
+    with an index outside [0, N), 1 for a face whose three bound edges have length 0."""
+    require_gpu()
+    dev = posed_verts.device
+    bind_verts = _f32(bind_verts, dev).reshape(-1, 3)
+    N = bind_verts.shape[0]
+    posed_verts = _f32(posed_verts, dev)
+    if posed_verts.dim() != 3 or tuple(posed_verts.shape[1:]) != (N, 3):
+        raise ValueError(f"mesh_stretch: posed_verts must be [P,{N},3], got {tuple(posed_verts.shape)}")
+    P = posed_verts.shape[0]
+    faces = faces.to(device=dev, dtype=torch.int32).reshape(-1, 3).contiguous()
+    T = faces.shape[0]
+    out = torch.empty(P, T, dtype=torch.float32, device=dev)
+    _check(lib().dsn_mesh_stretch(_ptr(bind_verts) if N else None, _ptr(posed_verts) if N else None, P, N, _ptr(faces) if T else None, T,
+                                  _ptr(out) if T else None, _stream()), "dsn_mesh_stretch")
+    return out
 
 
 RM_CLEAR, RM_PROJECT, RM_RASTER, RM_RASTER_BIG, RM_SHADE = 1, 2, 4, 8, 16      # DSN_RM_*: the kernels of dsn_raster_mesh_ex

@@ -1315,6 +1315,77 @@ class Renderer:
             _lib.scene_set_pose(self.scene, packed, poses, fi, zero)
         return out
 
+    # ---- an extracted mesh under other poses (novel_pose_vis.py's animation, for the mesh: the rule of include/dsnerf.h) ----
+    @torch.no_grad()
+    def bind_mesh(self, batch, mesh, slab=1 << 22):
+        """Bind a mesh of batch's posed body (world coordinates: extract_mesh's dict, or a (verts, faces[, normals]) tuple) to the
+        body, once: per slab of at most `slab` vertices dsn_warp as it is (want_uvh), so every vertex keeps the record the warp gives
+        a sample point there - "face_idx" [N] int32, "uv" [N,2], "h" [N], "valid" [N] bool (not transparent; reported only, the
+        record is never clamped) and "x_c" [N,3], the warp's canonical position - whatever the slab size.  The mesh's "normals",
+        where present, are bound with it: "cov" [N,3] (dsn_mesh_bind_normals; None without normals).  "verts" and "faces" are the
+        bound mesh's own tensors, and every other entry of the mesh dict (albedo, colour, source_vertex, ...) is passed through
+        untouched: vertex count and order never change under pose_mesh.  Frame state as mesh_attributes leaves it."""
+        self._ensure_mesh(batch)
+        fi = int(torch.as_tensor(batch["frame"]).reshape(-1)[0])
+        _lib.scene_set_pose(self.scene, self.net.packed(self.device), batch["poses"][0], fi, self.net.nerf.w is not None)
+        self._frame_src = None          # (as density_grid: stage calls set their frame again)
+        dev = self.device
+        if isinstance(mesh, dict):
+            verts, faces, normals = mesh["verts"], mesh["faces"], mesh.get("normals")
+        else:
+            verts, faces, normals = (tuple(mesh) + (None,))[:3]
+        verts = torch.as_tensor(verts).to(device=dev, dtype=torch.float32).reshape(-1, 3).contiguous()
+        faces = torch.as_tensor(faces).to(device=dev, dtype=torch.int32).reshape(-1, 3).contiguous()
+        N = verts.shape[0]
+        out = dict(mesh) if isinstance(mesh, dict) else {}
+        out.update(face_idx=torch.empty(N, dtype=torch.int32, device=dev), uv=torch.empty(N, 2, device=dev), h=torch.empty(N, device=dev),
+                   valid=torch.empty(N, dtype=torch.bool, device=dev), x_c=torch.empty(N, 3, device=dev), cov=None, verts=verts, faces=faces)
+        slab = max(int(slab), 1)
+        for s0 in range(0, N, slab):
+            sl = slice(s0, min(s0 + slab, N))
+            w = _lib.warp(self.scene, verts[sl].contiguous(), None, 1, want_dir=False, want_uvh=True)
+            out["face_idx"][sl], out["uv"][sl], out["h"][sl], out["x_c"][sl] = w["face_idx"], w["uv"], w["h"], w["x_c"]
+            out["valid"][sl] = w["transparent"] == 0
+        if normals is not None:
+            normals = torch.as_tensor(normals).to(device=dev, dtype=torch.float32).reshape(-1, 3).contiguous()
+            if normals.shape[0] != N:
+                raise ValueError(f"bind_mesh: {normals.shape[0]} normals for {N} vertices")
+            out["cov"] = _lib.mesh_bind_normals(self._dev(batch["xyz"][0]).reshape(-1, 3), self.scene._keep[1], out["face_idx"], normals)
+        return out
+
+    @torch.no_grad()
+    def pose_mesh(self, binding, targets, normals=True, stretch=False):
+        """bind_mesh's binding under other bodies of the same topology (dsn_mesh_pose): `targets` is a tensor or array [P,Vb,3] or
+        [Vb,3], a list of batches (each batch["xyz"][0]) or "canonical" (the renderer's canonical vertices: "verts" is then the
+        binding's "x_c", bit for bit).  Returns device tensors {"verts" [P,N,3], "normals" [P,N,3] (None without bound normals or
+        with normals=False), "stretch" [P,T] (dsn_mesh_stretch against the bound mesh; None unless stretch=True), "faces" [T,3]: the
+        binding's own}; a [Vb,3] input or "canonical" gives unbatched shapes.  The triangle list is constant: where neighbouring
+        vertices ride on different body parts a triangle tears, and visualizer.cull_stretched drops those by their stretch."""
+        dev = self.device
+        single = False
+        if isinstance(targets, str):
+            if targets != "canonical":
+                raise ValueError(f"pose_mesh: unknown target {targets!r} (\"canonical\")")
+            xyz, single = self.scene._keep[0][None], True
+        elif isinstance(targets, (list, tuple)):
+            if not targets:
+                raise ValueError("pose_mesh: no target pose")
+            xyz = torch.stack([self._dev(torch.as_tensor(t["xyz"][0] if isinstance(t, dict) else t)).reshape(-1, 3) for t in targets])
+        else:
+            xyz = torch.as_tensor(targets).to(device=dev, dtype=torch.float32)
+            if xyz.dim() == 2:
+                xyz, single = xyz[None], True
+        if xyz.dim() != 3 or xyz.shape[2] != 3:
+            raise ValueError(f"pose_mesh: targets must be [P,Vb,3] or [Vb,3], got {tuple(xyz.shape)}")
+        if xyz.shape[1] != self.scene.V:
+            raise ValueError(f"pose_mesh: a target body has {xyz.shape[1]} vertices, the renderer's body has {self.scene.V}")
+        if xyz.shape[0] < 1:
+            raise ValueError("pose_mesh: no target pose")
+        o = _lib.mesh_pose(binding if normals else dict(binding, cov=None), self.scene._keep[1], xyz.contiguous())
+        st = _lib.mesh_stretch(binding["verts"], o["verts"], binding["faces"]) if stretch else None
+        pick = (lambda t: None if t is None else t[0]) if single else (lambda t: t)
+        return {"verts": pick(o["verts"]), "normals": pick(o["normals"]), "stretch": pick(st), "faces": binding["faces"]}
+
     # ---- density query for marching cubes (reference :280-296) ----
     def query_volume(self, pts, code_idx, transparent_mask=None, batch_info={}):
         """batch_info needs only 'poses' (the density-only branch of the reference, model/spacenet.py:223-241)."""

@@ -1359,6 +1359,54 @@ int dsn_mesh_cc_emit(const float* verts, const int32_t* faces, int64_t n_verts, 
                                source_vertex, 0, stream);
 }
 
+// counts of the bound-mesh calls: every byte size fits size_t and every grid fits 2^31 - 1 workgroups of 256
+static bool dsn_mesh_pose_sizes_ok(int64_t P, int64_t N) {
+    return P >= 1 && N >= 0 && N < ((int64_t)1 << 38) && (uint64_t)N <= (uint64_t)SIZE_MAX / 12 / (uint64_t)P;
+}
+
+size_t dsn_mesh_pose_workspace_bytes(int P, int Fb) {
+    return (P >= 1 && Fb >= 1 && (uint64_t)P * (uint64_t)Fb < ((uint64_t)1 << 38)) ? sizeof(DsnFaceRec) * (size_t)P * (size_t)Fb : 0;
+}
+
+int dsn_mesh_bind_normals(const float* body_xyz, int Vb, const int32_t* body_faces, int Fb, const int32_t* face_idx, const float* normals,
+                          int64_t N, float* cov, void* stream) {
+    DSN_REQUIRE(N >= 0, "dsn_mesh_bind_normals: negative count");
+    DSN_REQUIRE(dsn_mesh_pose_sizes_ok(1, N), "dsn_mesh_bind_normals: too many vertices");
+    DSN_REQUIRE(Vb > 0 && Fb > 0, "dsn_mesh_bind_normals: bad Vb/Fb");
+    DSN_REQUIRE(body_xyz && body_faces, "dsn_mesh_bind_normals: null body");
+    DSN_REQUIRE(N == 0 || (face_idx && normals && cov), "dsn_mesh_bind_normals: null argument");
+    dsn_launch_mesh_bind_normals(body_xyz, Vb, body_faces, Fb, face_idx, normals, N, cov, (hipStream_t)stream);
+    return dsn_check_launch("dsn_mesh_bind_normals");
+}
+
+int dsn_mesh_pose(const float* target_xyz, int P, int Vb, const int32_t* body_faces, int Fb, const int32_t* face_idx, const float* uv,
+                  const float* h, const float* cov, int64_t N, float* out_verts, float* out_normals, int32_t* status, void* workspace,
+                  void* stream) {
+    DSN_REQUIRE(N >= 0, "dsn_mesh_pose: negative count");
+    DSN_REQUIRE(P >= 1, "dsn_mesh_pose: P must be at least 1");
+    DSN_REQUIRE(Vb > 0 && Fb > 0, "dsn_mesh_pose: bad Vb/Fb");
+    DSN_REQUIRE(dsn_mesh_pose_sizes_ok(P, N) && dsn_mesh_pose_workspace_bytes(P, Fb) != 0 &&
+                (uint64_t)Vb <= (uint64_t)SIZE_MAX / 12 / (uint64_t)P, "dsn_mesh_pose: counts too large");
+    DSN_REQUIRE(target_xyz && body_faces && workspace, "dsn_mesh_pose: null argument");
+    DSN_REQUIRE(((uintptr_t)workspace & 15) == 0, "dsn_mesh_pose: workspace must be 16-byte aligned");
+    DSN_REQUIRE(N == 0 || (face_idx && uv && h && out_verts), "dsn_mesh_pose: null binding or output");
+    DSN_REQUIRE(!out_normals || cov || N == 0, "dsn_mesh_pose: out_normals needs cov (null)");
+    dsn_launch_mesh_pose(target_xyz, P, Vb, body_faces, Fb, face_idx, uv, h, cov, N, out_verts, out_normals, status, workspace,
+                         (hipStream_t)stream);
+    return dsn_check_launch("dsn_mesh_pose");
+}
+
+int dsn_mesh_stretch(const float* bind_verts, const float* posed_verts, int P, int64_t N, const int32_t* faces, int64_t T, float* stretch,
+                     void* stream) {
+    DSN_REQUIRE(N >= 0 && T >= 0, "dsn_mesh_stretch: negative count");
+    DSN_REQUIRE(P >= 1, "dsn_mesh_stretch: P must be at least 1");
+    DSN_REQUIRE(dsn_mesh_pose_sizes_ok(P, N) && dsn_mesh_pose_sizes_ok(P, T), "dsn_mesh_stretch: counts too large");
+    DSN_REQUIRE(N == 0 || (bind_verts && posed_verts), "dsn_mesh_stretch: null vertices");
+    DSN_REQUIRE(T == 0 || (faces && stretch), "dsn_mesh_stretch: null faces or output");
+    dsn_launch_mesh_stretch(bind_verts, posed_verts, P, N, faces, T, stretch, (hipStream_t)stream);
+    return dsn_check_launch("dsn_mesh_stretch");
+}
+
 static bool dsn_raster_sizes_ok(int64_t V, int64_t T, int H, int W) {
     return V >= 0 && T >= 0 && V < ((int64_t)1 << 31) && T < ((int64_t)1 << 31) && H >= 1 && H <= 16384 && W >= 1 && W <= 16384;
 }

@@ -220,6 +220,14 @@ void dsn_launch_mesh_cc_label(const float* verts, const int32_t* faces, int64_t 
                               int64_t* out_counts, int phases, hipStream_t st);
 void dsn_launch_mesh_cc_emit(const float* verts, const int32_t* faces, int64_t V, int64_t T, void* workspace, float* out_verts, int64_t vcap,
                              int32_t* out_faces, int64_t fcap, int32_t* source_vertex, int phases, hipStream_t st);
+// dsn_mesh.hip: a mesh bound to the body (dsn_mesh_bind_normals / dsn_mesh_pose / dsn_mesh_stretch; workspace: DsnFaceRec [P, Fb])
+void dsn_launch_mesh_bind_normals(const float* body, int Vb, const int32_t* bfaces, int Fb, const int32_t* face_idx, const float* normals,
+                                  int64_t N, float* cov, hipStream_t st);
+void dsn_launch_mesh_pose(const float* target, int P, int Vb, const int32_t* bfaces, int Fb, const int32_t* face_idx, const float* uv,
+                          const float* h, const float* cov, int64_t N, float* out_verts, float* out_normals, int32_t* status, void* workspace,
+                          hipStream_t st);
+void dsn_launch_mesh_stretch(const float* bind, const float* posed, int P, int64_t N, const int32_t* faces, int64_t T, float* stretch,
+                             hipStream_t st);
 // dsn_raster.hip: the mesh preview (dsn_raster_mesh)
 size_t dsn_raster_workspace_size(int64_t V, int64_t T, int H, int W);
 void dsn_launch_raster_mesh(const float* verts, int64_t V, const int32_t* faces, int64_t T, const float* pose12, float fx, float fy,

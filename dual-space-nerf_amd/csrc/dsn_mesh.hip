@@ -719,3 +719,152 @@ void dsn_launch_mesh_cc_emit(const float* verts, const int32_t* faces, int64_t V
         hipLaunchKernelGGL(k_cc_emit_faces, dim3((unsigned)tilesT), dim3(MC_THREADS), 0, st, faces, (int)V, T, w.label, w.head, w.tf, w.vmap,
                            out_faces, fcap);
 }
+
+// ---------------------------------------------------------------------------------------------
+// a mesh bound to the body: dsn_mesh_bind_normals / dsn_mesh_pose / dsn_mesh_stretch (the rule of include/dsnerf.h)
+//   records: per pose and body face the DsnFaceRec of the target body - dsn_make_face, the values k_face_setup writes - into the workspace
+//            ([P, Fb] x 64 B: a few hundred KB per pose, read back from L2); a body face with an index outside [0, Vb) gives a NaN record.
+//   pose   : one thread per mesh vertex - its binding (face, u, v, h and the covector: 28 B) once, then per pose one record gather,
+//            dsn_map2face and the covector's image; consecutive lanes write consecutive 12-byte rows.  No atomics on floats: every
+//            output word has one writer.  A binding outside [0, Fb): NaN rows and one integer atomic OR on the status word.
+//   stretch: one thread per mesh face, the bind lengths once, then per pose the three posed edges.
+// ---------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(MC_THREADS) k_mesh_face_recs(const float* __restrict__ target, int P, int Vb, const int32_t* __restrict__ bfaces,
+                                                               int Fb, DsnFaceRec* __restrict__ recs) {
+    const int64_t k = (int64_t)blockIdx.x * MC_THREADS + threadIdx.x;
+    if (k >= (int64_t)P * Fb) return;
+    const int f = (int)(k % Fb);
+    const float* verts = target + (k / Fb) * 3 * (int64_t)Vb;
+    const int32_t i0 = bfaces[3 * f], i1 = bfaces[3 * f + 1], i2 = bfaces[3 * f + 2];
+    float4* o = (float4*)(recs + k);
+    if ((uint32_t)i0 >= (uint32_t)Vb || (uint32_t)i1 >= (uint32_t)Vb || (uint32_t)i2 >= (uint32_t)Vb) {
+        const float q = __builtin_nanf("");
+        o[0] = o[1] = o[2] = o[3] = make_float4(q, q, q, q);
+        return;
+    }
+    float v0[3], v1[3], v2[3];
+    for (int c = 0; c < 3; ++c) { v0[c] = verts[3 * i0 + c]; v1[c] = verts[3 * i1 + c]; v2[c] = verts[3 * i2 + c]; }
+    DsnFaceRec r;
+    dsn_make_face(v0, v1, v2, r);
+    o[0] = make_float4(r.m0[0], r.m0[1], r.m0[2], r.d00);
+    o[1] = make_float4(r.v10[0], r.v10[1], r.v10[2], r.d01);
+    o[2] = make_float4(r.v20[0], r.v20[1], r.v20[2], r.d11);
+    o[3] = make_float4(r.n[0], r.n[1], r.n[2], r.inv);
+}
+
+__global__ void __launch_bounds__(MC_THREADS) k_mesh_bind_normals(const float* __restrict__ body, int Vb, const int32_t* __restrict__ bfaces, int Fb,
+                                                                  const int32_t* __restrict__ face_idx, const float* __restrict__ normals,
+                                                                  int64_t N, float* __restrict__ cov) {
+    const int64_t i = (int64_t)blockIdx.x * MC_THREADS + threadIdx.x;
+    if (i >= N) return;
+    const int32_t f = face_idx[i];
+    float o[3] = {__builtin_nanf(""), __builtin_nanf(""), __builtin_nanf("")};
+    if ((uint32_t)f < (uint32_t)Fb) {
+        const int32_t i0 = bfaces[3 * f], i1 = bfaces[3 * f + 1], i2 = bfaces[3 * f + 2];
+        if ((uint32_t)i0 < (uint32_t)Vb && (uint32_t)i1 < (uint32_t)Vb && (uint32_t)i2 < (uint32_t)Vb) {
+            float v0[3], v1[3], v2[3];
+            for (int c = 0; c < 3; ++c) { v0[c] = body[3 * i0 + c]; v1[c] = body[3 * i1 + c]; v2[c] = body[3 * i2 + c]; }
+            DsnFaceRec r;
+            dsn_make_face(v0, v1, v2, r);
+            const float n[3] = {normals[3 * i], normals[3 * i + 1], normals[3 * i + 2]};
+            o[0] = dsn_dot3(n, r.v20); o[1] = dsn_dot3(n, r.v10); o[2] = dsn_dot3(n, r.n);
+        }
+    }
+    cov[3 * i] = o[0]; cov[3 * i + 1] = o[1]; cov[3 * i + 2] = o[2];
+}
+
+__global__ void __launch_bounds__(MC_THREADS) k_mesh_pose(const DsnFaceRec* __restrict__ recs, int P, int Fb, const int32_t* __restrict__ face_idx,
+                                                          const float* __restrict__ uv, const float* __restrict__ h, const float* __restrict__ cov,
+                                                          int64_t N, float* __restrict__ out_verts, float* __restrict__ out_normals,
+                                                          int32_t* __restrict__ status) {
+    const int64_t i = (int64_t)blockIdx.x * MC_THREADS + threadIdx.x;
+    if (i >= N) return;
+    const int32_t f = face_idx[i];
+    const bool want_n = out_normals != nullptr;
+    if ((uint32_t)f >= (uint32_t)Fb) {
+        const float q = __builtin_nanf("");
+        for (int p = 0; p < P; ++p) {
+            const int64_t o = 3 * ((int64_t)p * N + i);
+            out_verts[o] = q; out_verts[o + 1] = q; out_verts[o + 2] = q;
+            if (want_n) { out_normals[o] = q; out_normals[o + 1] = q; out_normals[o + 2] = q; }
+        }
+        if (status) atomicOr(status, DSN_MESH_POSE_BAD_BINDING);
+        return;
+    }
+    const float u = uv[2 * i], v = uv[2 * i + 1], hh = h[i];
+    float cv[3] = {0.f, 0.f, 0.f};
+    if (want_n) { cv[0] = cov[3 * i]; cv[1] = cov[3 * i + 1]; cv[2] = cov[3 * i + 2]; }
+    for (int p = 0; p < P; ++p) {
+        const DsnFaceRec r = dsn_load_face(recs + (int64_t)p * Fb, f);
+        const int64_t o = 3 * ((int64_t)p * N + i);
+        float x[3];
+        dsn_map2face(u, v, hh, r, x);
+        out_verts[o] = x[0]; out_verts[o + 1] = x[1]; out_verts[o + 2] = x[2];
+        if (want_n) {
+            float c[3], a[3], b[3], m[3], n[3];
+            dsn_cross3(r.v10, r.v20, c);      // (the record's n is c / |c|)
+            dsn_cross3(r.n, r.v10, a);
+            dsn_cross3(r.v20, r.n, b);
+            for (int k = 0; k < 3; ++k) m[k] = (cv[0] * a[k] + cv[1] * b[k]) + cv[2] * c[k];
+            dsn_normalize3(m, n);
+            out_normals[o] = n[0]; out_normals[o + 1] = n[1]; out_normals[o + 2] = n[2];
+        }
+    }
+}
+
+__global__ void __launch_bounds__(MC_THREADS) k_mesh_stretch(const float* __restrict__ bind, const float* __restrict__ posed, int P, int64_t N,
+                                                             const int32_t* __restrict__ faces, int64_t T, float* __restrict__ stretch) {
+    const int64_t t = (int64_t)blockIdx.x * MC_THREADS + threadIdx.x;
+    if (t >= T) return;
+    const int32_t idx[3] = {faces[3 * t], faces[3 * t + 1], faces[3 * t + 2]};
+    if (idx[0] < 0 || idx[0] >= N || idx[1] < 0 || idx[1] >= N || idx[2] < 0 || idx[2] >= N) {
+        for (int p = 0; p < P; ++p) stretch[(int64_t)p * T + t] = __builtin_inff();
+        return;
+    }
+    float lb[3];      // edge k: vertex k -> vertex k + 1 (mod 3)
+    for (int k = 0; k < 3; ++k) {
+        const float* a = bind + 3 * (int64_t)idx[k];
+        const float* b = bind + 3 * (int64_t)idx[(k + 1) % 3];
+        const float e[3] = {b[0] - a[0], b[1] - a[1], b[2] - a[2]};
+        lb[k] = dsn_norm3(e);
+    }
+    for (int p = 0; p < P; ++p) {
+        const float* pv = posed + 3 * (int64_t)p * N;
+        float s = 1.0f;
+        bool any = false;
+        for (int k = 0; k < 3; ++k) {
+            if (lb[k] == 0.0f) continue;
+            const float* a = pv + 3 * (int64_t)idx[k];
+            const float* b = pv + 3 * (int64_t)idx[(k + 1) % 3];
+            const float e[3] = {b[0] - a[0], b[1] - a[1], b[2] - a[2]};
+            const float r = dsn_div(dsn_norm3(e), lb[k]);
+            s = (!any || r > s || r != r) ? r : s;      // the maximum; a NaN ratio stays
+            any = true;
+        }
+        stretch[(int64_t)p * T + t] = s;
+    }
+}
+
+static unsigned mesh_blocks(int64_t n) { return (unsigned)((n + MC_THREADS - 1) / MC_THREADS); }
+
+void dsn_launch_mesh_bind_normals(const float* body, int Vb, const int32_t* bfaces, int Fb, const int32_t* face_idx, const float* normals,
+                                  int64_t N, float* cov, hipStream_t st) {
+    if (N <= 0) return;
+    hipLaunchKernelGGL(k_mesh_bind_normals, dim3(mesh_blocks(N)), dim3(MC_THREADS), 0, st, body, Vb, bfaces, Fb, face_idx, normals, N, cov);
+}
+
+void dsn_launch_mesh_pose(const float* target, int P, int Vb, const int32_t* bfaces, int Fb, const int32_t* face_idx, const float* uv,
+                          const float* h, const float* cov, int64_t N, float* out_verts, float* out_normals, int32_t* status, void* workspace,
+                          hipStream_t st) {
+    if (N <= 0) return;
+    DsnFaceRec* recs = (DsnFaceRec*)workspace;
+    hipLaunchKernelGGL(k_mesh_face_recs, dim3(mesh_blocks((int64_t)P * Fb)), dim3(MC_THREADS), 0, st, target, P, Vb, bfaces, Fb, recs);
+    hipLaunchKernelGGL(k_mesh_pose, dim3(mesh_blocks(N)), dim3(MC_THREADS), 0, st, recs, P, Fb, face_idx, uv, h, cov, N, out_verts,
+                       cov ? out_normals : nullptr, status);
+}
+
+void dsn_launch_mesh_stretch(const float* bind, const float* posed, int P, int64_t N, const int32_t* faces, int64_t T, float* stretch,
+                             hipStream_t st) {
+    if (T <= 0) return;
+    hipLaunchKernelGGL(k_mesh_stretch, dim3(mesh_blocks(T)), dim3(MC_THREADS), 0, st, bind, posed, P, N, faces, T, stretch);
+}

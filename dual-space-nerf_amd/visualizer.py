@@ -9,7 +9,10 @@ dsn_mesh_cc_label / dsn_mesh_cc_emit: get_mesh_from_grid(..., largest_component=
 or largest_component(mesh) below.  Components join through shared vertex INDICES (trimesh: shared edges - the same partition on a
 marching-cubes mesh, not at the pinch vertices of an arbitrary one), the largest summed float32 area wins, ties go to the smaller
 vertex index (include/dsnerf.h).  The constructor switch connected=True itself still raises NotImplementedError and names the keyword:
-wiring it to the keyword is one line, held back while a pinned test expects the raise."""
+wiring it to the keyword is one line, held back while a pinned test expects the raise.
+A mesh follows the body into other poses without a second extraction: Renderer.bind_mesh once, Renderer.pose_mesh per frame
+(dsn_mesh_pose, the rule of include/dsnerf.h); render_mesh_sequence previews such a sequence and cull_stretched drops the triangles
+a pose tore."""
 import numpy as np
 import torch
 
@@ -132,6 +135,34 @@ class Visualizer3D(object):
                                height=self.resolution_render, width=self.resolution_render, **kw)
         return out["color"].cpu().numpy()
 
+    @torch.no_grad()
+    def render_mesh_sequence(self, render, binding, targets, camera_pose=None, chunk=8, max_stretch=None, **render_mesh_kw):
+        """The preview of a bound mesh (Renderer.bind_mesh) under a sequence of poses - novel_pose_vis.py's animation, for the mesh:
+        numpy uint8 [P, resolution_render, resolution_render, 3].  `targets` as Renderer.pose_mesh takes them (a [Vb,3] body or
+        "canonical": P = 1); `chunk` poses are carried at a time (dsn_mesh_pose) and each is rasterised by render_mesh with
+        `camera_pose` and render_mesh's keywords (colors may name a per-vertex entry of the binding: "albedo", "colour"), so device
+        memory is bounded by the chunk, not by P.  max_stretch: triangles stretched beyond that ratio are dropped per frame
+        (cull_stretched)."""
+        if isinstance(targets, str):
+            if targets != "canonical":
+                raise ValueError(f"render_mesh_sequence: unknown target {targets!r} (\"canonical\")")
+            targets = torch.as_tensor(render.canonical_vertex).reshape(1, -1, 3)
+        elif not isinstance(targets, (list, tuple)) and np.ndim(targets) == 2:
+            targets = targets[None]
+        P = len(targets)
+        chunk = max(int(chunk), 1)
+        frames = np.empty((P, self.resolution_render, self.resolution_render, 3), np.uint8)
+        for p0 in range(0, P, chunk):
+            posed = render.pose_mesh(binding, targets[p0:p0 + chunk], stretch=max_stretch is not None)
+            for k in range(posed["verts"].shape[0]):
+                mesh = dict(binding, verts=posed["verts"][k])
+                if posed["normals"] is not None:
+                    mesh["normals"] = posed["normals"][k]
+                if max_stretch is not None:
+                    mesh = cull_stretched(mesh, posed["stretch"][k], max_stretch)
+                frames[p0 + k] = self.render_mesh(mesh, camera_pose=camera_pose, **render_mesh_kw)
+        return frames
+
 
 PER_VERTEX_KEYS = ("normals", "albedo", "normal", "colour", "sigma", "valid")
 
@@ -171,6 +202,21 @@ def largest_component(mesh):
         if out.get(k) is not None:
             out[k] = back(gather(out[k]))
     return out
+
+
+def cull_stretched(mesh, stretch, max_ratio=2.0):
+    """The mesh without the triangles a pose tore: faces[stretch <= max_ratio], with `stretch` [T] of Renderer.pose_mesh(...,
+    stretch=True) for that pose (NaN and +inf are dropped too).  mesh: a dict with "faces" (the other entries are carried over; the
+    vertices are kept, so per-vertex arrays stay valid) or a (verts, faces[, normals]) tuple; numpy or device.  2.0 is a default,
+    not a claim: the ratio that separates a fold from a tear depends on the motion."""
+    faces = mesh["faces"] if isinstance(mesh, dict) else mesh[1]
+    keep = torch.as_tensor(stretch).reshape(-1) <= max_ratio
+    if keep.shape[0] != faces.shape[0]:
+        raise ValueError(f"cull_stretched: {keep.shape[0]} stretch values for {faces.shape[0]} faces")
+    kept = faces[keep.to(faces.device)] if torch.is_tensor(faces) else np.asarray(faces)[keep.cpu().numpy()]
+    if isinstance(mesh, dict):
+        return dict(mesh, faces=kept)
+    return (mesh[0], kept) + tuple(mesh[2:])
 
 
 def save_ply(path, mesh, colors=None):

@@ -691,6 +691,53 @@ DSN_EXPORT int dsn_mesh_cc_emit_ex(const float* verts, const int32_t* faces, int
                                    size_t workspace_bytes, int64_t out_n_verts, int64_t out_n_faces, float* out_verts, int32_t* out_faces,
                                    int32_t* source_vertex, int phases, void* stream);
 
+/* ---- a mesh bound to the body (an addition within ABI 8: no existing entry point changes) --------------------------------------------
+ * novel_pose_vis.py and the novel-pose datasets animate one learned body by swapping batch["xyz"].  A mesh extracted in one pose follows
+ * the body the same way: dsn_warp expresses a world point in the frame of its nearest posed face as (face, u, v, h) and evaluates that
+ * record on the canonical mesh; evaluating it on the mesh of any other pose carries the point there.  The record is never clamped, so
+ * the map is a bijection per face.  The rule is fixed so that a numpy restatement (tests/mesh_pose_restate.py) reproduces every output bit
+ * for bit.  All float32, fused multiply-add only inside dsn_cross3 and dsn_norm3 (csrc/dsn_common.h), one rounding per operation otherwise.
+ *   Binding:  vertex i of a mesh bound against posed body A (body_xyz [Vb, 3], body_faces [Fb, 3]) keeps exactly what dsn_warp returns for
+ *             the point with A as the frame's mesh: face_idx[i], uv[i], h[i], transparent[i].  Nothing is clamped or replaced for
+ *             transparent vertices: they are carried by the same formula, the mask is only reported.
+ *   Position: under a target body B of the same topology, with r = dsn_make_face(B[f0], B[f1], B[f2]) of the bound face f, the position is
+ *             dsn_map2face(u, v, h, r): per component ((m0 + u v20) + v v10) + h n, the operation order the warp uses for x_c.  With the
+ *             canonical vertices as B this is dsn_warp's x_c, bit for bit.
+ *   Normal:   transported as a covector of the face frame.  Bound (dsn_mesh_bind_normals) with the source face's v20, v10 and unit n_f:
+ *             cov = (n . v20, n . v10, n . n_f), each (a0 b0 + a1 b1) + a2 b2.  Posed with the target face's w20, w10, c = w10 x w20
+ *             (dsn_cross3, not normalised) and the record's unit n_t = c / |c|:
+ *               m_k = (cov_0 (n_t x w10)_k + cov_1 (w20 x n_t)_k) + cov_2 c_k,   n' = dsn_normalize3(m) (eps 1e-12)
+ *             the cross products by dsn_cross3.  Target = source returns normalize(n); a rigid motion of the body rotates n.  (The
+ *             Gram-inverse form of the same covector loses three digits on sliver triangles; this form does not.)  A zero or NaN result is
+ *             what dsn_normalize3 and NaN propagation give: nothing is patched.
+ *   Stretch:  per mesh face t = (i0, i1, i2) and pose p the maximum over the edges (i0, i1), (i1, i2), (i2, i0) of
+ *             dsn_div(dsn_norm3(e_posed), dsn_norm3(e_bind)), e = second vertex - first, e_bind from the vertices the mesh was bound with.
+ *             An edge with |e_bind| == 0 is skipped; all three skipped: 1.  A NaN ratio stays (the value is NaN: every threshold test
+ *             `stretch <= max` drops the face).  A face with an index outside [0, N): +inf.
+ *   Bad bindings: a vertex whose face_idx lies outside [0, Fb) gets a NaN position and a NaN normal in every pose and sets
+ *             DSN_MESH_POSE_BAD_BINDING in *status (an int32 in device memory the CALLER zeroes; an integer atomic OR, no host read is
+ *             forced); dsn_mesh_bind_normals writes a NaN covector there.  A body face with a vertex index outside [0, Vb) gives a NaN
+ *             record: NaN for the vertices bound to it.
+ * dsn_mesh_pose: target_xyz [P, Vb, 3] (P bodies), the binding face_idx [N] int32, uv [N, 2], h [N], cov [N, 3] (NULL: no normals);
+ * out_verts [P, N, 3], out_normals [P, N, 3] (NULL: none; needs cov), status (NULL: not reported); workspace:
+ * dsn_mesh_pose_workspace_bytes(P, Fb) bytes (0 for bad sizes), 16-byte aligned, earlier contents not read - the call fills it with the
+ * P x Fb face records (64 B each), one launch, and poses all vertices in a second: one thread per vertex, its 28-byte binding read once,
+ * one record gather and 12 or 24 bytes of stores per pose.  P poses in one call give the bits of P calls.  No atomics on floats, every
+ * output word has one writer: every call returns the same bits.  N = 0 is a valid call.  All P N 3 indexing is 64-bit.
+ * dsn_mesh_stretch: bind_verts [N, 3], posed_verts [P, N, 3], faces [T, 3] int32 -> stretch [P, T].
+ * Rejected: N < 0, T < 0, P < 1, Vb or Fb < 1, counts whose byte sizes overflow size_t (or 2^38 and more: the launch grids), null
+ * required pointers (with N = 0 / T = 0 the per-vertex / per-face ones may be null), a workspace that is not 16-byte aligned,
+ * out_normals without cov.  No allocation, no synchronisation, all on `stream`. */
+#define DSN_MESH_POSE_BAD_BINDING 1
+DSN_EXPORT int dsn_mesh_bind_normals(const float* body_xyz, int Vb, const int32_t* body_faces, int Fb, const int32_t* face_idx,
+                                     const float* normals, int64_t N, float* cov, void* stream);
+DSN_EXPORT size_t dsn_mesh_pose_workspace_bytes(int P, int Fb);
+DSN_EXPORT int dsn_mesh_pose(const float* target_xyz, int P, int Vb, const int32_t* body_faces, int Fb, const int32_t* face_idx,
+                             const float* uv, const float* h, const float* cov, int64_t N, float* out_verts, float* out_normals,
+                             int32_t* status, void* workspace, void* stream);
+DSN_EXPORT int dsn_mesh_stretch(const float* bind_verts, const float* posed_verts, int P, int64_t N, const int32_t* faces, int64_t T,
+                                float* stretch, void* stream);
+
 /* ---- mesh preview (an addition within ABI 8: no existing entry point changes) -------------------------------------------------------
  * utils/visualizer.py:144-168 Visualizer3D.render_mesh (pyrender: PerspectiveCamera(yfov = pi/3, aspect 1), a SpotLight of intensity 30
  * with cone angles pi/16 and pi/6 at the camera's pose, white background, no ambient light): a deterministic triangle rasteriser with
