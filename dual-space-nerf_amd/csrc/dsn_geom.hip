@@ -117,6 +117,13 @@ void dsn_launch_pose_setup(const float* packed, const float* poses, int frame_id
 #define GG_TILE 512      // 8 KB of vertices + 4 KB of per-wave survivor lists: with 2048 the kernel held 51 KB of LDS and could not share a
                          // compute unit with k_field16<forward> (137 KB of 160) when two frames are in flight
 #define GG_THREADS 256
+#ifndef GG_FRAME_EMIT_GROUPS
+#define GG_FRAME_EMIT_GROUPS 8192      // workgroups the emission of a frame-size batch aims at (dsn_launch_sample_gg)
+#endif
+#ifndef GG_EMIT_U
+#define GG_EMIT_U 2      // stripes of GG_THREADS samples per iteration of the emission (gg_emit); 2 / 3 / 4 measured: 0.117 / - / 0.122 ms
+                         // for the frame's emission, and 2 keeps the kernels at 62 registers (4: 104, half the waves)
+#endif
 // order-preserving int key of a float (for atomicMin / atomicMax on intervals found by different vertex slices)
 __device__ __forceinline__ int gg_key(float f) {
     const int b = __float_as_int(f);
@@ -127,8 +134,8 @@ __device__ __forceinline__ float gg_unkey(int k) { return __int_as_float(k ^ ((k
 // the vertex sweep of utils/pts_utils.py:27-47 over [v_begin, v_end): interval of ray r (thread) in units of |d| = 1
 __device__ __forceinline__ void gg_sweep(const float* __restrict__ xyz, int v_begin, int v_end, const float* __restrict__ ray_o,
                                          const float* __restrict__ ray_d, int R, float& zmin, float& zmax, bool& any,
-                                         float& nrm) {
-    __shared__ float4 sv2[2][GG_TILE];      // two tiles: the next one is fetched while this one is swept (one barrier per tile)
+                                         float& nrm, float4 (*sv2)[GG_TILE]) {
+    // sv2: two tiles of LDS - the next one is fetched while this one is swept (one barrier per tile); free again when this returns
     const float gamma2 = (float)(0.05 * 0.05);
     const int tid = threadIdx.x;
     const int r = blockIdx.x * GG_THREADS + tid;
@@ -142,15 +149,42 @@ __device__ __forceinline__ void gg_sweep(const float* __restrict__ xyz, int v_be
     }
     zmin = 99999.f; zmax = -99999.f;
     any = false;
-    // Per-wave conservative cull: the 64 rays of a wave (consecutive pixels) form a narrow bundle around the axis a with
-    // half-angle theta = max angle(a, du_r).  A vertex w (relative to the common origin) at angle phi from the axis is at
-    // distance >= |w| sin(phi' - theta), phi' = min(phi, pi - phi), from every line of the bundle; when that exceeds
-    // gamma (+10 % and 0.1 mm of slack, far above the rounding of this test) it cannot satisfy rho^2 < gamma^2 for any
-    // ray of the wave and is left out.  The survivors go through the reference's exact test unchanged, and min / max
-    // do not depend on the order, so near / far are bit-identical to the full sweep.
-    __shared__ unsigned short s_keep[GG_THREADS / 64][GG_TILE];
+    // Two-level conservative cull.  The rays of a bundle (consecutive pixels) lie in a narrow cone around the axis a with half-angle
+    // theta = max angle(a, du_r).  A vertex w (relative to the common origin) at angle phi from the axis is at distance
+    // >= |w| sin(phi' - theta), phi' = min(phi, pi - phi), from every line of the bundle; when that exceeds gamma (+10 % and
+    // 0.1 mm of slack, far above the rounding of this test) it cannot satisfy rho^2 < gamma^2 for any ray of the bundle and is
+    // left out (a NaN bound keeps the vertex).  The rays of an image row also lie in a plane through the origin, which a cone of 64 or
+    // 256 pixels across does not use: with n a unit vector (the normal of the bundle's first and last ray) and e = max |n . du_r|, the
+    // foot of w on any line of the bundle is at most |w| from the origin and so at most |w| e off the plane, and w is at distance
+    // >= |n . w| - |w| e from every line - the second bound, culled against the same radius.  (It holds for any n: incoherent rays get
+    // a large e and lose nothing, identical rays a NaN normal that keeps everything.)  The sweep's time is the exact test of the
+    // survivors, not the cull (profiles/sampler_split.txt), and the slab leaves about a third of the cone's.  First level: the workgroup's 256 rays as ONE bundle - every thread tests the two
+    // vertices it fetched of a tile against the block's cone and the survivors go compacted into the LDS tile (the four waves used to
+    // repeat the test of all V vertices each, and almost half of them kept nothing).  Second level: each wave tests the block's
+    // survivors against the cone of its own 64 rays.  The wave's survivors go through the reference's exact test unchanged, and
+    // min / max do not depend on the order, so near / far are bit-identical to the full sweep.  A block that keeps nothing sweeps
+    // nothing; a block of incoherent rays (shuffled or strided batches) has a wide cone, keeps every vertex and does what the
+    // single-level cull did plus the block test.
+    // 4 KB as before the block's cull: a wave's list holds at most GG_TILE - 1 indices (a wave that keeps all GG_TILE of a tile needs no
+    // list), which leaves the last 8 bytes for the two survivor counters, one per tile buffer
+    __shared__ unsigned int s_list[GG_THREADS / 64 * GG_TILE / 2];
     const int lane = tid & 63, wave = tid >> 6;
+    unsigned short* s_keep = reinterpret_cast<unsigned short*>(s_list) + wave * (GG_TILE - 1);       // (this wave's)
+    // running totals of the block's survivors stored to buffer 0 / 1, never reset: a tile's count and places are differences with the
+    // total its buffer held before, which every thread has read one or two barriers earlier
+    int* s_cnt = reinterpret_cast<int*>(s_list) + (GG_THREADS / 64 * GG_TILE / 2 - 2);
+    float* s_cone = reinterpret_cast<float*>(s_list);             // (scratch of the cone set-up: the lists are first written after the next barriers)
+    struct Bundle { float ax, ay, az, cos_t, sin_t, nx, ny, nz, e; };      // cone: axis, half-angle; plane: normal, largest |n . du|
+    Bundle wv, bl;                          // the wave's rays, the block's
     float ax, ay, az, cos_t, sin_t;
+    float bx, by, bz, bcos, bsin;
+    // unit normal of the plane through the origin and the directions of rays ra, rb (NaN when they are parallel)
+    auto plane_of = [&](int ra, int rb, float& nx, float& ny, float& nz) {
+        const float a[3] = {ray_d[3 * ra], ray_d[3 * ra + 1], ray_d[3 * ra + 2]}, b[3] = {ray_d[3 * rb], ray_d[3 * rb + 1], ray_d[3 * rb + 2]};
+        const float cx = a[1] * b[2] - a[2] * b[1], cy = a[2] * b[0] - a[0] * b[2], cz = a[0] * b[1] - a[1] * b[0];
+        const float inv = 1.0f / sqrtf(cx * cx + cy * cy + cz * cz);
+        nx = cx * inv; ny = cy * inv; nz = cz * inv;
+    };
     {
         const bool ok = r < R;
         const int src = __ffsll((long long)__ballot(ok)) - 1;       // first valid lane (or -1)
@@ -167,8 +201,55 @@ __device__ __forceinline__ void gg_sweep(const float* __restrict__ xyz, int v_be
         for (int o = 32; o >= 1; o >>= 1) c = fminf(c, __shfl_xor(c, o));
         cos_t = fminf(c, 1.0f);
         sin_t = sqrtf(fmaxf(0.f, 1.0f - cos_t * cos_t));
+        // the block's cone the same way: invalid tail rays stand in as their wave's first valid ray, a wave without a valid ray
+        // (the last block's) stays out of the axis and of the angle
+        const bool wave_ok = src >= 0;
+        // the planes: first and last valid ray of the wave / of the block
+        const int b0 = blockIdx.x * GG_THREADS, w0 = min(b0 + wave * 64, R - 1);
+        plane_of(w0, min(w0 + 63, R - 1), wv.nx, wv.ny, wv.nz);
+        plane_of(b0, min(b0 + GG_THREADS, R) - 1, bl.nx, bl.ny, bl.nz);
+        float ew = fabsf(wv.nx * ux + wv.ny * uy + wv.nz * uz), eb = wave_ok ? fabsf(bl.nx * ux + bl.ny * uy + bl.nz * uz) : 0.f;
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) { ew = fmaxf(ew, __shfl_xor(ew, o)); eb = fmaxf(eb, __shfl_xor(eb, o)); }
+        wv.e = ew;
+        if (lane == 0) {
+            s_cone[4 * wave] = wave_ok ? sx : 0.f; s_cone[4 * wave + 1] = wave_ok ? sy : 0.f; s_cone[4 * wave + 2] = wave_ok ? sz : 0.f;
+            s_cone[4 * wave + 3] = eb;
+        }
+        if (tid < 2) s_cnt[tid] = 0;
+        __syncthreads();
+        float tx = 0.f, ty = 0.f, tz = 0.f;
+#pragma unroll
+        for (int w = 0; w < GG_THREADS / 64; ++w) { tx += s_cone[4 * w]; ty += s_cone[4 * w + 1]; tz += s_cone[4 * w + 2]; eb = fmaxf(eb, s_cone[4 * w + 3]); }
+        bl.e = eb;
+        const float binv = 1.0f / sqrtf(tx * tx + ty * ty + tz * tz);
+        bx = tx * binv; by = ty * binv; bz = tz * binv;
+        float cb = wave_ok ? bx * ux + by * uy + bz * uz : 1.0f;
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) cb = fminf(cb, __shfl_xor(cb, o));
+        if (lane == 0) s_cone[4 * (GG_THREADS / 64) + wave] = cb;
+        __syncthreads();
+#pragma unroll
+        for (int w = 0; w < GG_THREADS / 64; ++w) cb = fminf(cb, s_cone[4 * (GG_THREADS / 64) + w]);
+        bcos = fminf(cb, 1.0f);
+        bsin = sqrtf(fmaxf(0.f, 1.0f - bcos * bcos));
+        wv.ax = ax; wv.ay = ay; wv.az = az; wv.cos_t = cos_t; wv.sin_t = sin_t;
+        bl.ax = bx; bl.ay = by; bl.az = bz; bl.cos_t = bcos; bl.sin_t = bsin;
     }
     const float keep_r = 0.05f * 1.10f + 1e-4f;
+    // the two lower bounds of the distance of vertex v (relative to the origin, v.w = |v|^2) from every line of the bundle
+    auto bundle_keeps = [&](const float4 v, const Bundle& b) {
+        // (the hardware's approximate 1 / sqrt and sqrt, 1 ulp: the test runs once per vertex and wave, the radius has 10 % of slack;
+        //  |v| = 0 gives NaN bounds, which keep the vertex)
+        const float rs = __builtin_amdgcn_rsqf(v.w);
+        const float wn = v.w * rs;
+        const float ca = (b.ax * v.x + b.ay * v.y + b.az * v.z) * rs;
+        const float cc = fminf(fabsf(ca), 1.0f);
+        const float ss = __builtin_amdgcn_sqrtf(fmaxf(0.f, 1.0f - cc * cc));
+        const float lb = wn * fmaxf(0.f, ss * b.cos_t - cc * b.sin_t);
+        const float lp = fabsf(b.nx * v.x + b.ny * v.y + b.nz * v.z) - wn * b.e;
+        return !(lb > keep_r) && !(lp > keep_r);
+    };
     static_assert(GG_TILE == 2 * GG_THREADS, "two vertices per thread and tile");
     auto tile_fetch = [&](int base, float (&c)[2][3]) {           // (requests only: the values are used after the current tile's sweep)
 #pragma unroll
@@ -178,22 +259,49 @@ __device__ __forceinline__ void gg_sweep(const float* __restrict__ xyz, int v_be
             c[u][0] = xyz[3 * jj]; c[u][1] = xyz[3 * jj + 1]; c[u][2] = xyz[3 * jj + 2];
         }
     };
-    auto tile_store = [&](float4* dst, const float (&c)[2][3]) {
+    // the tile's vertices that pass the block's cone, compacted into dst in any order: each wave reserves the places of its survivors with
+    // one LDS atomic on *cnt, which held `before` when the tile's first wave came here; at most GG_TILE survive, so every place is inside
+    // the tile
+    auto tile_store = [&](float4* dst, int* cnt, int before, int base, const float (&c)[2][3]) {
+        float4 v[2];
+        bool keep[2];
+        unsigned long long m[2];
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
             const float dx = c[u][0] - o0x, dy = c[u][1] - o0y, dz = c[u][2] - o0z;
-            dst[tid + u * GG_THREADS] = make_float4(dx, dy, dz, dsn_sum3(dx * dx, dy * dy, dz * dz));
+            v[u] = make_float4(dx, dy, dz, dsn_sum3(dx * dx, dy * dy, dz * dz));
+            keep[u] = base + tid + u * GG_THREADS < v_end && bundle_keeps(v[u], bl);
+            m[u] = __ballot(keep[u]);
         }
+        const int n0 = __popcll(m[0]), n1 = __popcll(m[1]);
+        int at = 0;
+        if (lane == 0 && n0 + n1 > 0) at = atomicAdd(cnt, n0 + n1);
+        at = __shfl(at, 0) - before;
+        const unsigned long long below = (1ull << lane) - 1ull;
+        if (keep[0]) dst[at + __popcll(m[0] & below)] = v[0];
+        if (keep[1]) dst[at + n0 + __popcll(m[1] & below)] = v[1];
     };
     if (v_begin < v_end) {
         float c0[2][3];
         tile_fetch(v_begin, c0);
-        tile_store(sv2[0], c0);
+        tile_store(sv2[0], &s_cnt[0], 0, v_begin, c0);
     }
     __syncthreads();
     int buf = 0;
+    int seen = 0, seen_other = 0;           // the totals of this tile's buffer and of the other one before their current tiles were stored
+    auto exact = [&](const float4 v) {      // the reference's test of one vertex
+        float z0 = dsn_sum3(v.x * du[0], v.y * du[1], v.z * du[2]);
+        float tmp = v.w - z0 * z0;
+        if (tmp < gamma2) {
+            float dz = sqrtf(gamma2 - tmp);
+            zmin = fminf(zmin, z0 - dz);
+            zmax = fmaxf(zmax, z0 + dz);
+            any = true;
+        }
+    };
     for (int base = v_begin; base < v_end; base += GG_TILE, buf ^= 1) {
-        int n = min(GG_TILE, v_end - base);
+        const int total = __builtin_amdgcn_readfirstlane(s_cnt[buf]);
+        const int n = total - seen;                               // the block's survivors of this tile
         const float4* __restrict__ sv = sv2[buf];
         const bool more = base + GG_TILE < v_end;                 // (block-uniform)
         float cn[2][3];
@@ -201,35 +309,24 @@ __device__ __forceinline__ void gg_sweep(const float* __restrict__ xyz, int v_be
         int kept = 0;
         for (int j0 = 0; j0 < n; j0 += 64) {
             const int j = j0 + lane;
-            bool keep = false;
-            if (j < n) {
-                const float4 v = sv[j];
-                const float wn = sqrtf(v.w);
-                const float ca = (ax * v.x + ay * v.y + az * v.z) / fmaxf(wn, 1e-20f);
-                const float cc = fminf(fabsf(ca), 1.0f);
-                const float ss = sqrtf(fmaxf(0.f, 1.0f - cc * cc));
-                const float lb = wn * fmaxf(0.f, ss * cos_t - cc * sin_t);
-                keep = !(lb > keep_r);
-            }
+            const bool keep = j < n && bundle_keeps(sv[j], wv);
             const unsigned long long m = __ballot(keep);
-            if (keep) s_keep[wave][kept + __popcll(m & ((1ull << lane) - 1ull))] = (unsigned short)j;
+            const int at = kept + __popcll(m & ((1ull << lane) - 1ull));
+            if (keep && at < GG_TILE - 1) s_keep[at] = (unsigned short)j;       // (place GG_TILE - 1 is only reached when all GG_TILE are kept)
             kept += __popcll(m);
         }
         // (same-wave LDS writes are visible to the wave's later reads; no barrier needed for a wave-private list)
+        if (kept == GG_TILE) {
 #pragma unroll 4
-        for (int k = 0; k < kept; ++k) {
-            float4 v = sv[s_keep[wave][k]];
-            float z0 = dsn_sum3(v.x * du[0], v.y * du[1], v.z * du[2]);
-            float tmp = v.w - z0 * z0;
-            if (tmp < gamma2) {
-                float dz = sqrtf(gamma2 - tmp);
-                zmin = fminf(zmin, z0 - dz);
-                zmax = fmaxf(zmax, z0 + dz);
-                any = true;
-            }
+            for (int k = 0; k < GG_TILE; ++k) exact(sv[k]);
+        } else {
+#pragma unroll 4
+            for (int k = 0; k < kept; ++k) exact(sv[s_keep[k]]);
         }
-        if (more) tile_store(sv2[buf ^ 1], cn);                   // (the other buffer was last read before the previous barrier)
+        if (more) tile_store(sv2[buf ^ 1], &s_cnt[buf ^ 1], seen_other, base + GG_TILE, cn);      // (the other buffer was last read before the previous barrier)
         __syncthreads();
+        seen = seen_other;
+        seen_other = total;
     }
 }
 
@@ -241,6 +338,7 @@ struct GgClassify { const DsnGrid* gf; int32_t* cell_of; int32_t* counts; int32_
 __device__ __forceinline__ void gg_emit(const float* s_near, const float* s_far, const float* __restrict__ ray_o,
                                         const float* __restrict__ ray_d, int R, int S, const float* __restrict__ t_vals,
                                         const float* __restrict__ jitter, float* __restrict__ z_vals, float* __restrict__ pts,
+                                        int2* s_slots,          // LDS: DSN_CLASSIFY_SLOTS(GG_EMIT_U) per wave of the workgroup
                                         const GgClassify cls = GgClassify{nullptr, nullptr, nullptr, nullptr, nullptr},
                                         int part = 0, int nparts = 1) {
     // part / nparts (k_sample_gg_emit): this workgroup takes every nparts-th stripe of GG_THREADS samples of the block's rays
@@ -248,35 +346,75 @@ __device__ __forceinline__ void gg_emit(const float* s_near, const float* s_far,
     const int rays_here = min(GG_THREADS, R - blockIdx.x * GG_THREADS);
     const int total = rays_here * S;
     const int total_up = cls.gf ? (total + 63) & ~63 : total;      // (classification uses wave-wide ballots: whole waves iterate)
-    for (int e = part * GG_THREADS + tid; e < total_up; e += GG_THREADS * nparts) {
+    const int stride = GG_THREADS * nparts;
+    // The block's samples are consecutive in every per-sample array: sample e of the block is element e behind the block's first, a
+    // wave-uniform base + a 32-bit offset.  Ray and sample number of e advance from stripe to stripe by the quotient and remainder of
+    // stride / S (one division per thread in front of the loop instead of one per sample: the emission is bound by the instructions it
+    // issues, profiles/sampler_split.txt).
+    const int64_t first = (int64_t)blockIdx.x * GG_THREADS * S;
+    float* __restrict__ zb = z_vals + first;
+    float* __restrict__ pb = pts ? pts + 3 * first : nullptr;
+    const float* __restrict__ jb = jitter ? jitter + first : nullptr;
+    const float* __restrict__ ob = ray_o + 3 * (int64_t)blockIdx.x * GG_THREADS;
+    const float* __restrict__ db = ray_d + 3 * (int64_t)blockIdx.x * GG_THREADS;
+    const int step_r = stride / S, step_i = stride - step_r * S;
+    int e = part * GG_THREADS + tid;
+    int lr = e / S, i = e - lr * S;
+    // GG_EMIT_U stripes per iteration: their z, points and cells are independent, and the classification's returning atomics - one per
+    // run of equal cells, whose value the ranks wait for - go out together (dsn_nns_classify_batch).  (One stripe per iteration paid one
+    // atomic round trip per stripe: 64 in a row for a block of S = 64.)
+    while (e < total_up) {
         // ONE convergent call of the classification per iteration: its run detection uses wave-wide shuffles / ballots, so
-        // the tail lanes of a partial wave (e >= total) go through the same call site with valid = false instead of a call of their own
-        // under a partial exec mask
-        const bool valid = e < total;
-        const int ec = valid ? e : total - 1;
-        int lr = ec / S, i = ec - lr * S;
-        float nn = s_near[lr], ff = s_far[lr];
-        float ti = t_vals[i];
-        float z = nn * (1.0f - ti) + ff * ti;
-        int64_t g = (int64_t)(blockIdx.x * GG_THREADS + lr) * S + i;
-        if (jitter) {
-            float lower = z, upper = z;
-            if (i > 0) { float tp = t_vals[i - 1]; lower = 0.5f * (z + (nn * (1.0f - tp) + ff * tp)); }
-            if (i < S - 1) { float tn = t_vals[i + 1]; upper = 0.5f * ((nn * (1.0f - tn) + ff * tn) + z); }
-            z = lower + (upper - lower) * jitter[g];
+        // the tail lanes of a partial wave and the stripes past the block's end go through the same call site with valid = false
+        // instead of a call of their own under a partial exec mask
+        bool valid[GG_EMIT_U];
+        int at[GG_EMIT_U], si[GG_EMIT_U];
+        float p[GG_EMIT_U][3], ti[GG_EMIT_U], tp[GG_EMIT_U], tn[GG_EMIT_U], jt[GG_EMIT_U], nn[GG_EMIT_U], ff[GG_EMIT_U];
+        float o[GG_EMIT_U][3], d[GG_EMIT_U][3];
+        // every load of the batch first, with no lane-dependent branch between them (the compiler does not move a load across one, and a
+        // stripe that waits for its t and then for its ray before the next stripe asks for anything pays every round trip in a row)
+#pragma unroll
+        for (int u = 0; u < GG_EMIT_U; ++u) {
+            valid[u] = e < total;
+            at[u] = e;
+            si[u] = i;
+            const int lc = min(lr, rays_here - 1);                 // (past the block's end: any ray of the block, nothing is stored)
+            nn[u] = s_near[lc]; ff[u] = s_far[lc];
+            ti[u] = t_vals[i];
+            if (jb) {                                              // (uniform)
+                tp[u] = t_vals[max(i - 1, 0)]; tn[u] = t_vals[min(i + 1, S - 1)];
+                jt[u] = jb[valid[u] ? e : total - 1];
+            }
+            if (pb || cls.gf) {                                    // (uniform)
+#pragma unroll
+                for (int k = 0; k < 3; ++k) { o[u][k] = ob[3 * lc + k]; d[u][k] = db[3 * lc + k]; }
+            }
+            e += stride; lr += step_r; i += step_i;
+            if (i >= S) { i -= S; lr += 1; }
         }
-        if (valid) z_vals[g] = z;
-        if (pts || cls.gf) {
-            int rr = blockIdx.x * GG_THREADS + lr;
-            const float px = ray_o[3 * rr + 0] + ray_d[3 * rr + 0] * z;      // (the expression of k_warp / nns_point: same point, bit for bit)
-            const float py = ray_o[3 * rr + 1] + ray_d[3 * rr + 1] * z;
-            const float pz = ray_o[3 * rr + 2] + ray_d[3 * rr + 2] * z;
-            if (pts && valid) { pts[3 * g + 0] = px; pts[3 * g + 1] = py; pts[3 * g + 2] = pz; }
-            if (cls.gf) dsn_nns_classify_one(cls.gf, valid ? g : (int64_t)-1, valid, px, py, pz, cls.rank_of, cls.cell_of, cls.counts, cls.outside);
+#pragma unroll
+        for (int u = 0; u < GG_EMIT_U; ++u) {
+            float z = nn[u] * (1.0f - ti[u]) + ff[u] * ti[u];
+            if (jb) {
+                const float lower = si[u] > 0 ? 0.5f * (z + (nn[u] * (1.0f - tp[u]) + ff[u] * tp[u])) : z;
+                const float upper = si[u] < S - 1 ? 0.5f * ((nn[u] * (1.0f - tn[u]) + ff[u] * tn[u]) + z) : z;
+                z = lower + (upper - lower) * jt[u];
+            }
+            if (valid[u]) zb[at[u]] = z;
+            if (pb || cls.gf) {
+                p[u][0] = o[u][0] + d[u][0] * z;      // (the expression of k_warp / nns_point: same point, bit for bit)
+                p[u][1] = o[u][1] + d[u][1] * z;
+                p[u][2] = o[u][2] + d[u][2] * z;
+                if (pb && valid[u]) { pb[3 * at[u] + 0] = p[u][0]; pb[3 * at[u] + 1] = p[u][1]; pb[3 * at[u] + 2] = p[u][2]; }
+            }
         }
+        if (cls.gf) dsn_nns_classify_batch<GG_EMIT_U>(cls.gf, at, valid, p, cls.rank_of ? cls.rank_of + first : nullptr, cls.cell_of + first,
+                                                      cls.counts, cls.outside, s_slots + (tid >> 6) * DSN_CLASSIFY_SLOTS(GG_EMIT_U));
     }
 }
 
+// sweep and emission of a block of rays in ONE kernel: the batches neither cut below takes (S = 1, fewer than 512 vertices, and uniform
+// sampling, whose sweep is empty)
 __global__ void __launch_bounds__(GG_THREADS) k_sample_gg(const float* __restrict__ xyz, int V,
                                                            const float* __restrict__ ray_o,
                                                            const float* __restrict__ ray_d, float* __restrict__ near,
@@ -285,11 +423,13 @@ __global__ void __launch_bounds__(GG_THREADS) k_sample_gg(const float* __restric
                                                            const float* __restrict__ jitter, float* __restrict__ z_vals,
                                                            float* __restrict__ pts, GgClassify cls) {
     __shared__ float s_near[GG_THREADS], s_far[GG_THREADS];
+    __shared__ float4 sv2[2][GG_TILE];      // the sweep's two vertex tiles, then the emission's classification slots
+    static_assert(sizeof(sv2) >= GG_THREADS / 64 * DSN_CLASSIFY_SLOTS(GG_EMIT_U) * sizeof(int2), "the slots fit the tiles");
     const int tid = threadIdx.x;
     const int r = blockIdx.x * GG_THREADS + tid;
     float zmin, zmax, nrm;
     bool any;
-    gg_sweep(xyz, 0, V, ray_o, ray_d, R, zmin, zmax, any, nrm);
+    gg_sweep(xyz, 0, V, ray_o, ray_d, R, zmin, zmax, any, nrm, sv2);
     float n_ = 0.f, f_ = 0.f;
     if (r < R) {
         zmin = dsn_div(zmin, nrm);
@@ -299,7 +439,28 @@ __global__ void __launch_bounds__(GG_THREADS) k_sample_gg(const float* __restric
     }
     s_near[tid] = n_; s_far[tid] = f_;
     __syncthreads();
-    gg_emit(s_near, s_far, ray_o, ray_d, R, S, t_vals, jitter, z_vals, pts, cls);
+    // (the sweep's last barrier is behind every read of the tiles)
+    gg_emit(s_near, s_far, ray_o, ray_d, R, S, t_vals, jitter, z_vals, pts, reinterpret_cast<int2*>(&sv2[0][0]), cls);
+}
+
+// Frame size (more than 512 blocks of rays), cut in two: the whole sweep of a block's rays leaves near / far in place, and
+// k_sample_gg_emit turns them into z_vals with blockIdx.y parts per block.  In ONE kernel the emission of a block - 64 uniform stripes
+// for S = 64 - waited behind the slowest of its four sweeps (a wave keeps 0 .. 900 vertices), with four workgroups to a compute unit from
+// first to last; apart, the sweep runs at its own LDS and the emission on eight times the workgroups.  Same arithmetic on the same
+// values as k_sample_gg: the same near / far / z.  (profiles/sampler_split.txt)
+__global__ void __launch_bounds__(GG_THREADS) k_sample_gg_sweep(const float* __restrict__ xyz, int V, const float* __restrict__ ray_o,
+                                                                 const float* __restrict__ ray_d, float* __restrict__ near,
+                                                                 float* __restrict__ far, int R) {
+    __shared__ float4 sv2[2][GG_TILE];
+    const int r = blockIdx.x * GG_THREADS + threadIdx.x;
+    float zmin, zmax, nrm;
+    bool any;
+    gg_sweep(xyz, 0, V, ray_o, ray_d, R, zmin, zmax, any, nrm, sv2);
+    if (r < R) {
+        zmin = dsn_div(zmin, nrm);
+        zmax = dsn_div(zmax, nrm);
+        if (any && zmin < zmax) { near[r] = zmin; far[r] = zmax; }
+    }
 }
 
 // Few rays (a training batch, a 3072-ray chunk): the sweep of one block of rays is split over blockIdx.y vertex slices so the
@@ -320,9 +481,10 @@ __global__ void __launch_bounds__(GG_THREADS) k_sample_gg_slice(const float* __r
                                                                  float* __restrict__ z_vals) {
     const int r = blockIdx.x * GG_THREADS + threadIdx.x;
     const int v0 = blockIdx.y * slice, v1 = min(V, v0 + slice);
+    __shared__ float4 sv2[2][GG_TILE];
     float zmin, zmax, nrm;
     bool any;
-    gg_sweep(xyz, v0, v1, ray_o, ray_d, R, zmin, zmax, any, nrm);
+    gg_sweep(xyz, v0, v1, ray_o, ray_d, R, zmin, zmax, any, nrm, sv2);
     if (r < R && any) {
         atomicMin(reinterpret_cast<int*>(z_vals) + (int64_t)r * S, gg_key(zmin));
         atomicMax(reinterpret_cast<int*>(z_vals) + (int64_t)r * S + 1, gg_key(zmax));
@@ -352,12 +514,13 @@ __global__ void __launch_bounds__(GG_THREADS) k_sample_gg_emit(const float* __re
                                                                 const float* __restrict__ jitter, float* __restrict__ z_vals,
                                                                 float* __restrict__ pts, GgClassify cls) {
     __shared__ float s_near[GG_THREADS], s_far[GG_THREADS];
+    __shared__ int2 s_slots[GG_THREADS / 64 * DSN_CLASSIFY_SLOTS(GG_EMIT_U)];
     const int tid = threadIdx.x;
     const int r = blockIdx.x * GG_THREADS + tid;
     s_near[tid] = r < R ? near[r] : 0.f;
     s_far[tid] = r < R ? far[r] : 0.f;
     __syncthreads();
-    gg_emit(s_near, s_far, ray_o, ray_d, R, S, t_vals, jitter, z_vals, pts, cls, (int)blockIdx.y, (int)gridDim.y);
+    gg_emit(s_near, s_far, ray_o, ray_d, R, S, t_vals, jitter, z_vals, pts, s_slots, cls, (int)blockIdx.y, (int)gridDim.y);
 }
 
 void dsn_launch_sample_gg(const float* xyz, int V, const float* ray_o, const float* ray_d, float* near, float* far,
@@ -377,6 +540,15 @@ void dsn_launch_sample_gg(const float* xyz, int V, const float* ray_o, const flo
         hipLaunchKernelGGL(k_sample_gg_bounds, dim3(blocks), dim3(GG_THREADS), 0, st, ray_d, near, far, R, S, (const float*)z_vals);
         int parts = 2048 / blocks;                             // ~8 workgroups per CU for the emission
         if (parts > S) parts = S;                              // (a block of rays has S stripes of GG_THREADS samples)
+        if (parts < 1) parts = 1;
+        hipLaunchKernelGGL(k_sample_gg_emit, dim3(blocks, parts), dim3(GG_THREADS), 0, st, ray_o, ray_d, (const float*)near, (const float*)far, R, S,
+                           t_vals, jitter, z_vals, pts, cls);
+        return;
+    }
+    if (V > 0 && S >= 2 && blocks > 512) {                     // (above the few-ray path's reach: 1024 / blocks < 2)
+        hipLaunchKernelGGL(k_sample_gg_sweep, dim3(blocks), dim3(GG_THREADS), 0, st, xyz, V, ray_o, ray_d, near, far, R);
+        int parts = GG_FRAME_EMIT_GROUPS / blocks;             // measured at 1024 blocks: 1 / 4 / 8 parts 0.196 / 0.129 / 0.124 ms
+        if (parts > S) parts = S;
         if (parts < 1) parts = 1;
         hipLaunchKernelGGL(k_sample_gg_emit, dim3(blocks, parts), dim3(GG_THREADS), 0, st, ray_o, ray_d, (const float*)near, (const float*)far, R, S,
                            t_vals, jitter, z_vals, pts, cls);

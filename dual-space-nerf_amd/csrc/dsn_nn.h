@@ -178,6 +178,15 @@ __device__ __forceinline__ int dsn_grid_cell(const DsnGrid& g, float px, float p
     return (ix * g.ny + iy) * g.nz + iz;
 }
 
+// the same index without branches (dsn_nns_classify_batch): usable = the level's ok flag, or true for a lazy level's geometry
+__device__ __forceinline__ int dsn_grid_cell_flat(const DsnGrid& g, bool usable, float px, float py, float pz) {
+    const float fx = (px - g.lo[0]) * g.inv_cell, fy = (py - g.lo[1]) * g.inv_cell, fz = (pz - g.lo[2]) * g.inv_cell;
+    // (the conversions see 0 .. 2^20 only: what lies outside - or is NaN - is refused by the comparisons on fx, fy, fz themselves)
+    const int ix = (int)fminf(fmaxf(fx, 0.f), 1048576.f), iy = (int)fminf(fmaxf(fy, 0.f), 1048576.f), iz = (int)fminf(fmaxf(fz, 0.f), 1048576.f);
+    const bool in = usable && fx >= 0.f && fy >= 0.f && fz >= 0.f && ix < g.nx && iy < g.ny && iz < g.nz;
+    return in ? (ix * g.ny + iy) * g.nz + iz : -1;
+}
+
 // exact nearest centroid through the two-level lists; exhaustive scan (global memory) beyond them.
 // Fine lists carry the centroid inline (one 16-byte load per candidate, sequential addresses, lanes in the
 // same cell share them) and are scanned four at a time in list order, which keeps first-index-wins.
@@ -298,6 +307,56 @@ __device__ __forceinline__ int dsn_nns_classify_one(const DsnGrid* __restrict__ 
         if (om && lane == 0) atomicAdd(outside, __popcll(om));
     }
     return c;
+}
+
+// The same step for U samples per lane (the sampler's emit loop: U stripes of the block's samples per iteration), called by every lane of
+// a wave at ONE convergent call site, tail samples with valid = false.  Sample by sample the cell, the run and the rank rule are those of
+// the single form; what changes is who issues the atomics.  The heads of all U * 64 lanes' runs put (cell, length) into the wave's slot
+// array in LDS, compacted in (stripe, lane) order; then lane k takes slot k, so that ONE returning atomicAdd instruction serves up to 64
+// runs of the batch - a ray's 64 samples cross a handful of cells, so one round is the rule - and the wave waits for ONE atomic round
+// trip per batch, where U calls of the single form wait for U in a row.  (U atomics under U divergent branches do not do it: the
+// compiler waits for each before it leaves the branch.)  The bases come back through the slots.
+// slots: DSN_CLASSIFY_SLOTS(U) int2 of LDS owned by this wave (same-wave LDS accesses stay in order: no barrier).
+// i: the samples' places in cell_of / rank_of (32-bit: the caller hands in the arrays from its block's first sample on).
+#define DSN_CLASSIFY_SLOTS(U) ((U) * 64)
+template <int U>
+__device__ __forceinline__ void dsn_nns_classify_batch(const DsnGrid* __restrict__ gf, const int (&i)[U], const bool (&valid)[U],
+                                                       const float (&p)[U][3], int32_t* __restrict__ rank_of,
+                                                       int32_t* __restrict__ cell_of, int32_t* __restrict__ counts,
+                                                       int32_t* __restrict__ outside, int2* slots) {
+    const int lane = threadIdx.x & 63;
+    const bool usable = gf->lazy || gf->ok;      // (a lazy level classifies by its geometry, as in the single form)
+    int c[U], slot[U], rank[U];
+    int n_slots = 0;                         // (wave-uniform)
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        c[u] = valid[u] ? dsn_grid_cell_flat(*gf, usable, p[u][0], p[u][1], p[u][2]) : -1;
+        if (valid[u]) cell_of[i[u]] = c[u];
+        const NnsRun r = nns_run(c[u], lane);
+        const unsigned long long heads = __ballot(r.head);
+        slot[u] = n_slots + __popcll(heads & ((2ull << lane) - 1ull)) - 1;       // the slot of this lane's run (lane 0 is a head: >= 0)
+        rank[u] = r.rank;
+        if (r.head) slots[slot[u]] = make_int2(c[u], r.len);
+        n_slots += __popcll(heads);
+    }
+    for (int k0 = 0; k0 < n_slots; k0 += 64) {
+        const int k = k0 + lane;
+        if (k < n_slots) {
+            const int2 run = slots[k];
+            if (run.x >= 0) slots[k].x = atomicAdd(counts + run.x, run.y);
+        }
+    }
+    if (rank_of) {
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+            if (valid[u] && c[u] >= 0) rank_of[i[u]] = slots[slot[u]].x + rank[u];
+    }
+    if (outside) {
+        int n = 0;
+#pragma unroll
+        for (int u = 0; u < U; ++u) n += __popcll(__ballot(valid[u] && c[u] < 0));
+        if (n && lane == 0) atomicAdd(outside, n);
+    }
 }
 
 // fine level only: -1 when the point is outside the fine grid
