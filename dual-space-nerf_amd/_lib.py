@@ -50,6 +50,8 @@ EXPORTS = [
     "dsn_mesh_cc_workspace_bytes", "dsn_mesh_cc_label", "dsn_mesh_cc_emit", "dsn_mesh_cc_label_ex", "dsn_mesh_cc_emit_ex",
     "dsn_bound_mask", "dsn_train_rays_workspace_bytes", "dsn_train_rays",
     "dsn_mesh_bind_normals", "dsn_mesh_pose_workspace_bytes", "dsn_mesh_pose", "dsn_mesh_stretch",
+    "dsn_mesh_simplify_workspace_bytes", "dsn_mesh_simplify_count", "dsn_mesh_simplify_emit", "dsn_mesh_simplify_cells",
+    "dsn_mesh_simplify_count_ex", "dsn_mesh_simplify_emit_ex",
 ]
 
 SKIP_TRANSPARENT = 1
@@ -143,6 +145,16 @@ def lib():
         L.dsn_mesh_pose_workspace_bytes.argtypes = [C.c_int, C.c_int]
         L.dsn_mesh_pose.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_int64] + [C.c_void_p] * 5
         L.dsn_mesh_stretch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+        L.dsn_mesh_simplify_workspace_bytes.restype = C.c_size_t
+        L.dsn_mesh_simplify_workspace_bytes.argtypes = [C.c_int64, C.c_int64, C.c_void_p]
+        sp_count = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        sp_emit = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
+                   C.c_void_p]
+        L.dsn_mesh_simplify_count.argtypes = sp_count + [C.c_void_p]
+        L.dsn_mesh_simplify_count_ex.argtypes = sp_count + [C.c_int, C.c_void_p]
+        L.dsn_mesh_simplify_emit.argtypes = sp_emit + [C.c_void_p]
+        L.dsn_mesh_simplify_emit_ex.argtypes = sp_emit + [C.c_int, C.c_void_p]
+        L.dsn_mesh_simplify_cells.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
         if L.dsn_abi_version() != 8:
             raise RuntimeError(f"{LIB_PATH} has ABI version {L.dsn_abi_version()}, this binding needs 8 - rebuild it "
                                "(python dual-space-nerf_amd/build.py)")
@@ -757,6 +769,166 @@ def largest_component(verts, faces, want_source=True, info=None):
     if info is not None:
         info.update(n_components=n, winner=winner, area=math.ldexp(float(s), -shift - 1), faces_in_winner=fw, area_shift=shift)
     return out_v, out_f, src
+
+
+MESH_SIMPLIFY_MAX_G, MESH_SIMPLIFY_MAX_CLUSTERS = 4096, 1 << 21      # DSN_MESH_SIMPLIFY_MAX_G, 2^DSN_MESH_SIMPLIFY_MAX_LOG2
+MESH_SIMPLIFY_TOO_MANY, MESH_SIMPLIFY_TABLE_FULL = 1, 2               # DSN_MESH_SIMPLIFY_*: the status word of the counts
+SP_ZERO, SP_MARK, SP_RANK, SP_SUM, SP_PICK, SP_FACES, SP_KEEP, SP_EMIT_VERTS, SP_EMIT_FACES = 1, 2, 4, 8, 16, 32, 64, 128, 256      # DSN_SP_*
+MESH_SIMPLIFY_COUNTS = ("n_clusters", "n_faces", "live_faces", "duplicates_dropped", "vertices_outside", "bad_index_faces", "status")
+
+
+def _finite_box(verts):
+    """(lo [3], hi [3]) float32 numpy over the vertices whose coordinates are all finite, or None (one device->host read of six floats)"""
+    if verts.shape[0] == 0:
+        return None
+    fin = torch.isfinite(verts).all(dim=1, keepdim=True)
+    inf = torch.tensor(float("inf"), device=verts.device)
+    box = torch.cat([torch.where(fin, verts, inf).amin(dim=0), torch.where(fin, verts, -inf).amax(dim=0)]).cpu().numpy()
+    return (box[:3], box[3:]) if box[0] <= box[3] else None
+
+
+def mesh_simplify_grid(box, cell, origin=None, g=None):
+    """(origin float32 [3], g [3] ints) of dsn_mesh_simplify_* from the finite bounding box `box` = (lo, hi) or None: origin defaults to
+    lo (zeros without a finite vertex), g_a to floor((hi_a - origin_a) inv) + 1 in the rule's float32 operations, so that every
+    finite vertex is inside"""
+    import numpy as np
+    f32 = np.float32
+    if origin is None:
+        origin = np.zeros(3, f32) if box is None else box[0]
+    origin = np.ascontiguousarray(np.asarray(origin, f32).reshape(3))
+    if g is None:
+        if box is None:
+            g = [1, 1, 1]
+        else:
+            with np.errstate(all="ignore"):
+                tt = (np.asarray(box[1], f32) - origin) * (f32(1.0) / f32(cell))
+            g = [max(int(np.floor(x)) + 1, 1) if np.isfinite(x) else MESH_SIMPLIFY_MAX_G + 1 for x in tt]
+    g = [int(x) for x in g]
+    if len(g) != 3:
+        raise ValueError("mesh_simplify: g must hold three cell counts")
+    return origin, g
+
+
+def _mesh_simplify_check_grid(cell, origin, g):
+    import numpy as np
+    c = np.float32(cell)
+    if not (np.isfinite(c) and c > 0 and np.isfinite(np.float32(1.0) / c)):
+        raise ValueError(f"mesh_simplify: cell must be finite and > 0, got {cell!r}")
+    if not np.isfinite(origin).all():
+        raise ValueError("mesh_simplify: origin must be finite")
+    if not all(1 <= x <= MESH_SIMPLIFY_MAX_G for x in g) or g[0] * g[1] * g[2] > (1 << 31):
+        raise ValueError(f"mesh_simplify: the grid {g} is outside the limits (each count 1 ... {MESH_SIMPLIFY_MAX_G}, at most 2^31 cells): "
+                         "choose a larger cell")
+    return float(c), (C.c_int * 3)(*g)
+
+
+def mesh_cell_count(verts, cell, origin=None, g=None, box=None):
+    """dsn_mesh_simplify_cells: K, the number of grid cells the inside vertices of verts [V,3] (device float32) occupy - the vertex count
+    mesh_simplify would return.  One device->host read of 8 bytes (behind one of the bounding box unless origin and g, or `box`, are
+    given)."""
+    require_gpu()
+    assert verts.is_cuda, "verts: a device tensor"
+    verts = verts.reshape(-1, 3).to(torch.float32).contiguous()
+    V = verts.shape[0]
+    if box is None and (origin is None or g is None):
+        box = _finite_box(verts)
+    origin, g = mesh_simplify_grid(box, cell, origin, g)
+    c, g3 = _mesh_simplify_check_grid(cell, origin, g)
+    nbytes = lib().dsn_mesh_simplify_workspace_bytes(V, 0, g3)
+    if nbytes == 0:
+        raise RuntimeError("dsn_mesh_simplify_cells: the mesh must stay below 2^31 vertices")
+    ws = _scratch(nbytes, verts.device)
+    out = torch.empty(1, dtype=torch.int64, device=verts.device)
+    _check(lib().dsn_mesh_simplify_cells(_ptr(verts) if V else None, V, origin.ctypes.data, c, g3, _ptr(ws), nbytes, _ptr(out), _stream()),
+           "dsn_mesh_simplify_cells")
+    return int(out.cpu())
+
+
+def mesh_simplify(verts, faces, cell, origin=None, g=None, info=None):
+    """dsn_mesh_simplify_count + dsn_mesh_simplify_emit (the rule of include/dsnerf.h): vertex clustering on the grid of `cell`-sized
+    cells at `origin` with g = (g0, g1, g2) cells, every cluster represented by the member nearest to the members' mean.  Device
+    tensors in (verts [V,3] float32, faces [T,3] int32) and out: (verts' [K,3] float32, faces' [T',3] int32, cluster_source [K] int32,
+    vertex_cluster [V] int32) - verts' = verts[cluster_source] bit for bit, so per-vertex arrays follow by a[cluster_source.long()];
+    vertex_cluster holds the output vertex of every input vertex (-1: outside the grid).  origin defaults to the minimum over the
+    vertices whose coordinates are all finite, g to what covers them (mesh_simplify_grid).  One device->host read of the seven counts,
+    behind one of the bounding box where a default is taken.  More than 2^21 clusters: ValueError (choose a larger cell).  info: a
+    dict that receives the counts (MESH_SIMPLIFY_COUNTS), cell, origin and g."""
+    require_gpu()
+    assert verts.is_cuda and faces.is_cuda, "verts and faces: device tensors"
+    verts = verts.reshape(-1, 3).to(torch.float32).contiguous()
+    faces = faces.reshape(-1, 3).to(torch.int32).contiguous()
+    V, T = verts.shape[0], faces.shape[0]
+    dev = verts.device
+    box = _finite_box(verts) if origin is None or g is None else None
+    origin, g = mesh_simplify_grid(box, cell, origin, g)
+    c, g3 = _mesh_simplify_check_grid(cell, origin, g)
+    nbytes = lib().dsn_mesh_simplify_workspace_bytes(V, T, g3)
+    if nbytes == 0:
+        raise RuntimeError("dsn_mesh_simplify_count: the mesh must stay below 2^31 vertices and faces")
+    ws = _scratch(nbytes, dev)
+    counts = torch.empty(7, dtype=torch.int64, device=dev)
+    vc = torch.empty(V, dtype=torch.int32, device=dev)
+    vp, fp = (_ptr(verts) if V else None), (_ptr(faces) if T else None)
+    _check(lib().dsn_mesh_simplify_count(vp, fp, V, T, origin.ctypes.data, c, g3, _ptr(ws), nbytes, _ptr(vc) if V else None, _ptr(counts),
+                                         _stream()), "dsn_mesh_simplify_count")
+    n = [int(x) for x in counts.cpu()]
+    if info is not None:
+        info.update(dict(zip(MESH_SIMPLIFY_COUNTS, n)), cell=c, origin=origin.copy(), g=list(g))
+    if n[6] & MESH_SIMPLIFY_TOO_MANY:
+        raise ValueError(f"mesh_simplify: {n[0]} clusters, more than 2^21 = {MESH_SIMPLIFY_MAX_CLUSTERS}: choose a larger cell than {c:g}")
+    if n[6]:
+        raise RuntimeError(f"dsn_mesh_simplify_count: status {n[6]} (the duplicate table overflowed)")
+    K, nf = n[0], n[1]
+    out_v = torch.empty(K, 3, dtype=torch.float32, device=dev)
+    out_f = torch.empty(nf, 3, dtype=torch.int32, device=dev)
+    src = torch.empty(K, dtype=torch.int32, device=dev)
+    _check(lib().dsn_mesh_simplify_emit(vp, fp, V, T, g3, _ptr(ws), nbytes, K, nf, _ptr(out_v) if K else None, _ptr(out_f) if nf else None,
+                                        _ptr(src) if K else None, _stream()), "dsn_mesh_simplify_emit")
+    return out_v, out_f, src, vc
+
+
+MESH_TARGET_FACTOR = 1.0 + 2.0 ** -20      # the cell of n cells along the longest extent is a hair wider than extent / n: the far vertex stays in cell n - 1
+
+
+def mesh_target_cell(box, n):
+    """the cell of n cells along the longest finite extent of `box` = (lo, hi): float32(extent / n) (1 + 2^-20), every operation
+    float32; 1 where the extent is 0 or there is no finite vertex"""
+    import numpy as np
+    f32 = np.float32
+    if box is None:
+        return 1.0
+    ext = f32((np.asarray(box[1], f32) - np.asarray(box[0], f32)).max())
+    if not (ext > 0 and np.isfinite(ext)):
+        return 1.0
+    c = f32(f32(ext / f32(n)) * f32(MESH_TARGET_FACTOR))
+    return float(c) if (c > 0 and np.isfinite(c) and np.isfinite(f32(1.0) / c)) else 1.0
+
+
+def mesh_target_search(verts, target_vertices, info=None):
+    """The cell for at most `target_vertices` clusters: n = the number of cells along the longest finite extent, bisected in [1, 4096]
+    for the largest n with K(n) <= target_vertices by mesh_cell_count - at most 12 probes, one 8-byte host read each.  K(n) is treated
+    as monotone; it is not strictly so (a finer grid can by chance occupy fewer cells), so the n found is the bisection's, not
+    necessarily the largest that fits.  A grid outside the library's limits counts as too many.  Returns the cell; info receives n and
+    the probes."""
+    N = int(target_vertices)
+    if N < 1:
+        raise ValueError("target_vertices must be at least 1")
+    verts = verts.reshape(-1, 3).to(torch.float32).contiguous()
+    box = _finite_box(verts)
+    lo, hi, probes = 1, MESH_SIMPLIFY_MAX_G, []
+    while lo < hi:
+        mid = (lo + hi + 1) // 2
+        probes.append(mid)
+        c = mesh_target_cell(box, mid)
+        o, g = mesh_simplify_grid(box, c)
+        fits = all(1 <= x <= MESH_SIMPLIFY_MAX_G for x in g) and g[0] * g[1] * g[2] <= (1 << 31)
+        if fits and mesh_cell_count(verts, c, o, g) <= N:
+            lo = mid
+        else:
+            hi = mid - 1
+    if info is not None:
+        info.update(n=lo, probes=probes)
+    return mesh_target_cell(box, lo)
 
 
 MESH_POSE_BAD_BINDING = 1    # DSN_MESH_POSE_BAD_BINDING: dsn_mesh_pose's status bit

@@ -1220,7 +1220,8 @@ class Renderer:
         return axes, vol
 
     def extract_mesh(self, batch, resolution=512, level=0.5, gradient_direction="ascent", axes=None, points=None, frame=None,
-                     fp32=False, slab_points=None, normals=False, attributes=None, largest_component=False):
+                     fp32=False, slab_points=None, normals=False, attributes=None, largest_component=False, simplify_cell=None,
+                     target_vertices=None):
         """Visualizer3D's mesh of the posed body on the device: density_grid + marching cubes (dsn_mc_count / dsn_mc_emit, the rule of
         include/dsnerf.h).  Defaults are the visualizer's __main__ values.  Returns {"verts" [V,3] float32, "faces" [T,3] int32} device
         tensors in world coordinates, or None where the level is not crossed (the reference returns None there).
@@ -1231,7 +1232,13 @@ class Renderer:
         connected=True; dsn_mesh_cc_label / dsn_mesh_cc_emit, the rule of include/dsnerf.h) - floaters and inner shells go.  The
         filter runs right after marching cubes: the normals are gathered through "source_vertex" [V'] int32 (each kept vertex's index
         in the unfiltered mesh), the attributes are evaluated at the kept vertices only (per vertex and independent: the rows of
-        the unfiltered call, bit for bit), and "n_components" says how many pieces the surface had."""
+        the unfiltered call, bit for bit), and "n_components" says how many pieces the surface had.
+        simplify_cell / target_vertices (one of them): the mesh thinned by vertex clustering (visualizer.simplify_mesh: dsn_mesh_simplify_count
+        / dsn_mesh_simplify_emit, the rule of include/dsnerf.h) after the component filter and before the attributes, which are then
+        evaluated at the few vertices that stay - input vertices, so again the rows of the unsimplified call.  The dict gains
+        "cluster_source", "vertex_cluster" and "simplify_info"; normals and source_vertex are gathered."""
+        if simplify_cell is not None and target_vertices is not None:
+            raise ValueError("extract_mesh: give one of simplify_cell and target_vertices")
         names = tuple(attributes) if attributes else ()
         unknown = set(names) - set(self.MESH_ATTRIBUTES)
         if unknown:
@@ -1250,6 +1257,10 @@ class Renderer:
             if normals:
                 mesh["normals"] = out[2][src.long()]
             out = (v, f)
+        if simplify_cell is not None or target_vertices is not None:
+            from .visualizer import simplify_mesh
+            mesh = simplify_mesh(mesh, cell=simplify_cell, target_vertices=target_vertices)
+            out = (mesh["verts"], mesh["faces"])
         if names:
             a = self.mesh_attributes(batch, out[0], frame=frame)
             mesh.update({k: a[k] for k in names})

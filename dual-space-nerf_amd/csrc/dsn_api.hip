@@ -1359,6 +1359,92 @@ int dsn_mesh_cc_emit(const float* verts, const int32_t* faces, int64_t n_verts, 
                                source_vertex, 0, stream);
 }
 
+// the grid of dsn_mesh_simplify_*: every g_a in [1, 4096], at most 2^31 cells, a finite origin, a finite cell > 0 whose inverse is finite
+static bool dsn_mesh_simplify_grid_ok(const int* g) {
+    if (!g) return false;
+    for (int a = 0; a < 3; ++a)
+        if (g[a] < 1 || g[a] > DSN_MESH_SIMPLIFY_MAX_G) return false;
+    return (int64_t)g[0] * g[1] * g[2] <= ((int64_t)1 << 31);
+}
+
+size_t dsn_mesh_simplify_workspace_bytes(int64_t n_verts, int64_t n_faces, const int* g3_host) {
+    return dsn_mesh_cc_sizes_ok(n_verts, n_faces) && dsn_mesh_simplify_grid_ok(g3_host) ? dsn_mesh_simplify_workspace_size(n_verts, n_faces, g3_host) : 0;
+}
+
+#define DSN_SIMPLIFY_REQUIRE_GRID(name)                                                                                                       \
+    DSN_REQUIRE(origin_host && g3_host, name ": null argument");                                                                             \
+    DSN_REQUIRE(dsn_mesh_simplify_grid_ok(g3_host), name ": every g must be 1 ... 4096 and g0 g1 g2 at most 2^31");                          \
+    DSN_REQUIRE(std::isfinite(cell) && cell > 0.0f && std::isfinite(1.0f / cell), name ": cell must be finite and > 0");                     \
+    DSN_REQUIRE(std::isfinite(origin_host[0]) && std::isfinite(origin_host[1]) && std::isfinite(origin_host[2]), name ": origin must be finite")
+
+int dsn_mesh_simplify_count_ex(const float* verts, const int32_t* faces, int64_t n_verts, int64_t n_faces, const float* origin_host, float cell,
+                               const int* g3_host, void* workspace, size_t workspace_bytes, int32_t* vertex_cluster, int64_t* out_counts7,
+                               int phases, void* stream) {
+    DSN_REQUIRE(n_verts >= 0 && n_faces >= 0, "dsn_mesh_simplify_count: negative count");
+    DSN_REQUIRE(dsn_mesh_cc_sizes_ok(n_verts, n_faces), "dsn_mesh_simplify_count: 2^31 or more vertices or faces");
+    DSN_REQUIRE((n_verts == 0 || verts) && (n_faces == 0 || faces), "dsn_mesh_simplify_count: null mesh");
+    DSN_REQUIRE(workspace && out_counts7, "dsn_mesh_simplify_count: null argument");
+    DSN_SIMPLIFY_REQUIRE_GRID("dsn_mesh_simplify_count");
+    DSN_REQUIRE(workspace_bytes >= dsn_mesh_simplify_workspace_size(n_verts, n_faces, g3_host),
+                "dsn_mesh_simplify_count: workspace_bytes too small (dsn_mesh_simplify_workspace_bytes)");
+    DSN_REQUIRE(((uintptr_t)workspace & 15) == 0, "dsn_mesh_simplify_count: workspace must be 16-byte aligned");
+    DSN_REQUIRE(phases >= 0 && phases < 128, "dsn_mesh_simplify_count_ex: bad phases");
+    dsn_launch_mesh_simplify_count(verts, faces, n_verts, n_faces, origin_host, cell, g3_host, workspace, vertex_cluster, out_counts7,
+                                   phases ? phases : 127, (hipStream_t)stream);
+    return dsn_check_launch("dsn_mesh_simplify_count");
+}
+
+int dsn_mesh_simplify_count(const float* verts, const int32_t* faces, int64_t n_verts, int64_t n_faces, const float* origin_host, float cell,
+                            const int* g3_host, void* workspace, size_t workspace_bytes, int32_t* vertex_cluster, int64_t* out_counts7,
+                            void* stream) {
+    return dsn_mesh_simplify_count_ex(verts, faces, n_verts, n_faces, origin_host, cell, g3_host, workspace, workspace_bytes, vertex_cluster,
+                                      out_counts7, 0, stream);
+}
+
+int dsn_mesh_simplify_cells(const float* verts, int64_t n_verts, const float* origin_host, float cell, const int* g3_host, void* workspace,
+                            size_t workspace_bytes, int64_t* out_K, void* stream) {
+    DSN_REQUIRE(n_verts >= 0, "dsn_mesh_simplify_cells: negative count");
+    DSN_REQUIRE(dsn_mesh_cc_sizes_ok(n_verts, 0), "dsn_mesh_simplify_cells: 2^31 or more vertices");
+    DSN_REQUIRE(n_verts == 0 || verts, "dsn_mesh_simplify_cells: null mesh");
+    DSN_REQUIRE(workspace && out_K, "dsn_mesh_simplify_cells: null argument");
+    DSN_SIMPLIFY_REQUIRE_GRID("dsn_mesh_simplify_cells");
+    DSN_REQUIRE(workspace_bytes >= dsn_mesh_simplify_workspace_size(n_verts, 0, g3_host),
+                "dsn_mesh_simplify_cells: workspace_bytes too small (dsn_mesh_simplify_workspace_bytes with 0 faces)");
+    DSN_REQUIRE(((uintptr_t)workspace & 15) == 0, "dsn_mesh_simplify_cells: workspace must be 16-byte aligned");
+    dsn_launch_mesh_simplify_cells(verts, n_verts, origin_host, cell, g3_host, workspace, out_K, (hipStream_t)stream);
+    return dsn_check_launch("dsn_mesh_simplify_cells");
+}
+
+int dsn_mesh_simplify_emit_ex(const float* verts, const int32_t* faces, int64_t n_verts, int64_t n_faces, const int* g3_host, void* workspace,
+                              size_t workspace_bytes, int64_t out_n_verts, int64_t out_n_faces, float* out_verts, int32_t* out_faces,
+                              int32_t* cluster_source, int phases, void* stream) {
+    DSN_REQUIRE(n_verts >= 0 && n_faces >= 0 && out_n_verts >= 0 && out_n_faces >= 0, "dsn_mesh_simplify_emit: negative count");
+    DSN_REQUIRE(dsn_mesh_cc_sizes_ok(n_verts, n_faces), "dsn_mesh_simplify_emit: 2^31 or more vertices or faces");
+    DSN_REQUIRE(g3_host, "dsn_mesh_simplify_emit: null argument");
+    DSN_REQUIRE(dsn_mesh_simplify_grid_ok(g3_host), "dsn_mesh_simplify_emit: every g must be 1 ... 4096 and g0 g1 g2 at most 2^31");
+    DSN_REQUIRE(out_n_verts <= n_verts && out_n_verts <= (int64_t)g3_host[0] * g3_host[1] * g3_host[2] &&
+                    out_n_verts <= ((int64_t)1 << DSN_MESH_SIMPLIFY_MAX_LOG2) && out_n_faces <= n_faces,
+                "dsn_mesh_simplify_emit: more clusters or faces than dsn_mesh_simplify_count can have reported");
+    DSN_REQUIRE((n_verts == 0 || verts) && (n_faces == 0 || faces), "dsn_mesh_simplify_emit: null mesh");
+    DSN_REQUIRE(workspace, "dsn_mesh_simplify_emit: null argument");
+    DSN_REQUIRE((out_n_verts == 0 || out_verts) && (out_n_faces == 0 || out_faces), "dsn_mesh_simplify_emit: null output buffer");
+    DSN_REQUIRE(workspace_bytes >= dsn_mesh_simplify_workspace_size(n_verts, n_faces, g3_host),
+                "dsn_mesh_simplify_emit: workspace_bytes too small (dsn_mesh_simplify_workspace_bytes)");
+    DSN_REQUIRE(((uintptr_t)workspace & 15) == 0, "dsn_mesh_simplify_emit: workspace must be 16-byte aligned");
+    DSN_REQUIRE(phases == 0 || (phases & ~(DSN_SP_EMIT_VERTS | DSN_SP_EMIT_FACES)) == 0, "dsn_mesh_simplify_emit_ex: bad phases");
+    if (out_n_verts == 0 && out_n_faces == 0) return 0;
+    dsn_launch_mesh_simplify_emit(verts, faces, n_verts, n_faces, g3_host, workspace, out_verts, out_n_verts, out_faces, out_n_faces,
+                                  cluster_source, phases ? phases : (DSN_SP_EMIT_VERTS | DSN_SP_EMIT_FACES), (hipStream_t)stream);
+    return dsn_check_launch("dsn_mesh_simplify_emit");
+}
+
+int dsn_mesh_simplify_emit(const float* verts, const int32_t* faces, int64_t n_verts, int64_t n_faces, const int* g3_host, void* workspace,
+                           size_t workspace_bytes, int64_t out_n_verts, int64_t out_n_faces, float* out_verts, int32_t* out_faces,
+                           int32_t* cluster_source, void* stream) {
+    return dsn_mesh_simplify_emit_ex(verts, faces, n_verts, n_faces, g3_host, workspace, workspace_bytes, out_n_verts, out_n_faces, out_verts,
+                                     out_faces, cluster_source, 0, stream);
+}
+
 // counts of the bound-mesh calls: every byte size fits size_t and every grid fits 2^31 - 1 workgroups of 256
 static bool dsn_mesh_pose_sizes_ok(int64_t P, int64_t N) {
     return P >= 1 && N >= 0 && N < ((int64_t)1 << 38) && (uint64_t)N <= (uint64_t)SIZE_MAX / 12 / (uint64_t)P;

@@ -220,6 +220,14 @@ void dsn_launch_mesh_cc_label(const float* verts, const int32_t* faces, int64_t 
                               int64_t* out_counts, int phases, hipStream_t st);
 void dsn_launch_mesh_cc_emit(const float* verts, const int32_t* faces, int64_t V, int64_t T, void* workspace, float* out_verts, int64_t vcap,
                              int32_t* out_faces, int64_t fcap, int32_t* source_vertex, int phases, hipStream_t st);
+// dsn_mesh.hip: vertex clustering with a picked representative (dsn_mesh_simplify_*; g: the grid's three cell counts; phases: DSN_SP_*)
+size_t dsn_mesh_simplify_workspace_size(int64_t V, int64_t T, const int* g);
+void dsn_launch_mesh_simplify_count(const float* verts, const int32_t* faces, int64_t V, int64_t T, const float* origin, float cell, const int* g,
+                                    void* workspace, int32_t* vertex_cluster, int64_t* out_counts, int phases, hipStream_t st);
+void dsn_launch_mesh_simplify_cells(const float* verts, int64_t V, const float* origin, float cell, const int* g, void* workspace, int64_t* out_K,
+                                    hipStream_t st);
+void dsn_launch_mesh_simplify_emit(const float* verts, const int32_t* faces, int64_t V, int64_t T, const int* g, void* workspace, float* out_verts,
+                                   int64_t vcap, int32_t* out_faces, int64_t fcap, int32_t* cluster_source, int phases, hipStream_t st);
 // dsn_mesh.hip: a mesh bound to the body (dsn_mesh_bind_normals / dsn_mesh_pose / dsn_mesh_stretch; workspace: DsnFaceRec [P, Fb])
 void dsn_launch_mesh_bind_normals(const float* body, int Vb, const int32_t* bfaces, int Fb, const int32_t* face_idx, const float* normals,
                                   int64_t N, float* cov, hipStream_t st);

@@ -868,3 +868,425 @@ void dsn_launch_mesh_stretch(const float* bind, const float* posed, int P, int64
     if (T <= 0) return;
     hipLaunchKernelGGL(k_mesh_stretch, dim3(mesh_blocks(T)), dim3(MC_THREADS), 0, st, bind, posed, P, N, faces, T, stretch);
 }
+
+// ---------------------------------------------------------------------------------------------
+// vertex clustering with a picked representative (dsn_mesh_simplify_*, the rule of include/dsnerf.h)
+//   count: zero (the bit grid, the cluster slots, the triple table) -> mark (one thread per vertex: its cell, one bit per occupied cell)
+//          -> rank (popcount prefix over the bit-grid words, the tile scan of the marching cubes: a cell's cluster is the number of occupied
+//          cells below it) -> sum (64-bit integer adds of the members' fixed-point coordinates, aggregated per run of equal clusters in the
+//          wave) -> pick (one 64-bit unsigned atomic minimum of (float32 distance bits, vertex index) per run) -> faces (the clusters of a
+//          face; a live face claims the slot of its sorted triple in a lock-free open-addressing table by compare-and-swap and leaves the
+//          minimum of its index there) -> keep (a face is kept when it is its slot's minimum; the tile scan over the keep flags);
+//   emit : one thread per cluster copies its representative, the workgroup scan over the keep flags orders the faces.
+// Every value read back from the workspace is range-checked before it is used as an index: the measurement entries can run a phase on a
+// workspace the phases before it never wrote.
+// ---------------------------------------------------------------------------------------------
+#define SP_CAP ((int64_t)1 << DSN_MESH_SIMPLIFY_MAX_LOG2)
+#define SP_EMPTY 0xFFFFFFFFFFFFFFFFull          // (a packed triple has bit 63 clear)
+enum { SP_K = 0, SP_KEPT = 1, SP_LIVE = 2, SP_OUTSIDE = 3, SP_BAD = 4, SP_STATUS = 5 };      // the header's 64-bit words
+
+struct SpGrid { float o[3]; float inv; int g[3]; };
+
+static int64_t sp_cells(const int* g) { return (int64_t)g[0] * g[1] * g[2]; }
+static int64_t sp_table_slots(int64_t T) {      // a power of two, load <= 1/2
+    int64_t c = 64;
+    while (c < 2 * T) c <<= 1;
+    return c;
+}
+// header 64 B | cell int32 [V] | cluster int32 [V] | bit grid uint32 [W] | in-tile word prefix int32 [W] | word tile offsets int64
+// [tilesW + 1] | cluster sums int64 [Kmax, 4] (s0, s1, s2, n) | cluster keys uint64 [Kmax] | table keys uint64 [slots] | table minima
+// int32 [slots] | keep uint8 [T] | face tile offsets int64 [tilesT + 1]            (every part 16-byte aligned)
+struct SpWs {
+    unsigned long long* head; int32_t* cell; int32_t* vc; uint32_t* bits; int32_t* pre; int64_t* tw; unsigned long long* sum;
+    unsigned long long* key; unsigned long long* tab; int32_t* tmin; uint8_t* keep; int64_t* tf;
+    int64_t G, W, tilesW, Kmax, slots, tilesT; size_t bytes;
+};
+static SpWs sp_ws(void* w, int64_t V, int64_t T, const int* g) {
+    SpWs r;
+    r.G = sp_cells(g);
+    r.W = (r.G + 31) / 32;
+    r.tilesW = mc_tiles(r.W);
+    r.Kmax = V < r.G ? V : r.G;
+    if (r.Kmax > SP_CAP) r.Kmax = SP_CAP;
+    r.slots = sp_table_slots(T);
+    r.tilesT = cc_tiles(T);
+    char* p = (char*)w;
+    size_t o = 0;
+    r.head = (unsigned long long*)(p + o); o += 64;
+    r.cell = (int32_t*)(p + o); o += cc_up((size_t)4 * V);
+    r.vc = (int32_t*)(p + o); o += cc_up((size_t)4 * V);
+    r.bits = (uint32_t*)(p + o); o += cc_up((size_t)4 * r.W);
+    r.pre = (int32_t*)(p + o); o += cc_up((size_t)4 * r.W);
+    r.tw = (int64_t*)(p + o); o += cc_up((size_t)8 * (r.tilesW + 1));
+    r.sum = (unsigned long long*)(p + o); o += cc_up((size_t)32 * r.Kmax);
+    r.key = (unsigned long long*)(p + o); o += cc_up((size_t)8 * r.Kmax);
+    r.tab = (unsigned long long*)(p + o); o += cc_up((size_t)8 * r.slots);
+    r.tmin = (int32_t*)(p + o); o += cc_up((size_t)4 * r.slots);
+    r.keep = (uint8_t*)(p + o); o += cc_up((size_t)T);
+    r.tf = (int64_t*)(p + o); o += cc_up((size_t)8 * (r.tilesT + 1));
+    r.bytes = o;
+    return r;
+}
+size_t dsn_mesh_simplify_workspace_size(int64_t V, int64_t T, const int* g) { return sp_ws(nullptr, V, T, g).bytes; }
+
+static SpGrid sp_grid(const float* origin, float cell, const int* g) {
+    SpGrid r;
+    for (int a = 0; a < 3; ++a) { r.o[a] = origin[a]; r.g[a] = g[a]; }
+    r.inv = 1.0f / cell;
+    return r;
+}
+
+// zero: the bit grid, the cluster slots (sums 0, keys all ones), the table (keys empty, minima INT_MAX), the header's counters
+__global__ void __launch_bounds__(MC_THREADS) k_sp_zero(uint32_t* __restrict__ bits, int64_t W, unsigned long long* __restrict__ sum,
+                                                        unsigned long long* __restrict__ key, int64_t Kmax, unsigned long long* __restrict__ tab,
+                                                        int32_t* __restrict__ tmin, int64_t slots, unsigned long long* __restrict__ head) {
+    const int64_t stride = (int64_t)gridDim.x * MC_THREADS;
+    const int64_t i0 = (int64_t)blockIdx.x * MC_THREADS + threadIdx.x;
+    for (int64_t i = i0; i < W; i += stride) bits[i] = 0u;
+    for (int64_t i = i0; i < Kmax; i += stride) { sum[4 * i] = 0; sum[4 * i + 1] = 0; sum[4 * i + 2] = 0; sum[4 * i + 3] = 0; key[i] = SP_EMPTY; }
+    for (int64_t i = i0; i < slots; i += stride) { tab[i] = SP_EMPTY; tmin[i] = 0x7FFFFFFF; }
+    if (i0 < 8) head[i0] = 0;
+}
+
+// t_a = (x_a - origin_a) inv; inside: every t_a finite, >= 0 and < g_a (NaN fails the comparisons, +inf the second)
+__device__ __forceinline__ bool sp_locate(const float* __restrict__ verts, int64_t v, const SpGrid& G, float t[3], int64_t& cell) {
+    bool in = true;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        t[a] = (verts[3 * v + a] - G.o[a]) * G.inv;
+        in = in && t[a] >= 0.0f && t[a] < (float)G.g[a];
+    }
+    cell = -1;
+    if (in) cell = ((int64_t)(int)floorf(t[0]) * G.g[1] + (int)floorf(t[1])) * G.g[2] + (int)floorf(t[2]);
+    return in;
+}
+// q_a = floor(double(t_a) 2^20): exact, below 2^32
+__device__ __forceinline__ unsigned long long sp_q(float t) { return (unsigned long long)floor((double)t * 1048576.0); }
+
+__global__ void __launch_bounds__(MC_THREADS) k_sp_mark(const float* __restrict__ verts, int64_t V, SpGrid G, int32_t* __restrict__ cellv,
+                                                        uint32_t* __restrict__ bits, unsigned long long* __restrict__ head) {
+    const int64_t v = (int64_t)blockIdx.x * MC_THREADS + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    const bool have = v < V;
+    float t[3];
+    int64_t cell = -1;
+    const bool in = have && sp_locate(verts, v, G, t, cell);
+    const int32_t c = in ? (int32_t)cell : -1;      // (cells < 2^31)
+    if (have) cellv[v] = c;
+    // marching-cubes vertices arrive x-major: neighbouring lanes share cells, a run of equal cells issues one atomic
+    const int32_t prev = __shfl_up(c, 1);
+    if (in && (lane == 0 || prev != c)) __hip_atomic_fetch_or(bits + (c >> 5), 1u << (c & 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const unsigned long long out = __ballot(have && !in);
+    if (lane == 0 && out) atomicAdd(head + SP_OUTSIDE, (unsigned long long)__popcll(out));
+}
+
+// in-tile exclusive popcount prefix of every bit-grid word, and the tile's total
+__global__ void __launch_bounds__(MC_THREADS) k_sp_rank(const uint32_t* __restrict__ bits, int64_t W, int32_t* __restrict__ pre,
+                                                        int64_t* __restrict__ tw) {
+    const int64_t w0 = (int64_t)blockIdx.x * MC_TILE + (int64_t)threadIdx.x * MC_PER;
+    int n = 0;
+    for (int q = 0; q < MC_PER && w0 + q < W; ++q) n += __popc(bits[w0 + q]);
+    int a = n, b = 0, tot_a, tot_b;
+    mc_block_scan(a, b, tot_a, tot_b);
+    for (int q = 0; q < MC_PER && w0 + q < W; ++q) { pre[w0 + q] = a; a += __popc(bits[w0 + q]); }
+    if (threadIdx.x == 0) tw[blockIdx.x] = tot_a;
+}
+
+// one workgroup: exclusive scan of the tiles' totals in place, [tiles] = the total, also to *total; cap > 0: a total above it sets
+// DSN_MESH_SIMPLIFY_TOO_MANY in *status
+__global__ void __launch_bounds__(MC_SCAN_THREADS) k_sp_scan(int64_t* __restrict__ tv, int64_t tiles, unsigned long long* __restrict__ total,
+                                                             int64_t cap, unsigned long long* __restrict__ status) {
+    __shared__ int64_t sa[MC_SCAN_THREADS];
+    const int t = threadIdx.x;
+    const int64_t per = (tiles + MC_SCAN_THREADS - 1) / MC_SCAN_THREADS;
+    const int64_t b0 = t * per < tiles ? t * per : tiles, b1 = b0 + per < tiles ? b0 + per : tiles;
+    int64_t a = 0;
+    for (int64_t k = b0; k < b1; ++k) a += tv[k];
+    sa[t] = a;
+    __syncthreads();
+    for (int off = 1; off < MC_SCAN_THREADS; off <<= 1) {
+        const int64_t xa = t >= off ? sa[t - off] : 0;
+        __syncthreads();
+        sa[t] += xa;
+        __syncthreads();
+    }
+    int64_t ra = sa[t] - a;
+    for (int64_t k = b0; k < b1; ++k) { const int64_t va = tv[k]; tv[k] = ra; ra += va; }
+    if (t == MC_SCAN_THREADS - 1) {
+        tv[tiles] = sa[t];
+        *total = (unsigned long long)sa[t];
+        if (cap > 0 && sa[t] > cap) atomicOr(status, (unsigned long long)DSN_MESH_SIMPLIFY_TOO_MANY);
+    }
+}
+
+// the run of equal keys a lane belongs to (keys of neighbouring lanes; a key that comes back later in the wave starts a new run)
+__device__ __forceinline__ int sp_run(int32_t key, int lane, bool& first) {
+    const int32_t prev = __shfl_up(key, 1);
+    first = lane == 0 || prev != key;
+    const unsigned long long heads = __ballot(first);
+    return __popcll(heads & ((2ull << lane) - 1ull));
+}
+
+// every vertex's cluster = the occupied cells below its cell; the clusters' integer sums
+__global__ void __launch_bounds__(MC_THREADS) k_sp_sum(const float* __restrict__ verts, int64_t V, SpGrid G, int64_t ncell,
+                                                       const int32_t* __restrict__ cellv, const uint32_t* __restrict__ bits,
+                                                       const int32_t* __restrict__ pre, const int64_t* __restrict__ tw, int64_t Kmax,
+                                                       const unsigned long long* __restrict__ head, int32_t* __restrict__ vc,
+                                                       int32_t* __restrict__ vc_out, unsigned long long* __restrict__ sum) {
+    const int64_t v = (int64_t)blockIdx.x * MC_THREADS + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    const bool capped = (head[SP_STATUS] & DSN_MESH_SIMPLIFY_TOO_MANY) != 0;
+    int32_t cl = -1;
+    if (v < V) {
+        const int32_t c = cellv[v];
+        if ((uint64_t)(uint32_t)c < (uint64_t)ncell && c >= 0) {
+            const int64_t w = c >> 5;
+            cl = (int32_t)(tw[w / MC_TILE] + pre[w] + __popc(bits[w] & ((1u << (c & 31)) - 1u)));
+        }
+        vc[v] = cl;
+        if (vc_out) vc_out[v] = cl;
+    }
+    const bool doit = !capped && (uint64_t)(uint32_t)cl < (uint64_t)Kmax && cl >= 0;
+    unsigned long long q0 = 0, q1 = 0, q2 = 0;
+    int n = 0;
+    if (doit) {
+        float t[3];
+        int64_t cell;
+        sp_locate(verts, v, G, t, cell);
+        q0 = sp_q(t[0]); q1 = sp_q(t[1]); q2 = sp_q(t[2]); n = 1;
+    }
+    bool first;
+    const int32_t key = doit ? cl : -1;
+    const int run = sp_run(key, lane, first);
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const unsigned long long x0 = __shfl_down(q0, off), x1 = __shfl_down(q1, off), x2 = __shfl_down(q2, off);
+        const int xn = __shfl_down(n, off), xr = __shfl_down(run, off);
+        if (lane + off < 64 && xr == run) { q0 += x0; q1 += x1; q2 += x2; n += xn; }
+    }
+    if (first && doit) {
+        unsigned long long* s = sum + 4 * (int64_t)cl;
+        atomicAdd(s, q0); atomicAdd(s + 1, q1); atomicAdd(s + 2, q2); atomicAdd(s + 3, (unsigned long long)n);
+    }
+}
+
+// the representative: the member that minimises (bits of float32(d)) << 32 | vertex index
+__global__ void __launch_bounds__(MC_THREADS) k_sp_pick(const float* __restrict__ verts, int64_t V, SpGrid G, const int32_t* __restrict__ vc,
+                                                        int64_t Kmax, const unsigned long long* __restrict__ head,
+                                                        const unsigned long long* __restrict__ sum, unsigned long long* __restrict__ key) {
+    const int64_t v = (int64_t)blockIdx.x * MC_THREADS + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    const bool capped = (head[SP_STATUS] & DSN_MESH_SIMPLIFY_TOO_MANY) != 0;
+    const int32_t cl = v < V ? vc[v] : -1;
+    const bool doit = !capped && (uint64_t)(uint32_t)cl < (uint64_t)Kmax && cl >= 0;
+    unsigned long long k = SP_EMPTY;
+    if (doit) {
+        float t[3];
+        int64_t cell;
+        sp_locate(verts, v, G, t, cell);
+        const unsigned long long* s = sum + 4 * (int64_t)cl;
+        const double n = (double)(long long)s[3];
+        const double e0 = (double)(long long)sp_q(t[0]) - (double)(long long)s[0] / n;
+        const double e1 = (double)(long long)sp_q(t[1]) - (double)(long long)s[1] / n;
+        const double e2 = (double)(long long)sp_q(t[2]) - (double)(long long)s[2] / n;
+        const double d = (e0 * e0 + e1 * e1) + e2 * e2;
+        k = ((unsigned long long)__float_as_uint((float)d) << 32) | (unsigned long long)(uint32_t)v;
+    }
+    bool first;
+    const int run = sp_run(doit ? cl : -1, lane, first);
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const unsigned long long xk = __shfl_down(k, off);
+        const int xr = __shfl_down(run, off);
+        if (lane + off < 64 && xr == run && xk < k) k = xk;
+    }
+    if (first && doit) __hip_atomic_fetch_min(key + cl, k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// the clusters of face t: 0 a bad index, 1 not live (a vertex outside or two clusters equal), 2 live with the packed sorted triple
+__device__ __forceinline__ int sp_face(const int32_t* __restrict__ faces, int64_t t, int64_t V, const int32_t* __restrict__ vc, int32_t c[3],
+                                       unsigned long long& packed) {
+    int32_t i0, i1, i2;
+    if (!cc_face(faces, t, (int)V, i0, i1, i2)) return 0;
+    c[0] = vc[i0]; c[1] = vc[i1]; c[2] = vc[i2];
+    if ((uint32_t)c[0] >= (uint32_t)SP_CAP || (uint32_t)c[1] >= (uint32_t)SP_CAP || (uint32_t)c[2] >= (uint32_t)SP_CAP) return 1;
+    if (c[0] == c[1] || c[1] == c[2] || c[0] == c[2]) return 1;
+    const int32_t lo = min(c[0], min(c[1], c[2])), hi = max(c[0], max(c[1], c[2])), mid = c[0] ^ c[1] ^ c[2] ^ lo ^ hi;
+    packed = ((unsigned long long)lo << 42) | ((unsigned long long)mid << 21) | (unsigned long long)hi;
+    return 2;
+}
+__device__ __forceinline__ uint64_t sp_hash(unsigned long long k) {      // (splitmix64's finaliser)
+    k ^= k >> 30; k *= 0xBF58476D1CE4E5B9ull;
+    k ^= k >> 27; k *= 0x94D049BB133111EBull;
+    return k ^ (k >> 31);
+}
+
+// a live face claims the slot of its triple and leaves the minimum of its index there.  The probe is bounded by the table's capacity and
+// no thread waits for another: a slot's key goes from empty to one triple once and never changes again.
+__global__ void __launch_bounds__(MC_THREADS) k_sp_faces(const int32_t* __restrict__ faces, int64_t V, int64_t T, const int32_t* __restrict__ vc,
+                                                         unsigned long long* __restrict__ tab, int32_t* __restrict__ tmin, int64_t slots,
+                                                         unsigned long long* __restrict__ head) {
+    const int64_t t = (int64_t)blockIdx.x * MC_THREADS + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    const bool capped = (head[SP_STATUS] & DSN_MESH_SIMPLIFY_TOO_MANY) != 0;
+    int32_t c[3];
+    unsigned long long packed = 0;
+    const int kind = (t < T && !capped) ? sp_face(faces, t, V, vc, c, packed) : -1;
+    if (kind == 2) {
+        uint64_t s = sp_hash(packed) & (uint64_t)(slots - 1);
+        bool placed = false;
+        for (int64_t step = 0; step < slots; ++step) {
+            unsigned long long seen = __hip_atomic_load(tab + s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (seen == SP_EMPTY)
+                seen = __hip_atomic_compare_exchange_strong(tab + s, &seen, packed, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+                           ? packed : seen;      // (a failed exchange leaves the slot's triple in `seen`)
+            if (seen == packed) {
+                __hip_atomic_fetch_min(tmin + s, (int32_t)t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                placed = true;
+                break;
+            }
+            s = (s + 1) & (uint64_t)(slots - 1);
+        }
+        if (!placed) atomicOr(head + SP_STATUS, (unsigned long long)DSN_MESH_SIMPLIFY_TABLE_FULL);
+    }
+    const unsigned long long live = __ballot(kind == 2), bad = __ballot(kind == 0);
+    if (lane == 0 && live) atomicAdd(head + SP_LIVE, (unsigned long long)__popcll(live));
+    if (lane == 0 && bad) atomicAdd(head + SP_BAD, (unsigned long long)__popcll(bad));
+}
+
+// keep[t] = the face is live and the smallest index of its triple's slot; the kept faces of tile blockIdx.x
+__global__ void __launch_bounds__(MC_THREADS) k_sp_keep(const int32_t* __restrict__ faces, int64_t V, int64_t T, const int32_t* __restrict__ vc,
+                                                        const unsigned long long* __restrict__ tab, const int32_t* __restrict__ tmin,
+                                                        int64_t slots, const unsigned long long* __restrict__ head, uint8_t* __restrict__ keep,
+                                                        int64_t* __restrict__ tf) {
+    const bool capped = (head[SP_STATUS] & DSN_MESH_SIMPLIFY_TOO_MANY) != 0;
+    const int64_t n0 = (int64_t)blockIdx.x * CC_TILE + (int64_t)threadIdx.x * CC_PER;
+    int nf = 0, none = 0, tot_f, tot_n;
+    for (int q = 0; q < CC_PER && n0 + q < T; ++q) {
+        const int64_t t = n0 + q;
+        int32_t c[3];
+        unsigned long long packed = 0;
+        uint8_t k = 0;
+        if (!capped && sp_face(faces, t, V, vc, c, packed) == 2) {
+            uint64_t s = sp_hash(packed) & (uint64_t)(slots - 1);
+            for (int64_t step = 0; step < slots; ++step) {
+                const unsigned long long seen = tab[s];
+                if (seen == packed) { k = tmin[s] == (int32_t)t; break; }
+                if (seen == SP_EMPTY) break;
+                s = (s + 1) & (uint64_t)(slots - 1);
+            }
+        }
+        keep[t] = k;
+        nf += k;
+    }
+    mc_block_scan(nf, none, tot_f, tot_n);
+    if (threadIdx.x == 0) tf[blockIdx.x] = tot_f;
+}
+
+// out_counts: {K, kept faces, live faces, duplicates dropped, vertices outside, faces with a bad index, status}
+__global__ void k_sp_counts(const unsigned long long* __restrict__ head, int64_t* __restrict__ out) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    const bool capped = (head[SP_STATUS] & DSN_MESH_SIMPLIFY_TOO_MANY) != 0;
+    out[0] = (int64_t)head[SP_K];
+    out[1] = capped ? 0 : (int64_t)head[SP_KEPT];
+    out[2] = (int64_t)head[SP_LIVE];
+    out[3] = capped ? 0 : (int64_t)(head[SP_LIVE] - head[SP_KEPT]);
+    out[4] = (int64_t)head[SP_OUTSIDE];
+    out[5] = (int64_t)head[SP_BAD];
+    out[6] = (int64_t)head[SP_STATUS];
+}
+__global__ void k_sp_count_cells(const unsigned long long* __restrict__ head, int64_t* __restrict__ out) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) out[0] = (int64_t)head[SP_K];
+}
+
+__global__ void __launch_bounds__(MC_THREADS) k_sp_emit_verts(const float* __restrict__ verts, int64_t V, const unsigned long long* __restrict__ head,
+                                                              const unsigned long long* __restrict__ key, int64_t Kmax,
+                                                              float* __restrict__ out_verts, int64_t vcap, int32_t* __restrict__ source) {
+    const int64_t k = (int64_t)blockIdx.x * MC_THREADS + threadIdx.x;
+    if (head[SP_STATUS] != 0 || k >= vcap || k >= Kmax || (unsigned long long)k >= head[SP_K]) return;
+    const uint32_t src = (uint32_t)key[k];
+    if ((uint64_t)src >= (uint64_t)V) return;
+    const uint32_t* in = (const uint32_t*)verts + 3 * (int64_t)src;      // the representative's three words, copied
+    uint32_t* o = (uint32_t*)out_verts + 3 * k;
+    o[0] = in[0]; o[1] = in[1]; o[2] = in[2];
+    if (source) source[k] = (int32_t)src;
+}
+
+__global__ void __launch_bounds__(MC_THREADS) k_sp_emit_faces(const int32_t* __restrict__ faces, int64_t V, int64_t T, const int32_t* __restrict__ vc,
+                                                              const unsigned long long* __restrict__ head, const uint8_t* __restrict__ keep,
+                                                              const int64_t* __restrict__ tf, int32_t* __restrict__ out_faces, int64_t fcap) {
+    const bool off = head[SP_STATUS] != 0;
+    const int64_t n0 = (int64_t)blockIdx.x * CC_TILE + (int64_t)threadIdx.x * CC_PER;
+    int mask = 0, nf = 0, none = 0, tot_f, tot_n;
+    if (!off)
+        for (int q = 0; q < CC_PER && n0 + q < T; ++q)
+            if (keep[n0 + q] == 1) { mask |= 1 << q; ++nf; }
+    mc_block_scan(nf, none, tot_f, tot_n);
+    int64_t o = tf[blockIdx.x] + nf;
+    for (int q = 0; q < CC_PER; ++q) {
+        if (!((mask >> q) & 1)) continue;
+        int32_t i0, i1, i2;
+        if ((uint64_t)o < (uint64_t)fcap && (unsigned long long)o < head[SP_KEPT] && cc_face(faces, n0 + q, (int)V, i0, i1, i2)) {
+            out_faces[3 * o] = vc[i0]; out_faces[3 * o + 1] = vc[i1]; out_faces[3 * o + 2] = vc[i2];
+        }
+        ++o;
+    }
+}
+
+static unsigned sp_fill_blocks(int64_t n) {
+    const int64_t b = (n + MC_THREADS - 1) / MC_THREADS;
+    return (unsigned)(b < 1 ? 1 : (b > 65536 ? 65536 : b));
+}
+
+void dsn_launch_mesh_simplify_count(const float* verts, const int32_t* faces, int64_t V, int64_t T, const float* origin, float cell, const int* g,
+                                    void* workspace, int32_t* vertex_cluster, int64_t* out_counts, int phases, hipStream_t st) {
+    SpWs w = sp_ws(workspace, V, T, g);
+    const SpGrid G = sp_grid(origin, cell, g);
+    const unsigned gV = mesh_blocks(V), gT = mesh_blocks(T);
+    if (phases & DSN_SP_ZERO) {
+        const int64_t most = w.W > w.slots ? w.W : w.slots;
+        hipLaunchKernelGGL(k_sp_zero, dim3(sp_fill_blocks(most)), dim3(MC_THREADS), 0, st, w.bits, w.W, w.sum, w.key, w.Kmax, w.tab, w.tmin, w.slots,
+                           w.head);
+    }
+    if ((phases & DSN_SP_MARK) && gV) hipLaunchKernelGGL(k_sp_mark, dim3(gV), dim3(MC_THREADS), 0, st, verts, V, G, w.cell, w.bits, w.head);
+    if (phases & DSN_SP_RANK) {
+        hipLaunchKernelGGL(k_sp_rank, dim3((unsigned)w.tilesW), dim3(MC_THREADS), 0, st, w.bits, w.W, w.pre, w.tw);
+        hipLaunchKernelGGL(k_sp_scan, dim3(1), dim3(MC_SCAN_THREADS), 0, st, w.tw, w.tilesW, w.head + SP_K, SP_CAP, w.head + SP_STATUS);
+    }
+    if ((phases & DSN_SP_SUM) && gV)
+        hipLaunchKernelGGL(k_sp_sum, dim3(gV), dim3(MC_THREADS), 0, st, verts, V, G, w.G, w.cell, w.bits, w.pre, w.tw, w.Kmax, w.head, w.vc,
+                           vertex_cluster, w.sum);
+    if ((phases & DSN_SP_PICK) && gV)
+        hipLaunchKernelGGL(k_sp_pick, dim3(gV), dim3(MC_THREADS), 0, st, verts, V, G, w.vc, w.Kmax, w.head, w.sum, w.key);
+    if ((phases & DSN_SP_FACES) && gT)
+        hipLaunchKernelGGL(k_sp_faces, dim3(gT), dim3(MC_THREADS), 0, st, faces, V, T, w.vc, w.tab, w.tmin, w.slots, w.head);
+    if (phases & DSN_SP_KEEP) {
+        if (w.tilesT)
+            hipLaunchKernelGGL(k_sp_keep, dim3((unsigned)w.tilesT), dim3(MC_THREADS), 0, st, faces, V, T, w.vc, w.tab, w.tmin, w.slots, w.head, w.keep,
+                               w.tf);
+        hipLaunchKernelGGL(k_sp_scan, dim3(1), dim3(MC_SCAN_THREADS), 0, st, w.tf, w.tilesT, w.head + SP_KEPT, (int64_t)0, w.head + SP_STATUS);
+        hipLaunchKernelGGL(k_sp_counts, dim3(1), dim3(64), 0, st, w.head, out_counts);
+    }
+}
+
+void dsn_launch_mesh_simplify_cells(const float* verts, int64_t V, const float* origin, float cell, const int* g, void* workspace, int64_t* out_K,
+                                    hipStream_t st) {
+    SpWs w = sp_ws(workspace, V, 0, g);
+    const SpGrid G = sp_grid(origin, cell, g);
+    hipLaunchKernelGGL(k_sp_zero, dim3(sp_fill_blocks(w.W)), dim3(MC_THREADS), 0, st, w.bits, w.W, w.sum, w.key, (int64_t)0, w.tab, w.tmin, (int64_t)0,
+                       w.head);
+    if (V) hipLaunchKernelGGL(k_sp_mark, dim3(mesh_blocks(V)), dim3(MC_THREADS), 0, st, verts, V, G, w.cell, w.bits, w.head);
+    hipLaunchKernelGGL(k_sp_rank, dim3((unsigned)w.tilesW), dim3(MC_THREADS), 0, st, w.bits, w.W, w.pre, w.tw);
+    hipLaunchKernelGGL(k_sp_scan, dim3(1), dim3(MC_SCAN_THREADS), 0, st, w.tw, w.tilesW, w.head + SP_K, (int64_t)0, w.head + SP_STATUS);
+    hipLaunchKernelGGL(k_sp_count_cells, dim3(1), dim3(64), 0, st, w.head, out_K);
+}
+
+void dsn_launch_mesh_simplify_emit(const float* verts, const int32_t* faces, int64_t V, int64_t T, const int* g, void* workspace, float* out_verts,
+                                   int64_t vcap, int32_t* out_faces, int64_t fcap, int32_t* cluster_source, int phases, hipStream_t st) {
+    SpWs w = sp_ws(workspace, V, T, g);
+    if ((phases & DSN_SP_EMIT_VERTS) && vcap > 0)
+        hipLaunchKernelGGL(k_sp_emit_verts, dim3(mesh_blocks(vcap)), dim3(MC_THREADS), 0, st, verts, V, w.head, w.key, w.Kmax, out_verts, vcap,
+                           cluster_source);
+    if ((phases & DSN_SP_EMIT_FACES) && w.tilesT && fcap > 0)
+        hipLaunchKernelGGL(k_sp_emit_faces, dim3((unsigned)w.tilesT), dim3(MC_THREADS), 0, st, faces, V, T, w.vc, w.head, w.keep, w.tf, out_faces, fcap);
+}

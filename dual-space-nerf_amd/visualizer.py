@@ -12,7 +12,9 @@ vertex index (include/dsnerf.h).  The constructor switch connected=True itself s
 wiring it to the keyword is one line, held back while a pinned test expects the raise.
 A mesh follows the body into other poses without a second extraction: Renderer.bind_mesh once, Renderer.pose_mesh per frame
 (dsn_mesh_pose, the rule of include/dsnerf.h); render_mesh_sequence previews such a sequence and cull_stretched drops the triangles
-a pose tore."""
+a pose tore.  simplify_mesh (or simplify_cell= / target_vertices= of extract_mesh and get_mesh_from_grid) thins a mesh by vertex
+clustering (dsn_mesh_simplify_count / dsn_mesh_simplify_emit, the rule of include/dsnerf.h): the vertices that stay are input vertices, so
+every per-vertex array and a binding follow by one gather."""
 import numpy as np
 import torch
 
@@ -75,12 +77,14 @@ class Visualizer3D(object):
         grid_pts = grid["grid_pts"].reshape(B, X, Y, Z, 3).numpy()
         return grid_pts, grid_pred
 
-    def get_mesh_from_grid(self, grid_pts, grid_pred, return_normals=False, largest_component=False):
+    def get_mesh_from_grid(self, grid_pts, grid_pred, return_normals=False, largest_component=False, simplify_cell=None,
+                           target_vertices=None):
         """(verts [V,3] float32, faces [T,3] int32) numpy arrays of the iso-surface at mc_value in the grid's coordinates, or None
         where the level is not crossed.  grid_pts / grid_pred: [X,Y,Z,3] / [X,Y,Z,1] (or with the leading B = 1).
         return_normals=True: a third array, the unit vertex normals [V,3] float32 (skimage's vertex_normals, by dsn_mc_normals).
         largest_component=True: only the connected component with the largest area (the reference's connected=True; the rule of
-        include/dsnerf.h, on the device), the normals gathered with it."""
+        include/dsnerf.h, on the device), the normals gathered with it.
+        simplify_cell / target_vertices (one of them): the mesh thinned by simplify_mesh, after the component filter."""
         if self.connected:
             raise NotImplementedError("Visualizer3D(connected=True) is not wired up: pass largest_component=True to get_mesh_from_grid "
                                       "(or use dsnerf_amd.visualizer.largest_component) for the largest connected component")
@@ -96,6 +100,8 @@ class Visualizer3D(object):
         if largest_component:
             v, f, src = _lib.largest_component(out[0], out[1], want_source=bool(return_normals))
             out = (v, f) + ((out[2][src.long()],) if return_normals else ())
+        if simplify_cell is not None or target_vertices is not None:
+            out = simplify_mesh(tuple(out), cell=simplify_cell, target_vertices=target_vertices)
         return tuple(a.cpu().numpy() for a in out)
 
     @torch.no_grad()
@@ -201,6 +207,62 @@ def largest_component(mesh):
     for k in PER_VERTEX_KEYS:
         if out.get(k) is not None:
             out[k] = back(gather(out[k]))
+    return out
+
+
+BINDING_KEYS = ("face_idx", "uv", "h", "cov", "x_c")          # Renderer.bind_mesh's per-vertex entries ("valid" is in PER_VERTEX_KEYS)
+
+
+@torch.no_grad()
+def simplify_mesh(mesh, cell=None, target_vertices=None):
+    """A mesh thinned by vertex clustering (dsn_mesh_simplify_count / dsn_mesh_simplify_emit, the rule of include/dsnerf.h): the
+    vertices of every grid cell of edge `cell` (the grid starts at the minimum of the finite vertices) collapse to the one of them
+    nearest to their mean, faces that lose an edge and duplicates go.  The vertices that stay are input vertices, bit for bit.
+    mesh: a (verts, faces[, normals]) tuple or the dict of Renderer.extract_mesh / Renderer.bind_mesh, numpy or device; the result
+    has the same form and lives where verts lived.  Every per-vertex array the dict carries - largest_component's (normals, albedo,
+    normal, colour - also in its [K,V,3] form -, sigma, valid), the entries of a binding (face_idx, uv, h, cov, x_c) and
+    source_vertex - is gathered through "cluster_source" [V'] int32 (each output vertex's index in the mesh given), so a simplified
+    binding poses with Renderer.pose_mesh as it is; the dict also gains "vertex_cluster" [V] int32 (the output vertex every input
+    vertex went to; -1: not finite) and "simplify_info" (the counts of _lib.MESH_SIMPLIFY_COUNTS, cell, origin, g, and for a target
+    n and the probes).  Other keys are carried over as they are.
+    target_vertices=N instead of cell: the cell is float32(extent / n) (1 + 2^-20) for n cells along the longest finite extent, with
+    the largest n in [1, 4096] whose vertex count K(n) <= N found by bisection on the counting-only call (at most 12 probes, one
+    8-byte host read each).  K(n) is treated as monotone, which it is not strictly: the result has at most N vertices, not
+    necessarily as many as some other n would give.  Giving both or neither raises ValueError.  Clustering can pinch the surface;
+    no manifold repair is attempted."""
+    if (cell is None) == (target_vertices is None):
+        raise ValueError("simplify_mesh: give one of cell and target_vertices")
+    is_dict = isinstance(mesh, dict)
+    if is_dict:
+        verts, faces = mesh["verts"], mesh["faces"]
+    else:
+        verts, faces = mesh[0], mesh[1]
+    on_host = not torch.is_tensor(verts)
+
+    def dev(a, dtype=None):
+        a = a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))
+        return a.to(device="cuda", dtype=dtype)
+
+    def back(a):
+        return a.cpu().numpy() if on_host else a
+    dv, df = dev(verts, torch.float32).reshape(-1, 3), dev(faces, torch.int32)
+    info = {}
+    if target_vertices is not None:
+        cell = _lib.mesh_target_search(dv, target_vertices, info=info)
+    v, f, src, vc = _lib.mesh_simplify(dv, df, cell, info=info)
+    idx = src.long()
+    V = dv.shape[0]
+
+    def gather(a):
+        a = dev(a)
+        return a[:, idx] if (a.dim() == 3 and a.shape[1] == V) else a[idx]
+    if not is_dict:
+        return (back(v), back(f)) + tuple(back(gather(a)) for a in tuple(mesh)[2:3])
+    out = dict(mesh)
+    for k in PER_VERTEX_KEYS + BINDING_KEYS + ("source_vertex",):
+        if out.get(k) is not None:
+            out[k] = back(gather(out[k]))
+    out.update(verts=back(v), faces=back(f), cluster_source=back(src), vertex_cluster=back(vc), simplify_info=info)
     return out
 
 

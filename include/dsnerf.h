@@ -691,6 +691,83 @@ DSN_EXPORT int dsn_mesh_cc_emit_ex(const float* verts, const int32_t* faces, int
                                    size_t workspace_bytes, int64_t out_n_verts, int64_t out_n_faces, float* out_verts, int32_t* out_faces,
                                    int32_t* source_vertex, int phases, void* stream);
 
+/* ---- mesh simplification (an addition within ABI 8: no existing entry point changes) --------------------------------------------------
+ * Vertex clustering with a picked representative: the output vertices are a SUBSET of the input vertices, so every per-vertex array
+ * (normals, colours, the binding record of dsn_mesh_pose) follows by one gather through cluster_source, as through dsn_mesh_cc_emit's
+ * source_vertex.  There is no counterpart in the reference (its users would decimate with trimesh or open3d on the host); the rule is
+ * fixed so that a numpy restatement (tests/mesh_simplify_restate.py) reproduces every output bit for bit.  Integer sums and integer
+ * atomics only: every call returns the same bits.
+ *   Inputs:   verts [V, 3] float32, faces [T, 3] int32 (device); the grid: origin_host [3] float32 and g3_host [3] int in HOST memory
+ *             (read before the call returns), cell float32 > 0; every g_a in [1, DSN_MESH_SIMPLIFY_MAX_G], g0 g1 g2 <= 2^31.
+ *   Cell:     inv = 1.0f / cell (float32, once, on the host); t_a = (x_a - origin_a) inv, one float32 subtraction and one float32 product.
+ *             A vertex is INSIDE when all three t_a are finite, >= 0 and < g_a (NaN and infinite coordinates are outside); its cell
+ *             number is (i0 g1 + i1) g2 + i2 with i_a = floor(t_a).
+ *   Clusters: the occupied cells numbered in ascending cell number; that number is the cluster index = the output vertex index, K their
+ *             count.  vertex_cluster [V] int32: the cluster of every inside vertex, -1 for the others.  Inside vertices no face uses
+ *             still occupy their cell.
+ *   Representative: q_a = floor(double(t_a) 2^20) as a 64-bit integer (exact, below 2^32); per cluster s_a = the sum of q_a (below 2^63)
+ *             and the member count n; m_a = double(s_a) / double(n), e_a = double(q_a) - m_a, d = (e0 e0 + e1 e1) + e2 e2 in IEEE double,
+ *             one rounding per operation, nothing fused.  The representative minimises the 64-bit key
+ *             (bits of float32(d)) << 32 | vertex index: nearest to the members' mean, ties to the smaller index.  cluster_source [K]
+ *             int32 is its index; the output vertex is its three float32 words, copied.
+ *   Faces:    a face is LIVE when its three indices lie in [0, V), all three vertices are inside and the three clusters differ.  Two live
+ *             faces are DUPLICATES when their cluster triples agree as sets (any rotation or winding); of a set of duplicates only the
+ *             face with the smallest input index is kept.  Kept faces come out in input order and input winding, indices replaced by
+ *             clusters.  (Clustering can pinch a surface: no manifold repair is attempted.)
+ *   Cap:      duplicate detection packs a sorted triple into 63 bits: K <= 2^DSN_MESH_SIMPLIFY_MAX_LOG2.  A larger K sets
+ *             DSN_MESH_SIMPLIFY_TOO_MANY in the status: K, the vertices outside and vertex_cluster are still what the rule says, no face
+ *             is looked at (the other counts are 0) and dsn_mesh_simplify_emit writes nothing - choose a larger cell.
+ *   Counts:   out_counts7: 7 int64 in device memory {K, kept faces T', live faces, duplicates dropped, vertices outside, faces with an
+ *             index outside [0, V), status}.
+ * Two phases, as dsn_mesh_cc_label / dsn_mesh_cc_emit: dsn_mesh_simplify_count fills `workspace` (dsn_mesh_simplify_workspace_bytes(V, T,
+ * g3), 16-byte aligned; its earlier contents are never read), writes vertex_cluster (may be NULL) and the counts; the caller reads them,
+ * sizes out_verts [K, 3], out_faces [T', 3] and cluster_source [K] (may be NULL), and dsn_mesh_simplify_emit fills them from the same
+ * workspace.  The library cannot read the counts without synchronising: emit rejects counts no call could have reported (above V, the
+ * number of cells, the cap or T), never writes a row beyond K or T', and writes nothing at all while the status is not 0.
+ * dsn_mesh_simplify_cells marks and counts the occupied cells only (out_K: one int64 in device memory; workspace:
+ * dsn_mesh_simplify_workspace_bytes(V, 0, g3)): what a search for a cell size that gives a wanted K probes with.
+ * Kernels: one thread per vertex sets its cell's bit in a bit grid (an atomic OR per run of equal cells in the wave), a popcount prefix
+ * over the grid's words (the tile scan of the marching cubes, no atomics) ranks the cells, 64-bit integer atomic adds aggregated per
+ * run of equal clusters in the wave form the sums, one 64-bit unsigned atomic minimum per run picks the representative; a live face claims
+ * the slot of its sorted triple in a lock-free open-addressing table (capacity a power of two >= 2 T) by a 64-bit compare-and-swap and
+ * leaves the minimum of its index there - the probe is bounded by the capacity (exhaustion, which that load rules out, sets
+ * DSN_MESH_SIMPLIFY_TABLE_FULL), no thread waits for another - and a tile scan over the keep flags orders the output.  All atomics are
+ * relaxed and agent scope, all 3 V and 3 T indexing is 64-bit.  V = 0 or T = 0 is a valid call.  No allocation, no synchronisation, all
+ * on `stream`.
+ * Rejected: null verts with V > 0, null faces with T > 0, a null origin, g3, workspace or counts, negative sizes or 2^31 and more, a g
+ * outside its limits, a cell that is not finite or <= 0 (or whose float32 inverse is not finite), an origin that is not finite, a workspace
+ * that is not 16-byte aligned or smaller than dsn_mesh_simplify_workspace_bytes (0 for bad sizes); by dsn_mesh_simplify_emit also null
+ * outputs with non-zero counts. */
+#define DSN_MESH_SIMPLIFY_MAX_G 4096
+#define DSN_MESH_SIMPLIFY_MAX_LOG2 21
+#define DSN_MESH_SIMPLIFY_TOO_MANY 1
+#define DSN_MESH_SIMPLIFY_TABLE_FULL 2
+DSN_EXPORT size_t dsn_mesh_simplify_workspace_bytes(int64_t n_verts, int64_t n_faces, const int* g3_host);
+DSN_EXPORT int dsn_mesh_simplify_count(const float* verts, const int32_t* faces, int64_t n_verts, int64_t n_faces, const float* origin_host,
+                                       float cell, const int* g3_host, void* workspace, size_t workspace_bytes, int32_t* vertex_cluster,
+                                       int64_t* out_counts7, void* stream);
+DSN_EXPORT int dsn_mesh_simplify_emit(const float* verts, const int32_t* faces, int64_t n_verts, int64_t n_faces, const int* g3_host,
+                                      void* workspace, size_t workspace_bytes, int64_t out_n_verts, int64_t out_n_faces, float* out_verts,
+                                      int32_t* out_faces, int32_t* cluster_source, void* stream);
+DSN_EXPORT int dsn_mesh_simplify_cells(const float* verts, int64_t n_verts, const float* origin_host, float cell, const int* g3_host,
+                                       void* workspace, size_t workspace_bytes, int64_t* out_K, void* stream);
+/* measurement (scripts/bench_mesh_simplify.py): enqueue only these kernels (0 = all; one mesh and one workspace through the phases in order) */
+#define DSN_SP_ZERO 1
+#define DSN_SP_MARK 2
+#define DSN_SP_RANK 4
+#define DSN_SP_SUM 8
+#define DSN_SP_PICK 16
+#define DSN_SP_FACES 32
+#define DSN_SP_KEEP 64
+#define DSN_SP_EMIT_VERTS 128
+#define DSN_SP_EMIT_FACES 256
+DSN_EXPORT int dsn_mesh_simplify_count_ex(const float* verts, const int32_t* faces, int64_t n_verts, int64_t n_faces, const float* origin_host,
+                                          float cell, const int* g3_host, void* workspace, size_t workspace_bytes, int32_t* vertex_cluster,
+                                          int64_t* out_counts7, int phases, void* stream);
+DSN_EXPORT int dsn_mesh_simplify_emit_ex(const float* verts, const int32_t* faces, int64_t n_verts, int64_t n_faces, const int* g3_host,
+                                         void* workspace, size_t workspace_bytes, int64_t out_n_verts, int64_t out_n_faces, float* out_verts,
+                                         int32_t* out_faces, int32_t* cluster_source, int phases, void* stream);
+
 /* ---- a mesh bound to the body (an addition within ABI 8: no existing entry point changes) --------------------------------------------
  * novel_pose_vis.py and the novel-pose datasets animate one learned body by swapping batch["xyz"].  A mesh extracted in one pose follows
  * the body the same way: dsn_warp expresses a world point in the frame of its nearest posed face as (face, u, v, h) and evaluates that
