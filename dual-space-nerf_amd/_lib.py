@@ -52,6 +52,7 @@ EXPORTS = [
     "dsn_mesh_bind_normals", "dsn_mesh_pose_workspace_bytes", "dsn_mesh_pose", "dsn_mesh_stretch",
     "dsn_mesh_simplify_workspace_bytes", "dsn_mesh_simplify_count", "dsn_mesh_simplify_emit", "dsn_mesh_simplify_cells",
     "dsn_mesh_simplify_count_ex", "dsn_mesh_simplify_emit_ex",
+    "dsn_train_loss_workspace_bytes", "dsn_train_loss", "dsn_train_loss_grad",
 ]
 
 SKIP_TRANSPARENT = 1
@@ -76,6 +77,8 @@ RAYS_ZJU, RAYS_H36M = 0, 1
 TRAIN_RAYS_OK, TRAIN_RAYS_EMPTY_CLASS, TRAIN_RAYS_SHORT, TRAIN_RAYS_BAD_CAMERA = 0, 1, 2, 3     # dsn_train_rays' status (DSN_TRAIN_RAYS_*)
 TRAIN_RAYS_MAX_ROUNDS, TRAIN_RAYS_MAX_RAYS = 64, 65536
 SSIM_OK, SSIM_CROP_TOO_SMALL, SSIM_EMPTY_MASK = 0, 1, 2     # dsn_image_ssim's out_status (DSN_SSIM_*)
+LOSS_L2, LOSS_SMOOTH_L1 = 0, 1      # dsn_train_loss' kind (DSN_LOSS_*)
+LOSS_SHARE = 256                    # rays per workgroup of dsn_train_loss' forward (DSN_LOSS_SHARE)
 FRAME_FINE_ONLY = 1           # dsn_set_frame_ex: only the fine nearest-face level of the posed mesh (points beyond it: exhaustive sweep)
 FRAME_LAZY_LISTS = 2          # dsn_set_frame_ex: grid geometry only - the frame that uses the level builds the lists of the cells it visits
 LAZY_LISTS = 4096             # dsn_render_rays_ex: ... which is this flag (Scene.lazy says whether the scene's frame was set that way)
@@ -155,6 +158,10 @@ def lib():
         L.dsn_mesh_simplify_emit.argtypes = sp_emit + [C.c_void_p]
         L.dsn_mesh_simplify_emit_ex.argtypes = sp_emit + [C.c_int, C.c_void_p]
         L.dsn_mesh_simplify_cells.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        L.dsn_train_loss_workspace_bytes.restype = C.c_size_t
+        L.dsn_train_loss_workspace_bytes.argtypes = [C.c_int64]
+        L.dsn_train_loss.argtypes = [C.c_void_p] * 6 + [C.c_int64, C.c_int, C.c_int] + [C.c_void_p] * 3
+        L.dsn_train_loss_grad.argtypes = [C.c_void_p] * 6 + [C.c_int64, C.c_int] + [C.c_void_p] * 5
         if L.dsn_abi_version() != 8:
             raise RuntimeError(f"{LIB_PATH} has ABI version {L.dsn_abi_version()}, this binding needs 8 - rebuild it "
                                "(python dual-space-nerf_amd/build.py)")
@@ -1825,6 +1832,92 @@ def ssim_status_error(status, rect):
     x, y, w, h = (int(v) for v in rect)
     what = "the mask is empty" if int(status) == SSIM_EMPTY_MASK else f"the mask's bounding rectangle is {w} x {h}"
     return ValueError(f"ssim: win_size exceeds image extent ({what}; SSIM needs at least 7 x 7)")
+
+
+def _loss_args(color, target, acc, occupancy, kind):
+    """the device arrays of one loss call: (color [R,3] f32, target f32 | None, target f64 | None, acc [R] f32 | None, occupancy u8 |
+    None, occupancy f32 | None, R, kind).  [1,R,3] / [1,R] shapes are reshaped, non-contiguous inputs copied."""
+    if kind not in ("L2", "L1", LOSS_L2, LOSS_SMOOTH_L1):
+        raise ValueError(f"kind must be 'L2' or 'L1' (Smooth-L1), got {kind!r}")
+    kind = {"L2": LOSS_L2, "L1": LOSS_SMOOTH_L1}.get(kind, kind)
+    dev = color.device
+    if color.dtype != torch.float32 or color.shape[-1:] != (3,):
+        raise TypeError(f"color must be float32 [R,3], got {color.dtype} {tuple(color.shape)}")
+    color = color.reshape(-1, 3).contiguous()
+    R = color.shape[0]
+    target = target.to(dev).reshape(-1, 3).contiguous()
+    if target.dtype not in (torch.float64, torch.float32):
+        raise TypeError(f"target must be float64 or float32, got {target.dtype}")
+    if target.shape[0] != R:
+        raise ValueError(f"target has {target.shape[0]} rays, color {R}")
+    t32, t64 = (target, None) if target.dtype == torch.float32 else (None, target)
+    o8 = o32 = None
+    if occupancy is not None:
+        if acc is None:
+            raise ValueError("the mask term (occupancy) needs acc")
+        occupancy = occupancy.to(dev).reshape(-1)
+        if occupancy.dtype == torch.bool:
+            occupancy = occupancy.to(torch.uint8)
+        if occupancy.dtype not in (torch.uint8, torch.float32):
+            raise TypeError(f"occupancy must be uint8, bool or float32, got {occupancy.dtype}")
+        if occupancy.numel() != R:
+            raise ValueError(f"occupancy has {occupancy.numel()} rays, color {R}")
+        occupancy = occupancy.contiguous()
+        o8, o32 = (occupancy, None) if occupancy.dtype == torch.uint8 else (None, occupancy)
+    if acc is not None:
+        if acc.dtype != torch.float32 or acc.numel() != R:
+            raise TypeError(f"acc must be float32 [{R}], got {acc.dtype} {tuple(acc.shape)}")
+        acc = acc.reshape(-1)
+    return color, t32, t64, acc, o8, o32, R, kind
+
+
+def train_loss(color, target, acc=None, occupancy=None, kind="L2", overwrite_acc=True, workspace=None):
+    """utils/loss.py's MSELoss ("L2") / SmoothL1Loss ("L1") with the LOSSwMask term when `occupancy` is given, and the trainer's
+    mse / psnr of the same batch, on the device (dsn_train_loss, the rule of include/dsnerf.h).  color [R,3] float32, target [R,3]
+    float32 or float64, acc [R] float32, occupancy [R] uint8 / bool / float32 ([1,R,...] shapes too).  overwrite_acc: acc reads 1
+    where occupancy == 1 afterwards (the reference's in-place assignment; a non-contiguous acc is written back).  Returns 0-dim
+    device tensors, nothing synchronises: "loss_rgb", "loss_mask" (float32, views of "losses_f32"), "mse", "psnr" (float64, views of
+    "out4" = {loss_rgb, loss_mask, mse, psnr} in float64), and the "workspace" to hand to the next call."""
+    require_gpu()
+    color, t32, t64, acc_in, o8, o32, R, kind = _loss_args(color, target, acc, occupancy, kind)
+    dev = color.device
+    acc_c = None if acc_in is None else acc_in.contiguous()
+    nbytes = lib().dsn_train_loss_workspace_bytes(R)
+    ws = workspace if workspace is not None and workspace.numel() >= nbytes else _scratch(nbytes, dev)
+    out4 = torch.empty(4, dtype=torch.float64, device=dev)
+    mask_on = o8 is not None or o32 is not None
+    # (R = 0: empty tensors have no address; the mask term is announced by a pointer the call never reads)
+    p = (lambda t, dtype=None: _ptr(t, dtype)) if R else (lambda t, dtype=None: None if t is None else _ptr(ws))
+    _check(lib().dsn_train_loss(p(color, torch.float32), p(t32), p(t64), p(acc_c), p(o8), p(o32), R, kind,
+                                int(bool(overwrite_acc and mask_on)), _ptr(out4), _ptr(ws), _stream()), "dsn_train_loss")
+    if overwrite_acc and mask_on and R and acc_c.data_ptr() != acc.data_ptr():
+        acc.copy_(acc_c.reshape(acc.shape))
+    f32 = out4[:2].to(torch.float32)
+    return {"loss_rgb": f32[0], "loss_mask": f32[1], "mse": out4[2], "psnr": out4[3], "out4": out4, "losses_f32": f32, "workspace": ws}
+
+
+def train_loss_grad(color, target, acc=None, occupancy=None, kind="L2", up_rgb=None, up_mask=None, want_acc=True):
+    """The seeds of the backward (dsn_train_loss_grad): (g_color [R,3], g_acc [R] or None) = d(up_rgb loss_rgb + up_mask loss_mask) /
+    d(color, acc).  up_rgb / up_mask: float32 device scalars (tensors; Python numbers are copied over), None = 0 for that term.
+    g_acc is returned when acc is given and want_acc is set."""
+    require_gpu()
+    color, t32, t64, acc, o8, o32, R, kind = _loss_args(color, target, acc, occupancy, kind)
+    dev = color.device
+    acc = None if acc is None else acc.contiguous()
+
+    def up(u):
+        if u is None:
+            return None
+        u = torch.as_tensor(u, dtype=torch.float32) if not torch.is_tensor(u) else u
+        return u.detach().to(device=dev, dtype=torch.float32).reshape(()).contiguous()
+
+    up_rgb, up_mask = up(up_rgb), up(up_mask)
+    g_color = torch.empty(R, 3, dtype=torch.float32, device=dev)
+    g_acc = torch.empty(R, dtype=torch.float32, device=dev) if (want_acc and acc is not None) else None
+    if R:
+        _check(lib().dsn_train_loss_grad(_ptr(color, torch.float32), _ptr(t32), _ptr(t64), _ptr(acc), _ptr(o8), _ptr(o32), R, kind,
+                                         _ptr(up_rgb), _ptr(up_mask), _ptr(g_color), _ptr(g_acc), _stream()), "dsn_train_loss_grad")
+    return g_color, g_acc
 
 
 def camera_rays(K, R, T, bounds, H, W, device=None, convention="zju"):

@@ -364,6 +364,45 @@ int dsn_image_ssim(const float* img_rgb, const double* gt_f64, const float* gt_f
     return dsn_check_launch("dsn_image_ssim");
 }
 
+// the trainer's loss (dsn_loss.hip).  R = 0 is a valid call: nothing is read, the means are NaN (the per-ray pointers may be null then)
+#define DSN_LOSS_MAX_RAYS (((int64_t)1 << 31) - 1)
+static bool dsn_loss_rays_ok(int64_t R) { return R >= 0 && R <= DSN_LOSS_MAX_RAYS; }
+
+size_t dsn_train_loss_workspace_bytes(int64_t R) { return dsn_loss_rays_ok(R) ? dsn_train_loss_workspace_size(R) : 0; }
+
+int dsn_train_loss(const float* color, const float* target_f32, const double* target_f64, float* acc, const uint8_t* occ_u8,
+                   const float* occ_f32, int64_t R, int kind, int acc_overwrite, double* out4, void* workspace, void* stream) {
+    DSN_REQUIRE(dsn_loss_rays_ok(R), "dsn_train_loss: R must be 0 ... 2^31 - 1");
+    DSN_REQUIRE(kind == DSN_LOSS_L2 || kind == DSN_LOSS_SMOOTH_L1, "dsn_train_loss: unknown kind");
+    DSN_REQUIRE(out4, "dsn_train_loss: null argument");
+    DSN_REQUIRE(!(target_f32 && target_f64), "dsn_train_loss: exactly one target pointer");
+    DSN_REQUIRE(!(occ_u8 && occ_f32), "dsn_train_loss: at most one occupancy pointer");
+    if (R > 0) {
+        DSN_REQUIRE(color && workspace, "dsn_train_loss: null argument");
+        DSN_REQUIRE(target_f32 || target_f64, "dsn_train_loss: exactly one target pointer");
+        DSN_REQUIRE(!(occ_u8 || occ_f32) || acc, "dsn_train_loss: the mask term needs acc");
+    }
+    dsn_launch_train_loss(color, target_f32, target_f64, acc, occ_u8, occ_f32, R, kind, acc_overwrite, out4, workspace, (hipStream_t)stream);
+    return dsn_check_launch("dsn_train_loss");
+}
+
+int dsn_train_loss_grad(const float* color, const float* target_f32, const double* target_f64, const float* acc, const uint8_t* occ_u8,
+                        const float* occ_f32, int64_t R, int kind, const float* up_rgb, const float* up_mask, float* g_color, float* g_acc,
+                        void* stream) {
+    DSN_REQUIRE(dsn_loss_rays_ok(R), "dsn_train_loss_grad: R must be 0 ... 2^31 - 1");
+    DSN_REQUIRE(kind == DSN_LOSS_L2 || kind == DSN_LOSS_SMOOTH_L1, "dsn_train_loss_grad: unknown kind");
+    DSN_REQUIRE(!(target_f32 && target_f64), "dsn_train_loss_grad: exactly one target pointer");
+    DSN_REQUIRE(!(occ_u8 && occ_f32), "dsn_train_loss_grad: at most one occupancy pointer");
+    if (R > 0) {
+        DSN_REQUIRE(color && g_color, "dsn_train_loss_grad: null argument");
+        DSN_REQUIRE(target_f32 || target_f64, "dsn_train_loss_grad: exactly one target pointer");
+        DSN_REQUIRE(!(occ_u8 || occ_f32) || acc, "dsn_train_loss_grad: the mask term needs acc");
+    }
+    dsn_launch_train_loss_grad(color, target_f32, target_f64, acc, occ_u8, occ_f32, R, kind, up_rgb, up_mask, g_color, g_acc,
+                               (hipStream_t)stream);
+    return dsn_check_launch("dsn_train_loss_grad");
+}
+
 int dsn_field_screen(const void* scene, int V, int F, const void* packed, const float* x_c, int64_t N, const int32_t* active_list,
                      const int32_t* active_count, float* sigma, int32_t* keep_list, int32_t* keep_count, void* stream) {
     DSN_REQUIRE(scene && packed && x_c && sigma && keep_list && keep_count, "dsn_field_screen: null argument");

@@ -205,6 +205,13 @@ void dsn_launch_image_psnr(const float* img_rgb, const double* gt64, const float
 size_t dsn_image_ssim_workspace_size(int F, int H, int W);
 void dsn_launch_image_ssim(const float* img_rgb, const double* gt64, const float* gt32, const uint8_t* mask, int F, int H, int W,
                            int clamp_rgb, double* out_ssim, int32_t* out_rect, int32_t* out_status, void* workspace, hipStream_t st);
+// dsn_loss.hip: the trainer's loss and its two seed arrays (dsn_train_loss / dsn_train_loss_grad)
+size_t dsn_train_loss_workspace_size(int64_t R);
+void dsn_launch_train_loss(const float* color, const float* t32, const double* t64, float* acc, const uint8_t* o8, const float* o32,
+                           int64_t R, int kind, int overwrite, double* out4, void* workspace, hipStream_t st);
+void dsn_launch_train_loss_grad(const float* color, const float* t32, const double* t64, const float* acc, const uint8_t* o8,
+                                const float* o32, int64_t R, int kind, const float* up_rgb, const float* up_mask, float* g_color,
+                                float* g_acc, hipStream_t st);
 // dsn_mesh.hip: density grid points and marching cubes (dsn_density_grid, dsn_mc_*)
 void dsn_launch_grid_points(const float* x, const float* y, const float* z, int i0, int ny, int nz, int64_t n, float* pts, hipStream_t st);
 size_t dsn_mc_workspace_size(int64_t N);

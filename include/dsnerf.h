@@ -266,6 +266,50 @@ DSN_EXPORT int dsn_image_ssim(const float* img_rgb, const double* gt_f64, const 
                    int F, int H, int W, int clamp_rgb, double* out_ssim, int32_t* out_rect, int32_t* out_status,
                    void* workspace, void* stream);
 
+/* ---- the trainer's loss on the device (an addition within ABI 8: no existing entry point changes) -------------------------------------
+ * utils/loss.py make_loss: MSELoss / SmoothL1Loss, each with the optional LOSSwMask term and its in-place acc_map[occupancy == 1] = 1,
+ * and the psnr(coarse["color"], batch["rgb"]) trainer.py takes of the same tensors on every step - one pass over the batch forward, one
+ * backward that writes the two seed arrays of dsn_render_rays_grad (d_rgb, d_acc).
+ *   color [R,3] float32; the target [R,3] float32 or float64 (exactly one of target_f32 / target_f64 non-NULL, as dsn_image_psnr);
+ *   acc [R] float32 or NULL; occupancy [R] uint8 or float32 (at most one of occ_u8 / occ_f32 non-NULL).  The mask term is on iff an
+ *   occ_* pointer is given, and acc must be given then.  kind: DSN_LOSS_L2 or DSN_LOSS_SMOOTH_L1.
+ * The rule, all in float64 (parentheses give the order of the products; the sums' order is fixed but not part of the rule):
+ *   d = (double)color - (double)target, per element.
+ *   term      L2: d d.   Smooth-L1 (torch's default beta = 1): 0.5 d d where |d| < 1, else |d| - 0.5.
+ *   loss_rgb  = the mean of term over the 3R elements.
+ *   mse       = the mean of d d over the 3R elements, in both kinds (what the trainer's psnr needs).
+ *   psnr      = -10 log10(mse): +inf at mse = 0, as torch gives.
+ *   mask term a' = 1 where occ == 1, else acc;  loss_mask = 0.1 (the mean over R of |a' - occ|).  occ keeps whatever value it has: it
+ *             is not assumed to be 0 or 1.  acc_overwrite != 0: the kernel also stores 1.0f into acc where occ == 1 (the reference's
+ *             side effect, in the same pass; acc is not written otherwise).
+ *   out4 (device, float64) = {loss_rgb, loss_mask, mse, psnr}; loss_mask is 0 when the term is off.  NaN inputs propagate as in torch.
+ *   R = 0 is a valid call: nothing is read (the per-ray pointers and the workspace may be NULL), loss_rgb, mse and - with the mask
+ *   term on - loss_mask are NaN (the mean of nothing), and so is psnr.
+ * dsn_train_loss_grad: the derivatives of the two losses with respect to color and acc, times their upstream gradients.
+ *   up_rgb, up_mask: DEVICE float32 scalars, read by the kernel (no synchronisation, no multiply launches in the caller's autograd
+ *   chain); a NULL pointer means 0 for that term.  s = 1.0 / (3R) and m = 0.1 / R are computed on the host in double.
+ *   g_color[i] = (float)(((double)up_rgb s) e)  with  e = 2 d (L2);  e = d where |d| < 1, else sign(d) (Smooth-L1).
+ *   g_acc[r]   = (float)(((double)up_mask m) sign(acc - occ)) where occ != 1, and exactly +0 where occ == 1; acc - occ in double.
+ *   sign(x) = 1 for x > 0, -1 for x < 0, +0 for x == 0 (as torch's L1 backward), NaN for NaN.  acc is read only where occ != 1, so it
+ *   does not matter whether the overwrite has happened.  g_acc may be NULL; with the mask term off a given g_acc is filled with zeros.
+ *   One thread per element, one writer per word, no atomics.  R = 0 launches nothing.
+ * Reduction of the forward: workgroup b sums rays [b DSN_LOSS_SHARE, (b + 1) DSN_LOSS_SHARE) - a function of R alone, not of the
+ * device - into three fp64 partials in the workspace; a second one-workgroup launch adds the partials in index order.  No
+ * floating-point atomics: every call returns the same bits, whatever the workspace (dsn_train_loss_workspace_bytes(R) bytes; 0 for
+ * a bad R) held before.
+ * Rejected (non-zero, dsn_last_error): R < 0 or 2^31 and more, a kind out of range, both target pointers - or, with R > 0, neither -,
+ * both occupancy pointers, an occupancy pointer without acc, null color / out4 / workspace / g_color.  No allocation, no
+ * synchronisation, all on `stream`. */
+#define DSN_LOSS_L2 0
+#define DSN_LOSS_SMOOTH_L1 1
+#define DSN_LOSS_SHARE 256         /* rays per workgroup of the forward */
+DSN_EXPORT size_t dsn_train_loss_workspace_bytes(int64_t R);
+DSN_EXPORT int dsn_train_loss(const float* color, const float* target_f32, const double* target_f64, float* acc, const uint8_t* occ_u8,
+                              const float* occ_f32, int64_t R, int kind, int acc_overwrite, double* out4, void* workspace, void* stream);
+DSN_EXPORT int dsn_train_loss_grad(const float* color, const float* target_f32, const double* target_f64, const float* acc,
+                                   const uint8_t* occ_u8, const float* occ_f32, int64_t R, int kind, const float* up_rgb,
+                                   const float* up_mask, float* g_color, float* g_acc, void* stream);
+
 /* The density screen as a stage (what dsn_render_rays runs first in eval mode): for the listed points (or all N) the
  * plain-fp16 trunk; points whose fp16 density is negative by the safety margin (calibrated for the parameters: dsn_calibrate_screen) get that negative value in sigma [N] and are dropped, the
  * others are appended to keep_list (keep_count zeroed by the caller) for dsn_field_forward. */
