@@ -641,7 +641,11 @@ __global__ void __launch_bounds__(T_THREADS) k_t_composite_adjoint_w(
         if (d_weights && in[c]) gw += d_weights[b + i];
         const float p = in[c] ? gw * w[c] : 0.0f;
         const float incl = t_wave_incl_sum_down(p, lane);          // sum_{k >= lane} of this chunk
-        const float suffix = tail + (incl - p);
+        // sum_{k > lane}: the next lane's inclusive sum, never `incl - p` - the own term can be 1e10 times the tail (an opaque sample),
+        // and the tail, divided by f = 1e-10 there, is as large as gw T
+        float behind = __shfl_down(incl, 1);
+        if (lane == 63) behind = 0.0f;
+        const float suffix = tail + behind;
         tail += __shfl(incl, 0);
         if (!in[c]) continue;
         const float dalpha = gw * T[c] - suffix / f[c];
