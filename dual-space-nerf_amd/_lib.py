@@ -52,6 +52,7 @@ EXPORTS = [
     "dsn_mesh_bind_normals", "dsn_mesh_pose_workspace_bytes", "dsn_mesh_pose", "dsn_mesh_stretch",
     "dsn_mesh_simplify_workspace_bytes", "dsn_mesh_simplify_count", "dsn_mesh_simplify_emit", "dsn_mesh_simplify_cells",
     "dsn_mesh_simplify_count_ex", "dsn_mesh_simplify_emit_ex",
+    "dsn_mesh_smooth_workspace_bytes", "dsn_mesh_smooth", "dsn_mesh_smooth_ex", "dsn_mesh_vertex_normals", "dsn_mesh_vertex_normals_ex",
     "dsn_train_loss_workspace_bytes", "dsn_train_loss", "dsn_train_loss_grad",
 ]
 
@@ -158,6 +159,14 @@ def lib():
         L.dsn_mesh_simplify_emit.argtypes = sp_emit + [C.c_void_p]
         L.dsn_mesh_simplify_emit_ex.argtypes = sp_emit + [C.c_int, C.c_void_p]
         L.dsn_mesh_simplify_cells.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        L.dsn_mesh_smooth_workspace_bytes.restype = C.c_size_t
+        L.dsn_mesh_smooth_workspace_bytes.argtypes = [C.c_int64, C.c_int64]
+        sm = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        sm_normals = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
+        L.dsn_mesh_smooth.argtypes = sm + [C.c_void_p]
+        L.dsn_mesh_smooth_ex.argtypes = sm + [C.c_int, C.c_void_p]
+        L.dsn_mesh_vertex_normals.argtypes = sm_normals + [C.c_void_p]
+        L.dsn_mesh_vertex_normals_ex.argtypes = sm_normals + [C.c_int, C.c_void_p]
         L.dsn_train_loss_workspace_bytes.restype = C.c_size_t
         L.dsn_train_loss_workspace_bytes.argtypes = [C.c_int64]
         L.dsn_train_loss.argtypes = [C.c_void_p] * 6 + [C.c_int64, C.c_int, C.c_int] + [C.c_void_p] * 3
@@ -936,6 +945,89 @@ def mesh_target_search(verts, target_vertices, info=None):
     if info is not None:
         info.update(n=lo, probes=probes)
     return mesh_target_cell(box, lo)
+
+
+MESH_SMOOTH_HEAVY, MESH_SMOOTH_MAX_STEPS, MESH_SMOOTH_MAX_EXP = 64, 4096, 900      # DSN_MESH_SMOOTH_*
+SM_COUNT, SM_SCAN, SM_FILL, SM_STEP, SM_NORMALS = 1, 2, 4, 8, 16                    # DSN_SM_*
+MESH_SMOOTH_COUNTS = ("contributing_faces", "skipped_faces", "vertices_moved", "max_faces_at_vertex")
+
+
+def mesh_smooth_scale(box):
+    """(origin float32 [3], k) of dsn_mesh_smooth from the finite bounding box `box` = (lo, hi) or None (the rule of include/dsnerf.h):
+    origin = lo (zeros without a finite vertex), k = 27 - e with e the frexp exponent of the largest extent in double (0 when it is 0),
+    so that the box maps to [0, 2^27)"""
+    import numpy as np
+    if box is None:
+        return np.zeros(3, np.float32), 27
+    lo, hi = np.asarray(box[0], np.float32).reshape(3), np.asarray(box[1], np.float32).reshape(3)
+    D = float(np.max(hi.astype(np.float64) - lo.astype(np.float64)))
+    e = int(np.frexp(D)[1]) if D > 0 else 0
+    return np.ascontiguousarray(lo), 27 - e
+
+
+def _mesh_smooth_check(factors, origin, scale_exp):
+    import numpy as np
+    f = np.ascontiguousarray(np.asarray(factors, np.float32).reshape(-1))
+    if f.shape[0] > MESH_SMOOTH_MAX_STEPS:
+        raise ValueError(f"mesh_smooth: {f.shape[0]} steps, more than {MESH_SMOOTH_MAX_STEPS}")
+    if not np.isfinite(f).all():
+        raise ValueError("mesh_smooth: every factor must be finite")
+    origin = np.ascontiguousarray(np.asarray(origin, np.float32).reshape(3))
+    if not np.isfinite(origin).all():
+        raise ValueError("mesh_smooth: origin must be finite")
+    k = int(scale_exp)
+    if abs(k) > MESH_SMOOTH_MAX_EXP:
+        raise ValueError(f"mesh_smooth: scale_exp {k} outside -{MESH_SMOOTH_MAX_EXP} ... {MESH_SMOOTH_MAX_EXP}")
+    return f, origin, k
+
+
+def mesh_smooth(verts, faces, factors, origin=None, scale_exp=None, info=None, phases=0, state=None):
+    """dsn_mesh_smooth (the rule of include/dsnerf.h): one umbrella step per entry of `factors` (Taubin: lambda, mu, lambda, mu, ...;
+    Laplacian: lambda, lambda, ...) on a device mesh (verts [V,3] float32, faces [T,3] int32).  Returns the moved vertices [V,3] float32
+    on the device; faces, vertex count and order do not change.  origin / scale_exp default to mesh_smooth_scale of the vertices'
+    finite bounding box (one device->host read of six floats; none when both are given).  info: a dict that receives the counts
+    (MESH_SMOOTH_COUNTS: one device->host read of four int64, only then), origin, scale_exp and the factors.  phases / state: the
+    measurement entry (scripts/bench_mesh_smooth.py; state = {"ws", "counts", "out"} reused between calls)."""
+    require_gpu()
+    assert verts.is_cuda and faces.is_cuda, "verts and faces: device tensors"
+    verts = verts.reshape(-1, 3).to(torch.float32).contiguous()
+    faces = faces.reshape(-1, 3).to(torch.int32).contiguous()
+    V, T = verts.shape[0], faces.shape[0]
+    dev = verts.device
+    if origin is None or scale_exp is None:
+        o, k = mesh_smooth_scale(_finite_box(verts))
+        origin = o if origin is None else origin
+        scale_exp = k if scale_exp is None else scale_exp
+    f, origin, k = _mesh_smooth_check(factors, origin, scale_exp)
+    nbytes = lib().dsn_mesh_smooth_workspace_bytes(V, T)
+    if nbytes == 0:
+        raise RuntimeError("dsn_mesh_smooth: the mesh must stay below 2^31 vertices and faces")
+    if state is None:
+        state = {"ws": _scratch(nbytes, dev), "counts": torch.empty(4, dtype=torch.int64, device=dev),
+                 "out": torch.empty(V, 3, dtype=torch.float32, device=dev)}
+    _check(lib().dsn_mesh_smooth_ex(_ptr(verts) if V else None, _ptr(faces) if T else None, V, T, origin.ctypes.data, k,
+                                    f.ctypes.data if f.shape[0] else None, int(f.shape[0]), _ptr(state["ws"]), nbytes,
+                                    _ptr(state["out"]) if V else None, _ptr(state["counts"]), int(phases), _stream()), "dsn_mesh_smooth")
+    if info is not None:
+        info.update(dict(zip(MESH_SMOOTH_COUNTS, (int(c) for c in state["counts"].cpu()))), origin=origin.copy(), scale_exp=k, factors=f.copy())
+    return state["out"]
+
+
+def mesh_vertex_normals(verts, faces, phases=0, state=None):
+    """dsn_mesh_vertex_normals (the rule of include/dsnerf.h): area-weighted unit vertex normals [V,3] float32 from the faces of a device
+    mesh, oriented by the winding; (0, 0, 0) at a vertex no face with finite corners uses.  One device->host read of the bounding box
+    (six floats: the shift, mesh_area_shift's, is a host argument)."""
+    require_gpu()
+    verts, faces, V, T, shift = _mesh_cc_inputs(verts, faces)
+    dev = verts.device
+    nbytes = lib().dsn_mesh_smooth_workspace_bytes(V, T)
+    if nbytes == 0:
+        raise RuntimeError("dsn_mesh_vertex_normals: the mesh must stay below 2^31 vertices and faces")
+    if state is None:
+        state = {"ws": _scratch(nbytes, dev), "out": torch.empty(V, 3, dtype=torch.float32, device=dev)}
+    _check(lib().dsn_mesh_vertex_normals_ex(_ptr(verts) if V else None, _ptr(faces) if T else None, V, T, shift, _ptr(state["ws"]), nbytes,
+                                            _ptr(state["out"]) if V else None, int(phases), _stream()), "dsn_mesh_vertex_normals")
+    return state["out"]
 
 
 MESH_POSE_BAD_BINDING = 1    # DSN_MESH_POSE_BAD_BINDING: dsn_mesh_pose's status bit

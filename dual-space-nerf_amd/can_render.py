@@ -1221,7 +1221,7 @@ class Renderer:
 
     def extract_mesh(self, batch, resolution=512, level=0.5, gradient_direction="ascent", axes=None, points=None, frame=None,
                      fp32=False, slab_points=None, normals=False, attributes=None, largest_component=False, simplify_cell=None,
-                     target_vertices=None):
+                     target_vertices=None, smooth=None):
         """Visualizer3D's mesh of the posed body on the device: density_grid + marching cubes (dsn_mc_count / dsn_mc_emit, the rule of
         include/dsnerf.h).  Defaults are the visualizer's __main__ values.  Returns {"verts" [V,3] float32, "faces" [T,3] int32} device
         tensors in world coordinates, or None where the level is not crossed (the reference returns None there).
@@ -1236,7 +1236,11 @@ class Renderer:
         simplify_cell / target_vertices (one of them): the mesh thinned by vertex clustering (visualizer.simplify_mesh: dsn_mesh_simplify_count
         / dsn_mesh_simplify_emit, the rule of include/dsnerf.h) after the component filter and before the attributes, which are then
         evaluated at the few vertices that stay - input vertices, so again the rows of the unsimplified call.  The dict gains
-        "cluster_source", "vertex_cluster" and "simplify_info"; normals and source_vertex are gathered."""
+        "cluster_source", "vertex_cluster" and "simplify_info"; normals and source_vertex are gathered.
+        smooth: an int (Taubin pairs) or a dict of visualizer.smooth_mesh's keywords - the stair steps of the thresholded grid smoothed
+        out (dsn_mesh_smooth, the rule of include/dsnerf.h) after the component filter, before the thinning and before the attributes,
+        which are then evaluated at the final vertices.  "normals" are then those of the smoothed faces (dsn_mesh_vertex_normals:
+        oriented by the winding, which follows gradient_direction as marching cubes' do); the dict gains "smooth_info"."""
         if simplify_cell is not None and target_vertices is not None:
             raise ValueError("extract_mesh: give one of simplify_cell and target_vertices")
         names = tuple(attributes) if attributes else ()
@@ -1257,6 +1261,10 @@ class Renderer:
             if normals:
                 mesh["normals"] = out[2][src.long()]
             out = (v, f)
+        if smooth is not None:
+            from .visualizer import smooth_keywords, smooth_mesh
+            mesh = smooth_mesh(mesh, **smooth_keywords(smooth))
+            out = (mesh["verts"], mesh["faces"])
         if simplify_cell is not None or target_vertices is not None:
             from .visualizer import simplify_mesh
             mesh = simplify_mesh(mesh, cell=simplify_cell, target_vertices=target_vertices)

@@ -1484,6 +1484,69 @@ int dsn_mesh_simplify_emit(const float* verts, const int32_t* faces, int64_t n_v
                                      out_faces, cluster_source, 0, stream);
 }
 
+size_t dsn_mesh_smooth_workspace_bytes(int64_t n_verts, int64_t n_faces) {
+    return dsn_mesh_cc_sizes_ok(n_verts, n_faces) ? dsn_mesh_smooth_workspace_size(n_verts, n_faces) : 0;
+}
+
+// the byte ranges [a, a + n) and [b, b + n) share a byte
+static bool dsn_ranges_overlap(const void* a, const void* b, size_t n) {
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return n > 0 && (x < y ? y - x < n : x - y < n);
+}
+
+int dsn_mesh_smooth_ex(const float* verts, const int32_t* faces, int64_t n_verts, int64_t n_faces, const float* origin_host, int scale_exp,
+                       const float* factors_host, int n_steps, void* workspace, size_t workspace_bytes, float* out_verts, int64_t* out_counts4,
+                       int phases, void* stream) {
+    DSN_REQUIRE(n_verts >= 0 && n_faces >= 0, "dsn_mesh_smooth: negative count");
+    DSN_REQUIRE(dsn_mesh_cc_sizes_ok(n_verts, n_faces), "dsn_mesh_smooth: 2^31 or more vertices or faces");
+    DSN_REQUIRE((n_verts == 0 || verts) && (n_faces == 0 || faces), "dsn_mesh_smooth: null mesh");
+    DSN_REQUIRE(n_verts == 0 || out_verts, "dsn_mesh_smooth: null output buffer");
+    DSN_REQUIRE(workspace && origin_host, "dsn_mesh_smooth: null argument");
+    DSN_REQUIRE(n_steps >= 0 && n_steps <= DSN_MESH_SMOOTH_MAX_STEPS, "dsn_mesh_smooth: n_steps must be 0 ... 4096");
+    DSN_REQUIRE(n_steps == 0 || factors_host, "dsn_mesh_smooth: null factors");
+    DSN_REQUIRE(scale_exp >= -DSN_MESH_SMOOTH_MAX_EXP && scale_exp <= DSN_MESH_SMOOTH_MAX_EXP, "dsn_mesh_smooth: scale_exp must be -900 ... 900");
+    for (int a = 0; a < 3; ++a) DSN_REQUIRE(std::isfinite(origin_host[a]), "dsn_mesh_smooth: the origin must be finite");
+    for (int s = 0; s < n_steps; ++s) DSN_REQUIRE(std::isfinite(factors_host[s]), "dsn_mesh_smooth: every factor must be finite");
+    DSN_REQUIRE(workspace_bytes >= dsn_mesh_smooth_workspace_size(n_verts, n_faces),
+                "dsn_mesh_smooth: workspace_bytes too small (dsn_mesh_smooth_workspace_bytes)");
+    DSN_REQUIRE(((uintptr_t)workspace & 15) == 0, "dsn_mesh_smooth: workspace must be 16-byte aligned");
+    DSN_REQUIRE(!dsn_ranges_overlap(verts, out_verts, (size_t)12 * (size_t)n_verts), "dsn_mesh_smooth: out_verts must not overlap verts");
+    DSN_REQUIRE(phases == 0 || (phases & ~(DSN_SM_COUNT | DSN_SM_SCAN | DSN_SM_FILL | DSN_SM_STEP)) == 0, "dsn_mesh_smooth_ex: bad phases");
+    dsn_launch_mesh_smooth(verts, faces, n_verts, n_faces, origin_host, scale_exp, factors_host, n_steps, workspace, out_verts, out_counts4,
+                           phases ? phases : (DSN_SM_COUNT | DSN_SM_SCAN | DSN_SM_FILL | DSN_SM_STEP), (hipStream_t)stream);
+    return dsn_check_launch("dsn_mesh_smooth");
+}
+
+int dsn_mesh_smooth(const float* verts, const int32_t* faces, int64_t n_verts, int64_t n_faces, const float* origin_host, int scale_exp,
+                    const float* factors_host, int n_steps, void* workspace, size_t workspace_bytes, float* out_verts, int64_t* out_counts4,
+                    void* stream) {
+    return dsn_mesh_smooth_ex(verts, faces, n_verts, n_faces, origin_host, scale_exp, factors_host, n_steps, workspace, workspace_bytes,
+                              out_verts, out_counts4, 0, stream);
+}
+
+int dsn_mesh_vertex_normals_ex(const float* verts, const int32_t* faces, int64_t n_verts, int64_t n_faces, int shift, void* workspace,
+                               size_t workspace_bytes, float* out_normals, int phases, void* stream) {
+    DSN_REQUIRE(n_verts >= 0 && n_faces >= 0, "dsn_mesh_vertex_normals: negative count");
+    DSN_REQUIRE(dsn_mesh_cc_sizes_ok(n_verts, n_faces), "dsn_mesh_vertex_normals: 2^31 or more vertices or faces");
+    DSN_REQUIRE((n_verts == 0 || verts) && (n_faces == 0 || faces), "dsn_mesh_vertex_normals: null mesh");
+    DSN_REQUIRE(n_verts == 0 || out_normals, "dsn_mesh_vertex_normals: null output buffer");
+    DSN_REQUIRE(workspace, "dsn_mesh_vertex_normals: null argument");
+    DSN_REQUIRE(workspace_bytes >= dsn_mesh_smooth_workspace_size(n_verts, n_faces),
+                "dsn_mesh_vertex_normals: workspace_bytes too small (dsn_mesh_smooth_workspace_bytes)");
+    DSN_REQUIRE(((uintptr_t)workspace & 15) == 0, "dsn_mesh_vertex_normals: workspace must be 16-byte aligned");
+    DSN_REQUIRE(!dsn_ranges_overlap(verts, out_normals, (size_t)12 * (size_t)n_verts), "dsn_mesh_vertex_normals: out_normals must not overlap verts");
+    DSN_REQUIRE(shift >= -60 && shift <= 60, "dsn_mesh_vertex_normals: shift must be -60 ... 60");
+    DSN_REQUIRE(phases == 0 || (phases & ~(DSN_SM_COUNT | DSN_SM_SCAN | DSN_SM_FILL | DSN_SM_NORMALS)) == 0, "dsn_mesh_vertex_normals_ex: bad phases");
+    dsn_launch_mesh_vertex_normals(verts, faces, n_verts, n_faces, std::ldexp(1.0, shift), workspace, out_normals,
+                                   phases ? phases : (DSN_SM_COUNT | DSN_SM_SCAN | DSN_SM_FILL | DSN_SM_NORMALS), (hipStream_t)stream);
+    return dsn_check_launch("dsn_mesh_vertex_normals");
+}
+
+int dsn_mesh_vertex_normals(const float* verts, const int32_t* faces, int64_t n_verts, int64_t n_faces, int shift, void* workspace,
+                            size_t workspace_bytes, float* out_normals, void* stream) {
+    return dsn_mesh_vertex_normals_ex(verts, faces, n_verts, n_faces, shift, workspace, workspace_bytes, out_normals, 0, stream);
+}
+
 // counts of the bound-mesh calls: every byte size fits size_t and every grid fits 2^31 - 1 workgroups of 256
 static bool dsn_mesh_pose_sizes_ok(int64_t P, int64_t N) {
     return P >= 1 && N >= 0 && N < ((int64_t)1 << 38) && (uint64_t)N <= (uint64_t)SIZE_MAX / 12 / (uint64_t)P;

@@ -235,6 +235,12 @@ void dsn_launch_mesh_simplify_cells(const float* verts, int64_t V, const float* 
                                     hipStream_t st);
 void dsn_launch_mesh_simplify_emit(const float* verts, const int32_t* faces, int64_t V, int64_t T, const int* g, void* workspace, float* out_verts,
                                    int64_t vcap, int32_t* out_faces, int64_t fcap, int32_t* cluster_source, int phases, hipStream_t st);
+// dsn_mesh.hip: umbrella smoothing and vertex normals from the faces (dsn_mesh_smooth / dsn_mesh_vertex_normals; phases: DSN_SM_*)
+size_t dsn_mesh_smooth_workspace_size(int64_t V, int64_t T);
+void dsn_launch_mesh_smooth(const float* verts, const int32_t* faces, int64_t V, int64_t T, const float* origin, int k, const float* factors,
+                            int n_steps, void* workspace, float* out_verts, int64_t* out_counts, int phases, hipStream_t st);
+void dsn_launch_mesh_vertex_normals(const float* verts, const int32_t* faces, int64_t V, int64_t T, double scale, void* workspace,
+                                    float* out_normals, int phases, hipStream_t st);
 // dsn_mesh.hip: a mesh bound to the body (dsn_mesh_bind_normals / dsn_mesh_pose / dsn_mesh_stretch; workspace: DsnFaceRec [P, Fb])
 void dsn_launch_mesh_bind_normals(const float* body, int Vb, const int32_t* bfaces, int Fb, const int32_t* face_idx, const float* normals,
                                   int64_t N, float* cov, hipStream_t st);

@@ -1290,3 +1290,349 @@ void dsn_launch_mesh_simplify_emit(const float* verts, const int32_t* faces, int
     if ((phases & DSN_SP_EMIT_FACES) && w.tilesT && fcap > 0)
         hipLaunchKernelGGL(k_sp_emit_faces, dim3((unsigned)w.tilesT), dim3(MC_THREADS), 0, st, faces, V, T, w.vc, w.head, w.keep, w.tf, out_faces, fcap);
 }
+
+// ---------------------------------------------------------------------------------------------
+// umbrella smoothing and vertex normals from the faces (dsn_mesh_smooth / dsn_mesh_vertex_normals, the rule of include/dsnerf.h)
+//   lists : zero -> count (one thread per face: a contributing face adds 1 to each corner's row length, one int32 atomic per run of
+//           equal vertices in the wave) -> rank (the rows' 64-bit in-tile prefix over tiles of CC_TILE vertices, the vertices in use and
+//           the longest row) + k_sp_scan over the tiles -> fill (the face's entry into each corner's row through an atomic cursor).
+//           Entry of corner c of face (i0, i1, i2): the two corners after it in winding order, c in the two sign bits.
+//   step  : one thread per vertex gathers its row from the positions of the step before (the integer sums in registers) and writes x';
+//           a row longer than DSN_MESH_SMOOTH_HEAVY is summed by its whole wave.  No atomics.
+//   normals: the same gather over the same lists, the face normals in float32, the sums in integers.
+// Global atomics execute at the memory side: a scatter of 3 T 64-bit adds per step would run at the atomic rate, the gather runs at the
+// rate of the loads.  Every value read back from the workspace is range-checked before it is used as an index.
+// ---------------------------------------------------------------------------------------------
+enum { SM_FACES = 0, SM_USED = 2, SM_LONGEST = 3 };      // the header's 64-bit words
+
+// header 64 B | row lengths int32 [V] | cursors int32 [V] | in-tile row prefix int64 [V] | tile offsets int64 [tiles + 1] |
+// entries int32 [3 T, 2] | positions A float [3 V] | positions B float [3 V]            (every part 16-byte aligned)
+struct SmWs {
+    unsigned long long* head; int32_t* cnt; int32_t* cur; int64_t* pre; int64_t* tw; int2* ent; float* pa; float* pb;
+    int64_t tiles; size_t bytes;
+};
+static SmWs sm_ws(void* w, int64_t V, int64_t T) {
+    SmWs r;
+    r.tiles = cc_tiles(V);
+    char* p = (char*)w;
+    size_t o = 0;
+    r.head = (unsigned long long*)(p + o); o += 64;
+    r.cnt = (int32_t*)(p + o); o += cc_up((size_t)4 * V);
+    r.cur = (int32_t*)(p + o); o += cc_up((size_t)4 * V);
+    r.pre = (int64_t*)(p + o); o += cc_up((size_t)8 * V);
+    r.tw = (int64_t*)(p + o); o += cc_up((size_t)8 * (r.tiles + 1));
+    r.ent = (int2*)(p + o); o += cc_up((size_t)24 * T);
+    r.pa = (float*)(p + o); o += cc_up((size_t)12 * V);
+    r.pb = (float*)(p + o); o += cc_up((size_t)12 * V);
+    r.bytes = o;
+    return r;
+}
+size_t dsn_mesh_smooth_workspace_size(int64_t V, int64_t T) { return sm_ws(nullptr, V, T).bytes; }
+
+__global__ void __launch_bounds__(MC_THREADS) k_sm_zero(int32_t* __restrict__ cnt, int32_t* __restrict__ cur, int64_t V,
+                                                        unsigned long long* __restrict__ head) {
+    const int64_t v = (int64_t)blockIdx.x * MC_THREADS + threadIdx.x;
+    if (v < 8) head[v] = 0;
+    if (v < V) { cnt[v] = 0; cur[v] = 0; }
+}
+
+__device__ __forceinline__ bool sm_finite3(const float* __restrict__ p) {
+    const float inf = __builtin_inff();
+    return fabsf(p[0]) < inf && fabsf(p[1]) < inf && fabsf(p[2]) < inf;      // (NaN fails the comparison)
+}
+// a contributing face: indices in [0, V), pairwise different, nine finite coordinates
+__device__ __forceinline__ bool sm_face(const float* __restrict__ verts, const int32_t* __restrict__ faces, int64_t t, int64_t V, int32_t i[3]) {
+    if (!cc_face(faces, t, (int)V, i[0], i[1], i[2])) return false;
+    if (i[0] == i[1] || i[1] == i[2] || i[0] == i[2]) return false;
+    return sm_finite3(verts + 3 * (int64_t)i[0]) && sm_finite3(verts + 3 * (int64_t)i[1]) && sm_finite3(verts + 3 * (int64_t)i[2]);
+}
+
+// Neighbouring lanes with the same key form a run (the corners of a fan, the shared vertices of a marching-cubes strip): the run's first
+// lane adds the run's length to the key's counter with one atomic and every lane takes its own slot of the range that add returned.
+__device__ __forceinline__ int32_t sm_claim(int32_t* __restrict__ ctr, int32_t key, bool on, int lane) {
+    key = on ? key : -1;
+    const int32_t prev = __shfl_up(key, 1);
+    const bool first = lane == 0 || prev != key;
+    const unsigned long long heads = __ballot(first);                                        // (lane 0 is always a head)
+    const int head_lane = 63 - __clzll((long long)(heads & ((2ull << lane) - 1ull)));
+    const unsigned long long above = heads & ~((2ull << head_lane) - 1ull);
+    const int next = above ? __ffsll((long long)above) - 1 : 64;
+    int32_t base = 0;
+    if (first && on) base = __hip_atomic_fetch_add(ctr + key, next - head_lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    base = __shfl(base, head_lane);
+    return base + (lane - head_lane);
+}
+
+__global__ void __launch_bounds__(MC_THREADS) k_sm_count(const float* __restrict__ verts, const int32_t* __restrict__ faces, int64_t V, int64_t T,
+                                                         int32_t* __restrict__ cnt, unsigned long long* __restrict__ head) {
+    const int64_t t = (int64_t)blockIdx.x * MC_THREADS + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    int32_t i[3] = {0, 0, 0};
+    const bool on = t < T && sm_face(verts, faces, t, V, i);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) sm_claim(cnt, i[c], on, lane);
+    const unsigned long long m = __ballot(on);
+    if (lane == 0 && m) __hip_atomic_fetch_add(head + SM_FACES, (unsigned long long)__popcll(m), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// the rows' exclusive 64-bit prefix inside tile blockIdx.x and the tile's total; the vertices in use and the longest row
+__global__ void __launch_bounds__(MC_THREADS) k_sm_rank(const int32_t* __restrict__ cnt, int64_t V, int64_t* __restrict__ pre,
+                                                        int64_t* __restrict__ tw, unsigned long long* __restrict__ head) {
+    __shared__ int64_t sa[MC_THREADS];
+    const int t = threadIdx.x, lane = threadIdx.x & 63;
+    const int64_t v0 = (int64_t)blockIdx.x * CC_TILE + (int64_t)t * CC_PER;
+    int32_t c[CC_PER];
+    int64_t a = 0;
+    int used = 0, longest = 0;
+#pragma unroll
+    for (int q = 0; q < CC_PER; ++q) {
+        c[q] = v0 + q < V ? cnt[v0 + q] : 0;
+        if (c[q] < 0) c[q] = 0;
+        a += c[q];
+        used += c[q] > 0 ? 1 : 0;
+        longest = c[q] > longest ? c[q] : longest;
+    }
+    sa[t] = a;
+    __syncthreads();
+    for (int off = 1; off < MC_THREADS; off <<= 1) {
+        const int64_t x = t >= off ? sa[t - off] : 0;
+        __syncthreads();
+        sa[t] += x;
+        __syncthreads();
+    }
+    int64_t p = sa[t] - a;
+#pragma unroll
+    for (int q = 0; q < CC_PER; ++q) {
+        if (v0 + q < V) pre[v0 + q] = p;
+        p += c[q];
+    }
+    if (t == MC_THREADS - 1) tw[blockIdx.x] = sa[t];
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        used += __shfl_xor(used, off);
+        const int o = __shfl_xor(longest, off);
+        longest = o > longest ? o : longest;
+    }
+    if (lane == 0 && used) {
+        __hip_atomic_fetch_add(head + SM_USED, (unsigned long long)used, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_fetch_max(head + SM_LONGEST, (unsigned long long)longest, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+__global__ void k_sm_counts(const unsigned long long* __restrict__ head, int64_t T, int64_t* __restrict__ out) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    out[0] = (int64_t)head[SM_FACES];
+    out[1] = T - (int64_t)head[SM_FACES];
+    out[2] = (int64_t)head[SM_USED];
+    out[3] = (int64_t)head[SM_LONGEST];
+}
+
+// row of vertex v: start (into the entries) and length, clamped into [0, 3 T] whatever the workspace holds
+__device__ __forceinline__ void sm_row(const int32_t* __restrict__ cnt, const int64_t* __restrict__ pre, const int64_t* __restrict__ tw,
+                                       int64_t v, int64_t T, int64_t& start, int32_t& len) {
+    start = tw[v / CC_TILE] + pre[v];
+    len = cnt[v];
+    const int64_t cap = 3 * T;
+    if (start < 0 || start > cap || len < 0) { start = 0; len = 0; }
+    if (len > cap - start) len = (int32_t)(cap - start);
+}
+
+__global__ void __launch_bounds__(MC_THREADS) k_sm_fill(const float* __restrict__ verts, const int32_t* __restrict__ faces, int64_t V, int64_t T,
+                                                        const int32_t* __restrict__ cnt, const int64_t* __restrict__ pre,
+                                                        const int64_t* __restrict__ tw, int32_t* __restrict__ cur, int2* __restrict__ ent) {
+    const int64_t t = (int64_t)blockIdx.x * MC_THREADS + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    int32_t i[3] = {0, 0, 0};
+    const bool on = t < T && sm_face(verts, faces, t, V, i);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const int32_t slot = sm_claim(cur, i[c], on, lane);
+        if (!on) continue;
+        int64_t start; int32_t len;
+        sm_row(cnt, pre, tw, i[c], T, start, len);
+        if ((uint32_t)slot >= (uint32_t)len) continue;      // (never, after count and rank)
+        const int32_t j = i[(c + 1) % 3], l = i[(c + 2) % 3];
+        ent[start + slot] = make_int2(j | (int32_t)((uint32_t)(c & 1) << 31), l | (int32_t)((uint32_t)(c >> 1) << 31));
+    }
+}
+
+// q = floor((double(x) - double(origin)) 2^k) clamped to [-2^30, 2^30 - 1]; 0 where the difference is not finite
+__device__ __forceinline__ int64_t sm_q(float x, double o, double scale) {
+    const double r = (double)x - o;
+    if (!(fabs(r) < (double)__builtin_inff())) return 0;
+    double q = floor(r * scale);
+    q = q < -1073741824.0 ? -1073741824.0 : (q > 1073741823.0 ? 1073741823.0 : q);
+    return (int64_t)q;
+}
+
+struct SmGrid { double o[3]; double scale; double inv; };
+
+// the step's row sum: per entry q_j + q_l over the three axes (the caller takes 2 len q_i off)
+struct SmStepAcc {
+    int64_t s[3];
+    const float* pos; double o[3]; double scale; int64_t V;
+    __device__ __forceinline__ void i_set(int64_t) {}
+    __device__ __forceinline__ void add(int2 e) {
+        const int64_t j = e.x & 0x7FFFFFFF, l = e.y & 0x7FFFFFFF;
+        if (j >= V || l >= V) return;                      // (never, after fill)
+        const float* a = pos + 3 * j; const float* b = pos + 3 * l;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) s[c] += sm_q(a[c], o[c], scale) + sm_q(b[c], o[c], scale);
+    }
+};
+
+// the normals' row sum: the face of every entry in its own winding, its float32 normal, floor(n_c 2^shift).  Branch-free: the loads of
+// an entry do not wait for one another's tests (what an entry must not add is selected to 0 at the end).
+struct SmNormalAcc {
+    int64_t s[3];
+    const float* pos; double scale; int64_t V; float p[3];      // p: the row's own vertex
+    __device__ __forceinline__ void i_set(int64_t v) { p[0] = pos[3 * v]; p[1] = pos[3 * v + 1]; p[2] = pos[3 * v + 2]; }
+    __device__ __forceinline__ void add(int2 e) {
+        const int64_t j = e.x & 0x7FFFFFFF, l = e.y & 0x7FFFFFFF;
+        const int c = (int)((uint32_t)e.x >> 31) | ((int)((uint32_t)e.y >> 31) << 1);
+        bool ok = j < V && l < V && c <= 2;                // (always, after fill)
+        const float* pj = pos + 3 * (ok ? j : 0); const float* pl = pos + 3 * (ok ? l : 0);
+        const float xj[3] = {pj[0], pj[1], pj[2]}, xl[3] = {pl[0], pl[1], pl[2]};
+        float a[3], b[3], cc[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {                      // corner c of (a, b, cc) is the row's vertex, j and l follow it in the winding
+            a[k] = c == 0 ? p[k] : (c == 1 ? xl[k] : xj[k]);
+            b[k] = c == 0 ? xj[k] : (c == 1 ? p[k] : xl[k]);
+            cc[k] = c == 0 ? xl[k] : (c == 1 ? xj[k] : p[k]);
+        }
+        ok = ok && sm_finite3(p) && sm_finite3(xj) && sm_finite3(xl);
+        const float e1x = b[0] - a[0], e1y = b[1] - a[1], e1z = b[2] - a[2];
+        const float e2x = cc[0] - a[0], e2y = cc[1] - a[1], e2z = cc[2] - a[2];
+        const float n[3] = {e1y * e2z - e1z * e2y, e1z * e2x - e1x * e2z, e1x * e2y - e1y * e2x};
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            double q = floor((double)n[k] * scale);
+            q = q < -4611686018427387904.0 ? -4611686018427387904.0 : (q > 4611686018427387904.0 ? 4611686018427387904.0 : q);
+            s[k] += (int64_t)(ok && fabsf(n[k]) < __builtin_inff() ? q : 0.0);
+        }
+    }
+};
+
+// the row of every lane's vertex into acc.s: a light row by its own lane, a heavy one by the whole wave (every lane of the wave calls this)
+template <class Acc>
+__device__ __forceinline__ void sm_gather(const int2* __restrict__ ent, int64_t start, int32_t len, int64_t v, Acc& acc, int lane) {
+    acc.s[0] = acc.s[1] = acc.s[2] = 0;
+    if (len <= DSN_MESH_SMOOTH_HEAVY)
+        for (int32_t e = 0; e < len; ++e) acc.add(ent[start + e]);
+    unsigned long long heavy = __ballot(len > DSN_MESH_SMOOTH_HEAVY);
+    while (heavy) {
+        const int leader = __ffsll((long long)heavy) - 1;
+        heavy &= heavy - 1;
+        const int64_t hs = __shfl(start, leader), hv = __shfl(v, leader);
+        const int32_t hl = __shfl(len, leader);
+        Acc part = acc;
+        part.s[0] = part.s[1] = part.s[2] = 0;
+        part.i_set(hv);
+#pragma unroll 4
+        for (int32_t e = lane; e < hl; e += 64) part.add(ent[hs + e]);
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+#pragma unroll
+            for (int off = 32; off >= 1; off >>= 1) part.s[c] += __shfl_xor(part.s[c], off);
+        if (lane == leader) { acc.s[0] = part.s[0]; acc.s[1] = part.s[1]; acc.s[2] = part.s[2]; }
+    }
+}
+
+__global__ void __launch_bounds__(MC_THREADS) k_sm_step(const float* __restrict__ src, float* __restrict__ dst, int64_t V, int64_t T,
+                                                        const int32_t* __restrict__ cnt, const int64_t* __restrict__ pre,
+                                                        const int64_t* __restrict__ tw, const int2* __restrict__ ent, SmGrid G, double f) {
+    const int64_t v = (int64_t)blockIdx.x * MC_THREADS + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    int64_t start = 0; int32_t len = 0;
+    if (v < V) sm_row(cnt, pre, tw, v, T, start, len);
+    SmStepAcc acc;
+    acc.pos = src; acc.o[0] = G.o[0]; acc.o[1] = G.o[1]; acc.o[2] = G.o[2]; acc.scale = G.scale; acc.V = V;
+    sm_gather(ent, start, len, v, acc, lane);
+    if (v >= V) return;
+    if (len == 0) {                                        // n_i = 0: the three words, copied
+        const uint32_t* in = (const uint32_t*)src + 3 * v;
+        uint32_t* o = (uint32_t*)dst + 3 * v;
+        o[0] = in[0]; o[1] = in[1]; o[2] = in[2];
+        return;
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const float x = src[3 * v + c];
+        const int64_t S = acc.s[c] - 2 * (int64_t)len * sm_q(x, G.o[c], G.scale);
+        const double delta = (double)S / (double)(2 * (int64_t)len);
+        const double t = f * delta;
+        const double u = t * G.inv;
+        dst[3 * v + c] = (float)((double)x + u);
+    }
+}
+
+__global__ void __launch_bounds__(MC_THREADS) k_sm_normals(const float* __restrict__ verts, float* __restrict__ out, int64_t V, int64_t T,
+                                                           const int32_t* __restrict__ cnt, const int64_t* __restrict__ pre,
+                                                           const int64_t* __restrict__ tw, const int2* __restrict__ ent, double scale) {
+    const int64_t v = (int64_t)blockIdx.x * MC_THREADS + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    int64_t start = 0; int32_t len = 0;
+    if (v < V) sm_row(cnt, pre, tw, v, T, start, len);
+    SmNormalAcc acc;
+    acc.pos = verts; acc.scale = scale; acc.V = V;
+    acc.p[0] = acc.p[1] = acc.p[2] = 0.0f;
+    if (v < V) acc.i_set(v);
+    sm_gather(ent, start, len, v, acc, lane);
+    if (v >= V) return;
+    const double N0 = (double)acc.s[0], N1 = (double)acc.s[1], N2 = (double)acc.s[2];
+    const double L = sqrt((N0 * N0 + N1 * N1) + N2 * N2);
+    const bool ok = L > 0.0;
+    out[3 * v] = ok ? (float)(N0 / L) : 0.0f;
+    out[3 * v + 1] = ok ? (float)(N1 / L) : 0.0f;
+    out[3 * v + 2] = ok ? (float)(N2 / L) : 0.0f;
+}
+
+__global__ void __launch_bounds__(MC_THREADS) k_sm_copy(const uint32_t* __restrict__ src, uint32_t* __restrict__ dst, int64_t n) {
+    const int64_t k = (int64_t)blockIdx.x * MC_THREADS + threadIdx.x;
+    if (k < n) dst[k] = src[k];
+}
+
+static void sm_lists(const float* verts, const int32_t* faces, int64_t V, int64_t T, const SmWs& w, int64_t* out_counts, int phases,
+                     hipStream_t st) {
+    const unsigned gV = mesh_blocks(V), gT = mesh_blocks(T);
+    if (phases & DSN_SM_COUNT) {
+        hipLaunchKernelGGL(k_sm_zero, dim3(gV ? gV : 1), dim3(MC_THREADS), 0, st, w.cnt, w.cur, V, w.head);
+        if (gT && gV) hipLaunchKernelGGL(k_sm_count, dim3(gT), dim3(MC_THREADS), 0, st, verts, faces, V, T, w.cnt, w.head);
+    }
+    if (phases & DSN_SM_SCAN) {
+        if (w.tiles) hipLaunchKernelGGL(k_sm_rank, dim3((unsigned)w.tiles), dim3(MC_THREADS), 0, st, w.cnt, V, w.pre, w.tw, w.head);
+        hipLaunchKernelGGL(k_sp_scan, dim3(1), dim3(MC_SCAN_THREADS), 0, st, w.tw, w.tiles, w.head + 4, (int64_t)0, w.head + 5);
+        if (out_counts) hipLaunchKernelGGL(k_sm_counts, dim3(1), dim3(64), 0, st, w.head, T, out_counts);
+    }
+    if ((phases & DSN_SM_FILL) && gT && gV)
+        hipLaunchKernelGGL(k_sm_fill, dim3(gT), dim3(MC_THREADS), 0, st, verts, faces, V, T, w.cnt, w.pre, w.tw, w.cur, w.ent);
+}
+
+void dsn_launch_mesh_smooth(const float* verts, const int32_t* faces, int64_t V, int64_t T, const float* origin, int k, const float* factors,
+                            int n_steps, void* workspace, float* out_verts, int64_t* out_counts, int phases, hipStream_t st) {
+    SmWs w = sm_ws(workspace, V, T);
+    sm_lists(verts, faces, V, T, w, out_counts, phases, st);
+    if (!(phases & DSN_SM_STEP) || V == 0) return;
+    const unsigned gV = mesh_blocks(V);
+    if (n_steps == 0) {
+        hipLaunchKernelGGL(k_sm_copy, dim3(mesh_blocks(3 * V)), dim3(MC_THREADS), 0, st, (const uint32_t*)verts, (uint32_t*)out_verts, 3 * V);
+        return;
+    }
+    SmGrid G;
+    for (int a = 0; a < 3; ++a) G.o[a] = (double)origin[a];
+    G.scale = ldexp(1.0, k); G.inv = ldexp(1.0, -k);
+    const float* src = verts;
+    for (int s = 0; s < n_steps; ++s) {
+        float* dst = s == n_steps - 1 ? out_verts : ((s & 1) ? w.pb : w.pa);
+        hipLaunchKernelGGL(k_sm_step, dim3(gV), dim3(MC_THREADS), 0, st, src, dst, V, T, w.cnt, w.pre, w.tw, w.ent, G, (double)factors[s]);
+        src = dst;
+    }
+}
+
+void dsn_launch_mesh_vertex_normals(const float* verts, const int32_t* faces, int64_t V, int64_t T, double scale, void* workspace,
+                                    float* out_normals, int phases, hipStream_t st) {
+    SmWs w = sm_ws(workspace, V, T);
+    sm_lists(verts, faces, V, T, w, nullptr, phases, st);
+    if ((phases & DSN_SM_NORMALS) && V)
+        hipLaunchKernelGGL(k_sm_normals, dim3(mesh_blocks(V)), dim3(MC_THREADS), 0, st, verts, out_normals, V, T, w.cnt, w.pre, w.tw, w.ent, scale);
+}

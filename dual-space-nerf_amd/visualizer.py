@@ -14,7 +14,10 @@ A mesh follows the body into other poses without a second extraction: Renderer.b
 (dsn_mesh_pose, the rule of include/dsnerf.h); render_mesh_sequence previews such a sequence and cull_stretched drops the triangles
 a pose tore.  simplify_mesh (or simplify_cell= / target_vertices= of extract_mesh and get_mesh_from_grid) thins a mesh by vertex
 clustering (dsn_mesh_simplify_count / dsn_mesh_simplify_emit, the rule of include/dsnerf.h): the vertices that stay are input vertices, so
-every per-vertex array and a binding follow by one gather."""
+every per-vertex array and a binding follow by one gather.  smooth_mesh (or smooth= of extract_mesh and get_mesh_from_grid) takes the
+stair steps of the thresholded grid out with Taubin or Laplacian umbrella steps (dsn_mesh_smooth), and vertex_normals gives a mesh whose
+vertices moved - smoothed, posed, loaded from a file - normals from its faces (dsn_mesh_vertex_normals); both by the rules of
+include/dsnerf.h, in integer sums: the same bits every call."""
 import numpy as np
 import torch
 
@@ -78,13 +81,15 @@ class Visualizer3D(object):
         return grid_pts, grid_pred
 
     def get_mesh_from_grid(self, grid_pts, grid_pred, return_normals=False, largest_component=False, simplify_cell=None,
-                           target_vertices=None):
+                           target_vertices=None, smooth=None):
         """(verts [V,3] float32, faces [T,3] int32) numpy arrays of the iso-surface at mc_value in the grid's coordinates, or None
         where the level is not crossed.  grid_pts / grid_pred: [X,Y,Z,3] / [X,Y,Z,1] (or with the leading B = 1).
         return_normals=True: a third array, the unit vertex normals [V,3] float32 (skimage's vertex_normals, by dsn_mc_normals).
         largest_component=True: only the connected component with the largest area (the reference's connected=True; the rule of
         include/dsnerf.h, on the device), the normals gathered with it.
-        simplify_cell / target_vertices (one of them): the mesh thinned by simplify_mesh, after the component filter."""
+        simplify_cell / target_vertices (one of them): the mesh thinned by simplify_mesh, after the component filter.
+        smooth: an int (Taubin pairs) or a dict of smooth_mesh's keywords - the mesh smoothed by smooth_mesh after the component filter
+        and before the thinning; the normals returned are then those of the smoothed faces."""
         if self.connected:
             raise NotImplementedError("Visualizer3D(connected=True) is not wired up: pass largest_component=True to get_mesh_from_grid "
                                       "(or use dsnerf_amd.visualizer.largest_component) for the largest connected component")
@@ -100,6 +105,8 @@ class Visualizer3D(object):
         if largest_component:
             v, f, src = _lib.largest_component(out[0], out[1], want_source=bool(return_normals))
             out = (v, f) + ((out[2][src.long()],) if return_normals else ())
+        if smooth is not None:
+            out = smooth_mesh(tuple(out), **smooth_keywords(smooth))
         if simplify_cell is not None or target_vertices is not None:
             out = simplify_mesh(tuple(out), cell=simplify_cell, target_vertices=target_vertices)
         return tuple(a.cpu().numpy() for a in out)
@@ -263,6 +270,78 @@ def simplify_mesh(mesh, cell=None, target_vertices=None):
         if out.get(k) is not None:
             out[k] = back(gather(out[k]))
     out.update(verts=back(v), faces=back(f), cluster_source=back(src), vertex_cluster=back(vc), simplify_info=info)
+    return out
+
+
+def smooth_keywords(smooth):
+    """smooth= of Renderer.extract_mesh / get_mesh_from_grid as smooth_mesh's keywords: an int is the number of Taubin pairs"""
+    if isinstance(smooth, dict):
+        return dict(smooth)
+    if isinstance(smooth, bool) or not isinstance(smooth, (int, np.integer)):
+        raise ValueError(f"smooth: an int (Taubin pairs) or a dict of smooth_mesh's keywords, got {smooth!r}")
+    return {"iterations": int(smooth)}
+
+
+def _mesh_parts(mesh):
+    if isinstance(mesh, dict):
+        return mesh["verts"], mesh["faces"], mesh.get("normals")
+    return (tuple(mesh) + (None,))[:3]
+
+
+def _to_device(a, dtype=None):
+    a = a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))
+    return a.to(device="cuda", dtype=dtype)
+
+
+@torch.no_grad()
+def vertex_normals(mesh):
+    """Unit vertex normals [V,3] float32 from the faces of a mesh (dsn_mesh_vertex_normals, the rule of include/dsnerf.h): area-weighted,
+    oriented by the winding, (0, 0, 0) at a vertex no face with finite corners uses.  For a mesh whose vertices moved since marching
+    cubes gave it normals - smoothed, posed - or that never had any: mesh["normals"] = vertex_normals(mesh) and render_mesh shades it
+    smooth.  mesh: a (verts, faces[, ...]) tuple or a dict with "verts" and "faces", numpy or device; the result lives where verts
+    lived."""
+    verts, faces, _ = _mesh_parts(mesh)
+    n = _lib.mesh_vertex_normals(_to_device(verts, torch.float32).reshape(-1, 3), _to_device(faces, torch.int32))
+    return n if torch.is_tensor(verts) else n.cpu().numpy()
+
+
+@torch.no_grad()
+def smooth_mesh(mesh, iterations=10, lamb=0.5, mu=-0.53, normals=None):
+    """A mesh smoothed by umbrella steps on the device (dsn_mesh_smooth, the rule of include/dsnerf.h): every vertex moves by a factor
+    times the mean offset of its neighbours, every face giving each corner its two others (on a closed surface trimesh's uniform
+    filter_laplacian weights; a boundary edge counts once).  `iterations` Taubin pairs of a lambda step and a mu step (mu < -lambda < 0:
+    the second step undoes the shrinkage of the first), or with mu=None `iterations` plain lambda steps, which shrink.  Faces, vertex
+    count and order do not change; vertices no face with finite, distinct corners uses stay bit for bit.
+    mesh: a (verts, faces[, normals]) tuple or the dict of Renderer.extract_mesh, numpy or device; the result has the same form and
+    lives where verts lived.  normals=None: a mesh that carries normals gets them recomputed from the smoothed faces (vertex_normals:
+    marching cubes' normals describe the surface before); True: computed in any case; False: none, stale ones are dropped.
+    The entries of a binding (face_idx, uv, h, cov, x_c) are DROPPED - they describe the old positions: bind after smoothing.  Other
+    per-vertex arrays (albedo, colour, source_vertex, ...) and keys are carried over as they are; the field's attributes are not
+    evaluated again at the moved vertices (Renderer.extract_mesh(smooth=...) evaluates them after smoothing).  The dict gains
+    "smooth_info": the counts of _lib.MESH_SMOOTH_COUNTS, origin, scale_exp and the factors."""
+    iterations = int(iterations)
+    if iterations < 0:
+        raise ValueError("smooth_mesh: iterations must be >= 0")
+    factors = [float(lamb)] * iterations if mu is None else [float(lamb), float(mu)] * iterations
+    if len(factors) > _lib.MESH_SMOOTH_MAX_STEPS:
+        raise ValueError(f"smooth_mesh: {len(factors)} steps, more than {_lib.MESH_SMOOTH_MAX_STEPS}")
+    is_dict = isinstance(mesh, dict)
+    verts, faces, had = _mesh_parts(mesh)
+    on_host = not torch.is_tensor(verts)
+
+    def back(a):
+        return a.cpu().numpy() if on_host else a
+    dv, df = _to_device(verts, torch.float32).reshape(-1, 3), _to_device(faces, torch.int32)
+    info = {}
+    v = _lib.mesh_smooth(dv, df, factors, info=info)
+    want = had is not None if normals is None else bool(normals)
+    n = _lib.mesh_vertex_normals(v, df) if want else None
+    if not is_dict:
+        return (back(v), faces) + ((back(n),) if want else ())
+    out = {k: a for k, a in mesh.items() if k not in BINDING_KEYS and k != "normals"}
+    out.update(verts=back(v), smooth_info=info)
+    if want:
+        out["normals"] = back(n)
     return out
 
 

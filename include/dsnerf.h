@@ -812,6 +812,76 @@ DSN_EXPORT int dsn_mesh_simplify_emit_ex(const float* verts, const int32_t* face
                                          void* workspace, size_t workspace_bytes, int64_t out_n_verts, int64_t out_n_faces, float* out_verts,
                                          int32_t* out_faces, int32_t* cluster_source, int phases, void* stream);
 
+/* ---- mesh smoothing and normals from the faces (an addition within ABI 8: no existing entry point changes) ---------------------------
+ * An iso-surface of a thresholded density grid is stair-stepped; the reference's users would call trimesh.smoothing.filter_taubin or
+ * filter_laplacian on the host.  Here: umbrella steps on the device, and area-weighted vertex normals from the faces for meshes whose
+ * marching-cubes normals are stale (smoothed, posed, loaded from a file).  There is no counterpart in the reference; both rules are fixed
+ * so that a numpy restatement (tests/mesh_smooth_restate.py) reproduces every output bit for bit.  Integer sums only: every call returns
+ * the same bits, whatever the order of the faces.
+ * dsn_mesh_smooth:
+ *   Inputs:   verts [V, 3] float32, faces [T, 3] int32 (device); origin_host [3] float32, scale_exp = k and factors_host [n_steps] float32
+ *             in HOST memory (read before the call returns), 0 <= n_steps <= DSN_MESH_SMOOTH_MAX_STEPS, |k| <= DSN_MESH_SMOOTH_MAX_EXP.
+ *             Output out_verts [V, 3] float32, which must not overlap verts.  Faces, vertex count and vertex order never change.
+ *   Contributing face: its three indices lie in [0, V), are pairwise different, and all nine coordinates of its vertices IN THE INPUT are
+ *             finite.  The set is fixed for the whole call; every other face is skipped.  n_i = 2 x the number of contributing faces at
+ *             vertex i; a vertex with n_i = 0 (unused, not finite) is copied bit for bit.
+ *   Weights:  every contributing face gives each of its corners the other two as neighbours: w_ij = the number of contributing faces that
+ *             hold both i and j.  On a closed manifold every edge counts twice - the uniform umbrella operator of
+ *             trimesh.smoothing.filter_laplacian - ; a BOUNDARY edge has weight 1, so a boundary vertex leans towards the interior.
+ *   Scale:    the caller's: origin = the minimum of the vertices whose coordinates are all finite (zeros without one), D = the largest
+ *             extent max_a double(hi_a) - double(lo_a), e = the frexp exponent of D (0 when D = 0), k = 27 - e: the box maps to [0, 2^27).
+ *   Quantised coordinate, per step from that step's float32 positions: r = double(x_a) - double(origin_a); q = floor(r 2^k), formed in
+ *             double and clamped to [-2^30, 2^30 - 1]; q = 0 where r is not finite.  (The clamp is eight extents away: only factors that
+ *             make the iteration diverge reach it.)
+ *   Step with factor f, every vertex with n_i > 0 and every axis: S = the signed 64-bit sum over the contributing faces (i, j, l) at i of
+ *             (q_j - q_i) + (q_l - q_i)  (|S| <= 2 T (2^31 - 1) < 2^63);  delta = double(S) / double(n_i);  t = double(f) delta;
+ *             u = t 2^-k (exact);  x' = float32(double(x) + u).  One IEEE rounding per operation, nothing fused.  All vertices of a step
+ *             read the positions of the step before it.  The sum does not depend on the order of the faces or on their rotation, and a
+ *             coordinate a vertex shares with all its neighbours keeps its bits.
+ *   Modes:    Taubin smoothing is the factor sequence lambda, mu, lambda, mu, ... (mu < -lambda < 0), plain Laplacian lambda, lambda, ...
+ *   Counts:   out_counts4 (may be NULL): 4 int64 in device memory {contributing faces, skipped faces, vertices with n_i > 0, the largest
+ *             number of contributing faces at one vertex}.
+ * dsn_mesh_vertex_normals: out_normals [V, 3] float32.
+ *   A face counts when its indices lie in [0, V) and its nine coordinates are finite.  Its normal is dsn_mesh_cc_label's float32 cross
+ *   product (e1 = b - a, e2 = c - a, each component two rounded products and one subtraction: a face with a repeated index gives exactly
+ *   0); a component that is not finite counts as 0.  Every component adds floor(double(n_c) 2^shift), clamped to +-2^62, to a signed
+ *   64-bit sum at each of the face's three vertices; `shift` is dsn_mesh_cc_label's area_shift, unchanged (it keeps T such terms below
+ *   2^61).  With N = the three sums as doubles: L = sqrt((N0 N0 + N1 N1) + N2 N2), out_c = float32(N_c / L); L = 0, or a vertex in no
+ *   such face: (0, 0, 0), which dsn_raster_mesh_attr already treats.  Area-weighted, oriented by the winding.
+ * Kernels: once per call a vertex -> corner list (CSR): int32 atomic counts per vertex, one per run of equal vertices in the wave; the tile
+ * scan of the simplification over tiles of DSN_MESH_CC_TILE vertices for the 64-bit offsets (3 T can pass 2^31); a fill through atomic
+ * cursors (the order inside a row is arbitrary: rows are summed in integers).  An entry is 8 bytes: the face's two other corners in
+ * winding order, the corner's number in the two sign bits.  Each step is one launch with one thread per vertex that gathers its row
+ * from the positions of the step before and writes x' - no atomics; positions ping-pong between two buffers of the workspace.  A row
+ * longer than DSN_MESH_SMOOTH_HEAVY entries is summed by its whole wave with a wave reduction.  The normals gather through the same
+ * lists.  All atomics are relaxed and agent scope, all 3 V and 3 T indexing is 64-bit, everything read back from the workspace is
+ * range-checked before it is used as an index.  V = 0, T = 0 and n_steps = 0 (a bit-for-bit copy) are valid calls.  No allocation, no
+ * synchronisation, all on `stream`.  `workspace`: dsn_mesh_smooth_workspace_bytes(V, T) (0 for bad sizes) for both calls, 16-byte
+ * aligned; its earlier contents are never read.
+ * Rejected: null verts or out_verts / out_normals with V > 0, null faces with T > 0, a null workspace, a null origin, null factors with
+ * n_steps > 0, negative sizes or 2^31 and more, n_steps or k outside their limits, factors or an origin that are not finite, a workspace
+ * that is misaligned or too small, an output that overlaps verts, a shift outside +-60. */
+#define DSN_MESH_SMOOTH_HEAVY 64
+#define DSN_MESH_SMOOTH_MAX_STEPS 4096
+#define DSN_MESH_SMOOTH_MAX_EXP 900
+DSN_EXPORT size_t dsn_mesh_smooth_workspace_bytes(int64_t n_verts, int64_t n_faces);
+DSN_EXPORT int dsn_mesh_smooth(const float* verts, const int32_t* faces, int64_t n_verts, int64_t n_faces, const float* origin_host,
+                               int scale_exp, const float* factors_host, int n_steps, void* workspace, size_t workspace_bytes,
+                               float* out_verts, int64_t* out_counts4, void* stream);
+DSN_EXPORT int dsn_mesh_vertex_normals(const float* verts, const int32_t* faces, int64_t n_verts, int64_t n_faces, int shift, void* workspace,
+                                       size_t workspace_bytes, float* out_normals, void* stream);
+/* measurement (scripts/bench_mesh_smooth.py): enqueue only these kernels (0 = all; one mesh and one workspace through the phases in order) */
+#define DSN_SM_COUNT 1
+#define DSN_SM_SCAN 2
+#define DSN_SM_FILL 4
+#define DSN_SM_STEP 8
+#define DSN_SM_NORMALS 16
+DSN_EXPORT int dsn_mesh_smooth_ex(const float* verts, const int32_t* faces, int64_t n_verts, int64_t n_faces, const float* origin_host,
+                                  int scale_exp, const float* factors_host, int n_steps, void* workspace, size_t workspace_bytes,
+                                  float* out_verts, int64_t* out_counts4, int phases, void* stream);
+DSN_EXPORT int dsn_mesh_vertex_normals_ex(const float* verts, const int32_t* faces, int64_t n_verts, int64_t n_faces, int shift,
+                                          void* workspace, size_t workspace_bytes, float* out_normals, int phases, void* stream);
+
 /* ---- a mesh bound to the body (an addition within ABI 8: no existing entry point changes) --------------------------------------------
  * novel_pose_vis.py and the novel-pose datasets animate one learned body by swapping batch["xyz"].  A mesh extracted in one pose follows
  * the body the same way: dsn_warp expresses a world point in the frame of its nearest posed face as (face, u, v, h) and evaluates that
