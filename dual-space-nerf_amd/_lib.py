@@ -54,6 +54,8 @@ EXPORTS = [
     "dsn_mesh_simplify_count_ex", "dsn_mesh_simplify_emit_ex",
     "dsn_mesh_smooth_workspace_bytes", "dsn_mesh_smooth", "dsn_mesh_smooth_ex", "dsn_mesh_vertex_normals", "dsn_mesh_vertex_normals_ex",
     "dsn_train_loss_workspace_bytes", "dsn_train_loss", "dsn_train_loss_grad",
+    "dsn_grid_hier_workspace_bytes", "dsn_grid_hier_mark", "dsn_grid_hier_list", "dsn_grid_hier_assemble",
+    "dsn_density_points_workspace_bytes", "dsn_density_points",
 ]
 
 SKIP_TRANSPARENT = 1
@@ -171,6 +173,16 @@ def lib():
         L.dsn_train_loss_workspace_bytes.argtypes = [C.c_int64]
         L.dsn_train_loss.argtypes = [C.c_void_p] * 6 + [C.c_int64, C.c_int, C.c_int] + [C.c_void_p] * 3
         L.dsn_train_loss_grad.argtypes = [C.c_void_p] * 6 + [C.c_int64, C.c_int] + [C.c_void_p] * 5
+        L.dsn_grid_hier_workspace_bytes.restype = C.c_size_t
+        L.dsn_grid_hier_workspace_bytes.argtypes = [C.c_int] * 4
+        L.dsn_grid_hier_mark.argtypes = [C.c_void_p] + [C.c_int] * 8 + [C.c_float, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        L.dsn_grid_hier_list.argtypes = [C.c_int] * 4 + [C.c_void_p, C.c_size_t, C.c_int64, C.c_void_p, C.c_void_p]
+        L.dsn_grid_hier_assemble.argtypes = ([C.c_void_p] + [C.c_int] * 7 + [C.c_float, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int64]
+                                             + [C.c_void_p] * 3)
+        L.dsn_density_points_workspace_bytes.restype = C.c_size_t
+        L.dsn_density_points_workspace_bytes.argtypes = [C.c_int64]
+        L.dsn_density_points.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                         C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p]
         if L.dsn_abi_version() != 8:
             raise RuntimeError(f"{LIB_PATH} has ABI version {L.dsn_abi_version()}, this binding needs 8 - rebuild it "
                                "(python dual-space-nerf_amd/build.py)")
@@ -247,6 +259,14 @@ def _scratch(nbytes, device):
     t = torch.empty(int(nbytes), dtype=torch.uint8, device=device)
     if os.environ.get("DSN_POISON_SCRATCH"):
         t.fill_(255)
+    return t
+
+
+def _output(shape, dtype, device):
+    """an output tensor the library fills completely: uninitialised; DSN_POISON_SCRATCH=1 (tests): every byte 0xFF, as _scratch"""
+    t = torch.empty(shape, dtype=dtype, device=device)
+    if os.environ.get("DSN_POISON_SCRATCH"):
+        t.view(torch.uint8).fill_(255)
     return t
 
 
@@ -701,6 +721,120 @@ def marching_cubes(volume, axes, level, gradient_direction="descent", want_norma
     _check(lib().dsn_mc_normals(_ptr(vol), nx, ny, nz, _ptr(x), _ptr(y), _ptr(z), float(level), MC_GRADIENT[gradient_direction], _ptr(ws),
                                 V, _ptr(normals) if V else None, _stream()), "dsn_mc_normals")
     return verts, faces, normals
+
+
+GRID_HIER_FACTORS = (2, 4, 8, 16)
+
+
+def grid_hier_axes(axes, factor):
+    """the coarse lattice of a grid (rule 1 of include/dsnerf.h's coarse-to-fine grid): per axis the int64 numpy array of the fine
+    indices 0, c, 2c, ... < n, plus n - 1 if it is not among them.  `axes`: the three axis arrays, or their three lengths."""
+    import numpy as np
+    if factor not in GRID_HIER_FACTORS:
+        raise ValueError(f"factor must be one of {GRID_HIER_FACTORS}")
+    out = []
+    for a in axes:
+        n = int(a) if isinstance(a, (int, np.integer)) else len(a)
+        if n < 2:
+            raise ValueError("every grid axis needs at least 2 points")
+        idx = list(range(0, n, factor))
+        if idx[-1] != n - 1:
+            idx.append(n - 1)
+        out.append(np.asarray(idx, dtype=np.int64))
+    return tuple(out)
+
+
+def density_points(scene: Scene, packed: PackedParams, axes, index, slab_points=None, fp32=False, exhaustive=False):
+    """dsn_density_points: values [m] float32 (device) = density_grid(scene, packed, axes).reshape(-1)[index[m]], bit for bit, for a
+    device int32 list `index` of linear grid indices (i ny + j) nz + k in any order, duplicates allowed.  slab_points: scratch bound
+    in points (default DENSITY_GRID_SLAB_POINTS, at most the list); the result does not depend on it."""
+    dev = scene.device
+    x, y, z = _axes_dev(axes, dev)
+    nx, ny, nz = x.numel(), y.numel(), z.numel()
+    index = index.to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
+    M = index.numel()
+    values = _output(M, torch.float32, dev)
+    if M == 0:
+        return values
+    P = int(slab_points) if slab_points is not None else min(DENSITY_GRID_SLAB_POINTS, M)
+    nbytes = lib().dsn_density_points_workspace_bytes(P)
+    ws = _scratch(max(nbytes, 1), dev)
+    flags = (FIELD_FP32 if fp32 else 0) | (NN_EXHAUSTIVE if exhaustive else 0)
+    _check(lib().dsn_density_points(_ptr(scene.buf), scene.V, scene.F, _ptr(packed.buf), _ptr(x), nx, _ptr(y), ny, _ptr(z), nz,
+                                    _ptr(index), M, flags, _ptr(values), P, _ptr(ws), nbytes, _stream()), "dsn_density_points")
+    return values
+
+
+def grid_hier_mark(coarse, shape, factor, dilate, level):
+    """dsn_grid_hier_mark on a device coarse volume [mx, my, mz] of the grid `shape` = (nx, ny, nz): (workspace, counts) - counts a
+    device int64 [3]: core cells, active cells, evaluated points."""
+    assert coarse.is_cuda and coarse.dtype == torch.float32 and coarse.dim() == 3, "coarse: device float32 [mx, my, mz]"
+    coarse = coarse.contiguous()
+    nx, ny, nz = (int(n) for n in shape)
+    nbytes = lib().dsn_grid_hier_workspace_bytes(nx, ny, nz, int(factor))
+    ws = _scratch(max(nbytes, 1), coarse.device)
+    counts = _output(3, torch.int64, coarse.device)
+    mx, my, mz = coarse.shape
+    _check(lib().dsn_grid_hier_mark(_ptr(coarse), mx, my, mz, nx, ny, nz, int(factor), int(dilate), float(level), _ptr(ws), nbytes,
+                                    _ptr(counts), _stream()), "dsn_grid_hier_mark")
+    return ws, counts
+
+
+def grid_hier_list(ws, shape, factor, n_points):
+    """dsn_grid_hier_list: the ascending device int32 list of the n_points evaluated points (n_points: counts[2] of grid_hier_mark)"""
+    nx, ny, nz = (int(n) for n in shape)
+    index = _output(int(n_points), torch.int32, ws.device)
+    _check(lib().dsn_grid_hier_list(nx, ny, nz, int(factor), _ptr(ws), ws.numel(), int(n_points), _ptr(index) if n_points else None,
+                                    _stream()), "dsn_grid_hier_list")
+    return index
+
+
+def grid_hier_assemble(coarse, shape, factor, level, ws, index, values):
+    """dsn_grid_hier_assemble: (volume [nx, ny, nz] device float32 - the fill everywhere, then the listed values - and the device
+    int64 [1] number of leaking edges)"""
+    coarse = coarse.contiguous()
+    nx, ny, nz = (int(n) for n in shape)
+    mx, my, mz = coarse.shape
+    M = index.numel()
+    assert values.numel() == M and values.dtype == torch.float32 and index.dtype == torch.int32
+    vol = _output((nx, ny, nz), torch.float32, coarse.device)
+    leaks = _output(1, torch.int64, coarse.device)
+    _check(lib().dsn_grid_hier_assemble(_ptr(coarse), mx, my, mz, nx, ny, nz, int(factor), float(level), _ptr(ws), ws.numel(),
+                                        _ptr(index.contiguous()) if M else None, _ptr(values.contiguous()) if M else None, M, _ptr(vol),
+                                        _ptr(leaks), _stream()), "dsn_grid_hier_assemble")
+    return vol, leaks
+
+
+def density_grid_hier(scene: Scene, packed: PackedParams, axes, level, factor=4, dilate=1, slab_points=None, fp32=False, evaluate=None):
+    """The density volume of density_grid, evaluated coarse to fine (the rule of include/dsnerf.h): the density at the coarse lattice
+    of grid_hier_axes(axes, factor), then only at the fine points in the closed boxes of the coarse cells the level crosses, dilated
+    `dilate` times; every other point holds the coarse value at the lowest corner of its owner cell.  Returns (volume [nx, ny, nz]
+    device float32, info) with info = {factor, dilate, coarse_shape, core_cells, active_cells, evaluated_points, points, leaks}.
+    What info["leaks"] == 0 proves: every vertex and every normal marching_cubes(volume, ...) returns was computed from evaluated
+    values only - where the volume also has the dense grid's inside mask, verts, faces and normals are the dense grid's, bit for bit.
+    What it does not: a piece of surface wholly among unevaluated points (a floater smaller than a coarse cell, more than `dilate`
+    cells from any coarse sign change) is neither seen nor counted.
+    evaluate: a callable index (device int32 [m]) -> values (device float32 [m]) that replaces the field (scene and packed may then
+    be None).  Listed coarse points are evaluated again (about 1 / factor^3 of the list; the bits are the same).  Two device->host
+    reads (the counts, the leaks)."""
+    dev = scene.device if scene is not None else torch.device("cuda", torch.cuda.current_device())
+    x, y, z = _axes_dev(axes, dev)
+    shape = (x.numel(), y.numel(), z.numel())
+    if evaluate is None:
+        def evaluate(index):
+            return density_points(scene, packed, (x, y, z), index, slab_points=None if slab_points is None else min(int(slab_points), max(index.numel(), 1)),
+                                  fp32=fp32)
+    ix, iy, iz = (torch.from_numpy(a).to(dev) for a in grid_hier_axes(shape, factor))
+    lin = ((ix[:, None, None] * shape[1] + iy[None, :, None]) * shape[2] + iz[None, None, :]).to(torch.int32)
+    coarse = evaluate(lin.reshape(-1)).reshape(lin.shape).contiguous()
+    ws, counts = grid_hier_mark(coarse, shape, factor, dilate, level)
+    core, active, n_eval = (int(c) for c in counts.cpu())
+    index = grid_hier_list(ws, shape, factor, n_eval)
+    values = evaluate(index) if n_eval else torch.empty(0, dtype=torch.float32, device=dev)
+    vol, leaks = grid_hier_assemble(coarse, shape, factor, level, ws, index, values)
+    info = {"factor": int(factor), "dilate": int(dilate), "coarse_shape": tuple(coarse.shape), "core_cells": core, "active_cells": active,
+            "evaluated_points": n_eval, "points": shape[0] * shape[1] * shape[2], "leaks": int(leaks.cpu())}
+    return vol, info
 
 
 MESH_CC_TILE = 1024          # DSN_MESH_CC_TILE: vertices / faces per tile of the compaction scans

@@ -161,6 +161,23 @@ class _Renderers:
     lowered = None     # (the caller's torch.get_num_threads(), what fit_host_pool lowered it to)
 
 
+def hier_retry(attempt, dilate=1, max_dilate=3):
+    """The retry rule of extract_mesh(coarse=...): attempt(r) -> (result, info) builds the coarse-to-fine grid with r rings of
+    dilation, info["leaks"] being its certificate.  The first attempt runs with `dilate`; while leaks > 0 and r < max_dilate it is
+    repeated with one more ring.  Returns (result, info) of the last attempt, info extended by "attempts" and "fell_back"; result is
+    None where the last attempt still leaks - the caller then falls back to the dense grid (fell_back = True)."""
+    r, attempts = int(dilate), 0
+    while True:
+        result, info = attempt(r)
+        attempts += 1
+        if info["leaks"] == 0 or r >= max_dilate:
+            break
+        r += 1
+    fell_back = info["leaks"] > 0
+    info = dict(info, attempts=attempts, fell_back=fell_back)
+    return (None if fell_back else result), info
+
+
 class Renderer:
     def __init__(self, net, fine_net=None, cfg=None, canonical_vertex=None, body_data=None, device=None, host_pool="fit"):
         """`body_data` (optional, not in the reference): dict with 'f' [F,3] (and optionally 'weights',
@@ -1219,9 +1236,32 @@ class Renderer:
         vol = _lib.density_grid(self.scene, packed, axes, slab_points=slab_points, fp32=fp32)
         return axes, vol
 
+    def density_grid_hier(self, batch, resolution=None, level=0.5, coarse=4, dilate=1, axes=None, points=None, frame=None, fp32=False,
+                          slab_points=None):
+        """density_grid's volume evaluated coarse to fine (dsn_grid_hier_* + dsn_density_points, the rule of include/dsnerf.h): the
+        density on the sub-lattice of every `coarse`-th grid point (2, 4, 8 or 16), then only at the grid points in and around the
+        coarse cells `level` crosses (`dilate` rings of cells around them); every other point holds a coarse value of its own side of
+        the level.  Returns (axes, volume [nx, ny, nz] device float32, info): info = {factor, dilate, coarse_shape, core_cells,
+        active_cells, evaluated_points, points, leaks}.  Evaluated points have density_grid's bits.
+        info["leaks"] == 0 proves that every vertex and normal of marching cubes on this volume was computed from evaluated values
+        only; where the volume also has the dense grid's inside mask, the mesh is the dense grid's, bit for bit.  It does not prove
+        that nothing was missed: a piece of surface wholly among unevaluated points (a floater smaller than a coarse cell, more than
+        `dilate` cells from any coarse sign change) is neither seen nor counted - largest_component would drop such pieces anyway."""
+        if axes is None:
+            if resolution is None:
+                raise ValueError("density_grid_hier: give `resolution` or `axes`")
+            axes = self.grid_axes(batch["xyz"][0] if points is None else points, resolution)
+        self._ensure_mesh(batch)
+        fi = int(torch.as_tensor(batch["frame"] if frame is None else frame).reshape(-1)[0])
+        packed = self.net.packed(self.device)
+        _lib.scene_set_pose(self.scene, packed, batch["poses"][0], fi, self.net.nerf.w is not None)
+        self._frame_src = None          # (as density_grid: stage calls set their frame again)
+        vol, info = _lib.density_grid_hier(self.scene, packed, axes, level, factor=coarse, dilate=dilate, slab_points=slab_points, fp32=fp32)
+        return axes, vol, info
+
     def extract_mesh(self, batch, resolution=512, level=0.5, gradient_direction="ascent", axes=None, points=None, frame=None,
                      fp32=False, slab_points=None, normals=False, attributes=None, largest_component=False, simplify_cell=None,
-                     target_vertices=None, smooth=None):
+                     target_vertices=None, smooth=None, coarse=None, dilate=1, max_dilate=3):
         """Visualizer3D's mesh of the posed body on the device: density_grid + marching cubes (dsn_mc_count / dsn_mc_emit, the rule of
         include/dsnerf.h).  Defaults are the visualizer's __main__ values.  Returns {"verts" [V,3] float32, "faces" [T,3] int32} device
         tensors in world coordinates, or None where the level is not crossed (the reference returns None there).
@@ -1240,14 +1280,29 @@ class Renderer:
         smooth: an int (Taubin pairs) or a dict of visualizer.smooth_mesh's keywords - the stair steps of the thresholded grid smoothed
         out (dsn_mesh_smooth, the rule of include/dsnerf.h) after the component filter, before the thinning and before the attributes,
         which are then evaluated at the final vertices.  "normals" are then those of the smoothed faces (dsn_mesh_vertex_normals:
-        oriented by the winding, which follows gradient_direction as marching cubes' do); the dict gains "smooth_info"."""
+        oriented by the winding, which follows gradient_direction as marching cubes' do); the dict gains "smooth_info".
+        coarse (2, 4, 8 or 16; None: the dense grid, as ever): the volume comes from density_grid_hier(coarse=coarse, dilate=dilate)
+        - the density only near the iso-surface.  While the certificate fails (info["leaks"] > 0) and dilate < max_dilate the grid is
+        built again with one more ring; if it still fails, the dense grid is used (hier_retry).  The dict gains "grid_info": the last
+        attempt's info plus "attempts" and "fell_back".  With leaks == 0 every vertex and normal comes from evaluated densities; a
+        floater smaller than a coarse cell and far from the surface can be missing (density_grid_hier's docstring).  Everything
+        after marching cubes works on the result as before.  A field with structure below a coarse cell near the surface keeps the
+        certificate from holding (the w4 body does, README): the call then costs the attempts plus the dense grid - look at grid_info."""
         if simplify_cell is not None and target_vertices is not None:
             raise ValueError("extract_mesh: give one of simplify_cell and target_vertices")
         names = tuple(attributes) if attributes else ()
         unknown = set(names) - set(self.MESH_ATTRIBUTES)
         if unknown:
             raise ValueError(f"extract_mesh: unknown attributes {sorted(unknown)} {self.MESH_ATTRIBUTES}")
-        axes, vol = self.density_grid(batch, resolution, axes, points, frame, fp32, slab_points)
+        grid_info = None
+        if coarse is None:
+            axes, vol = self.density_grid(batch, resolution, axes, points, frame, fp32, slab_points)
+        else:
+            def attempt(r):
+                a, v, info = self.density_grid_hier(batch, resolution, level, coarse, r, axes, points, frame, fp32, slab_points)
+                return (a, v), info
+            got, grid_info = hier_retry(attempt, dilate, max_dilate)
+            axes, vol = got if got is not None else self.density_grid(batch, resolution, axes, points, frame, fp32, slab_points)
         out = _lib.marching_cubes(vol, axes, level, gradient_direction, want_normals=bool(normals))
         if out[1].shape[0] == 0:
             return None
@@ -1272,6 +1327,8 @@ class Renderer:
         if names:
             a = self.mesh_attributes(batch, out[0], frame=frame)
             mesh.update({k: a[k] for k in names})
+        if grid_info is not None:
+            mesh["grid_info"] = grid_info
         return mesh
 
     MESH_ATTRIBUTES = ("albedo", "normal", "colour", "sigma", "valid")

@@ -1348,6 +1348,111 @@ int dsn_mc_table_host(int32_t* out_host, size_t out_ints) {
     return 0;
 }
 
+// ---- density grid, coarse to fine (the rule of include/dsnerf.h) ----
+static int dsn_hier_shift(int factor) { return factor == 2 ? 1 : factor == 4 ? 2 : factor == 8 ? 3 : factor == 16 ? 4 : -1; }
+
+size_t dsn_grid_hier_workspace_bytes(int nx, int ny, int nz, int factor) {
+    return dsn_mc_sizes_ok(nx, ny, nz) && dsn_hier_shift(factor) > 0 ? dsn_grid_hier_workspace_size(nx, ny, nz, dsn_hier_shift(factor)) : 0;
+}
+
+static bool dsn_hier_coarse_ok(int nx, int ny, int nz, int sh, int mx, int my, int mz) {
+    int m[3];
+    dsn_grid_hier_coarse_shape(nx, ny, nz, sh, m);
+    return m[0] == mx && m[1] == my && m[2] == mz;
+}
+
+int dsn_grid_hier_mark(const float* coarse, int mx, int my, int mz, int nx, int ny, int nz, int factor, int dilate, float level,
+                       void* workspace, size_t workspace_bytes, int64_t* out_counts3, void* stream) {
+    DSN_REQUIRE(coarse && workspace && out_counts3, "dsn_grid_hier_mark: null argument");
+    DSN_REQUIRE(dsn_mc_sizes_ok(nx, ny, nz), "dsn_grid_hier_mark: bad grid size (every axis >= 2, fewer than 2^31 points)");
+    const int sh = dsn_hier_shift(factor);
+    DSN_REQUIRE(sh > 0, "dsn_grid_hier_mark: factor must be 2, 4, 8 or 16");
+    DSN_REQUIRE(dilate >= 0, "dsn_grid_hier_mark: negative dilate");
+    DSN_REQUIRE(level == level, "dsn_grid_hier_mark: NaN level");
+    DSN_REQUIRE(dsn_hier_coarse_ok(nx, ny, nz, sh, mx, my, mz), "dsn_grid_hier_mark: coarse shape is not the grid's coarse lattice (ceil((n - 1) / factor) + 1 per axis)");
+    DSN_REQUIRE(workspace_bytes >= dsn_grid_hier_workspace_size(nx, ny, nz, sh), "dsn_grid_hier_mark: workspace smaller than dsn_grid_hier_workspace_bytes");
+    hipStream_t st = (hipStream_t)stream;
+    if (hipMemsetAsync(out_counts3, 0, 3 * sizeof(int64_t), st) != hipSuccess) return dsn_fail("%s", "dsn_grid_hier_mark: memset failed");
+    dsn_launch_grid_hier_mark(coarse, nx, ny, nz, sh, dilate, level, workspace, out_counts3, st);
+    return dsn_check_launch("dsn_grid_hier_mark");
+}
+
+int dsn_grid_hier_list(int nx, int ny, int nz, int factor, const void* workspace, size_t workspace_bytes, int64_t n_points,
+                       int32_t* point_index, void* stream) {
+    DSN_REQUIRE(workspace, "dsn_grid_hier_list: null argument");
+    DSN_REQUIRE(dsn_mc_sizes_ok(nx, ny, nz), "dsn_grid_hier_list: bad grid size (every axis >= 2, fewer than 2^31 points)");
+    const int sh = dsn_hier_shift(factor);
+    DSN_REQUIRE(sh > 0, "dsn_grid_hier_list: factor must be 2, 4, 8 or 16");
+    DSN_REQUIRE(n_points >= 0 && n_points <= (int64_t)nx * ny * nz, "dsn_grid_hier_list: n_points outside 0 .. nx ny nz");
+    DSN_REQUIRE(n_points == 0 || point_index, "dsn_grid_hier_list: null output buffer");
+    DSN_REQUIRE(workspace_bytes >= dsn_grid_hier_workspace_size(nx, ny, nz, sh), "dsn_grid_hier_list: workspace smaller than dsn_grid_hier_workspace_bytes");
+    if (n_points == 0) return 0;
+    dsn_launch_grid_hier_list(nx, ny, nz, sh, workspace, point_index, n_points, (hipStream_t)stream);
+    return dsn_check_launch("dsn_grid_hier_list");
+}
+
+int dsn_grid_hier_assemble(const float* coarse, int mx, int my, int mz, int nx, int ny, int nz, int factor, float level,
+                           const void* workspace, size_t workspace_bytes, const int32_t* point_index, const float* values, int64_t n_points,
+                           float* volume, int64_t* out_leaks, void* stream) {
+    DSN_REQUIRE(coarse && workspace && volume && out_leaks, "dsn_grid_hier_assemble: null argument");
+    DSN_REQUIRE(dsn_mc_sizes_ok(nx, ny, nz), "dsn_grid_hier_assemble: bad grid size (every axis >= 2, fewer than 2^31 points)");
+    const int sh = dsn_hier_shift(factor);
+    DSN_REQUIRE(sh > 0, "dsn_grid_hier_assemble: factor must be 2, 4, 8 or 16");
+    DSN_REQUIRE(level == level, "dsn_grid_hier_assemble: NaN level");
+    DSN_REQUIRE(dsn_hier_coarse_ok(nx, ny, nz, sh, mx, my, mz), "dsn_grid_hier_assemble: coarse shape is not the grid's coarse lattice (ceil((n - 1) / factor) + 1 per axis)");
+    DSN_REQUIRE(n_points >= 0 && n_points <= (int64_t)nx * ny * nz, "dsn_grid_hier_assemble: n_points outside 0 .. nx ny nz");
+    DSN_REQUIRE(n_points == 0 || (point_index && values), "dsn_grid_hier_assemble: null point list");
+    DSN_REQUIRE(workspace_bytes >= dsn_grid_hier_workspace_size(nx, ny, nz, sh), "dsn_grid_hier_assemble: workspace smaller than dsn_grid_hier_workspace_bytes");
+    hipStream_t st = (hipStream_t)stream;
+    if (hipMemsetAsync(out_leaks, 0, sizeof(int64_t), st) != hipSuccess) return dsn_fail("%s", "dsn_grid_hier_assemble: memset failed");
+    dsn_launch_grid_hier_assemble(coarse, nx, ny, nz, sh, level, workspace, point_index, values, n_points, volume, out_leaks, st);
+    return dsn_check_launch("dsn_grid_hier_assemble");
+}
+
+size_t dsn_density_points_workspace_bytes(int64_t slab_points) {
+    return slab_points > 0 && slab_points < ((int64_t)1 << 31) ? dsn_grid_ws(slab_points) : 0;
+}
+
+// dsn_density_grid's slab loop over a list of grid points instead of whole x-planes: the same warp and field launches
+int dsn_density_points(const void* scene, int V, int F, const void* packed, const float* x, int nx, const float* y, int ny, const float* z,
+                       int nz, const int32_t* point_index, int64_t n_points, int flags, float* values, int64_t slab_points, void* workspace,
+                       size_t workspace_bytes, void* stream) {
+    DSN_REQUIRE(scene && packed && x && y && z && workspace, "dsn_density_points: null argument");
+    DSN_REQUIRE(V > 0 && F > 0, "dsn_density_points: bad V/F");
+    DSN_REQUIRE(nx > 0 && ny > 0 && nz > 0, "dsn_density_points: empty grid axis");
+    const int64_t N = (int64_t)nx * ny * nz;
+    DSN_REQUIRE(N < ((int64_t)1 << 31), "dsn_density_points: more than 2^31 - 1 grid points");
+    DSN_REQUIRE(n_points >= 0, "dsn_density_points: negative n_points");
+    DSN_REQUIRE(n_points == 0 || (point_index && values), "dsn_density_points: null point list");
+    DSN_REQUIRE(slab_points >= 1 && slab_points < ((int64_t)1 << 31), "dsn_density_points: slab_points must be 1 .. 2^31 - 1");
+    DSN_REQUIRE(workspace_bytes >= dsn_grid_ws(slab_points), "dsn_density_points: workspace smaller than dsn_density_points_workspace_bytes(slab_points)");
+    DSN_REQUIRE((flags & ~(DSN_FIELD_FP32 | DSN_NN_EXHAUSTIVE)) == 0, "dsn_density_points: flags other than DSN_FIELD_FP32 / DSN_NN_EXHAUSTIVE");
+    hipStream_t st = (hipStream_t)stream;
+    DsnSceneView s = dsn_scene_view((void*)scene, V, F);
+    char* p = (char*)workspace;
+    float* pts = (float*)p;                      p += dsn_align256(12 * (size_t)slab_points);
+    float* x_c = (float*)p;                      p += dsn_align256(12 * (size_t)slab_points);
+    int32_t* list = (int32_t*)p;                 p += dsn_align256(4 * (size_t)slab_points);
+    int32_t* cnt = (int32_t*)p;                  // [0] active points of the slab, [16] samples the split-fp16 kernel flagged
+    for (int64_t m0 = 0; m0 < n_points; m0 += slab_points) {
+        const int64_t Ns = n_points - m0 < slab_points ? n_points - m0 : slab_points;
+        float* vs = values + m0;
+        if (hipMemsetAsync(cnt, 0, 256, st) != hipSuccess || hipMemsetAsync(vs, 0, sizeof(float) * (size_t)Ns, st) != hipSuccess)
+            return dsn_fail("%s", "dsn_density_points: memset failed");
+        dsn_launch_list_points(x, y, z, point_index + m0, ny, nz, N, Ns, pts, st);
+        dsn_launch_warp(s, pts, nullptr, nullptr, nullptr, Ns, 1, nullptr, nullptr, nullptr, nullptr, x_c, nullptr, list, cnt,
+                        (flags & DSN_NN_EXHAUSTIVE) != 0, st);
+        if (flags & DSN_FIELD_FP32)
+            dsn_launch_field((const float*)packed, s.frame, x_c, Ns, list, cnt, vs, nullptr, nullptr, st);
+        else {
+            dsn_launch_field16_den((const float*)packed, s.frame, x_c, Ns, list, cnt, vs, st, cnt + 16);
+            dsn_launch_field_fix((const float*)packed, s.frame, x_c, Ns, list, cnt, vs, nullptr, nullptr, st, cnt + 16);
+        }
+        dsn_launch_points_invalid(point_index + m0, N, Ns, vs, st);
+    }
+    return dsn_check_launch("dsn_density_points");
+}
+
 static bool dsn_mesh_cc_sizes_ok(int64_t V, int64_t T) { return V >= 0 && T >= 0 && V < ((int64_t)1 << 31) && T < ((int64_t)1 << 31); }
 
 size_t dsn_mesh_cc_workspace_bytes(int64_t n_verts, int64_t n_faces) {

@@ -221,6 +221,18 @@ void dsn_launch_mc_emit(const float* vol, int nx, int ny, int nz, const float* x
 void dsn_launch_mc_normals(const float* vol, int nx, int ny, int nz, const float* x, const float* y, const float* z, float level, int ascent,
                            const void* workspace, float* normals, int64_t vcap, hipStream_t st);
 void dsn_mc_table_copy(int32_t* out_host);
+// dsn_mesh.hip: the density grid coarse to fine (dsn_grid_hier_*, dsn_density_points; sh = log2 of the factor; the counters an entry
+// point hands in are zero on entry)
+size_t dsn_grid_hier_workspace_size(int nx, int ny, int nz, int sh);
+void dsn_grid_hier_coarse_shape(int nx, int ny, int nz, int sh, int* m3);
+void dsn_launch_grid_hier_mark(const float* coarse, int nx, int ny, int nz, int sh, int dilate, float level, void* workspace,
+                               int64_t* out_counts, hipStream_t st);
+void dsn_launch_grid_hier_list(int nx, int ny, int nz, int sh, const void* workspace, int32_t* index, int64_t cap, hipStream_t st);
+void dsn_launch_grid_hier_assemble(const float* coarse, int nx, int ny, int nz, int sh, float level, const void* workspace,
+                                   const int32_t* index, const float* values, int64_t M, float* volume, int64_t* out_leaks, hipStream_t st);
+void dsn_launch_list_points(const float* x, const float* y, const float* z, const int32_t* index, int ny, int nz, int64_t N, int64_t n,
+                            float* pts, hipStream_t st);
+void dsn_launch_points_invalid(const int32_t* index, int64_t N, int64_t n, float* values, hipStream_t st);
 // dsn_mesh.hip: connected components and the largest piece of an indexed mesh (dsn_mesh_cc_*; scale = 2^area_shift; phases: DSN_CC_*)
 size_t dsn_mesh_cc_workspace_size(int64_t V, int64_t T);
 void dsn_launch_mesh_cc_label(const float* verts, const int32_t* faces, int64_t V, int64_t T, double scale, void* workspace, int32_t* labels_v,

@@ -418,6 +418,305 @@ void dsn_launch_mc_normals(const float* vol, int nx, int ny, int nz, const float
 }
 
 // ---------------------------------------------------------------------------------------------
+// density grid, coarse to fine (dsn_grid_hier_mark / _list / _assemble + the points of dsn_density_points; the rule of include/dsnerf.h)
+//   mark    : core (one thread per coarse cell: its eight corners) -> active (box maximum of radius r over the core mask) -> count (tiles
+//             of MC_TILE consecutive fine points: how many lie in the closed box of an active cell; one workgroup scans the tiles'
+//             totals).  The cell counters are integer adds, one per wave.
+//   list    : the same tiles again: the points' prefixes inside the tile are one workgroup scan, the tile's offset comes from the mark
+//             stage - ascending fine indices without atomics.
+//   assemble: fill (every fine point: the coarse value at the lowest corner of its owner cell) -> scatter (the listed values) -> leaks
+//             (one thread per listed point: a sign-changing edge has an evaluated end - two filled neighbours never differ in side - so
+//             edge (n, d) is looked at from n where n is listed and from its other end where it is not; an integer add per wave).
+// A fine point is evaluated when one of the (up to eight) coarse cells whose closed box holds it is active; neither stage stores that
+// per point - it is a few reads of the active mask, which stays in cache.
+// ---------------------------------------------------------------------------------------------
+struct HierGeom { int n[3]; int m[3]; int sh; };      // fine points and coarse points per axis, log2 of the factor
+
+static int hier_coarse_n(int n, int sh) { return ((n - 1 + (1 << sh) - 1) >> sh) + 1; }
+static HierGeom hier_geom(int nx, int ny, int nz, int sh) {
+    HierGeom g;
+    g.n[0] = nx; g.n[1] = ny; g.n[2] = nz; g.sh = sh;
+    for (int a = 0; a < 3; ++a) g.m[a] = hier_coarse_n(g.n[a], sh);
+    return g;
+}
+static int64_t hier_cells(const HierGeom& g) { return (int64_t)(g.m[0] - 1) * (g.m[1] - 1) * (g.m[2] - 1); }
+static size_t hier_up(size_t b) { return (b + 255) / 256 * 256; }
+// core mask uint8 [cells] | active mask uint8 [cells] | tile offsets of the evaluated points int64 [tiles + 1]
+struct HierWs { uint8_t* core; uint8_t* active; int64_t* tp; size_t bytes; };
+static HierWs hier_ws(void* w, const HierGeom& g) {
+    char* p = (char*)w;
+    const size_t cells = (size_t)hier_cells(g);
+    const int64_t N = (int64_t)g.n[0] * g.n[1] * g.n[2];
+    HierWs r;
+    r.core = (uint8_t*)p;                 p += hier_up(cells);
+    r.active = (uint8_t*)p;               p += hier_up(cells);
+    r.tp = (int64_t*)p;                   p += hier_up(8 * (size_t)(mc_tiles(N) + 1));
+    r.bytes = (size_t)(p - (char*)w);
+    return r;
+}
+size_t dsn_grid_hier_workspace_size(int nx, int ny, int nz, int sh) { return hier_ws(nullptr, hier_geom(nx, ny, nz, sh)).bytes; }
+void dsn_grid_hier_coarse_shape(int nx, int ny, int nz, int sh, int* m3) {
+    const HierGeom g = hier_geom(nx, ny, nz, sh);
+    m3[0] = g.m[0]; m3[1] = g.m[1]; m3[2] = g.m[2];
+}
+
+// the coarse cells along one axis whose closed index box holds fine index i: [lo, hi] (two where i is an inner coarse point)
+__device__ __forceinline__ void hier_span(int i, int sh, int cells, int& lo, int& hi) {
+    const int q = i >> sh;
+    hi = q < cells ? q : cells - 1;
+    lo = (q < cells && q > 0 && (i & ((1 << sh) - 1)) == 0) ? q - 1 : hi;
+}
+__device__ __forceinline__ bool hier_evaluated(const uint8_t* __restrict__ active, const HierGeom& g, int i, int j, int k) {
+    int l0, h0, l1, h1, l2, h2;
+    const int c1 = g.m[1] - 1, c2 = g.m[2] - 1;
+    hier_span(i, g.sh, g.m[0] - 1, l0, h0);
+    hier_span(j, g.sh, c1, l1, h1);
+    hier_span(k, g.sh, c2, l2, h2);
+    for (int a = l0; a <= h0; ++a)
+        for (int b = l1; b <= h1; ++b)
+            for (int c = l2; c <= h2; ++c)
+                if (active[((int64_t)a * c1 + b) * c2 + c]) return true;
+    return false;
+}
+// the fill of a fine point: the coarse value at the lowest corner of its owner cell
+__device__ __forceinline__ float hier_fill(const float* __restrict__ coarse, const HierGeom& g, int i, int j, int k) {
+    const int a = min(i >> g.sh, g.m[0] - 2), b = min(j >> g.sh, g.m[1] - 2), c = min(k >> g.sh, g.m[2] - 2);
+    return coarse[((int64_t)a * g.m[1] + b) * g.m[2] + c];
+}
+
+__global__ void __launch_bounds__(MC_THREADS) k_hier_core(const float* __restrict__ coarse, HierGeom g, float level, int64_t cells,
+                                                          uint8_t* __restrict__ core, unsigned long long* __restrict__ counts) {
+    const int64_t cell = (int64_t)blockIdx.x * MC_THREADS + threadIdx.x;
+    bool is = false;
+    if (cell < cells) {
+        const int c1 = g.m[1] - 1, c2 = g.m[2] - 1;
+        const int64_t ab = cell / c2;
+        const int a = (int)(ab / c1), b = (int)(ab % c1), c = (int)(cell % c2);
+        const int64_t sx = (int64_t)g.m[1] * g.m[2], sy = g.m[2], base = ((int64_t)a * g.m[1] + b) * g.m[2] + c;
+        int in = 0;
+#pragma unroll
+        for (int q = 0; q < 8; ++q) in += mc_in(coarse[base + (q & 1) * sx + ((q >> 1) & 1) * sy + ((q >> 2) & 1)], level) ? 1 : 0;
+        is = in != 0 && in != 8;
+        core[cell] = is ? 1 : 0;
+    }
+    const unsigned long long m = __ballot(is);
+    if ((threadIdx.x & 63) == 0 && m) atomicAdd(counts, (unsigned long long)__popcll(m));
+}
+
+__global__ void __launch_bounds__(MC_THREADS) k_hier_dilate(const uint8_t* __restrict__ core, HierGeom g, int r, int64_t cells,
+                                                            uint8_t* __restrict__ active, unsigned long long* __restrict__ counts) {
+    const int64_t cell = (int64_t)blockIdx.x * MC_THREADS + threadIdx.x;
+    bool is = false;
+    if (cell < cells) {
+        const int c0 = g.m[0] - 1, c1 = g.m[1] - 1, c2 = g.m[2] - 1;
+        const int64_t ab = cell / c2;
+        const int a = (int)(ab / c1), b = (int)(ab % c1), c = (int)(cell % c2);
+        const int a0 = max(a - r, 0), a1 = min(a + r, c0 - 1), b0 = max(b - r, 0), b1 = min(b + r, c1 - 1);
+        const int z0 = max(c - r, 0), z1 = min(c + r, c2 - 1);
+        for (int u = a0; u <= a1 && !is; ++u)
+            for (int v = b0; v <= b1 && !is; ++v)
+                for (int w = z0; w <= z1; ++w)
+                    if (core[((int64_t)u * c1 + v) * c2 + w]) { is = true; break; }
+        active[cell] = is ? 1 : 0;
+    }
+    const unsigned long long m = __ballot(is);
+    if ((threadIdx.x & 63) == 0 && m) atomicAdd(counts + 1, (unsigned long long)__popcll(m));
+}
+
+// evaluated flags of the thread's MC_PER consecutive fine points from n0 on (bit q: point n0 + q)
+__device__ __forceinline__ uint32_t hier_flags(const uint8_t* __restrict__ active, const HierGeom& g, int64_t n0, int64_t N) {
+    uint32_t f = 0;
+    if (n0 < N) {
+        McPoint p = mc_ijk(n0, g.n[1], g.n[2]);
+        for (int q = 0; q < MC_PER && n0 + q < N; ++q) {
+            if (hier_evaluated(active, g, p.i, p.j, p.k)) f |= 1u << q;
+            mc_step(p, g.n[1], g.n[2]);
+        }
+    }
+    return f;
+}
+
+__global__ void __launch_bounds__(MC_THREADS) k_hier_count(const uint8_t* __restrict__ active, HierGeom g, int64_t N,
+                                                           int64_t* __restrict__ tp) {
+    const int64_t n0 = (int64_t)blockIdx.x * MC_TILE + (int64_t)threadIdx.x * MC_PER;
+    int a = __popc(hier_flags(active, g, n0, N)), b = 0, tot_a, tot_b;
+    mc_block_scan(a, b, tot_a, tot_b);
+    if (threadIdx.x == 0) tp[blockIdx.x] = tot_a;
+}
+
+// one workgroup: exclusive scan of the tiles' totals in place, [tiles] = the grand total, also written to *out
+__global__ void __launch_bounds__(MC_SCAN_THREADS) k_hier_scan(int64_t* __restrict__ tp, int64_t tiles, unsigned long long* __restrict__ out) {
+    __shared__ int64_t sa[MC_SCAN_THREADS];
+    const int t = threadIdx.x;
+    const int64_t per = (tiles + MC_SCAN_THREADS - 1) / MC_SCAN_THREADS;
+    const int64_t b0 = t * per, b1 = b0 + per < tiles ? b0 + per : tiles;
+    int64_t a = 0;
+    for (int64_t k = b0; k < b1; ++k) a += tp[k];
+    sa[t] = a;
+    __syncthreads();
+    for (int off = 1; off < MC_SCAN_THREADS; off <<= 1) {
+        const int64_t xa = t >= off ? sa[t - off] : 0;
+        __syncthreads();
+        sa[t] += xa;
+        __syncthreads();
+    }
+    int64_t ra = sa[t] - a;
+    for (int64_t k = b0; k < b1; ++k) {
+        const int64_t va = tp[k];
+        tp[k] = ra;
+        ra += va;
+    }
+    if (t == MC_SCAN_THREADS - 1) { tp[tiles] = sa[t]; *out = (unsigned long long)sa[t]; }
+}
+
+__global__ void __launch_bounds__(MC_THREADS) k_hier_list(const uint8_t* __restrict__ active, HierGeom g, int64_t N,
+                                                          const int64_t* __restrict__ tp, int32_t* __restrict__ index, int64_t cap) {
+    const int64_t n0 = (int64_t)blockIdx.x * MC_TILE + (int64_t)threadIdx.x * MC_PER;
+    const uint32_t f = hier_flags(active, g, n0, N);
+    int a = __popc(f), b = 0, tot_a, tot_b;
+    mc_block_scan(a, b, tot_a, tot_b);
+    int64_t o = tp[blockIdx.x] + a;
+    for (int q = 0; q < MC_PER; ++q)
+        if ((f >> q) & 1) {
+            if (o < cap) index[o] = (int32_t)(n0 + q);
+            ++o;
+        }
+}
+
+__global__ void __launch_bounds__(MC_THREADS) k_hier_fill(const float* __restrict__ coarse, HierGeom g, int64_t N, float* __restrict__ vol) {
+    const int64_t n0 = ((int64_t)blockIdx.x * MC_THREADS + threadIdx.x) * 4;      // four consecutive points a thread
+    if (n0 >= N) return;
+    McPoint p = mc_ijk(n0, g.n[1], g.n[2]);
+    for (int q = 0; q < 4 && n0 + q < N; ++q) {
+        vol[n0 + q] = hier_fill(coarse, g, p.i, p.j, p.k);
+        mc_step(p, g.n[1], g.n[2]);
+    }
+}
+
+__global__ void __launch_bounds__(MC_THREADS) k_hier_scatter(const int32_t* __restrict__ index, const float* __restrict__ values, int64_t M,
+                                                             int64_t N, float* __restrict__ vol) {
+    const int64_t m = (int64_t)blockIdx.x * MC_THREADS + threadIdx.x;
+    if (m >= M) return;
+    const int64_t n = index[m];
+    if (n >= 0 && n < N) vol[n] = values[m];
+}
+
+// is one of the points of the normal stencil of (i, j, k) - the point and its in-grid +-1 neighbours along the three axes - filled?
+__device__ __forceinline__ bool hier_stencil_filled(const uint8_t* __restrict__ active, const HierGeom& g, int i, int j, int k) {
+    if (!hier_evaluated(active, g, i, j, k)) return true;
+    if (i > 0 && !hier_evaluated(active, g, i - 1, j, k)) return true;
+    if (i + 1 < g.n[0] && !hier_evaluated(active, g, i + 1, j, k)) return true;
+    if (j > 0 && !hier_evaluated(active, g, i, j - 1, k)) return true;
+    if (j + 1 < g.n[1] && !hier_evaluated(active, g, i, j + 1, k)) return true;
+    if (k > 0 && !hier_evaluated(active, g, i, j, k - 1)) return true;
+    if (k + 1 < g.n[2] && !hier_evaluated(active, g, i, j, k + 1)) return true;
+    return false;
+}
+
+__global__ void __launch_bounds__(MC_THREADS) k_hier_leaks(const float* __restrict__ vol, const uint8_t* __restrict__ active, HierGeom g,
+                                                           int64_t N, float level, const int32_t* __restrict__ index, int64_t M,
+                                                           unsigned long long* __restrict__ leaks) {
+    const int64_t m = (int64_t)blockIdx.x * MC_THREADS + threadIdx.x;
+    int found = 0;
+    const int64_t n = m < M ? (int64_t)index[m] : -1;
+    if (n >= 0 && n < N) {
+        const McPoint p = mc_ijk(n, g.n[1], g.n[2]);
+        const int at[3] = {p.i, p.j, p.k};
+        const int64_t stride[3] = {(int64_t)g.n[1] * g.n[2], g.n[2], 1};
+        const bool in0 = mc_in(vol[n], level);
+        int own = -1;      // (the point's own stencil: looked at only once a crossing edge needs it)
+        for (int d = 0; d < 3; ++d)
+            for (int s = -1; s <= 1; s += 2) {
+                const int o = at[d] + s;
+                if (o < 0 || o >= g.n[d]) continue;
+                int q[3] = {p.i, p.j, p.k};
+                q[d] = o;
+                // the edge to the neighbour below belongs to that neighbour where it is listed itself
+                if (s < 0 && hier_evaluated(active, g, q[0], q[1], q[2])) continue;
+                if (mc_in(vol[n + s * stride[d]], level) == in0) continue;
+                if (own < 0) own = hier_stencil_filled(active, g, p.i, p.j, p.k) ? 1 : 0;
+                if (own || hier_stencil_filled(active, g, q[0], q[1], q[2])) ++found;
+            }
+    }
+    // (up to six edges a thread: the wave's sum by one ballot per possible count bit)
+    unsigned long long total = 0;
+    for (int bit = 0; bit < 3; ++bit) total += (unsigned long long)__popcll(__ballot((found >> bit) & 1)) << bit;
+    if ((threadIdx.x & 63) == 0 && total) atomicAdd(leaks, total);
+}
+
+// grid points of a list: point m = the grid point with the linear index index[m] (an index outside the grid: point 0, and
+// k_points_invalid puts NaN where its value would go)
+__global__ void __launch_bounds__(256) k_list_points(const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ z,
+                                                     const int32_t* __restrict__ index, int ny, int nz, int64_t N, int64_t n,
+                                                     float* __restrict__ pts) {
+    const int64_t m = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (m >= n) return;
+    int64_t l = index[m];
+    if (l < 0 || l >= N) l = 0;
+    const int64_t plane = (int64_t)ny * nz;
+    const int64_t r = l % plane;
+    pts[3 * m + 0] = x[(int)(l / plane)];
+    pts[3 * m + 1] = y[(int)(r / nz)];
+    pts[3 * m + 2] = z[(int)(r % nz)];
+}
+
+__global__ void __launch_bounds__(256) k_points_invalid(const int32_t* __restrict__ index, int64_t N, int64_t n, float* __restrict__ values) {
+    const int64_t m = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (m >= n) return;
+    const int64_t l = index[m];
+    if (l < 0 || l >= N) values[m] = __builtin_nanf("");
+}
+
+void dsn_launch_list_points(const float* x, const float* y, const float* z, const int32_t* index, int ny, int nz, int64_t N, int64_t n,
+                            float* pts, hipStream_t st) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(k_list_points, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, x, y, z, index, ny, nz, N, n, pts);
+}
+
+void dsn_launch_points_invalid(const int32_t* index, int64_t N, int64_t n, float* values, hipStream_t st) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(k_points_invalid, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, index, N, n, values);
+}
+
+static unsigned hier_blocks(int64_t n) { return (unsigned)((n + MC_THREADS - 1) / MC_THREADS); }
+
+// out_counts (3 int64) must be zero on entry (the API zeroes it on the stream)
+void dsn_launch_grid_hier_mark(const float* coarse, int nx, int ny, int nz, int sh, int dilate, float level, void* workspace,
+                               int64_t* out_counts, hipStream_t st) {
+    const HierGeom g = hier_geom(nx, ny, nz, sh);
+    const HierWs w = hier_ws(workspace, g);
+    const int64_t cells = hier_cells(g), N = (int64_t)nx * ny * nz, tiles = mc_tiles(N);
+    unsigned long long* cnt = (unsigned long long*)out_counts;
+    const int longest = g.m[0] > g.m[1] ? (g.m[0] > g.m[2] ? g.m[0] : g.m[2]) : (g.m[1] > g.m[2] ? g.m[1] : g.m[2]);
+    const int r = dilate < longest ? dilate : longest;            // (a radius beyond the lattice's longest axis changes nothing)
+    hipLaunchKernelGGL(k_hier_core, dim3(hier_blocks(cells)), dim3(MC_THREADS), 0, st, coarse, g, level, cells, w.core, cnt);
+    hipLaunchKernelGGL(k_hier_dilate, dim3(hier_blocks(cells)), dim3(MC_THREADS), 0, st, w.core, g, r, cells, w.active, cnt);
+    hipLaunchKernelGGL(k_hier_count, dim3((unsigned)tiles), dim3(MC_THREADS), 0, st, w.active, g, N, w.tp);
+    hipLaunchKernelGGL(k_hier_scan, dim3(1), dim3(MC_SCAN_THREADS), 0, st, w.tp, tiles, cnt + 2);
+}
+
+void dsn_launch_grid_hier_list(int nx, int ny, int nz, int sh, const void* workspace, int32_t* index, int64_t cap, hipStream_t st) {
+    const HierGeom g = hier_geom(nx, ny, nz, sh);
+    const HierWs w = hier_ws((void*)workspace, g);
+    const int64_t N = (int64_t)nx * ny * nz;
+    hipLaunchKernelGGL(k_hier_list, dim3((unsigned)mc_tiles(N)), dim3(MC_THREADS), 0, st, w.active, g, N, w.tp, index, cap);
+}
+
+// out_leaks (int64) must be zero on entry (the API zeroes it on the stream)
+void dsn_launch_grid_hier_assemble(const float* coarse, int nx, int ny, int nz, int sh, float level, const void* workspace,
+                                   const int32_t* index, const float* values, int64_t M, float* volume, int64_t* out_leaks, hipStream_t st) {
+    const HierGeom g = hier_geom(nx, ny, nz, sh);
+    const HierWs w = hier_ws((void*)workspace, g);
+    const int64_t N = (int64_t)nx * ny * nz;
+    hipLaunchKernelGGL(k_hier_fill, dim3(hier_blocks((N + 3) / 4)), dim3(MC_THREADS), 0, st, coarse, g, N, volume);
+    if (M > 0) {
+        hipLaunchKernelGGL(k_hier_scatter, dim3(hier_blocks(M)), dim3(MC_THREADS), 0, st, index, values, M, N, volume);
+        hipLaunchKernelGGL(k_hier_leaks, dim3(hier_blocks(M)), dim3(MC_THREADS), 0, st, volume, w.active, g, N, level, index, M,
+                           (unsigned long long*)out_leaks);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 // connected components of an indexed mesh and its largest piece (dsn_mesh_cc_label / dsn_mesh_cc_emit, the rule of include/dsnerf.h)
 //   label : init -> unite (lock-free union-find over the vertex array, one thread per face) -> flatten (every vertex to its root, unused
 //           vertices -1) -> sums (per face 64-bit integer adds to its root's slots, aggregated per wave) -> select (the arg-max over the

@@ -37,6 +37,7 @@ class Visualizer3D(object):
         self.uniform_grid = uniform_grid
         self.connected = connected
         self.verbose = verbose
+        self.grid_info = None          # get_grid_pred_batch(coarse=...): that call's certificate; None after a dense call
 
     @staticmethod
     def _grid(axes, length, shortest):
@@ -57,10 +58,14 @@ class Visualizer3D(object):
         return self._grid(Renderer.grid_axes_uniform(self.resolution_mc), 2.4, 0)
 
     @torch.no_grad()
-    def get_grid_pred_batch(self, render, points=None, batch=None, chunk=100000):
+    def get_grid_pred_batch(self, render, points=None, batch=None, chunk=100000, coarse=None, dilate=1):
         """numpy grid_pts [1, X, Y, Z, 3] and grid_pred [1, X, Y, Z, 1] as the reference returns them: the density volume of the grid
         over `points` (or the uniform grid) for `batch`'s posed body, with a frame code drawn as the reference draws it
-        (torch.randperm(300)[:B]).  `chunk` is accepted and unused: the grid runs in device slabs."""
+        (torch.randperm(300)[:B]).  `chunk` is accepted and unused: the grid runs in device slabs.
+        coarse (2, 4, 8 or 16; default None: every point evaluated): the volume of Renderer.density_grid_hier at this visualizer's
+        mc_value - densities only near that level's surface, elsewhere a coarse value of the same side, which get_mesh_from_grid
+        turns into the same mesh wherever self.grid_info["leaks"] == 0 (no retry here: check it, or use Renderer.extract_mesh;
+        self.grid_info is None after a dense call)."""
         if batch is None:
             raise ValueError("get_grid_pred_batch: needs the batch (the reference warps the grid with it)")
         if self.uniform_grid:
@@ -74,7 +79,12 @@ class Visualizer3D(object):
         code_idx = torch.randperm(300)[:B]
         if self.verbose:
             print("Code_idx:", code_idx)
-        _, vol = render.density_grid(batch, axes=tuple(grid["xyz"]), frame=int(code_idx[0]))
+        if coarse is None:
+            self.grid_info = None
+            _, vol = render.density_grid(batch, axes=tuple(grid["xyz"]), frame=int(code_idx[0]))
+        else:
+            _, vol, self.grid_info = render.density_grid_hier(batch, level=self.mc_value, coarse=coarse, dilate=dilate,
+                                                              axes=tuple(grid["xyz"]), frame=int(code_idx[0]))
         X, Y, Z = (len(a) for a in grid["xyz"])
         grid_pred = vol.cpu().numpy().reshape(B, X, Y, Z, 1)
         grid_pts = grid["grid_pts"].reshape(B, X, Y, Z, 3).numpy()

@@ -671,6 +671,60 @@ DSN_EXPORT int dsn_mc_normals(const float* volume, int nx, int ny, int nz, const
 /* the case table (host function, no device work): 256 rows of DSN_MC_TABLE_ROW int32 into a HOST array of out_ints >= 256 rows */
 DSN_EXPORT int dsn_mc_table_host(int32_t* out_host, size_t out_ints);
 
+/* ---- density grid, coarse to fine (an addition within ABI 8: no existing entry point changes) ---------------------------------------
+ * The reference's visualizer carries a commented-out `from utils.mise import MISE` (multiresolution iso-surface extraction) it never
+ * wired up.  Here: a two-level form with a certificate.  The density is evaluated on a coarse sub-lattice of the SAME grid, then only
+ * at the fine points in and around the coarse cells the level crosses; every other point is filled so that it can neither create nor
+ * move a vertex, and dsn_mc_count / dsn_mc_emit / dsn_mc_normals run unchanged on the assembled dense volume.  The rule, fixed so that
+ * a numpy restatement (tests/grid_hier_restate.py) reproduces every output bit for bit - inputs: the fine grid nx, ny, nz (every axis
+ * >= 2, fewer than 2^31 points), a level, a factor c in {2, 4, 8, 16} and a dilate r >= 0:
+ *   1. Coarse lattice.  Per axis of n points the indices 0, c, 2c, ... < n, plus n - 1 if it is not among them: m = ceil((n - 1) / c) + 1
+ *      coarse points, coarse point q = fine index min(q c, n - 1), m - 1 cells of which the last may be shorter.  Coarse points ARE fine
+ *      points: coarse [mx, my, mz] holds the dense grid's values at those points, bit for bit (the density of a point depends on
+ *      nothing but the point).
+ *   2. Core cells.  A coarse cell whose eight corners are not all on the same side of the level, with marching cubes' inside =
+ *      v > level (strict; NaN is outside).
+ *   3. Active cells.  The core cells dilated r times over the 26-neighbourhood: a box maximum of radius r, clipped at the lattice's
+ *      border.
+ *   4. Evaluated points.  Every fine point in the closed index box of an active cell; their linear fine indices n = (i ny + j) nz + k
+ *      as an ascending int32 list.
+ *   5. Fill.  An unevaluated point gets the coarse value at the lowest corner of its owner cell - per axis the last coarse index <= the
+ *      point's index, clamped to the last cell: min(i / c, m - 2).  Every cell that contains an unevaluated point is inactive, hence no
+ *      core cell, hence has all corners on one side; neighbouring inactive cells share corners: no two filled points differ in side.
+ *   6. Assembled volume [nx, ny, nz].  Evaluated points hold the caller's values (dsn_density_points': dsn_density_grid's bits at that
+ *      point), all other points the fill.
+ *   7. Leaks, the certificate.  Of the grid edges of the assembled volume whose ends differ in side, an edge is a leak when a filled
+ *      point is among its two end points or among the in-grid +-1 neighbours of either end point along any of the three axes (the
+ *      stencil of dsn_mc_normals).  `leaks` counts those edges, each once.
+ * What this proves: where the assembled and the dense volume have the same inside mask everywhere and leaks == 0, dsn_mc_count,
+ * dsn_mc_emit and dsn_mc_normals return the dense grid's vertices, faces and normals bit for bit (every value they read was evaluated).
+ * What it does not: a piece of surface that lies wholly among unevaluated points - a floater smaller than a coarse cell, more than r
+ * cells away from any coarse sign change - cannot be seen and is not counted; leaks == 0 says nothing about it.
+ * Stages (the library never allocates; integer counters only, so the same call returns the same bits):
+ *   dsn_grid_hier_mark     coarse volume -> core and active masks in `workspace` (dsn_grid_hier_workspace_bytes), out_counts3 (int64,
+ *                          device): core cells, active cells, evaluated points;
+ *   dsn_grid_hier_list     that workspace -> point_index [n_points] int32 ascending; the caller sizes it from out_counts3[2];
+ *   dsn_density_points     values [m] = the dense grid's value at point_index [m] (below);
+ *   dsn_grid_hier_assemble fill everywhere, then the scatter of the listed values -> volume; out_leaks (int64, device).  point_index
+ *                          must be dsn_grid_hier_list's list of the same workspace (indices outside the grid are skipped). */
+DSN_EXPORT size_t dsn_grid_hier_workspace_bytes(int nx, int ny, int nz, int factor);
+DSN_EXPORT int dsn_grid_hier_mark(const float* coarse, int mx, int my, int mz, int nx, int ny, int nz, int factor, int dilate, float level,
+                                  void* workspace, size_t workspace_bytes, int64_t* out_counts3, void* stream);
+DSN_EXPORT int dsn_grid_hier_list(int nx, int ny, int nz, int factor, const void* workspace, size_t workspace_bytes, int64_t n_points,
+                                  int32_t* point_index, void* stream);
+DSN_EXPORT int dsn_grid_hier_assemble(const float* coarse, int mx, int my, int mz, int nx, int ny, int nz, int factor, float level,
+                                      const void* workspace, size_t workspace_bytes, const int32_t* point_index, const float* values,
+                                      int64_t n_points, float* volume, int64_t* out_leaks, void* stream);
+/* The density of listed grid points: values [m] = dsn_density_grid's value at grid point point_index [m] = (i ny + j) nz + k of the
+ * axes x, y, z, bit for bit (transparent points 0, flagged points re-evaluated by the exact-fp32 kernel; DSN_FIELD_FP32 and
+ * DSN_NN_EXHAUSTIVE as there).  The list may be in any order and hold duplicates; an index outside the grid gives NaN.  The list runs
+ * in slabs of at most slab_points (>= 1) points; the scratch `workspace` of dsn_density_points_workspace_bytes(slab_points) bytes does
+ * not grow with the list, and the result does not depend on the slab size. */
+DSN_EXPORT size_t dsn_density_points_workspace_bytes(int64_t slab_points);
+DSN_EXPORT int dsn_density_points(const void* scene, int V, int F, const void* packed, const float* x, int nx, const float* y, int ny,
+                                  const float* z, int nz, const int32_t* point_index, int64_t n_points, int flags, float* values,
+                                  int64_t slab_points, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- mesh components (an addition within ABI 8: no existing entry point changes) ----------------------------------------------------
  * utils/visualizer.py:129-138, Visualizer3D(connected=True): the reference splits the mesh with trimesh and keeps the component with the
  * largest area.  Here: the connected components of an indexed mesh (verts [V, 3] float32, faces [T, 3] int32, device) and its largest
