@@ -49,6 +49,25 @@ def per_point_dirs(g):
     return np.repeat(g["ray_d"][:, None, :], S, 1).reshape(-1, 3)
 
 
+def workspace_arrays(ws, N):
+    """per-sample arrays of a render workspace of N = R x S samples, by dsn_carve's layout (csrc/dsn_api.hip): transparent, x_c, sigma,
+    n_w, colour - clones, as torch tensors on the workspace's device"""
+    import torch
+    al = lambda n: (n + 255) // 256 * 256      # noqa: E731
+    b = ws.buf
+    p = 8192 + al(4 * N)
+    out = {"transparent": b[p:p + N].clone()}
+    p += al(N) + al(4 * N)
+    out["x_c"] = b[p:p + 12 * N].view(torch.float32).reshape(N, 3).clone()
+    p += al(12 * N)
+    out["sigma"] = b[p:p + 4 * N].view(torch.float32).clone()
+    p += al(4 * N)
+    out["n_w"] = b[p:p + 12 * N].view(torch.float32).reshape(N, 3).clone()
+    p += 12 * N
+    out["colour"] = b[p:p + 12 * N].view(torch.float32).reshape(N, 3).clone()
+    return out
+
+
 def maxdiff(a, b):
     a = np.asarray(a, np.float64)
     b = np.asarray(b, np.float64)

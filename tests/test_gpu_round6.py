@@ -5,7 +5,7 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import state
+from helpers import state, workspace_arrays
 from test_gpu_round2 import full_frame, renderer_with
 
 pytestmark = pytest.mark.gpu
@@ -132,21 +132,7 @@ def test_training_backward_beside_frames_leaves_them_bit_identical():
     tv = r._t_vals(S)
     VF = [(_lib.Scene(torch.from_numpy(canon), torch.from_numpy(faces), dev), _lib.RenderWorkspace(dev)) for _ in range(NF)]
     A, B = torch.cuda.Stream(device=dev), torch.cuda.Stream(device=dev)
-    al = lambda n: (n + 255) // 256 * 256
-
-    def arrays(ws):      # per-sample arrays of a render workspace (dsn_carve): transparent, x_c, sigma, n_w, colour
-        b = ws.buf
-        p = 8192 + al(4 * N)
-        out = {"transparent": b[p:p + N].clone()}
-        p += al(N) + al(4 * N)
-        out["x_c"] = b[p:p + 12 * N].view(torch.float32).reshape(N, 3).clone()
-        p += al(12 * N)
-        out["sigma"] = b[p:p + 4 * N].view(torch.float32).clone()
-        p += al(4 * N)
-        out["n_w"] = b[p:p + 12 * N].view(torch.float32).reshape(N, 3).clone()
-        p += 12 * N
-        out["colour"] = b[p:p + 12 * N].view(torch.float32).reshape(N, 3).clone()
-        return out
+    arrays = lambda ws: workspace_arrays(ws, N)      # noqa: E731  (transparent, x_c, sigma, n_w, colour)
 
     PH = {"geom": _lib.PHASE_GEOMETRY, "field": _lib.PHASE_FIELD, "shade": _lib.PHASE_SHADE}
 
