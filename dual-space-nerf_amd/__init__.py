@@ -8,8 +8,9 @@ the repo-root shim dsnerf_amd.py because a hyphenated directory is not an import
 from . import synth  # noqa: F401
 from . import _lib  # noqa: F401
 from . import loss  # noqa: F401  (make_loss, MSELoss, SmoothL1Loss: utils/loss.py on the device)
+from . import optim  # noqa: F401  (make_optimizer, Adam: solver/build.py on the device)
 from .can_render import Renderer  # noqa: F401
 from .model.spacenet import DualSpaceNeRF, LightingMLP, SpaceNet  # noqa: F401
 from .parallel import RayParallel  # noqa: F401
 
-__all__ = ["Renderer", "DualSpaceNeRF", "SpaceNet", "LightingMLP", "RayParallel", "synth", "loss"]
+__all__ = ["Renderer", "DualSpaceNeRF", "SpaceNet", "LightingMLP", "RayParallel", "synth", "loss", "optim"]

@@ -56,6 +56,7 @@ EXPORTS = [
     "dsn_train_loss_workspace_bytes", "dsn_train_loss", "dsn_train_loss_grad",
     "dsn_grid_hier_workspace_bytes", "dsn_grid_hier_mark", "dsn_grid_hier_list", "dsn_grid_hier_assemble",
     "dsn_density_points_workspace_bytes", "dsn_density_points",
+    "dsn_adam_step", "dsn_adam_scalars_host",
 ]
 
 SKIP_TRANSPARENT = 1
@@ -183,6 +184,8 @@ def lib():
         L.dsn_density_points_workspace_bytes.argtypes = [C.c_int64]
         L.dsn_density_points.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                                          C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p]
+        L.dsn_adam_step.argtypes = [C.c_void_p] * 5 + [C.c_int, C.c_void_p, C.c_void_p] + [C.c_double] * 4 + [C.c_void_p, C.c_void_p]
+        L.dsn_adam_scalars_host.argtypes = [C.c_double] * 6 + [C.c_void_p]
         if L.dsn_abi_version() != 8:
             raise RuntimeError(f"{LIB_PATH} has ABI version {L.dsn_abi_version()}, this binding needs 8 - rebuild it "
                                "(python dual-space-nerf_amd/build.py)")
@@ -313,11 +316,22 @@ class PackedParams:
         ptrs = (C.c_void_p * len(dev))(*[t.data_ptr() for t in dev])
         _check(lib().dsn_pack_params(ptrs, _ptr(self.buf), _stream()), "dsn_pack_params")
         self._keep = dev  # keep sources alive until the pack kernel has run (stream-ordered)
+        self._repacked(versions)
+        return self
+
+    def _repacked(self, versions):
         self._versions = versions
         self.generation += 1
         self.screen = None         # the packed image carries the conservative default margin again
         self.early_stop = None
         self.colour_scale = 1.0    # (dsn_pack_params resets it)
+
+    def note_repacked(self, tensors):
+        """The image was rebuilt outside update() from the 33 `tensors` (PARAM_ORDER), as they are now - adam_step(..., packed=self)
+        does that behind its update: update()'s bookkeeping, so that the next update() of the same tensors launches nothing."""
+        assert len(tensors) == len(PARAM_ORDER)
+        self._keep = None          # (the image was packed from the parameters themselves)
+        self._repacked(tuple((t.data_ptr(), t._version) for t in tensors))
         return self
 
     def set_early_stop_colour_scale(self, scale: float):
@@ -2144,6 +2158,60 @@ def train_loss_grad(color, target, acc=None, occupancy=None, kind="L2", up_rgb=N
         _check(lib().dsn_train_loss_grad(_ptr(color, torch.float32), _ptr(t32), _ptr(t64), _ptr(acc), _ptr(o8), _ptr(o32), R, kind,
                                          _ptr(up_rgb), _ptr(up_mask), _ptr(g_color), _ptr(g_acc), _stream()), "dsn_train_loss_grad")
     return g_color, g_acc
+
+
+ADAM_TABLE, ADAM_BLOCK = 48, 1024      # dsn_adam_step: segments per launch, elements per workgroup (DSN_ADAM_*)
+
+
+def adam_scalars(lr, weight_decay, betas, eps, step):
+    """the float32 host scalars of dsn_adam_step's rule, as the library computes them: dict(w1, w2, b2, eps, wd, ss, c2) of Python
+    floats (dsn_adam_scalars_host; no device work)"""
+    out = (C.c_float * 7)()
+    _check(lib().dsn_adam_scalars_host(float(lr), float(weight_decay), float(betas[0]), float(betas[1]), float(eps), float(step), out),
+           "dsn_adam_scalars_host")
+    return dict(zip(("w1", "w2", "b2", "eps", "wd", "ss", "c2"), (float(v) for v in out)))
+
+
+def adam_step(params, grads, exp_avgs, exp_avg_sqs, lrs, weight_decays, betas, eps, step, packed=None):
+    """One Adam step of every tensor in one launch (dsn_adam_step, the rule of include/dsnerf.h; more than ADAM_TABLE tensors: one
+    launch per table): params, exp_avgs and exp_avg_sqs are updated in place - through their storage, so the version counters do not
+    move (the caller's business: optim.Adam bumps them).  Lists of equal length of contiguous float32 tensors on one GPU (views at
+    any 4-byte offset included); a None in `grads` skips that tensor.  lrs / weight_decays: one number per tensor, or one for all.
+    step: the count t of this step (1 for the first), one for all tensors.  packed: a PackedParams - the lists must then be the
+    model's 33 tensors in PARAM_ORDER, and the image is rebuilt from the new parameters behind the update on the same stream
+    (follow with packed.note_repacked(params) once the version counters are final).  Nothing synchronises."""
+    require_gpu()
+    count = len(params)
+    if not (len(grads) == len(exp_avgs) == len(exp_avg_sqs) == count):
+        raise ValueError("params, grads, exp_avgs and exp_avg_sqs must have one entry per tensor")
+    lrs = [float(lrs)] * count if not hasattr(lrs, "__len__") else [float(x) for x in lrs]
+    weight_decays = [float(weight_decays)] * count if not hasattr(weight_decays, "__len__") else [float(x) for x in weight_decays]
+    if len(lrs) != count or len(weight_decays) != count:
+        raise ValueError("lrs and weight_decays must have one entry per tensor (or be one number)")
+    if packed is not None and count != len(PARAM_ORDER):
+        raise ValueError(f"packed needs the model's {len(PARAM_ORDER)} tensors in PARAM_ORDER, got {count}")
+    if count == 0:
+        return
+    dev = params[0].device
+    ptrs = [[], [], [], []]
+    ns = []
+    for row in zip(params, grads, exp_avgs, exp_avg_sqs):
+        p = row[0]
+        for k, t in enumerate(row):
+            if t is None and k == 1:
+                ptrs[k].append(None)
+                continue
+            if t.dtype != torch.float32 or not t.is_cuda or t.device != dev or not t.is_contiguous() or t.numel() != p.numel():
+                raise ValueError("adam_step: every tensor must be contiguous float32 on the parameters' GPU, with its parameter's size: "
+                                 f"got {t.dtype} {tuple(t.shape)} on {t.device} (contiguous: {t.is_contiguous()}) for a parameter "
+                                 f"{tuple(p.shape)} on {dev}")
+            ptrs[k].append(t.data_ptr() or None)
+        ns.append(p.numel())
+    arr = [(C.c_void_p * count)(*col) for col in ptrs]
+    with torch.cuda.device(dev):
+        _check(lib().dsn_adam_step(arr[0], arr[1], arr[2], arr[3], (C.c_int64 * count)(*ns), count, (C.c_double * count)(*lrs),
+                                   (C.c_double * count)(*weight_decays), float(betas[0]), float(betas[1]), float(eps), float(step),
+                                   None if packed is None else _ptr(packed.buf), _stream()), "dsn_adam_step")
 
 
 def camera_rays(K, R, T, bounds, H, W, device=None, convention="zju"):

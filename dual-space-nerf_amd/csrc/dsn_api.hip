@@ -403,6 +403,49 @@ int dsn_train_loss_grad(const float* color, const float* target_f32, const doubl
     return dsn_check_launch("dsn_train_loss_grad");
 }
 
+static bool dsn_adam_scalars_ok(double beta1, double beta2, double eps, double t) {
+    return beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && std::isfinite(eps) && eps >= 0.0 && std::isfinite(t) && t >= 1.0;
+}
+
+int dsn_adam_scalars_host(double lr, double weight_decay, double beta1, double beta2, double eps, double t, float* out7_host) {
+    DSN_REQUIRE(out7_host, "dsn_adam_scalars_host: null argument");
+    DSN_REQUIRE(dsn_adam_scalars_ok(beta1, beta2, eps, t), "dsn_adam_scalars_host: betas must lie in [0, 1), eps be finite and >= 0, t be finite and >= 1");
+    DSN_REQUIRE(std::isfinite(lr) && lr >= 0.0 && std::isfinite(weight_decay) && weight_decay >= 0.0,
+                "dsn_adam_scalars_host: lr and weight_decay must be finite and >= 0");
+    dsn_adam_scalars(lr, weight_decay, beta1, beta2, eps, t, out7_host);
+    return 0;
+}
+
+int dsn_adam_step(float* const* params_host, const float* const* grads_host, float* const* exp_avgs_host, float* const* exp_avg_sqs_host,
+                  const int64_t* n_host, int count, const double* lr_host, const double* weight_decay_host, double beta1, double beta2,
+                  double eps, double t, void* packed, void* stream) {
+    DSN_REQUIRE(count >= 0, "dsn_adam_step: count must not be negative");
+    DSN_REQUIRE(count == 0 || (params_host && grads_host && exp_avgs_host && exp_avg_sqs_host && n_host && lr_host && weight_decay_host),
+                "dsn_adam_step: null argument");
+    DSN_REQUIRE(dsn_adam_scalars_ok(beta1, beta2, eps, t), "dsn_adam_step: betas must lie in [0, 1), eps be finite and >= 0, t be finite and >= 1");
+    for (int i = 0; i < count; ++i) {
+        DSN_REQUIRE(n_host[i] >= 0 && n_host[i] <= DSN_ADAM_MAX_N, "dsn_adam_step: a length must be 0 ... 2^33");
+        DSN_REQUIRE(std::isfinite(lr_host[i]) && lr_host[i] >= 0.0 && std::isfinite(weight_decay_host[i]) && weight_decay_host[i] >= 0.0,
+                    "dsn_adam_step: lr and weight_decay must be finite and >= 0");
+        if (grads_host[i] && n_host[i] > 0)
+            DSN_REQUIRE(params_host[i] && exp_avgs_host[i] && exp_avg_sqs_host[i], "dsn_adam_step: null tensor pointer");
+    }
+    if (packed) {
+        DSN_REQUIRE(count == DSN_NUM_PARAMS, "dsn_adam_step: packed needs the model's 33 tensors");
+        for (int i = 0; i < DSN_NUM_PARAMS; ++i)
+            DSN_REQUIRE(params_host[i] && n_host[i] == DSN_PARAM_COUNT[i], "dsn_adam_step: packed needs the model's 33 tensors (a null parameter or another length)");
+    }
+    hipStream_t st = (hipStream_t)stream;
+    dsn_launch_adam_step(params_host, grads_host, exp_avgs_host, exp_avg_sqs_host, n_host, count, lr_host, weight_decay_host, beta1, beta2,
+                         eps, t, st);
+    if (packed) {       // what dsn_pack_params enqueues, behind the update
+        dsn_launch_pack_params(params_host, (float*)packed, st);
+        dsn_launch_set_screen_margin((float*)packed, DSN_SCREEN_MARGIN_DEFAULT, st);
+        dsn_launch_set_packed_scalar((float*)packed, 6, 1.0f, st);
+    }
+    return dsn_check_launch("dsn_adam_step");
+}
+
 int dsn_field_screen(const void* scene, int V, int F, const void* packed, const float* x_c, int64_t N, const int32_t* active_list,
                      const int32_t* active_count, float* sigma, int32_t* keep_list, int32_t* keep_count, void* stream) {
     DSN_REQUIRE(scene && packed && x_c && sigma && keep_list && keep_count, "dsn_field_screen: null argument");

@@ -12,6 +12,10 @@
 
 #define DSN_WAVE 64
 #define DSN_NUM_PARAMS_INTERNAL 33
+// element counts of the 33 parameters in state_dict order (host tables: the gradient arena of dsn_train.hip, dsn_adam_step's check)
+constexpr int DSN_PARAM_COUNT[DSN_NUM_PARAMS_INTERNAL] = {500 * 8, 256 * 87, 256, 256 * 256, 256, 256 * 256, 256, 256 * 256, 256, 256 * 319, 256,
+                                                          256 * 256, 256, 256 * 256, 256, 256, 1, 128 * 256, 128, 3 * 128, 3, 128 * 9, 128,
+                                                          128 * 128, 128, 128, 1, 64 * 92, 64, 64 * 64, 64, 16 * 64, 16};
 
 // ---------------------------------------------------------------------------------------------
 // scene blob (device memory owned by the caller, dsn_scene_bytes(V,F) bytes)

@@ -212,6 +212,11 @@ void dsn_launch_train_loss(const float* color, const float* t32, const double* t
 void dsn_launch_train_loss_grad(const float* color, const float* t32, const double* t64, const float* acc, const uint8_t* o8,
                                 const float* o32, int64_t R, int kind, const float* up_rgb, const float* up_mask, float* g_color,
                                 float* g_acc, hipStream_t st);
+// dsn_optim.hip: the optimizer step (dsn_adam_step): out7 = {w1, w2, b2, eps, wd, ss, c2}; the launcher returns its launch count
+void dsn_adam_scalars(double lr, double weight_decay, double beta1, double beta2, double eps, double t, float* out7);
+int dsn_launch_adam_step(float* const* params, const float* const* grads, float* const* exp_avgs, float* const* exp_avg_sqs,
+                         const int64_t* n, int count, const double* lr, const double* weight_decay, double beta1, double beta2, double eps,
+                         double t, hipStream_t st);
 // dsn_mesh.hip: density grid points and marching cubes (dsn_density_grid, dsn_mc_*)
 void dsn_launch_grid_points(const float* x, const float* y, const float* z, int i0, int ny, int nz, int64_t n, float* pts, hipStream_t st);
 size_t dsn_mc_workspace_size(int64_t N);

@@ -32,10 +32,6 @@ enum { P_EMB = 0, P_S1_0W, P_S1_0B, P_S1_2W, P_S1_2B, P_S1_4W, P_S1_4B, P_S1_6W,
        P_S2_2B, P_S2_4W, P_S2_4B, P_DEN_W, P_DEN_B, P_RGB1_W, P_RGB1_B, P_RGB3_W, P_RGB3_B, P_L0_W, P_L0_B, P_L2_W,
        P_L2_B, P_L4_W, P_L4_B, P_PM0_W, P_PM0_B, P_PM2_W, P_PM2_B, P_PM4_W, P_PM4_B };
 
-const int kParamCount[33] = {500 * 8, 256 * 87, 256, 256 * 256, 256, 256 * 256, 256, 256 * 256, 256, 256 * 319, 256,
-                             256 * 256, 256, 256 * 256, 256, 256, 1, 128 * 256, 128, 3 * 128, 3, 128 * 9, 128,
-                             128 * 128, 128, 128, 1, 64 * 92, 64, 64 * 64, 64, 16 * 64, 16};
-
 // trunk layer l: weight / bias parameter index, input width (leading dimension of W), column of the h-part
 const int kTrunkW[7] = {P_S1_0W, P_S1_2W, P_S1_4W, P_S1_6W, P_S2_0W, P_S2_2W, P_S2_4W};
 const int kTrunkB[7] = {P_S1_0B, P_S1_2B, P_S1_4B, P_S1_6B, P_S2_0B, P_S2_2B, P_S2_4B};
@@ -2458,7 +2454,7 @@ const char* dsn_train_run(const DsnSceneView& s, const float* packed, const floa
     TrainWs w = carve(workspace, N64);
     {
         TrainZero z;
-        for (int i = 0; i < 33; ++i) { z.p[i] = grd[i]; z.n[i] = kParamCount[i]; }
+        for (int i = 0; i < 33; ++i) { z.p[i] = grd[i]; z.n[i] = DSN_PARAM_COUNT[i]; }
         z.p[33] = w.small; z.n[33] = 1024;
         hipLaunchKernelGGL(k_t_zero, dim3(32, 34), dim3(T_THREADS), 0, st, z);
     }

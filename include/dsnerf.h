@@ -310,6 +310,52 @@ DSN_EXPORT int dsn_train_loss_grad(const float* color, const float* target_f32, 
                                    const uint8_t* occ_u8, const float* occ_f32, int64_t R, int kind, const float* up_rgb,
                                    const float* up_mask, float* g_color, float* g_acc, void* stream);
 
+/* ---- the optimizer step on the device (an addition within ABI 8: no existing entry point changes) ---------------------------------
+ * solver/build.py:9-15 builds torch.optim.Adam and trainer.py:80 steps it: with the model's 33 small tensors a chain of multi-tensor
+ * launches, and a re-pack of the MFMA image in front of the next render.  dsn_adam_step updates every tensor of the call in one launch
+ * (a table of segments in the kernel arguments; more than DSN_ADAM_TABLE tensors with a gradient: one launch per table) and, given
+ * `packed`, leaves the image of the new parameters behind it on the same stream.
+ *   params_host, grads_host, exp_avgs_host, exp_avg_sqs_host: HOST arrays of `count` DEVICE pointers to float32 arrays of n_host[i]
+ *   elements; 4-byte alignment is enough (a view into a larger buffer), 16-byte aligned tensors take 16-byte accesses.  A NULL
+ *   gradient skips the tensor (torch skips parameters whose .grad is None): nothing of it is read or written, its other pointers may
+ *   be NULL.  So does n_host[i] = 0.  lr_host, weight_decay_host: `count` doubles each (param groups differ).  beta1, beta2, eps
+ *   and the step count t (1 for the first step, the same for every tensor of the call) are doubles.
+ * The rule.  Host scalars, computed in double and rounded to float32 once each (dsn_adam_scalars_host returns them):
+ *   w1 = f32(1 - beta1), w2 = f32(1 - beta2), b2 = f32(beta2), e = f32(eps), wd = f32(weight_decay),
+ *   ss = f32(lr / (1 - pow(beta1, t))), c2 = f32(sqrt(1 - pow(beta2, t))).
+ * Per element, float32, one IEEE rounding per operation, nothing fused, division and square root correctly rounded (parentheses give
+ * the order):
+ *   g' = g + wd p  where wd != 0, else g                    (L2 decay: the gradient, not the parameter, takes it)
+ *   m' = m + w1 (g' - m)
+ *   v' = b2 v + w2 (g' g')
+ *   p' = p - ss (m' / (sqrt(v') / c2 + e))
+ * and m', v', p' are stored.  This is torch/optim/adam.py's _single_tensor_adam operation for operation (add with alpha, lerp's
+ * low-weight branch, mul_ then addcmul_, sqrt / div / add_, addcdiv_), so a numpy float32 restatement reproduces every bit
+ * (tests/adam_restate.py).  Nothing is skipped or clamped: NaN and infinite gradients propagate as the rule says, g = 0 with v = 0
+ * gives 0 / e.  lr = 0 (a frozen group): ss = 0, m' and v' advance and p' = p - 0 x quotient keeps p's bits wherever the quotient is
+ * finite (the one exception IEEE makes: p = -0 with a negative quotient becomes +0).
+ *   packed: NULL, or the image of dsn_packed_param_bytes() bytes; then the table must be the model's 33 tensors in state_dict order
+ *   (count = DSN_NUM_PARAMS, the lengths of the model's tensors, no NULL parameter), and after the update the call enqueues what
+ *   dsn_pack_params enqueues, on the new parameters: the image equals dsn_pack_params' of them, calibrations included (the screen's
+ *   margin and the early-stop colour scale are back at their defaults).
+ * Kernel: 256 threads, DSN_ADAM_BLOCK elements per workgroup, the grid the sum of the segments' workgroups (a launch also ends before
+ * its grid would reach 2^24 workgroups: grid x 256 threads stays below the runtime's 2^32; sizes near that were not run); a workgroup finds its
+ * segment by its index in the prefix of workgroup counts the table carries.  One writer per word, no atomics, no LDS: the same call
+ * from the same state gives the same bits.  The device pointers are arguments: no process state is kept.  No allocation, no
+ * synchronisation, all on `stream`.
+ * Rejected before anything is enqueued: count < 0, null arrays with count > 0, a negative length or one above DSN_ADAM_MAX_N, a tensor with a
+ * gradient and n > 0 whose p, m or v is NULL, t < 1 or not finite, a beta outside [0, 1), eps, a lr or a weight_decay that is
+ * negative or not finite, `packed` with a table that is not the 33 tensors. */
+#define DSN_ADAM_TABLE 48          /* segments per launch */
+#define DSN_ADAM_BLOCK 1024        /* elements per workgroup */
+#define DSN_ADAM_MAX_N ((int64_t)1 << 33)   /* elements per tensor */
+DSN_EXPORT int dsn_adam_step(float* const* params_host, const float* const* grads_host, float* const* exp_avgs_host,
+                             float* const* exp_avg_sqs_host, const int64_t* n_host, int count, const double* lr_host,
+                             const double* weight_decay_host, double beta1, double beta2, double eps, double t, void* packed,
+                             void* stream);
+/* the rule's host scalars (no device work): out7_host = {w1, w2, b2, e, wd, ss, c2} */
+DSN_EXPORT int dsn_adam_scalars_host(double lr, double weight_decay, double beta1, double beta2, double eps, double t, float* out7_host);
+
 /* The density screen as a stage (what dsn_render_rays runs first in eval mode): for the listed points (or all N) the
  * plain-fp16 trunk; points whose fp16 density is negative by the safety margin (calibrated for the parameters: dsn_calibrate_screen) get that negative value in sigma [N] and are dropped, the
  * others are appended to keep_list (keep_count zeroed by the caller) for dsn_field_forward. */
