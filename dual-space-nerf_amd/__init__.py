@@ -9,8 +9,10 @@ from . import synth  # noqa: F401
 from . import _lib  # noqa: F401
 from . import loss  # noqa: F401  (make_loss, MSELoss, SmoothL1Loss: utils/loss.py on the device)
 from . import optim  # noqa: F401  (make_optimizer, Adam: solver/build.py on the device)
+from . import body  # noqa: F401  (BodyModel: SMPL parameters -> posed vertices, joint transforms and bounds on the device)
+from .body import BodyModel  # noqa: F401
 from .can_render import Renderer  # noqa: F401
 from .model.spacenet import DualSpaceNeRF, LightingMLP, SpaceNet  # noqa: F401
 from .parallel import RayParallel  # noqa: F401
 
-__all__ = ["Renderer", "DualSpaceNeRF", "SpaceNet", "LightingMLP", "RayParallel", "synth", "loss", "optim"]
+__all__ = ["Renderer", "DualSpaceNeRF", "SpaceNet", "LightingMLP", "RayParallel", "synth", "loss", "optim", "body", "BodyModel"]

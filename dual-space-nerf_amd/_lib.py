@@ -57,6 +57,7 @@ EXPORTS = [
     "dsn_grid_hier_workspace_bytes", "dsn_grid_hier_mark", "dsn_grid_hier_list", "dsn_grid_hier_assemble",
     "dsn_density_points_workspace_bytes", "dsn_density_points",
     "dsn_adam_step", "dsn_adam_scalars_host",
+    "dsn_body_shape", "dsn_body_pose_workspace_bytes", "dsn_body_pose",
 ]
 
 SKIP_TRANSPARENT = 1
@@ -186,6 +187,11 @@ def lib():
                                          C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p]
         L.dsn_adam_step.argtypes = [C.c_void_p] * 5 + [C.c_int, C.c_void_p, C.c_void_p] + [C.c_double] * 4 + [C.c_void_p, C.c_void_p]
         L.dsn_adam_scalars_host.argtypes = [C.c_double] * 6 + [C.c_void_p]
+        L.dsn_body_shape.argtypes = [C.c_void_p] * 3 + [C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 3
+        L.dsn_body_pose_workspace_bytes.restype = C.c_size_t
+        L.dsn_body_pose_workspace_bytes.argtypes = [C.c_int, C.c_int]
+        L.dsn_body_pose.argtypes = ([C.c_void_p] * 5 + [C.c_int] + [C.c_void_p] * 3 + [C.c_int, C.c_int] + [C.c_void_p] * 6
+                                    + [C.c_size_t, C.c_void_p])
         if L.dsn_abi_version() != 8:
             raise RuntimeError(f"{LIB_PATH} has ABI version {L.dsn_abi_version()}, this binding needs 8 - rebuild it "
                                "(python dual-space-nerf_amd/build.py)")
@@ -1238,6 +1244,94 @@ def mesh_pose(binding, body_faces, target_xyz):
                                _ptr(h) if n else None, _ptr(cov) if n else None, N, _ptr(verts) if n else None,
                                _ptr(normals) if n else None, _ptr(status), _ptr(ws), _stream()), "dsn_mesh_pose")
     return {"verts": verts, "normals": normals, "status": status}
+
+
+BODY_PADS = {None: 0, "none": 0, "zju_train": 1, "zju_eval": 2, "h36m": 3}      # DSN_BODY_PAD_*
+BODY_OUTPUTS = ("xyz", "xyz_smpl", "A", "bounds", "Rh_mat")
+
+
+def body_parents(parents):
+    """24 int32 parents in host memory (a ctypes array) from anything array-like; entry 0 is ignored by the library"""
+    p = [int(x) for x in torch.as_tensor(parents).reshape(-1).tolist()]
+    if len(p) != 24:
+        raise ValueError(f"body model: parents must have 24 entries, got {len(p)}")
+    p[0] = -1
+    return (C.c_int32 * 24)(*p)
+
+
+def body_shape(v_template, shapedirs=None, betas=None, J_regressor=None):
+    """dsn_body_shape (the rule of include/dsnerf.h): v_template [V,3], shapedirs [V,3,B] and betas [B] (both or neither), a dense
+    J_regressor [24,V] or None -> (v_shaped [V,3], joints [24,3] or None).  Device tensors in and out."""
+    require_gpu()
+    dev = v_template.device
+    v_template = _f32(v_template, dev).reshape(-1, 3)
+    V = v_template.shape[0]
+    B = 0
+    if (shapedirs is None) != (betas is None):
+        raise ValueError("body_shape: shapedirs and betas go together")
+    if betas is not None:
+        betas = _f32(betas, dev).reshape(-1)
+        B = betas.shape[0]
+        shapedirs = _f32(shapedirs, dev)
+        if shapedirs.numel() != V * 3 * B:
+            raise ValueError(f"body_shape: shapedirs must be [V,3,B] = [{V},3,{B}], got {tuple(shapedirs.shape)}")
+    if J_regressor is not None:
+        J_regressor = _f32(J_regressor, dev)
+        if tuple(J_regressor.shape) != (24, V):
+            raise ValueError(f"body_shape: J_regressor must be [24,{V}], got {tuple(J_regressor.shape)}")
+    v_shaped = _output((V, 3), torch.float32, dev)
+    joints = _output((24, 3), torch.float32, dev) if J_regressor is not None else None
+    _check(lib().dsn_body_shape(_ptr(v_template), _ptr(shapedirs) if B else None, _ptr(betas) if B else None, B, _ptr(J_regressor), V,
+                                _ptr(v_shaped), _ptr(joints), _stream()), "dsn_body_shape")
+    return v_shaped, joints
+
+
+def body_pose(v_shaped, joints, parents, weights, posedirs, poses, Rh=None, Th=None, pad=None, want=("xyz", "A", "bounds"), workspace=None):
+    """dsn_body_pose (the rule of include/dsnerf.h) for the P poses of `poses` [P,24,3] in ONE call: device tensors v_shaped [V,3], joints
+    [24,3], weights [V,24], posedirs [207,3V] or None, Rh / Th [P,3] or None; `parents`: body_parents()' host array (or array-like).
+    Returns a dict with the outputs named in `want` (BODY_OUTPUTS; "xyz" always).  P = 0: empty tensors, no launch."""
+    require_gpu()
+    dev = v_shaped.device
+    if pad not in BODY_PADS:
+        raise ValueError(f"body_pose: pad must be one of {sorted(k for k in BODY_PADS if k)} or None, got {pad!r}")
+    unknown = set(want) - set(BODY_OUTPUTS)
+    if unknown:
+        raise ValueError(f"body_pose: unknown outputs {sorted(unknown)} (known: {BODY_OUTPUTS})")
+    if not isinstance(parents, C.Array):
+        parents = body_parents(parents)
+    if v_shaped.dim() != 2 or v_shaped.shape[1] != 3 or v_shaped.shape[0] < 1:
+        raise ValueError(f"body_pose: v_shaped must be [V,3], got {tuple(v_shaped.shape)}")
+    V = v_shaped.shape[0]
+    for name, t, shape in (("joints", joints, (24, 3)), ("weights", weights, (V, 24)), ("posedirs", posedirs, (207, 3 * V))):
+        if t is None and name == "posedirs":
+            continue
+        if not torch.is_tensor(t) or tuple(t.shape) != shape:
+            raise ValueError(f"body_pose: {name} must be a tensor [{shape[0]},{shape[1]}], got {tuple(t.shape) if torch.is_tensor(t) else type(t)}")
+    for name, t in (("v_shaped", v_shaped), ("joints", joints), ("weights", weights), ("posedirs", posedirs)):
+        if t is not None and (t.dtype != torch.float32 or t.device != dev or not t.is_contiguous()):
+            raise ValueError(f"body_pose: {name} must be a contiguous float32 tensor on {dev}, got {t.dtype} on {t.device}")
+    if poses.numel() % 72:
+        raise ValueError(f"body_pose: poses must be [P,24,3], got {tuple(poses.shape)}")
+    poses = _f32(poses, dev).reshape(-1, 24, 3)
+    P = poses.shape[0]
+    if Rh is not None:
+        Rh = _f32(Rh, dev).reshape(-1, 3)
+    if Th is not None:
+        Th = _f32(Th, dev).reshape(-1, 3)
+    if any(t is not None and t.shape[0] != P for t in (Rh, Th)):
+        raise ValueError(f"body_pose: Rh / Th must have {P} rows like poses")
+    shapes = {"xyz": (P, V, 3), "xyz_smpl": (P, V, 3), "A": (P, 24, 4, 4), "bounds": (P, 2, 3), "Rh_mat": (P, 3, 3)}
+    out = {k: _output(shapes[k], torch.float32, dev) for k in BODY_OUTPUTS if k == "xyz" or k in want}
+    nbytes = lib().dsn_body_pose_workspace_bytes(V, P)
+    if P and nbytes == 0:
+        raise RuntimeError(f"dsn_body_pose: bad sizes (V = {V}, P = {P})")
+    if P and (workspace is None or workspace.numel() < nbytes):
+        workspace = _scratch(nbytes, dev)
+    o = lambda k: _ptr(out[k]) if (k in out and P) else None      # noqa: E731
+    _check(lib().dsn_body_pose(_ptr(v_shaped, torch.float32), _ptr(joints, torch.float32), parents, _ptr(weights, torch.float32),
+                               _ptr(posedirs), V, _ptr(poses) if P else None, _ptr(Rh), _ptr(Th), P, BODY_PADS[pad], o("xyz"), o("xyz_smpl"),
+                               o("A"), o("bounds"), o("Rh_mat"), _ptr(workspace) if P else None, nbytes, _stream()), "dsn_body_pose")
+    return out
 
 
 def mesh_stretch(bind_verts, posed_verts, faces):

@@ -1462,6 +1462,53 @@ class Renderer:
         pick = (lambda t: None if t is None else t[0]) if single else (lambda t: t)
         return {"verts": pick(o["verts"]), "normals": pick(o["normals"]), "stretch": pick(st), "faces": binding["faces"]}
 
+    # ---- a motion clip without new_vertices/: the posed bodies and their view batches made on the device ----
+    @torch.no_grad()
+    def pose_body(self, model, poses, Rh=None, Th=None, pad="zju_eval"):
+        """The posed bodies of a clip from its SMPL parameters (body.BodyModel.pose, dsn_body_pose): poses [P,24,3] or [P,72], Rh / Th
+        [P,3] or None -> device tensors {"xyz" [P,V,3], "A" [P,24,4,4], "bounds" [P,2,3] (pad: "zju_eval" as the test split pads them,
+        "zju_train", "h36m" or None), "Rh_mat" [P,3,3]} plus the inputs as given, on the device: "poses" [P,24,3], "Th" [P,3] (zeros
+        without Th).  xyz[k][None] is a valid batch["xyz"], xyz a valid `targets` of pose_mesh / render_mesh_sequence, A[k] the
+        joint_transforms of lbs_warp; view_batch() makes the whole batch of pose k."""
+        if model.V != self.scene.V:
+            raise ValueError(f"pose_body: the body model has {model.V} vertices, the renderer's body has {self.scene.V}")
+        out = model.pose(poses, Rh=Rh, Th=Th, pad=pad, want=("xyz", "A", "bounds", "Rh_mat"))
+        P = out["xyz"].shape[0]
+        dev = out["xyz"].device
+        out["poses"] = torch.as_tensor(poses).to(device=dev, dtype=torch.float32).reshape(P, 24, 3).contiguous()
+        out["Th"] = (torch.zeros(P, 3, device=dev) if Th is None
+                     else torch.as_tensor(Th).to(device=dev, dtype=torch.float32).reshape(P, 3).contiguous())
+        return out
+
+    @torch.no_grad()
+    def view_batch(self, posed, k, K, R, T, H, W, poses=None, frame=0, convention="zju", **extra):
+        """The batch render_view / render_views take for pose k of pose_body()'s result, seen by the camera K, R [3,3], T [3]: "xyz",
+        "poses", "frame", "Th", "Rh", "bounds" of that pose, the rays of the H x W image against its bounds ("ray_o", "ray_d", "near",
+        "far": the rays that meet the box, as the test split hands them over; "mask_at_box" [1,H*W]; _lib.camera_rays, convention "zju"
+        or "h36m") and a zero "img" [1,H,W,3] for the image shape - everything on the device, nothing copied to the host.  The one
+        wait is for the NUMBER of rays that meet the box, which sizes the compacted arrays (the frame's workspaces are sized from it
+        on the host as well).  `poses`: the clip's [P,24,3] / [P,72] or pose k's own [24,3]; None: posed["poses"].  The use_x_pose edit
+        of the pose the pose MLP sees (zju_mocap_dataset.py:76-78: poses[1,2] -= 0.6, poses[2,2] += 0.6) is the caller's, as it is
+        with the datasets' batches: hand the edited poses over here.  `extra` entries are added as given."""
+        k = int(k)
+        P = posed["xyz"].shape[0]
+        if not 0 <= k < P:
+            raise IndexError(f"view_batch: pose {k} of {P}")
+        dev = posed["xyz"].device
+        bounds = posed["bounds"][k]
+        ray_o, ray_d, near, far, mask = _lib.camera_rays(K, R, T, bounds, int(H), int(W), device=dev, convention=convention)
+        poses = posed["poses"] if poses is None else torch.as_tensor(poses).to(device=dev, dtype=torch.float32)
+        poses = poses.reshape(-1, 24, 3)
+        pose = poses[0] if poses.shape[0] == 1 else poses[k]
+        idx = mask.nonzero().reshape(-1)          # the one wait: its length comes to the host; the four gathers below need none
+        ray_o, ray_d, near, far = (t.index_select(0, idx) for t in (ray_o, ray_d, near, far))
+        batch = {"xyz": posed["xyz"][k][None], "poses": pose[None].contiguous(), "frame": torch.tensor([int(frame)]),
+                 "Th": posed["Th"][k].reshape(1, 1, 3), "Rh": posed["Rh_mat"][k][None], "bounds": bounds[None],
+                 "ray_o": ray_o[None], "ray_d": ray_d[None], "near": near[None], "far": far[None],
+                 "mask_at_box": mask[None], "img": torch.zeros(1, int(H), int(W), 3, device=dev)}
+        batch.update(extra)
+        return batch
+
     # ---- density query for marching cubes (reference :280-296) ----
     def query_volume(self, pts, code_idx, transparent_mask=None, batch_info={}):
         """batch_info needs only 'poses' (the density-only branch of the reference, model/spacenet.py:223-241)."""

@@ -1743,6 +1743,45 @@ int dsn_mesh_stretch(const float* bind_verts, const float* posed_verts, int P, i
     return dsn_check_launch("dsn_mesh_stretch");
 }
 
+// the body model: vertex counts whose [P, V, 3] byte sizes fit size_t, pose counts whose pose blocks fit the launch grid's y axis
+static bool dsn_body_sizes_ok(int64_t V, int64_t P) {
+    return V >= 1 && V <= ((int64_t)1 << 28) && P >= 0 && P <= ((int64_t)1 << 18) && (P == 0 || (uint64_t)V <= (uint64_t)SIZE_MAX / 12 / (uint64_t)P);
+}
+
+int dsn_body_shape(const float* v_template, const float* shapedirs, const float* betas, int B, const float* J_regressor, int V,
+                   float* v_shaped, float* joints, void* stream) {
+    DSN_REQUIRE(dsn_body_sizes_ok(V, 1), "dsn_body_shape: bad V");
+    DSN_REQUIRE(B >= 0 && B <= 4096, "dsn_body_shape: bad B");
+    DSN_REQUIRE(v_template && v_shaped, "dsn_body_shape: null v_template or v_shaped");
+    DSN_REQUIRE(B == 0 || ((shapedirs == nullptr) == (betas == nullptr)), "dsn_body_shape: shapedirs and betas go together");
+    DSN_REQUIRE((joints == nullptr) == (J_regressor == nullptr), "dsn_body_shape: joints and J_regressor go together");
+    dsn_launch_body_shape(v_template, shapedirs, betas, B, J_regressor, V, v_shaped, joints, (hipStream_t)stream);
+    return dsn_check_launch("dsn_body_shape");
+}
+
+size_t dsn_body_pose_workspace_bytes(int V, int P) {
+    return (dsn_body_sizes_ok(V, P) && P >= 1) ? dsn_body_pose_workspace_size(V, P) : 0;
+}
+
+int dsn_body_pose(const float* v_shaped, const float* joints, const int32_t* parents_host, const float* weights, const float* posedirs, int V,
+                  const float* poses, const float* Rh, const float* Th, int P, int pad_mode, float* xyz, float* xyz_smpl, float* A,
+                  float* bounds, float* Rh_mat, void* workspace, size_t workspace_bytes, void* stream) {
+    DSN_REQUIRE(V >= 1, "dsn_body_pose: V must be at least 1");
+    DSN_REQUIRE(P >= 0, "dsn_body_pose: negative pose count");
+    DSN_REQUIRE(dsn_body_sizes_ok(V, P), "dsn_body_pose: counts too large");
+    DSN_REQUIRE(pad_mode >= DSN_BODY_PAD_NONE && pad_mode <= DSN_BODY_PAD_H36M, "dsn_body_pose: unknown pad_mode");
+    DSN_REQUIRE(v_shaped && joints && parents_host && weights, "dsn_body_pose: null body model argument");
+    for (int i = 1; i < 24; ++i)
+        if (parents_host[i] < 0 || parents_host[i] >= i) return dsn_fail("dsn_body_pose: parents[%s%lld] is not an earlier joint", "", i);
+    if (P == 0) return 0;      // an empty clip: nothing to write, no launch
+    DSN_REQUIRE(poses && xyz, "dsn_body_pose: null poses or xyz");
+    DSN_REQUIRE(workspace && ((uintptr_t)workspace & 255) == 0, "dsn_body_pose: workspace must be 256-byte aligned (null)");
+    DSN_REQUIRE(workspace_bytes >= dsn_body_pose_workspace_size(V, P), "dsn_body_pose: workspace too small (dsn_body_pose_workspace_bytes)");
+    dsn_launch_body_pose(v_shaped, joints, parents_host, weights, posedirs, V, poses, Rh, Th, P, pad_mode, xyz, xyz_smpl, A, bounds, Rh_mat,
+                         workspace, (hipStream_t)stream);
+    return dsn_check_launch("dsn_body_pose");
+}
+
 static bool dsn_raster_sizes_ok(int64_t V, int64_t T, int H, int W) {
     return V >= 0 && T >= 0 && V < ((int64_t)1 << 31) && T < ((int64_t)1 << 31) && H >= 1 && H <= 16384 && W >= 1 && W <= 16384;
 }

@@ -266,6 +266,13 @@ void dsn_launch_mesh_pose(const float* target, int P, int Vb, const int32_t* bfa
                           hipStream_t st);
 void dsn_launch_mesh_stretch(const float* bind, const float* posed, int P, int64_t N, const int32_t* faces, int64_t T, float* stretch,
                              hipStream_t st);
+// dsn_body.hip: the SMPL forward pass (dsn_body_shape / dsn_body_pose; parents24: host memory, entries 1..23 already checked)
+size_t dsn_body_pose_workspace_size(int V, int P);
+void dsn_launch_body_shape(const float* v_template, const float* shapedirs, const float* betas, int B, const float* J_regressor, int V,
+                           float* v_shaped, float* joints, hipStream_t st);
+void dsn_launch_body_pose(const float* v_shaped, const float* joints, const int* parents24, const float* weights, const float* posedirs, int V,
+                          const float* poses, const float* Rh, const float* Th, int P, int pad_mode, float* xyz, float* xyz_smpl, float* A,
+                          float* bounds, float* Rh_mat, void* workspace, hipStream_t st);
 // dsn_raster.hip: the mesh preview (dsn_raster_mesh)
 size_t dsn_raster_workspace_size(int64_t V, int64_t T, int H, int W);
 void dsn_launch_raster_mesh(const float* verts, int64_t V, const int32_t* faces, int64_t T, const float* pose12, float fx, float fy,

@@ -1029,6 +1029,59 @@ DSN_EXPORT int dsn_mesh_pose(const float* target_xyz, int P, int Vb, const int32
 DSN_EXPORT int dsn_mesh_stretch(const float* bind_verts, const float* posed_verts, int P, int64_t N, const int32_t* faces, int64_t T,
                                 float* stretch, void* stream);
 
+/* ---- the body model: SMPL parameters -> posed vertices for a whole clip (an addition within ABI 8: no existing entry point changes) ------
+ * The reference reads the posed body's vertices from new_vertices/{i}.npy (tool/generate_novelpose_vertices.py writes them off-line with
+ * EasyMocap's SMPL layer) and the Human3.6M datasets run utils/h36m_utils.get_rigid_transformation and get_bounds per item.  These two
+ * calls make the same arrays on the device, P poses at a time: batch["xyz"], the datasets' pxyz, the joint_transforms of dsn_lbs_warp and
+ * the bounds of dsn_camera_rays.  24 joints, as everywhere in this header.  The rule is fixed so that a numpy restatement
+ * (tests/body_pose_restate.py) reproduces every output bit for bit, up to the float64 sin / cos / sqrt of the two platforms.
+ * Parentheses give the order of operations; nothing is fused; "sum from 0" is s = 0, s = s + term in ascending index order.
+ *   Shape (dsn_body_shape, float32): v_shaped[v,c] = v_template[v,c] + (sum from 0 over b of shapedirs[v,c,b] betas[b]); with shapedirs
+ *             or betas NULL or B = 0: v_shaped = v_template.  joints[j,c] = sum from 0 over v of J_regressor[j,v] v_shaped[v,c] (dense
+ *             regressor [24, V]; J_regressor and joints NULL together: the caller has the joints, the datasets ship joints.npy).
+ *   Joint chain (float64 from the float32 inputs; utils/h36m_utils.py:210-264 batch_rodrigues + get_rigid_transformation, operation for
+ *             operation):  per joint p = poses[j]:  q = p + 1e-8;  angle = sqrt((q0 q0 + q1 q1) + q2 q2);  r = p / angle;
+ *             K = [0 -r2 r1; r2 0 -r0; -r1 r0 0];  (K K)_ij = (K_i0 K_0j + K_i1 K_1j) + K_i2 K_2j;
+ *             R = (I + sin(angle) K) + (1 - cos(angle)) (K K).
+ *             T_j = [R_j | t_j; 0 0 0 1] with t_0 = joints[0], t_j = joints[j] - joints[parents[j]];  G_0 = T_0,
+ *             G_j = G_parents[j] T_j, every element ((a_r0 b_0c + a_r1 b_1c) + a_r2 b_2c) + a_r3 b_3c, all four rows;
+ *             rel_r = ((G_r0 J_0 + G_r1 J_1) + G_r2 J_2) + G_r3 0 with J = joints[j];  A_j = G_j with column 3 replaced by G_r3 - rel_r
+ *             (A = G [I | -J]), rounded to float32 once.  Rh_mat = the same R of Rh, rounded to float32 (Rh NULL: the identity).
+ *   Pose feature: pf[9 (j - 1) + 3 r + c] = float32(R_j[r,c] - (r == c)), j = 1..23: 207 values.
+ *   Vertex work (float32): v_posed[v,c] = v_shaped[v,c] + (sum from 0 over k = 0..206 of pf[k] posedirs[k, 3 v + c]) (posedirs NULL:
+ *             v_posed = v_shaped);  T[e] = sum from 0 over j = 0..23 of weights[v,j] A_j[e], e over the 12 elements of rows 0-2;
+ *             xyz_smpl_r = ((T_r0 v_0 + T_r1 v_1) + T_r2 v_2) + T_r3;   xyz_r = ((Rh_mat_r0 s_0 + Rh_mat_r1 s_1) + Rh_mat_r2 s_2) + Th_r
+ *             with s = xyz_smpl (EasyMocap's vertices @ R.T + Th, the inverse of h36m_dataset.py:113; Th NULL: zeros).
+ *   Bounds:   per pose and axis the exact minimum and maximum of xyz under the total order of the values with -0 below +0; an axis
+ *             with a NaN coordinate anywhere in the pose: NaN for both.  Then the float32 padding of the datasets:
+ *             DSN_BODY_PAD_ZJU_TRAIN min - 0.1f, max + 0.1f (zju_mocap_dataset.py:60-62); DSN_BODY_PAD_ZJU_EVAL z only, 0.05f (:64-65);
+ *             DSN_BODY_PAD_H36M all axes, 0.05f (h36m_utils.py:372-379); DSN_BODY_PAD_NONE nothing.
+ *   NaN:      nothing is patched.  A NaN in one pose's parameters reaches that pose's outputs only: no sum runs across poses.
+ * dsn_body_shape: v_template [V,3], shapedirs [V,3,B], betas [B], J_regressor [24,V] -> v_shaped [V,3], joints [24,3] (all device).
+ * dsn_body_pose: v_shaped [V,3], joints [24,3], weights [V,24], posedirs [207, 3V] or NULL, poses [P,24,3], Rh [P,3] or NULL, Th [P,3]
+ * or NULL (device); parents_host: 24 int32 in HOST memory (the kinematic tree; entry 0 is ignored), read before the call returns.
+ * Outputs (device; any but xyz may be NULL): xyz [P,V,3], xyz_smpl [P,V,3], A [P,24,4,4] row-major, bounds [P,2,3], Rh_mat [P,3,3].
+ * workspace: dsn_body_pose_workspace_bytes(V, P) bytes (0 for bad sizes and for P = 0), 256-byte aligned, earlier contents not read;
+ * after the call it begins with the pose features the call used, [P][208] float32 (207 and a zero), for whoever wants to look.
+ * Three launches: the chain (one wave per pose), the vertex work (256 vertices x 8 poses per workgroup: a posedirs element is loaded
+ * once per 8 poses), the bounds' final pass.  No atomics, one writer per output word, no sum whose order depends on the launch: P poses
+ * in one call give the bits of P calls of one, wherever a pose sits in the call, and every call returns the same bits.
+ * P = 0 is a valid call that launches nothing (poses, outputs and workspace may be NULL).  Rejected: V < 1, P < 0, V > 2^28, P > 2^18,
+ * an unknown pad_mode, a parents_host[i] outside [0, i) for i >= 1, null required pointers, a small or misaligned workspace; for
+ * dsn_body_shape B < 0 or > 4096, shapedirs without betas, joints without J_regressor or the reverse.  No allocation, no
+ * synchronisation, all on `stream`. */
+#define DSN_BODY_PAD_NONE 0
+#define DSN_BODY_PAD_ZJU_TRAIN 1
+#define DSN_BODY_PAD_ZJU_EVAL 2
+#define DSN_BODY_PAD_H36M 3
+DSN_EXPORT int dsn_body_shape(const float* v_template, const float* shapedirs, const float* betas, int B, const float* J_regressor, int V,
+                              float* v_shaped, float* joints, void* stream);
+DSN_EXPORT size_t dsn_body_pose_workspace_bytes(int V, int P);
+DSN_EXPORT int dsn_body_pose(const float* v_shaped, const float* joints, const int32_t* parents_host, const float* weights,
+                             const float* posedirs, int V, const float* poses, const float* Rh, const float* Th, int P, int pad_mode,
+                             float* xyz, float* xyz_smpl, float* A, float* bounds, float* Rh_mat, void* workspace, size_t workspace_bytes,
+                             void* stream);
+
 /* ---- mesh preview (an addition within ABI 8: no existing entry point changes) -------------------------------------------------------
  * utils/visualizer.py:144-168 Visualizer3D.render_mesh (pyrender: PerspectiveCamera(yfov = pi/3, aspect 1), a SpotLight of intensity 30
  * with cone angles pi/16 and pi/6 at the camera's pose, white background, no ambient light): a deterministic triangle rasteriser with
