@@ -56,7 +56,7 @@ EXPORTS = [
     "dsn_train_loss_workspace_bytes", "dsn_train_loss", "dsn_train_loss_grad",
     "dsn_grid_hier_workspace_bytes", "dsn_grid_hier_mark", "dsn_grid_hier_list", "dsn_grid_hier_assemble",
     "dsn_density_points_workspace_bytes", "dsn_density_points",
-    "dsn_adam_step", "dsn_adam_scalars_host",
+    "dsn_adam_step", "dsn_adam_scalars_host", "dsn_train_draws",
     "dsn_body_shape", "dsn_body_pose_workspace_bytes", "dsn_body_pose",
 ]
 
@@ -187,6 +187,7 @@ def lib():
                                          C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p]
         L.dsn_adam_step.argtypes = [C.c_void_p] * 5 + [C.c_int, C.c_void_p, C.c_void_p] + [C.c_double] * 4 + [C.c_void_p, C.c_void_p]
         L.dsn_adam_scalars_host.argtypes = [C.c_double] * 6 + [C.c_void_p]
+        L.dsn_train_draws.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_int, C.c_int, C.c_float] + [C.c_void_p] * 3
         L.dsn_body_shape.argtypes = [C.c_void_p] * 3 + [C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 3
         L.dsn_body_pose_workspace_bytes.restype = C.c_size_t
         L.dsn_body_pose_workspace_bytes.argtypes = [C.c_int, C.c_int]
@@ -2306,6 +2307,47 @@ def adam_step(params, grads, exp_avgs, exp_avg_sqs, lrs, weight_decays, betas, e
         _check(lib().dsn_adam_step(arr[0], arr[1], arr[2], arr[3], (C.c_int64 * count)(*ns), count, (C.c_double * count)(*lrs),
                                    (C.c_double * count)(*weight_decays), float(betas[0]), float(betas[1]), float(eps), float(step),
                                    None if packed is None else _ptr(packed.buf), _stream()), "dsn_adam_step")
+
+
+def train_draws(R, S, seed, step, ray_base=0, ray_ids=None, noise_std=1.0, want_jitter=True, want_noise=True, out=None, device=None):
+    """The training step's stratified jitter and density noise drawn on the device (dsn_train_draws, the rule of include/dsnerf.h):
+    (jitter, noise), float32 [R, S] device tensors, None for the one not wanted.  A value is a pure function of (seed, step, ray id,
+    sample, kind): seed is taken modulo 2^64, step and ray_base modulo 2^32; ray_ids: int32 [R] on the device (ray r's id) instead
+    of ray_base + r.  noise = the unit draw times noise_std in float32.  out = (jitter, noise): float32 [R, S] device tensors to
+    fill instead of fresh ones (contiguous; a view at any 4-byte offset will do), None where not wanted.  One launch on the current
+    stream; nothing is allocated on the host, copied or read back."""
+    require_gpu()
+    R, S = int(R), int(S)
+    if R < 0 or S < 0:
+        raise ValueError("train_draws: R and S must not be negative")
+    if ray_ids is not None:
+        if not (torch.is_tensor(ray_ids) and ray_ids.is_cuda and ray_ids.dtype == torch.int32 and ray_ids.is_contiguous()
+                and ray_ids.numel() == R):
+            raise ValueError("train_draws: ray_ids must be a contiguous int32 device tensor with one id per ray")
+        dev = ray_ids.device
+    else:
+        dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    given = (None, None) if out is None else tuple(out)
+    arrays = []
+    for name, want, t in (("jitter", want_jitter, given[0]), ("noise", want_noise, given[1])):
+        if not want:
+            arrays.append(None)
+        elif t is None:
+            arrays.append(_output((R, S), torch.float32, dev))
+        else:
+            if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (R, S)):
+                raise ValueError(f"train_draws: out's {name} must be a contiguous float32 device tensor [{R}, {S}]")
+            dev = t.device if ray_ids is None else dev
+            arrays.append(t)
+    if any(a is not None and a.device != dev for a in arrays):
+        raise ValueError("train_draws: ray_ids and the outputs must live on one device")
+    if arrays[0] is None and arrays[1] is None:
+        raise ValueError("train_draws: neither jitter nor noise is wanted")
+    with torch.cuda.device(dev):
+        _check(lib().dsn_train_draws(int(seed) & 0xFFFFFFFFFFFFFFFF, int(step) & 0xFFFFFFFF, int(ray_base) & 0xFFFFFFFF,
+                                     _ptr(ray_ids) if R else None, R, S, float(noise_std), _ptr(arrays[0]) if R * S else None,
+                                     _ptr(arrays[1]) if R * S else None, _stream()), "dsn_train_draws")
+    return arrays[0], arrays[1]
 
 
 def camera_rays(K, R, T, bounds, H, W, device=None, convention="zju"):

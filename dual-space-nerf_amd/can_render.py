@@ -238,6 +238,14 @@ class Renderer:
         # awaited (_HostPoolGuard; None = leave the pool alone); and for good at the cgroup's CPU quota (_lib.fit_host_pool: a pool
         # larger than the quota gets the whole process frozen by the kernel's bandwidth control whenever the caller runs a torch op)
         self.host_pool_limit = 8
+        # train mode: where the stratified jitter and the density noise come from.  "host" (default): the CPU default generator in the
+        # reference's order (_draws) - the reference's stream, which pins train-mode outputs to its own.  "device": dsn_train_draws, a
+        # pure function of (seed, step, ray id, sample, kind) - not the reference's values, but independent of every other torch.rand
+        # call, of the order of the rays and of the rank that holds them, and repeatable from draw_state() alone (seed_draws).
+        self.draws = "host"
+        self._draw_seed = 0
+        self._draw_step = 0
+        self.last_draws = None            # (jitter, noise) of the last train-mode render call (tests read them)
         if host_pool not in ("fit", "keep"):
             raise ValueError('host_pool must be "fit" or "keep"')
         self.host_pool = _lib.fit_host_pool(keep=(host_pool == "keep"))
@@ -416,6 +424,45 @@ class Renderer:
         noise = slot["dev"][k:k + R * S].view(R, S).clone() if want_n else None
         return jitter, noise
 
+    # ---- draws="device": the same two arrays from dsn_train_draws (the rule of include/dsnerf.h) ----
+    def seed_draws(self, seed, step=0):
+        """seed (taken modulo 2^64) and step counter (modulo 2^32) of the device draws: every train-mode render call with
+        draws == "device" draws at the current step and then advances it by one"""
+        self._draw_seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        self._draw_step = int(step) & 0xFFFFFFFF
+        return self
+
+    def draw_state(self):
+        """what a checkpoint keeps of the device draws: the next train-mode render call draws at this step"""
+        return {"seed": self._draw_seed, "step": self._draw_step}
+
+    def load_draw_state(self, d):
+        return self.seed_draws(d["seed"], d["step"])
+
+    def _draw_source(self):
+        if self.draws not in ("host", "device"):
+            raise ValueError('Renderer.draws must be "host" or "device"')
+        return self.draws
+
+    def _device_draws(self, R, S, batch=None, want_jitter=True, want_noise=True):
+        """_draws' two arrays at the current step, without advancing it.  The rays' ids: batch["ray_ids"] ([1, R] or [R], int32 or
+        int64, on the device - e.g. coord[:, 0] * W + coord[:, 1] of sample_batch), else batch["ray_base"] + r (an int - e.g. a
+        rank's offset), else r.  One launch: no pinned memory, no copy from the host, nothing read back."""
+        want_j = want_jitter and self.net.training and self.cfg.MODEL.perturb > 0.0
+        want_n = want_noise and self.net.training and self.cfg.MODEL.raw_noise_std > 0.0
+        if not (want_j or want_n):
+            return None, None
+        ids, base = None, 0
+        if batch is not None and batch.get("ray_ids") is not None:
+            ids = batch["ray_ids"]
+            if not (torch.is_tensor(ids) and ids.is_cuda and ids.dtype in (torch.int32, torch.int64) and ids.numel() == R):
+                raise ValueError("batch['ray_ids'] must be an int32 or int64 device tensor with one id per ray")
+            ids = ids.reshape(R).to(torch.int32).contiguous()          # (int64 ids: modulo 2^32, as the rule takes them)
+        elif batch is not None and batch.get("ray_base") is not None:
+            base = int(batch["ray_base"])
+        return _lib.train_draws(R, S, self._draw_seed, self._draw_step, ray_base=base, ray_ids=ids,
+                                noise_std=float(self.cfg.MODEL.raw_noise_std), want_jitter=want_j, want_noise=want_n, device=self.device)
+
     # ---- sampling (reference :40-63) ----
     def get_sampling_points(self, ray_o, ray_d, near, far, xyz, mode="GG"):
         """ray_o/ray_d [1,R,3], near/far [1,R] (updated in place in GG mode), xyz [1,V,3] ->
@@ -426,7 +473,9 @@ class Renderer:
         o, d = self._dev(ray_o[0]), self._dev(ray_d[0])
         n_dev, f_dev = self._dev(near[0]), self._dev(far[0])
         jitter = None
-        if self.net.training and self.cfg.MODEL.perturb > 0.0:
+        if self._draw_source() == "device":      # the rule's jitter at the current step (render() advances it, this does not)
+            jitter = self._device_draws(R, S, want_noise=False)[0]
+        elif self.net.training and self.cfg.MODEL.perturb > 0.0:
             jitter = torch.rand(1, R, S).reshape(R, S).to(self.device)
         if not self._is_frame_src(xyz):
             self._upload_xyz(xyz)
@@ -500,7 +549,9 @@ class Renderer:
         rays_d = rays[:, 0, :3].contiguous()
         B, sp = pts.shape[:2]
         noise = None
-        if self.net.training and self.cfg.MODEL.raw_noise_std > 0.0:
+        if self._draw_source() == "device":      # the rule's noise at the current step, not advanced (as get_sampling_points' jitter)
+            noise = self._device_draws(B, sp, batch_info, want_jitter=False)[1]
+        elif self.net.training and self.cfg.MODEL.raw_noise_std > 0.0:
             noise = (torch.randn(B, sp) * self.cfg.MODEL.raw_noise_std).to(self.device)
         bi = self._module_info(batch_info or {}, frame_idx)
         with torch.no_grad():
@@ -564,7 +615,13 @@ class Renderer:
         # (lazily set for training too since round 6: the training forward builds the lists of the cells its batch visits, or - small
         #  batches - completes every cell's lists itself; `train_lazy_lists = False` keeps the per-step build of every cell in set_frame)
         frame_args = self._set_frame(batch, lazy=(not differentiable) or self.train_lazy_lists)
-        jitter, noise = self._draws(R, S)
+        if self._draw_source() == "device" and self.net.training:
+            jitter, noise = self._device_draws(R, S, batch)
+            self._draw_step = (self._draw_step + 1) & 0xFFFFFFFF
+        else:
+            jitter, noise = self._draws(R, S)
+        if self.net.training:
+            self.last_draws = (jitter, noise)
         if self.sample_points_mode not in ("GG", "uniform"):
             raise Exception("error")   # the reference fails on unknown modes too (get_sampling_points returns nothing)
         uniform = self.sample_points_mode == "uniform"

@@ -4,6 +4,7 @@
 #include "../../include/dsnerf.h"
 #include "dsn_common.h"
 #include "dsn_kernels.h"
+#include <climits>
 #include <cmath>
 #include <cstdlib>
 
@@ -444,6 +445,17 @@ int dsn_adam_step(float* const* params_host, const float* const* grads_host, flo
         dsn_launch_set_packed_scalar((float*)packed, 6, 1.0f, st);
     }
     return dsn_check_launch("dsn_adam_step");
+}
+
+int dsn_train_draws(uint64_t seed, uint32_t step, uint32_t ray_base, const int32_t* ray_ids, int R, int S, float noise_std, float* jitter,
+                    float* noise, void* stream) {
+    DSN_REQUIRE(R >= 0 && S >= 0, "dsn_train_draws: R and S must not be negative");
+    DSN_REQUIRE((int64_t)R * S <= (int64_t)INT_MAX, "dsn_train_draws: R * S must not exceed INT_MAX");
+    DSN_REQUIRE((((uintptr_t)ray_ids | (uintptr_t)jitter | (uintptr_t)noise) & 3) == 0, "dsn_train_draws: a pointer is not 4-byte aligned");
+    if (R == 0 || S == 0) return 0;
+    DSN_REQUIRE(jitter || noise, "dsn_train_draws: jitter and noise are both null");
+    dsn_launch_train_draws(seed, step, ray_base, ray_ids, R, S, noise_std, jitter, noise, (hipStream_t)stream);
+    return dsn_check_launch("dsn_train_draws");
 }
 
 int dsn_field_screen(const void* scene, int V, int F, const void* packed, const float* x_c, int64_t N, const int32_t* active_list,

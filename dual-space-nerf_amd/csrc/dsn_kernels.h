@@ -217,6 +217,9 @@ void dsn_adam_scalars(double lr, double weight_decay, double beta1, double beta2
 int dsn_launch_adam_step(float* const* params, const float* const* grads, float* const* exp_avgs, float* const* exp_avg_sqs,
                          const int64_t* n, int count, const double* lr, const double* weight_decay, double beta1, double beta2, double eps,
                          double t, hipStream_t st);
+// dsn_rng.hip: the training step's jitter and noise (dsn_train_draws; R, S > 0, R * S <= INT_MAX, not both arrays null)
+void dsn_launch_train_draws(uint64_t seed, uint32_t step, uint32_t ray_base, const int32_t* ray_ids, int R, int S, float noise_std,
+                            float* jitter, float* noise, hipStream_t st);
 // dsn_mesh.hip: density grid points and marching cubes (dsn_density_grid, dsn_mc_*)
 void dsn_launch_grid_points(const float* x, const float* y, const float* z, int i0, int ny, int nz, int64_t n, float* pts, hipStream_t st);
 size_t dsn_mc_workspace_size(int64_t N);

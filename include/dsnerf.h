@@ -356,6 +356,42 @@ DSN_EXPORT int dsn_adam_step(float* const* params_host, const float* const* grad
 /* the rule's host scalars (no device work): out7_host = {w1, w2, b2, e, wd, ss, c2} */
 DSN_EXPORT int dsn_adam_scalars_host(double lr, double weight_decay, double beta1, double beta2, double eps, double t, float* out7_host);
 
+/* ---- the training step's random draws on the device (an addition within ABI 8: no existing entry point changes) ----------------------
+ * can_render.py draws the stratified jitter (utils/pts_utils.py:12, torch.rand(1, R, S)) and the density noise
+ * (utils/nerf_net_utils.py:31, torch.randn(R, S) * raw_noise_std) from the CPU default generator.  dsn_train_draws fills both arrays
+ * in one launch from a counter-based generator: a draw is a pure function of (seed, step, ray id, sample, kind) - no generator state,
+ * no host memory, no copy - so it does not depend on what else drew random numbers, on the order of the rays or on the rank that
+ * holds a ray, and a resumed run repeats it from (seed, step) alone.  It is NOT the reference's stream: the values differ from
+ * torch.rand / torch.randn's for every seed.
+ * The rule.
+ *   Generator: Philox4x32 with 10 rounds, multipliers M0 = 0xD2511F53, M1 = 0xCD9E8D57, key increments 0x9E3779B9, 0xBB67AE85.  One
+ *   round maps the counter (c0, c1, c2, c3) under the key (k0, k1) to
+ *       (hi(M1 c2) ^ c1 ^ k0,  lo(M1 c2),  hi(M0 c0) ^ c3 ^ k1,  lo(M0 c0))          hi / lo: the halves of the 64-bit product
+ *   and then adds the increments to (k0, k1); the output is the counter after the tenth round.  Known answers (counter, key -> output):
+ *       00000000 x 4, 00000000 x 2                                   -> 6627e8d5 e169c58d bc57ac4c 9b00dbd8
+ *       ffffffff x 4, ffffffff x 2                                   -> 408f276d 41c83b0e a20bc7c6 6d5451fd
+ *       243f6a88 85a308d3 13198a2e 03707344, a4093822 299f31d0       -> d16cfe09 94fdcceb 5001e420 24126ea1
+ *   Addressing: key = (seed's low 32 bits, seed's high 32 bits); counter = (q, ray id, step, kind) with q = s / 4 the quad of samples
+ *   along the ray, ray id = (uint32)ray_ids[r] where ray_ids is given, else ray_base + r modulo 2^32, kind = 0 for the jitter and 1
+ *   for the noise.  The output words x0 .. x3 belong to the samples 4 q .. 4 q + 3; words past S are dropped.  A row therefore depends
+ *   on its ray id only, and the first S columns are the same for every S.
+ *   Jitter: u = (x >> 8) 2^-24 as float32 - exact, in [0, 1 - 2^-24], on torch.rand's float32 lattice.
+ *   Noise: Box-Muller in float64 on the word pairs (x0, x1) and (x2, x3):
+ *       u1 = (x0 + 1) 2^-32  (in (0, 1], exact),   u2 = x1 2^-32  (exact),   r = sqrt(-2 log(u1)),   t = 6.283185307179586 u2,
+ *       z0 = r cos(t),   z1 = r sin(t)               one float64 rounding per operation, nothing fused,
+ *   each z rounded to float32 once and then multiplied in float32 by noise_std (what the host path's mul_ does; noise_std = 0 leaves
+ *   zeros that carry z's sign).  |z| <= sqrt(64 ln 2) = 6.66: with a finite noise_std nothing is NaN or infinite.  log, cos and sin are the
+ *   device library's float64 functions: against another correct libm a float32 result can differ by one ulp where the float64 value
+ *   falls next to a float32 rounding boundary (of the order of 1e-8 of the values); everything else is exact (tests/draws_restate.py).
+ *   jitter, noise: float32 [R, S], either may be NULL (not drawn); 4-byte alignment is enough (a view into a larger buffer).
+ *   ray_ids: int32 [R] or NULL.
+ * Kernel: a thread owns one (ray, quad); 16-byte stores where S % 4 == 0 and the array is 16-byte aligned, scalar stores otherwise
+ * (decided per array).  One writer per word, no atomics, no workspace, no synchronisation, all on `stream`.
+ * R == 0 or S == 0: success, nothing is enqueued.  Rejected before anything is enqueued: R < 0, S < 0, R S > INT_MAX, a ray_ids, jitter
+ * or noise pointer off the 4-byte grid, and - with R S > 0 - jitter and noise both NULL. */
+DSN_EXPORT int dsn_train_draws(uint64_t seed, uint32_t step, uint32_t ray_base, const int32_t* ray_ids, int R, int S, float noise_std,
+                               float* jitter, float* noise, void* stream);
+
 /* The density screen as a stage (what dsn_render_rays runs first in eval mode): for the listed points (or all N) the
  * plain-fp16 trunk; points whose fp16 density is negative by the safety margin (calibrated for the parameters: dsn_calibrate_screen) get that negative value in sigma [N] and are dropped, the
  * others are appended to keep_list (keep_count zeroed by the caller) for dsn_field_forward. */
