@@ -58,6 +58,7 @@ EXPORTS = [
     "dsn_density_points_workspace_bytes", "dsn_density_points",
     "dsn_adam_step", "dsn_adam_scalars_host", "dsn_train_draws",
     "dsn_body_shape", "dsn_body_pose_workspace_bytes", "dsn_body_pose",
+    "dsn_grad_workspace_layout",
 ]
 
 SKIP_TRANSPARENT = 1
@@ -193,6 +194,7 @@ def lib():
         L.dsn_body_pose_workspace_bytes.argtypes = [C.c_int, C.c_int]
         L.dsn_body_pose.argtypes = ([C.c_void_p] * 5 + [C.c_int] + [C.c_void_p] * 3 + [C.c_int, C.c_int] + [C.c_void_p] * 6
                                     + [C.c_size_t, C.c_void_p])
+        L.dsn_grad_workspace_layout.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int]
         if L.dsn_abi_version() != 8:
             raise RuntimeError(f"{LIB_PATH} has ABI version {L.dsn_abi_version()}, this binding needs 8 - rebuild it "
                                "(python dual-space-nerf_amd/build.py)")
@@ -1999,12 +2001,50 @@ def grad_range_word(ws: "GradWorkspace", R, S):
     return ws.buf[off:off + 4].view(torch.int32)
 
 
+# the per-row arrays of the training workspace in the order of dsn_grad_workspace_layout (include/dsnerf.h: DSN_GRAD_WS_*):
+# (name, dtype, columns; 0 columns = [N])
+GRAD_WS_ARRAYS = [
+    ("transparent", torch.uint8, 0), ("x_c", torch.float32, 3), ("sig", torch.float32, 0), ("ess", torch.float32, 3),
+    ("g", torch.float32, 3), ("n_w", torch.float32, 3), ("xl", torch.float32, 9), ("hl1", torch.float32, 128),
+    ("hl2", torch.float32, 128), ("pre", torch.float32, 0), ("wl", torch.float32, 0), ("col", torch.float32, 3),
+    ("rr", torch.float32, 128), ("h6", torch.float32, 256),
+    ("d_sig", torch.float32, 0), ("d_col", torch.float32, 3), ("d_ess", torch.float32, 3), ("d_pre", torch.float32, 0),
+    ("d_hl2", torch.float32, 128), ("d_hl1", torch.float32, 128), ("d_xl", torch.float32, 9), ("d_rr", torch.float32, 128),
+    ("u", torch.float32, 3), ("list1", torch.int32, 0), ("list2", torch.int32, 0), ("rowcnt", torch.int32, 0),
+]
+
+
+def grad_workspace_layout(R, S):
+    """{array name: byte offset} of the training workspace of R x S samples, from the library's own carve (dsn_grad_workspace_layout)"""
+    off = (C.c_int64 * len(GRAD_WS_ARRAYS))()
+    _check(lib().dsn_grad_workspace_layout(int(R), int(S), off, len(GRAD_WS_ARRAYS)), "dsn_grad_workspace_layout")
+    return {name: int(o) for (name, _, _), o in zip(GRAD_WS_ARRAYS, off)}
+
+
+def grad_rows(ws: "GradWorkspace", R, S):
+    """(synchronises) clones of the per-row arrays the last dsn_render_rays_grad over R x S samples left in this workspace, as a dict
+    of device tensors: [N] or [N,k] by sample, `list1` / `list2` cut to their entries, `rowcnt` = the two counts.  Rows that are not on
+    the lists hold stale values.  For tests and diagnostics: nothing in the product reads it."""
+    N = int(R) * int(S)
+    off = grad_workspace_layout(R, S)
+    torch.cuda.synchronize(ws.buf.device)
+    out = {}
+    for name, dt, cols in GRAD_WS_ARRAYS:
+        rows = 2 if name == "rowcnt" else N
+        nbytes = rows * max(cols, 1) * torch.empty(0, dtype=dt).element_size()
+        t = ws.buf[off[name]:off[name] + nbytes].view(dt)
+        out[name] = (t.reshape(rows, cols) if cols else t).clone()
+    n1, n2 = (int(v) for v in out["rowcnt"].cpu())
+    out["list1"], out["list2"] = out["list1"][:n1], out["list2"][:n2]
+    torch.cuda.synchronize(ws.buf.device)
+    return out
+
+
 def grad_row_counts(ws: "GradWorkspace", R, S):
     """(synchronises) (rows the last training forward evaluated, rows its backward propagated) of R x S samples: the forward skips
     transparent samples whose noise is <= 0 (alpha = 0 exactly), the backward every row whose cotangents are all zero (dsn_train.hip,
-    Rows) - two int32 words in the 256 bytes in front of the workspace's last 4 KB"""
-    need = lib().dsn_grad_workspace_bytes(int(R), int(S))
-    off = need - 4096 - 256
+    Rows) - two int32 words of the workspace (dsn_grad_workspace_layout: rowcnt)"""
+    off = grad_workspace_layout(R, S)["rowcnt"]
     c = ws.buf[off:off + 8].view(torch.int32).cpu()
     return int(c[0]), int(c[1])
 

@@ -482,6 +482,14 @@ int dsn_debug_screen(const void* scene, int V, int F, const void* packed, const 
 
 size_t dsn_grad_workspace_bytes(int R, int S) { return (R > 0 && S > 0) ? dsn_train_workspace_size((int64_t)R * S) : 0; }
 
+// read-only view of the training workspace for tests and diagnostics (host function): see dsnerf.h
+int dsn_grad_workspace_layout(int R, int S, int64_t* out_offsets_host, int n) {
+    DSN_REQUIRE(out_offsets_host && R > 0 && S > 0, "dsn_grad_workspace_layout: bad argument");
+    DSN_REQUIRE(dsn_train_workspace_layout((int64_t)R * S, out_offsets_host, n) == 0,
+                "dsn_grad_workspace_layout: n is not DSN_GRAD_WS_COUNT");
+    return 0;
+}
+
 int dsn_render_rays_grad(const void* scene, int V, int F, const void* packed, const float* const* params33_host, const float* poses24x3,
                          int frame_idx, int zero_code, const float* ray_o, const float* ray_d, const float* z_vals,
                          const float* noise, int R, int S, const float* d_rgb, const float* d_disp, const float* d_acc,

@@ -166,6 +166,8 @@ void dsn_launch_light(const float* packed, const DsnFrameState* fs, const float*
 // dsn_train.hip: parameter gradients of Renderer.render / DualSpaceNeRF.forward (fused split-fp16 passes + in-tree fp32 / split-fp16
 // weight-gradient and small-GEMM kernels; no library calls)
 size_t dsn_train_workspace_size(int64_t N);
+// where that workspace keeps its per-row arrays (byte offsets in the order of DSN_GRAD_WS_*, dsnerf.h); 0, or the number of entries if n is not it
+int dsn_train_workspace_layout(int64_t N, int64_t* out, int n);
 // the part of that workspace a training FORWARD fills for its backward (dsn_render_rays_train -> dsn_render_rays_grad)
 struct DsnTrainCache {
     uint8_t* transparent; int32_t* idx_c; float *x_c, *sigma, *essence, *grad, *n_w, *h0, *a0, *rr; void* masks;

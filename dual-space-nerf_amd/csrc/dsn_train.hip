@@ -325,9 +325,13 @@ __global__ void __launch_bounds__(T_THREADS) k_t_wcolsum(const float* __restrict
     const int64_t base = (int64_t)blockIdx.x * rows_per_block;
     int64_t end = base + rows_per_block;
     if (end > NL) end = NL;
-    float acc[OUT], bs[OUT], wv[OUT];
+    // (bs in double: a bias gradient is a plain sum of signed cotangents - sum |dY| / |sum dY| was 34 on lights_encoding.4.bias of a
+    //  37 x 64 batch - and a thread walks up to rows_per_block / rs of them one after the other; the float32 chain alone was 2.7e-6 off.
+    //  The four rows in flight are added pairwise in float32 first: one conversion and one double add per four rows)
+    float acc[OUT], wv[OUT];
+    double bs[OUT];
 #pragma unroll
-    for (int o = 0; o < OUT; ++o) { acc[o] = 0.0f; bs[o] = 0.0f; wv[o] = dX ? W[o * C + c] : 0.0f; }
+    for (int o = 0; o < OUT; ++o) { acc[o] = 0.0f; bs[o] = 0.0; wv[o] = dX ? W[o * C + c] : 0.0f; }
     auto data_grad = [&](int64_t row, float x, const float (&y)[OUT]) {
         float v = y[0] * wv[0];
 #pragma unroll
@@ -358,7 +362,9 @@ __global__ void __launch_bounds__(T_THREADS) k_t_wcolsum(const float* __restrict
 #pragma unroll
         for (int k = 0; k < 4; ++k)
 #pragma unroll
-            for (int o = 0; o < OUT; ++o) { acc[o] = fmaf(x[k], y[k][o], acc[o]); bs[o] += y[k][o]; }
+            for (int o = 0; o < OUT; ++o) acc[o] = fmaf(x[k], y[k][o], acc[o]);
+#pragma unroll
+        for (int o = 0; o < OUT; ++o) bs[o] += (double)((y[0][o] + y[1][o]) + (y[2][o] + y[3][o]));      // (four rows pairwise, then the chain)
         if (dX) {
             const int64_t rid[4] = {id4[0], id4[1], id4[2], id4[3]};
 #pragma unroll
@@ -370,7 +376,7 @@ __global__ void __launch_bounds__(T_THREADS) k_t_wcolsum(const float* __restrict
         const float x = X[row * C + c];
         float yy[OUT];
 #pragma unroll
-        for (int o = 0; o < OUT; ++o) { const float y = dY[row * OUT + o]; yy[o] = y; acc[o] = fmaf(x, y, acc[o]); bs[o] += y; }
+        for (int o = 0; o < OUT; ++o) { const float y = dY[row * OUT + o]; yy[o] = y; acc[o] = fmaf(x, y, acc[o]); bs[o] += (double)y; }
         if (dX) data_grad(row, x, yy);
     }
 #pragma unroll
@@ -386,7 +392,7 @@ __global__ void __launch_bounds__(T_THREADS) k_t_wcolsum(const float* __restrict
     }
     if (db && c == 0) {                  // one thread per row group saw every row of its group
 #pragma unroll
-        for (int o = 0; o < OUT; ++o) atomicAdd(db + o, bs[o]);
+        for (int o = 0; o < OUT; ++o) atomicAdd(db + o, (float)bs[o]);
     }
     if (gmax) {                          // (one look-before-atomicMax per wave: see k_t_pe_tangent)
 #pragma unroll
@@ -2183,12 +2189,25 @@ void lin(const float* X, const float* W, float* Y, int64_t N, const float* bias_
 // heads' backward, d_hl1 = (hl1 > 0) (d_hl2 W_l2) and ahat_6 = m_6 (d_rr W_rgb1 + d_sig w_den).  On the fp32 MFMA they were bound by the
 // matrix pipe (0.17 + 0.25 ms per 8192 x 64 step at 60 - 80 TFLOP/s); with hi + lo halves (X / sx and W, three K = 16 products per tile
 // and step, as everywhere else in the backward) the pipe's share drops to a sixth and the sweeps run at what their 1.5 KB per row cost.
-// sx: the batch-wide magnitude of X the producing sweep left (k_t_wcolsum's gmax).  W is split as it is staged: [k / 8][column] half8
+// X is scaled ROW BY ROW, by the power of two at or above the row's own largest |x| (a lane owns a row; the other half of its k sits in
+// lane ^ 32): with the batch-wide magnitude of X as the scale, as it was at first, hi + lo of a row at 1e-4 of the batch's largest
+// kept 3e-4 of the row and a row at 1e-6 nothing at all - harmless in a sum over rows, but d_hl1 goes on, row by row, into the normal
+// map's adjoint, which divides by |g|: on the converged field u = dL/dg was more than 1e-3 off on 3 962 of 9 041 rows
+// (tests/test_gpu_row_cotangents.py).  W is split as it is staged: [k / 8][column] half8
 // pairs, K M 4 bytes of LDS (128 KB for 128 x 256), one workgroup per CU.  A lane owns one row of the wave's 32-row tile and the k-groups
 // of its half-wave: its 16 float4 of the NEXT tile are requested before the products of this one.  Same accumulator layout, same
 // epilogues and stores as k_t_lin.
+// a row's scale: the power of two at or above s, within [2^-100, 2^127] (the reciprocal is a normal float, x / scale <= 1 or, at the
+// very top of the range, 2); 1 for a row that is zero or not finite
+__device__ __forceinline__ float t_row_pow2(float s) {
+    if (!(s > 0.0f) || !(s < 3.0e38f)) return 1.0f;
+    int e;
+    const float m = frexpf(s, &e);
+    e = m == 0.5f ? e - 1 : e;
+    return ldexpf(1.0f, e < -100 ? -100 : (e > 127 ? 127 : e));
+}
 template <int K, int M, int EPI>
-__global__ void __launch_bounds__(256, 1) k_t_lin16(const float* __restrict__ X, const float* __restrict__ sx_ptr, const float* __restrict__ W,
+__global__ void __launch_bounds__(256, 1) k_t_lin16(const float* __restrict__ X, const float* __restrict__ W,
                                                     float* __restrict__ Y, int64_t N, const float* __restrict__ wv,
                                                     const float* __restrict__ msrc, const float* __restrict__ sc, Rows rw,
                                                     const uint4* __restrict__ recs, int rec_layer) {
@@ -2216,7 +2235,6 @@ __global__ void __launch_bounds__(256, 1) k_t_lin16(const float* __restrict__ X,
         for (int i = tid; i < M; i += 256) sV[i] = wv[i];
     __syncthreads();
     const int lane = tid & 63, wave = tid >> 6, half = lane >> 5, col = lane & 31;
-    const float sx = sx_ptr ? t_pow2_at_least(*sx_ptr) : 1.0f, inv = 1.0f / sx;
     const int64_t NL = rows_n(rw, N);
     const int64_t ntile = (NL + 31) / 32;
     const int64_t stride = (int64_t)gridDim.x * 4;
@@ -2240,6 +2258,12 @@ __global__ void __launch_bounds__(256, 1) k_t_lin16(const float* __restrict__ X,
 #pragma unroll
         for (int i = 0; i < 2 * ST; ++i) xc[i] = xn[i];
         if (tile + stride < ntile) request(tile + stride);
+        float xmax = 0.0f;                                  // (fmaxf skips a NaN: such an element poisons its own row, as before)
+#pragma unroll
+        for (int i = 0; i < 2 * ST; ++i)
+            xmax = fmaxf(xmax, fmaxf(fmaxf(fabsf(xc[i].x), fabsf(xc[i].y)), fmaxf(fabsf(xc[i].z), fabsf(xc[i].w))));
+        xmax = fmaxf(xmax, __shfl_xor(xmax, 32));
+        const float sx = t_row_pow2(xmax), inv = 1.0f / sx;
         // what the epilogue needs from memory is requested now and used behind the products
         float4 mk[EPI == EPI_MASK ? NT : 1][4];
         float scn = 0.0f;
@@ -2306,12 +2330,12 @@ __global__ void __launch_bounds__(256, 1) k_t_lin16(const float* __restrict__ X,
     }
 }
 template <int K, int M, int EPI>
-void lin16(const float* X, const float* sx, const float* W, float* Y, int64_t N, const float* wv, const float* msrc, const float* sc,
+void lin16(const float* X, const float* W, float* Y, int64_t N, const float* wv, const float* msrc, const float* sc,
            hipStream_t st, Rows rw, const void* recs = nullptr, int rec_layer = 0) {
     const int64_t ntile = (N + 31) / 32;
     int groups = (int)((ntile + 3) / 4);
     if (groups > 256) groups = 256;               // one workgroup per CU: W is split and staged once per workgroup
-    hipLaunchKernelGGL((k_t_lin16<K, M, EPI>), dim3((unsigned)groups), dim3(256), 0, st, X, sx, W, Y, N, wv, msrc, sc, rw, (const uint4*)recs,
+    hipLaunchKernelGGL((k_t_lin16<K, M, EPI>), dim3((unsigned)groups), dim3(256), 0, st, X, W, Y, N, wv, msrc, sc, rw, (const uint4*)recs,
                        rec_layer);
 }
 
@@ -2402,6 +2426,17 @@ void wcolsum(const float* X, int C, const float* dY, int64_t N, float* dW, float
 }  // namespace
 
 size_t dsn_train_workspace_size(int64_t N) { return carve(nullptr, N).bytes; }
+
+// byte offsets of the per-row arrays inside that workspace, from carve() itself, in the order of DSN_GRAD_WS_* (dsnerf.h)
+int dsn_train_workspace_layout(int64_t N, int64_t* out, int n) {
+    const TrainWs w = carve(nullptr, N);
+    const void* const at[] = {w.transparent, w.x_c, w.sig, w.ess, w.g, w.n_w, w.xl, w.hl1, w.hl2, w.pre, w.wl, w.col, w.rr, w.h[6],
+                              w.d_sig, w.d_col, w.d_ess, w.d_pre, w.d_hl2, w.d_hl1, w.d_xl, w.d_rr, w.u, w.list1, w.list2, w.rowcnt};
+    const int have = (int)(sizeof(at) / sizeof(at[0]));
+    if (n != have) return have;
+    for (int i = 0; i < have; ++i) out[i] = (int64_t)((const char*)at[i] - (const char*)nullptr);
+    return 0;
+}
 
 DsnTrainCache dsn_train_cache(void* workspace, int64_t N) {
     const TrainWs w = carve(workspace, N);
@@ -2550,8 +2585,8 @@ const char* dsn_train_run(const DsnSceneView& s, const float* packed, const floa
     else T_CHECK(wgrad_mfma(N64, 128, 128, 128, w.hl1, 128, w.d_hl2, 128, grd[P_L2_W], 128, st, grd[P_L2_B], R2));
     // (round 6: the two data-gradient products of the heads on the split-fp16 kernel k_t_lin16; DSN_TRAIN_LIN=fp32 keeps k_t_lin, A/B and cross-check)
     static const bool lin_fp32 = [] { const char* e = getenv("DSN_TRAIN_LIN"); return e && e[0] == 'f'; }();
-    const bool lin16_ = heads16 && !lin_fp32;      // (the operand scales come from the fused sweeps)
-    if (lin16_) lin16<128, 128, EPI_MASK>(w.d_hl2, g_dhl2, prm[P_L2_W], w.d_hl1, N64, nullptr, w.hl1, nullptr, st, R2);   // d_hl1 = (hl1 > 0) (d_hl2 W2)
+    const bool lin16_ = heads16 && !lin_fp32;
+    if (lin16_) lin16<128, 128, EPI_MASK>(w.d_hl2, prm[P_L2_W], w.d_hl1, N64, nullptr, w.hl1, nullptr, st, R2);   // d_hl1 = (hl1 > 0) (d_hl2 W2)
     else lin<128, 128, false, EPI_MASK>(w.d_hl2, prm[P_L2_W], w.d_hl1, N64, nullptr, w.hl1, nullptr, st, R2);
     // (the first lighting layer keeps its two passes over d_hl1: a VALU kernel that also accumulates dW0 takes 0.39 ms against
     //  0.107 for the exact-fp32 MFMA product + 0.129 for the data gradient - tried in round 5)
@@ -2606,7 +2641,7 @@ const char* dsn_train_run(const DsnSceneView& s, const float* packed, const floa
     // (round 6: the relu pattern of layer 6 from the forward's records - 32 bytes per row instead of the 1 KB row of h_6;
     //  DSN_TRAIN_SEED_MASK=h keeps the `h_6 > 0` form, A/B and cross-check)
     static const bool seed_by_h = [] { const char* e = getenv("DSN_TRAIN_SEED_MASK"); return e && e[0] == 'h'; }();
-    if (lin16_ && !seed_by_h) lin16<128, 256, EPI_SEED>(w.d_rr, g_drr, prm[P_RGB1_W], cur, N64, prm[P_DEN_W], nullptr, d_sig, sa, R2, w.masks, 6);   // (pattern from the records only)
+    if (lin16_ && !seed_by_h) lin16<128, 256, EPI_SEED>(w.d_rr, prm[P_RGB1_W], cur, N64, prm[P_DEN_W], nullptr, d_sig, sa, R2, w.masks, 6);   // (pattern from the records only)
     else lin<128, 256, false, EPI_SEED>(w.d_rr, prm[P_RGB1_W], cur, N64, prm[P_DEN_W], w.h[6], d_sig, sa, R2, seed_by_h ? nullptr : w.masks, 6);
     // cur = ahat_6.  The layers below it in one fused split-fp16 launch (k_adjoint16 -> ahat_5 ... ahat_0 in the buffers the
     // tangent products are done with), then  dW_l += ahat_l^T h_{l-1}  and the bias gradients (column sums)

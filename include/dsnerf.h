@@ -442,6 +442,20 @@ DSN_EXPORT int dsn_debug_screen(const void* scene, int V, int F, const void* pac
  * tangent pass.  `packed` = dsn_pack_params image of the same parameters.  Activations stay resident in `workspace`
  * (dsn_grad_workspace_bytes(R,S), 34 KB per sample). */
 DSN_EXPORT size_t dsn_grad_workspace_bytes(int R, int S);
+/* Read-only view of that workspace for tests and diagnostics (host function, nothing is launched): byte offsets of the per-row
+ * arrays a dsn_render_rays_grad over R x S samples leaves there, N = R S rows each, indexed by sample.  None of them is overwritten
+ * before the call returns; rows that are not on the lists hold stale values.  out_offsets_host: n = DSN_GRAD_WS_COUNT entries, in
+ * this order (float32 unless said otherwise; [N,k] row-major):
+ *   forward   0 transparent (uint8)  1 x_c [N,3]  2 sig  3 ess [N,3]  4 g = d sigma/dx [N,3]  5 n_w [N,3]  6 xl [N,9] = (n_w, x_w, view)
+ *             7 hl1 [N,128]  8 hl2 [N,128] (after their ReLUs)  9 pre  10 wl = ELU(pre) + 1  11 col [N,3]  12 rr [N,128] (after ReLU)
+ *             13 h[6] [N,256] (the trunk's last layer, after ReLU)
+ *   backward  14 d_sig  15 d_col [N,3]  16 d_ess [N,3]  17 d_pre  18 d_hl2 [N,128]  19 d_hl1 [N,128]  20 d_xl [N,9]  21 d_rr [N,128]
+ *             (18, 19, 21: behind the ReLU masks, i.e. cotangents of the layers' pre-activations)  22 u = dL/dg [N,3]
+ *   lists     23 list1 (int32, rows the forward evaluated)  24 list2 (int32, rows with a non-zero cotangent; both ascending)
+ *             25 rowcnt (int32 [2]: entries of list1, of list2)
+ * Returns non-zero (dsn_last_error) when n is not DSN_GRAD_WS_COUNT or a size is not positive. */
+#define DSN_GRAD_WS_COUNT 26
+DSN_EXPORT int dsn_grad_workspace_layout(int R, int S, int64_t* out_offsets_host, int n);
 /* Renderer.render in train mode (can_render.py:137-168 with net.training): dsn_render_rays (dense evaluation, jitter / noise
  * as given) that also leaves what its backward needs in `grad_workspace` (dsn_grad_workspace_bytes(R,S)): canonical points,
  * transparency, per-layer activations, sigma-adjoints, relu records, normals.  A following dsn_render_rays_grad on the same

@@ -73,7 +73,7 @@ def embed(u, v, h, fr):
 def render(params: dict, g: dict, jitter_z=None, noise=None, zero_code=False, dtype=torch.float32, geom=None):
     """params: name -> torch tensor (requires_grad as wanted); g: batch arrays (ray_o, ray_d, xyz, canonical_vertex,
     faces, poses, frame) and z_vals [R,S] (the sampler's output, float32).  Returns the outputs of
-    can_render.py:137-168 as torch tensors attached to the graph.
+    can_render.py:137-168 as torch tensors attached to the graph, and the per-row nodes of the colour head and the lighting MLP.
     geom (optional, used by bench.py's eager-torch baseline): precomputed parameter-independent geometry as torch
     tensors {x_c [N,3], transparent [N] bool, idx_canon [N] int64} on the device the parameters live on; the
     nearest-face searches are then NOT part of what runs here."""
@@ -107,7 +107,9 @@ def render(params: dict, g: dict, jitter_z=None, noise=None, zero_code=False, dt
     for k in (0, 2, 4):
         h = torch.relu(linear(params, f"nerf.stage2.{k}", h))
     sigma = linear(params, "nerf.density_net.0", h)
-    essence = linear(params, "nerf.rgb_net.3", torch.relu(linear(params, "nerf.rgb_net.1", torch.relu(h))))
+    rr_pre = linear(params, "nerf.rgb_net.1", torch.relu(h))
+    rr = torch.relu(rr_pre)
+    essence = linear(params, "nerf.rgb_net.3", rr)
     # model/spacenet.py:301-311
     grad = torch.autograd.grad(sigma.sum(), x_c, create_graph=True)[0]
     # model/spacenet.py:278-298: nearest canonical face (a constant index), both points through the same face pair
@@ -122,9 +124,12 @@ def render(params: dict, g: dict, jitter_z=None, noise=None, zero_code=False, dt
     dd = _t(d, dtype)
     view = (dd / torch.norm(dd, dim=-1, keepdim=True))[:, None, :].expand(R, S, 3).reshape(-1, 3)
     li = torch.cat([n_w, x_w, view], dim=-1)
-    hl = torch.relu(linear(params, "lighting_mlp.lights_encoding.0", li))
-    hl = torch.relu(linear(params, "lighting_mlp.lights_encoding.2", hl))
-    wl = torch.nn.functional.elu(linear(params, "lighting_mlp.lights_encoding.4", hl)) + 1
+    hl1_pre = linear(params, "lighting_mlp.lights_encoding.0", li)
+    hl1 = torch.relu(hl1_pre)
+    hl2_pre = linear(params, "lighting_mlp.lights_encoding.2", hl1)
+    hl2 = torch.relu(hl2_pre)
+    pre = linear(params, "lighting_mlp.lights_encoding.4", hl2)
+    wl = torch.nn.functional.elu(pre) + 1
     colour = wl * essence
     # can_render.py:115-120 + utils/nerf_net_utils.py:5-56
     sig = sigma.reshape(R, S)
@@ -142,7 +147,12 @@ def render(params: dict, g: dict, jitter_z=None, noise=None, zero_code=False, dt
     acc = weights.sum(-1)
     disp = 1.0 / torch.max(torch.full_like(depth, 1e-10), depth / acc)
     return {"color": rgb, "disp_map": disp, "acc_map": acc, "depth_map": depth, "weights": weights,
-            "sigma": sigma.reshape(-1), "essence": essence, "grad_sigma": grad, "n_w": n_w, "colour": colour}
+            "sigma": sigma.reshape(-1), "essence": essence, "grad_sigma": grad, "n_w": n_w, "colour": colour,
+            # the graph nodes themselves (tests/row_cotangents.py takes torch.autograd.grad of a loss with respect to them): the density
+            # head's output [N,1] that the compositor masks and reshapes, the trunk's last layer, the colour head's hidden layer and
+            # the lighting MLP's layers before / after their ReLUs, its input rows and its output before the ELU
+            "sigma_node": sigma, "h6": h, "rr_pre": rr_pre, "rr": rr, "li": li, "hl1_pre": hl1_pre, "hl1": hl1,
+            "hl2_pre": hl2_pre, "hl2": hl2, "pre": pre, "wl": wl, "transparent": transparent.reshape(-1)}
 
 
 def loss_and_grads(state: dict, g: dict, z_vals, noise, target, occupancy=None, dtype=torch.float32):

@@ -10,6 +10,7 @@ import torch
 
 import train_oracle as TO
 from helpers import load, maxdiff, ref_tol, state
+from row_cotangents import load_case, oracle_loss, output_cotangents, sliced_case  # noqa: F401  (one copy, shared with the per-row tests)
 from test_gpu_render import make_batch, make_renderer
 
 pytestmark = pytest.mark.gpu
@@ -46,31 +47,6 @@ def achieved(kind, case):
 
 def bar(recorded):
     return max(HEADROOM * float(recorded), FLOOR)
-
-
-def load_case(name):
-    """a gradient fixture as a dict.  The compact S > 64 cases (make_golden_grads.py --samples) keep only what cannot be regenerated:
-    their body, 128 rays of the 32 x 32 view, targets and draws are rebuilt here from the seeds as the generator made them, and the
-    draws are checked against the sums it kept"""
-    g = dict(load(name).items())
-    if "ray_o" in g:
-        return g
-    from dsnerf_amd import synth
-    R, S, seed = int(g["rays"]), int(g["S"]), int(g["seed"])
-    canon, faces = synth.make_body()
-    xyz = synth.pose_body(canon)
-    rays = synth.make_rays(32, 32, xyz, fit_box=True)
-    sel = np.arange(0, 1024, 8)[:R]
-    g.update(canonical_vertex=canon, faces=faces.astype(np.int32), xyz=xyz, poses=synth.make_poses(),
-             ray_o=rays["ray_o"][sel], ray_d=rays["ray_d"][sel], near=rays["near"][sel], far=rays["far"][sel],
-             target_rgb=synth.hash_uniform(R * 3, 91).reshape(R, 3).astype(np.float32),
-             occupancy=(synth.hash_uniform(R, 92) > 0.5).astype(np.float32))
-    torch.manual_seed(seed)                     # (the reference's draws: jitter, then noise, from the CPU generator)
-    g["jitter"] = torch.rand(1, R, S).numpy()[0]
-    g["noise"] = (torch.randn(R, S) * float(g["raw_noise_std"])).numpy()
-    assert float(g["jitter"].astype(np.float64).sum()) == float(g["jitter_sum"])
-    assert float(g["noise"].astype(np.float64).sum()) == float(g["noise_sum"])
-    return g
 
 
 def reference_case_errors(name):
@@ -150,28 +126,17 @@ def oracle_case_errors(name, nrays, nsamp):
     """dsn_render_rays_grad with cotangents on every output (colour, disp, acc, depth, weights) against autograd of the CPU oracle on
     the same inputs, full tensors -> {tensor: rel. L2}"""
     from dsnerf_amd import _lib
-    g = load_case(name)
-    if nrays is not None:                      # a ray count that is no multiple of the 32-point wave tiles / 128-point blocks
-        for k in ("ray_o", "ray_d", "near", "far", "render:z_vals", "noise", "jitter"):
-            g[k] = g[k][:nrays]
-    if nsamp is not None:                      # 37 x 21 = 777 samples: not a multiple of 16 (the weight-gradient kernels' ragged tail)
-        for k in ("render:z_vals", "noise", "jitter"):
-            g[k] = np.ascontiguousarray(g[k][:, :nsamp])
+    g = sliced_case(name, nrays, nsamp)
     sd = state(name)
     r = make_renderer(g, name)
     z = g["render:z_vals"]
     R, S = z.shape
     noise = g["noise"] if float(g["raw_noise_std"]) > 0 else None
-    rng = np.random.default_rng(4)
-    cot = {k: rng.standard_normal(s).astype(np.float32) for k, s in
-           (("color", (R, 3)), ("disp_map", (R,)), ("acc_map", (R,)), ("depth_map", (R,)), ("weights", (R, S)))}
+    cot = output_cotangents(R, S)
     # oracle: L = sum(cotangent * output); disparity only where the ray hit something (NaN elsewhere, as the reference)
     params = {k: torch.from_numpy(v.copy()).requires_grad_(True) for k, v in sd.items()}
     out = TO.render(params, g, jitter_z=z, noise=noise)
-    ok = out["acc_map"].detach() > 1e-3
-    cot["disp_map"] = np.where(ok.numpy(), cot["disp_map"] * 1e-2, 0.0).astype(np.float32)
-    L = sum((torch.from_numpy(cot[k]) * out[k]).sum() for k in ("color", "acc_map", "depth_map", "weights"))
-    L = L + (torch.from_numpy(cot["disp_map"])[ok] * out["disp_map"][ok]).sum()
+    L, _ = oracle_loss(out, cot)
     L.backward()
     dev = r.device
     b = make_batch(g)
