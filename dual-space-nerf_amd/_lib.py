@@ -59,6 +59,7 @@ EXPORTS = [
     "dsn_adam_step", "dsn_adam_scalars_host", "dsn_train_draws",
     "dsn_body_shape", "dsn_body_pose_workspace_bytes", "dsn_body_pose",
     "dsn_grad_workspace_layout",
+    "dsn_image_undistort", "dsn_image_morph", "dsn_image_resize", "dsn_image_prep",
 ]
 
 SKIP_TRANSPARENT = 1
@@ -195,6 +196,10 @@ def lib():
         L.dsn_body_pose.argtypes = ([C.c_void_p] * 5 + [C.c_int] + [C.c_void_p] * 3 + [C.c_int, C.c_int] + [C.c_void_p] * 6
                                     + [C.c_size_t, C.c_void_p])
         L.dsn_grad_workspace_layout.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int]
+        L.dsn_image_undistort.argtypes = [C.c_void_p] * 4 + [C.c_int] * 6 + [C.c_void_p]
+        L.dsn_image_morph.argtypes = [C.c_void_p] * 2 + [C.c_int] * 5 + [C.c_void_p]
+        L.dsn_image_resize.argtypes = [C.c_void_p] * 2 + [C.c_int] * 7 + [C.c_void_p]
+        L.dsn_image_prep.argtypes = [C.c_void_p] * 4 + [C.c_int] * 7 + [C.c_void_p] * 5
         if L.dsn_abi_version() != 8:
             raise RuntimeError(f"{LIB_PATH} has ABI version {L.dsn_abi_version()}, this binding needs 8 - rebuild it "
                                "(python dual-space-nerf_amd/build.py)")
@@ -2486,3 +2491,144 @@ def train_rays(img, K, R, T, bounds, mask_a, nrays, seed, convention="zju", mask
     out["mask_at_box"] = out["mask_at_box"].bool()
     out["workspace"] = ws
     return out
+
+
+# ---- the datasets' image preparation (dsn_image_undistort / _morph / _resize / _prep: the rule of include/dsnerf.h) ---------------------
+PREP_U8, PREP_F32, PREP_F64 = 0, 1, 2          # DSN_PREP_*
+PREP_DILATE, PREP_ERODE = 0, 1
+PREP_NEAREST, PREP_AREA = 0, 1
+PREP_TILE_W, PREP_TILE_H = 64, 16              # DSN_PREP_TILE_*: the full-resolution tile a workgroup owns
+PREP_MAX_SIDE, PREP_MAX_BATCH = 32768, 65535
+
+
+def _prep_image(what, x, dtypes, name="x"):
+    """(N, H, W, channels) of a batch of images [N, H, W] or [N, H, W, 3]: a contiguous tensor of one of `dtypes`"""
+    if not torch.is_tensor(x):
+        raise ValueError(f"{what}: {name} must be a torch tensor, got {type(x).__name__}")
+    if x.dtype not in dtypes:
+        raise ValueError(f"{what}: {name} must be {' or '.join(str(d) for d in dtypes)}, got {x.dtype}")
+    if x.dim() not in (3, 4) or (x.dim() == 4 and x.shape[3] != 3):
+        raise ValueError(f"{what}: {name} must be [N, H, W] or [N, H, W, 3], got {tuple(x.shape)}")
+    N, H, W = (int(v) for v in x.shape[:3])
+    if H < 1 or W < 1 or H > PREP_MAX_SIDE or W > PREP_MAX_SIDE or N > PREP_MAX_BATCH:
+        raise ValueError(f"{what}: {name} has {N} images of {H} x {W}; sides 1 ... {PREP_MAX_SIDE}, at most {PREP_MAX_BATCH} images")
+    if not x.is_contiguous():
+        raise ValueError(f"{what}: {name} must be contiguous")
+    return N, H, W, (3 if x.dim() == 4 else 1)
+
+
+def _prep_on_device(what, *tensors):
+    require_gpu()
+    dev = tensors[0].device
+    for t in tensors:
+        if not t.is_cuda or t.device != dev:
+            raise ValueError(f"{what}: the images must be tensors on one ROCm device, got {t.device}")
+    return dev
+
+
+def prep_camera(what, K, D, N, device=None):
+    """K [N, 3, 3] (or one [3, 3] for all N) and D [N, nd] (or one [nd]), nd = 4, 5 or 8, as the contiguous float64 arrays
+    dsn_image_undistort and dsn_image_prep read.  Host arrays (numpy, lists, CPU tensors) are checked on the host and, with `device`,
+    uploaded in one copy; device tensors are used where they are, after their skew entries have been read back for the check (N
+    numbers: pass host cameras to avoid the wait).  A skew K[0, 1] other than 0 is refused: the rule has no such term."""
+    Kt = torch.as_tensor(K).to(torch.float64)
+    Dt = torch.as_tensor(D).to(torch.float64)
+    if Kt.dim() == 2:
+        Kt = Kt.unsqueeze(0).expand(N, -1, -1)
+    if Dt.dim() == 1:
+        Dt = Dt.unsqueeze(0).expand(N, -1)
+    if tuple(Kt.shape) != (N, 3, 3):
+        raise ValueError(f"{what}: K must be [3, 3] or [{N}, 3, 3], got {tuple(Kt.shape)}")
+    if Dt.dim() != 2 or Dt.shape[0] != N or Dt.shape[1] not in (4, 5, 8):
+        raise ValueError(f"{what}: D must be [nd] or [{N}, nd] with nd = 4, 5 or 8, got {tuple(Dt.shape)}")
+    if N and bool((Kt[:, 0, 1] != 0).any()):
+        raise ValueError(f"{what}: K has a skew term K[0, 1] other than 0, which the undistortion rule does not model")
+    Kt, Dt = Kt.contiguous(), Dt.contiguous()
+    if device is None:
+        return Kt, Dt
+    if not Kt.is_cuda and not Dt.is_cuda:          # the usual case: one upload for both
+        both = torch.cat([Kt.reshape(-1), Dt.reshape(-1)]).to(device)
+        return both[:9 * N].view(N, 3, 3), both[9 * N:].view(N, Dt.shape[1])
+    return Kt.to(device), Dt.to(device)
+
+
+def image_undistort(x, K, D):
+    """dsn_image_undistort: x uint8 or float32 device tensor [N, H, W] or [N, H, W, 3]; K, D as prep_camera takes them -> the
+    undistorted images, same shape and dtype.  N = 0: an empty tensor, no launch."""
+    N, H, W, ch = _prep_image("image_undistort", x, (torch.uint8, torch.float32))
+    Kd, Dd = prep_camera("image_undistort", K, D, N, x.device if x.is_cuda else None)          # (its checks need no device: they come first)
+    dev = _prep_on_device("image_undistort", x)
+    out = _output(tuple(x.shape), x.dtype, dev)
+    with torch.cuda.device(dev):
+        _check(lib().dsn_image_undistort(_ptr(x) if N else None, _ptr(out) if N else None, _ptr(Kd) if N else None, _ptr(Dd) if N else None,
+                                         Dd.shape[1], N, H, W, ch, PREP_U8 if x.dtype == torch.uint8 else PREP_F32, _stream()),
+               "dsn_image_undistort")
+    return out
+
+
+def image_morph(m, k, op):
+    """dsn_image_morph: m uint8 device tensor [N, H, W], box k = 1 ... 15, op PREP_DILATE or PREP_ERODE -> uint8 [N, H, W]"""
+    N, H, W, ch = _prep_image("image_morph", m, (torch.uint8,), "m")
+    if ch != 1:
+        raise ValueError(f"image_morph: m must be [N, H, W], got {tuple(m.shape)}")
+    if int(k) != k or not 1 <= int(k) <= 15:
+        raise ValueError(f"image_morph: k must be an integer 1 ... 15, got {k!r}")
+    if op not in (PREP_DILATE, PREP_ERODE):
+        raise ValueError(f"image_morph: op must be PREP_DILATE or PREP_ERODE, got {op!r}")
+    dev = _prep_on_device("image_morph", m)
+    out = _output(tuple(m.shape), torch.uint8, dev)
+    with torch.cuda.device(dev):
+        _check(lib().dsn_image_morph(_ptr(m) if N else None, _ptr(out) if N else None, N, H, W, int(k), op, _stream()), "dsn_image_morph")
+    return out
+
+
+def _prep_factor(what, c, H, W):
+    if c not in (1, 2, 4):
+        raise ValueError(f"{what}: the factor must be 1, 2 or 4, got {c!r}")
+    if H % c or W % c:
+        raise ValueError(f"{what}: {H} x {W} is not a multiple of the factor {c} (OpenCV's path for such sizes is another algorithm)")
+    return int(c)
+
+
+def image_resize(x, c, mode):
+    """dsn_image_resize: x uint8 or float32 device tensor [N, H, W] or [N, H, W, 3], c = 1, 2 or 4 dividing H and W, mode PREP_AREA or
+    PREP_NEAREST -> [N, H / c, W / c(, 3)] of x's dtype"""
+    N, H, W, ch = _prep_image("image_resize", x, (torch.uint8, torch.float32))
+    c = _prep_factor("image_resize", c, H, W)
+    if mode not in (PREP_NEAREST, PREP_AREA):
+        raise ValueError(f"image_resize: mode must be PREP_NEAREST or PREP_AREA, got {mode!r}")
+    dev = _prep_on_device("image_resize", x)
+    out = _output((N, H // c, W // c) + ((3,) if ch == 3 else ()), x.dtype, dev)
+    with torch.cuda.device(dev):
+        _check(lib().dsn_image_resize(_ptr(x) if N else None, _ptr(out) if N else None, N, H, W, ch,
+                                      PREP_U8 if x.dtype == torch.uint8 else PREP_F32, c, mode, _stream()), "dsn_image_resize")
+    return out
+
+
+def image_prep(img_u8, msk_cihp, K, D, c=2, border=5, dtype=torch.float64, want_u8=False, want_masks=True):
+    """dsn_image_prep, the fused ZJU item in one launch: img_u8 [N, H0, W0, 3] and msk_cihp [N, H0, W0] uint8 device tensors, K, D as
+    prep_camera takes them -> (img [N, H, W, 3] of `dtype` (float64 or float32), img_u8 [N, H, W, 3] or None, msk_fg, msk_cihp
+    [N, H, W] uint8 or None) with H = H0 / c, W = W0 / c."""
+    N, H0, W0, ch = _prep_image("image_prep", img_u8, (torch.uint8,), "img_u8")
+    if ch != 3:
+        raise ValueError(f"image_prep: img_u8 must be [N, H0, W0, 3], got {tuple(img_u8.shape)}")
+    Nm, Hm, Wm, chm = _prep_image("image_prep", msk_cihp, (torch.uint8,), "msk_cihp")
+    if (Nm, Hm, Wm, chm) != (N, H0, W0, 1):
+        raise ValueError(f"image_prep: msk_cihp must be [{N}, {H0}, {W0}], got {tuple(msk_cihp.shape)}")
+    c = _prep_factor("image_prep", c, H0, W0)
+    if int(border) != border or not 1 <= int(border) <= 15:
+        raise ValueError(f"image_prep: border must be an integer 1 ... 15, got {border!r}")
+    if dtype not in (torch.float64, torch.float32):
+        raise ValueError(f"image_prep: dtype must be torch.float64 or torch.float32, got {dtype}")
+    Kd, Dd = prep_camera("image_prep", K, D, N, img_u8.device if img_u8.is_cuda else None)
+    dev = _prep_on_device("image_prep", img_u8, msk_cihp)
+    H, W = H0 // c, W0 // c
+    img = _output((N, H, W, 3), dtype, dev)
+    u8 = _output((N, H, W, 3), torch.uint8, dev) if want_u8 else None
+    fg = _output((N, H, W), torch.uint8, dev) if want_masks else None
+    ci = _output((N, H, W), torch.uint8, dev) if want_masks else None
+    p = lambda t: _ptr(t) if (t is not None and N) else None      # noqa: E731
+    with torch.cuda.device(dev):
+        _check(lib().dsn_image_prep(p(img_u8), p(msk_cihp), p(Kd), p(Dd), Dd.shape[1], N, H0, W0, c, int(border),
+                                    PREP_F64 if dtype == torch.float64 else PREP_F32, p(img), p(u8), p(fg), p(ci), _stream()), "dsn_image_prep")
+    return img, u8, fg, ci

@@ -1863,4 +1863,64 @@ int dsn_raster_mesh(const float* verts, int64_t n_verts, const int32_t* faces, i
                               out_color, workspace, workspace_bytes, 0, 0, stream);
 }
 
+// ---- the datasets' image preparation (dsn_prep.hip) ----
+#define DSN_PREP_COMMON(name, N, H, W)                                                                        \
+    DSN_REQUIRE((N) >= 0 && (N) <= 65535, name ": N must be 0 ... 65535");                                   \
+    DSN_REQUIRE((H) > 0 && (W) > 0 && (H) <= DSN_PREP_MAX_SIDE && (W) <= DSN_PREP_MAX_SIDE, name ": H and W must be 1 ... 32768")
+
+int dsn_image_undistort(const void* src, void* dst, const double* K, const double* D, int nd, int N, int H, int W, int channels, int dtype,
+                        void* stream) {
+    DSN_PREP_COMMON("dsn_image_undistort", N, H, W);
+    DSN_REQUIRE(nd == 4 || nd == 5 || nd == 8, "dsn_image_undistort: nd must be 4, 5 or 8");
+    DSN_REQUIRE(channels == 1 || channels == 3, "dsn_image_undistort: channels must be 1 or 3");
+    DSN_REQUIRE(dtype == DSN_PREP_U8 || dtype == DSN_PREP_F32, "dsn_image_undistort: dtype must be DSN_PREP_U8 or DSN_PREP_F32");
+    if (N == 0) return 0;
+    DSN_REQUIRE(src && dst && K && D, "dsn_image_undistort: null argument");
+    DSN_REQUIRE(src != dst, "dsn_image_undistort: src and dst must differ");
+    dsn_launch_image_undistort(src, dst, K, D, nd, N, H, W, channels, dtype, (hipStream_t)stream);
+    return dsn_check_launch("dsn_image_undistort");
+}
+
+int dsn_image_morph(const uint8_t* src, uint8_t* dst, int N, int H, int W, int k, int op, void* stream) {
+    DSN_PREP_COMMON("dsn_image_morph", N, H, W);
+    DSN_REQUIRE(k >= 1 && k <= 15, "dsn_image_morph: k must be 1 ... 15");
+    DSN_REQUIRE(op == DSN_PREP_DILATE || op == DSN_PREP_ERODE, "dsn_image_morph: op must be DSN_PREP_DILATE or DSN_PREP_ERODE");
+    if (N == 0) return 0;
+    DSN_REQUIRE(src && dst, "dsn_image_morph: null argument");
+    DSN_REQUIRE(src != dst, "dsn_image_morph: src and dst must differ");
+    dsn_launch_image_morph(src, dst, N, H, W, k, op, (hipStream_t)stream);
+    return dsn_check_launch("dsn_image_morph");
+}
+
+int dsn_image_resize(const void* src, void* dst, int N, int H, int W, int channels, int dtype, int c, int mode, void* stream) {
+    DSN_PREP_COMMON("dsn_image_resize", N, H, W);
+    DSN_REQUIRE(c == 1 || c == 2 || c == 4, "dsn_image_resize: c must be 1, 2 or 4");
+    DSN_REQUIRE(H % c == 0 && W % c == 0, "dsn_image_resize: H and W must be multiples of c");
+    DSN_REQUIRE(channels == 1 || channels == 3, "dsn_image_resize: channels must be 1 or 3");
+    DSN_REQUIRE(dtype == DSN_PREP_U8 || dtype == DSN_PREP_F32, "dsn_image_resize: dtype must be DSN_PREP_U8 or DSN_PREP_F32");
+    DSN_REQUIRE(mode == DSN_PREP_NEAREST || mode == DSN_PREP_AREA, "dsn_image_resize: mode must be DSN_PREP_NEAREST or DSN_PREP_AREA");
+    if (N == 0) return 0;
+    DSN_REQUIRE(src && dst, "dsn_image_resize: null argument");
+    DSN_REQUIRE(src != dst, "dsn_image_resize: src and dst must differ");
+    DSN_REQUIRE(dtype == DSN_PREP_U8 || (((uintptr_t)src | (uintptr_t)dst) & 3) == 0, "dsn_image_resize: a float32 pointer is not 4-byte aligned");
+    dsn_launch_image_resize(src, dst, N, H, W, channels, dtype, c, mode, (hipStream_t)stream);
+    return dsn_check_launch("dsn_image_resize");
+}
+
+int dsn_image_prep(const uint8_t* img, const uint8_t* msk_cihp, const double* K, const double* D, int nd, int N, int H0, int W0, int c,
+                   int border, int out_dtype, void* out_img, uint8_t* out_img_u8, uint8_t* out_msk_fg, uint8_t* out_msk_cihp, void* stream) {
+    DSN_PREP_COMMON("dsn_image_prep", N, H0, W0);
+    DSN_REQUIRE(nd == 4 || nd == 5 || nd == 8, "dsn_image_prep: nd must be 4, 5 or 8");
+    DSN_REQUIRE(c == 1 || c == 2 || c == 4, "dsn_image_prep: c must be 1, 2 or 4");
+    DSN_REQUIRE(H0 % c == 0 && W0 % c == 0, "dsn_image_prep: H0 and W0 must be multiples of c");
+    DSN_REQUIRE(border >= 1 && border <= 15, "dsn_image_prep: border must be 1 ... 15");
+    DSN_REQUIRE(out_dtype == DSN_PREP_F64 || out_dtype == DSN_PREP_F32, "dsn_image_prep: out_dtype must be DSN_PREP_F64 or DSN_PREP_F32");
+    if (N == 0) return 0;
+    DSN_REQUIRE(img && msk_cihp && K && D && out_img, "dsn_image_prep: null argument");
+    DSN_REQUIRE(((uintptr_t)out_img & (out_dtype == DSN_PREP_F64 ? 7 : 3)) == 0, "dsn_image_prep: out_img is not aligned to its element");
+    dsn_launch_image_prep(img, msk_cihp, K, D, nd, N, H0, W0, c, border, out_dtype, out_img, out_img_u8, out_msk_fg, out_msk_cihp,
+                          (hipStream_t)stream);
+    return dsn_check_launch("dsn_image_prep");
+}
+
 }  // extern "C"

@@ -222,6 +222,14 @@ int dsn_launch_adam_step(float* const* params, const float* const* grads, float*
 // dsn_rng.hip: the training step's jitter and noise (dsn_train_draws; R, S > 0, R * S <= INT_MAX, not both arrays null)
 void dsn_launch_train_draws(uint64_t seed, uint32_t step, uint32_t ray_base, const int32_t* ray_ids, int R, int S, float noise_std,
                             float* jitter, float* noise, hipStream_t st);
+// dsn_prep.hip: the datasets' image preparation (dsn_image_undistort / _morph / _resize / _prep; arguments checked by the entry points)
+void dsn_launch_image_undistort(const void* src, void* dst, const double* K, const double* D, int nd, int N, int H, int W, int channels,
+                                int dtype, hipStream_t st);
+void dsn_launch_image_morph(const uint8_t* src, uint8_t* dst, int N, int H, int W, int k, int op, hipStream_t st);
+void dsn_launch_image_resize(const void* src, void* dst, int N, int H, int W, int channels, int dtype, int c, int mode, hipStream_t st);
+void dsn_launch_image_prep(const uint8_t* img, const uint8_t* msk_cihp, const double* K, const double* D, int nd, int N, int H0, int W0, int c,
+                           int border, int out_dtype, void* out_img, uint8_t* out_img_u8, uint8_t* out_msk_fg, uint8_t* out_msk_cihp,
+                           hipStream_t st);
 // dsn_mesh.hip: density grid points and marching cubes (dsn_density_grid, dsn_mc_*)
 void dsn_launch_grid_points(const float* x, const float* y, const float* z, int i0, int ny, int nz, int64_t n, float* pts, hipStream_t st);
 size_t dsn_mc_workspace_size(int64_t N);

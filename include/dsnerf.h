@@ -1215,6 +1215,71 @@ DSN_EXPORT int dsn_raster_mesh_attr(const float* verts, int64_t n_verts, const i
                                     int big_pixels, const float* vertex_normals, const float* vertex_colors, int mode, float* out_normal,
                                     float* out_attr, void* stream);
 
+/* ---- the datasets' image preparation on the device (an addition within ABI 8: no existing entry point changes) -------------------------
+ * Between cv2.imread and the ray sampler the reference's datasets run OpenCV on the host (dataloader/zju_mocap_dataset.py:84-123,
+ * :192-213; dataloader/h36m_dataset.py:88-93, :128-158, :182-184): cv2.undistort, cv2.dilate / cv2.erode with box kernels, an
+ * INTER_AREA and INTER_NEAREST cv2.resize, / 255.  The four entry points below do that work on device arrays.  They follow the rule
+ * written out here, which has the shape of OpenCV's fixed-point path (CV_16SC2 maps, INTER_BITS = 5) - cv2's own undistortion map
+ * differs between its versions and SIMD paths, and its bits are NOT claimed.  tests/image_prep_restate.py restates the rule in numpy;
+ * the kernels reproduce the restatement bit for bit.
+ * The rule.
+ *   1. Map.  Per image: K [3, 3] float64 row-major (fx = K[0], cx = K[2], fy = K[4], cy = K[5]; K[1], the skew, is not read - callers
+ *      refuse a value other than 0) and D [nd] float64 = (k1, k2, p1, p2[, k3[, k4, k5, k6]]), nd = 4, 5 or 8, missing terms 0.  For the
+ *      destination pixel (i, j) (row, column), directly from these inputs in float64, one rounding per operation, nothing fused and
+ *      nothing carried from pixel to pixel:
+ *          x = (j - cx) / fx          y = (i - cy) / fy          x2 = x x     y2 = y y     r2 = x2 + y2     t = (2 x) y
+ *          kr = (1 + ((k3 r2 + k2) r2 + k1) r2) / (1 + ((k6 r2 + k5) r2 + k4) r2)
+ *          xd = (x kr + p1 t) + p2 (r2 + 2 x2)          yd = (y kr + p1 (r2 + 2 y2)) + p2 t
+ *          us = (fx xd + cx) 32       vs = (fy yd + cy) 32
+ *      If us or vs is not finite or |us| >= 2^30 or |vs| >= 2^30 the pixel is an OUTSIDE pixel: every tap reads 0.  Otherwise
+ *      iu = rint(us), iv = rint(vs) (halves to even), sx = iu >> 5, ax = iu & 31, sy = iv >> 5, ay = iv & 31 (arithmetic shifts).
+ *   2. Taps.  s00 = src(sy, sx), s01 = src(sy, sx + 1), s10 = src(sy + 1, sx), s11 = src(sy + 1, sx + 1); a tap outside the image
+ *      reads 0.  Integer weights w00 = (32 - ay)(32 - ax), w01 = (32 - ay) ax, w10 = ay (32 - ax), w11 = ay ax (their sum is 1024).
+ *          uint8:    out = (s00 w00 + s01 w01 + s10 w10 + s11 w11 + 512) >> 10          (integers: no order)
+ *          float32:  out = ((s00 f00 + s01 f01) + s10 f10) + s11 f11,  f = float32(w) / 1024 (exact), float32, nothing fused.
+ *      Per channel, 1 or 3 interleaved channels.
+ *   3. Box morphology on uint8 [H, W], k = 1 ... 15: dst(y, x) = max (DSN_PREP_DILATE) or min (DSN_PREP_ERODE) of src(y - a + dy,
+ *      x - a + dx) over dy, dx = 0 ... k - 1 with the anchor a = k / 2 (integer division: an even box reaches k / 2 up and left and
+ *      k - 1 - k / 2 down and right); pixels outside the image do not take part.
+ *   4. Resize by c = 1, 2 or 4 (H and W multiples of c; output [H / c, W / c]).  DSN_PREP_NEAREST: dst(y, x) = src(c y, c x).
+ *      DSN_PREP_AREA over the block src(c y .. c y + c - 1, c x .. c x + c - 1) per channel: uint8 with the integer block sum s:
+ *      c = 2: (s + 2) >> 2 (half up); c = 4: s / 16 rounded half to even; float32: the block summed in row-major order in float32,
+ *      times float32(1 / c^2).  c = 1 copies.
+ *   5. The ZJU item (dsn_image_prep), in the reference's order: fg = (msk_cihp != 0) as 0 / 1; fg_u = undistort(fg) (rule 1-2, uint8:
+ *      1 where the weights of the foreground taps reach 512); msk_fg = dilate(fg_u, border); im = undistort(img) msk_fg; im_small =
+ *      area(im, c); msk_fg_small = nearest(msk_fg, c); msk_cihp_small = nearest(msk_cihp, c) - the RAW mask, not undistorted, as the
+ *      reference has it; out_img = float64(im_small) / 255.0 (one float64 division), for DSN_PREP_F32 rounded to float32 once more.
+ * Arrays: images [N, H, W] or [N, H, W, 3] (channels interleaved), contiguous; K [N, 3, 3], D [N, nd] float64, on the device.
+ * Kernels (csrc/dsn_prep.hip): workgroups of 256 threads own tiles of DSN_PREP_TILE_W x DSN_PREP_TILE_H pixels at full resolution of
+ * image blockIdx.z.  Morphology loads the tile with its halo into LDS and runs a row pass and a column pass.  dsn_image_prep is ONE
+ * launch: map and foreground bit of tile and halo into LDS (the halo's map is recomputed by the neighbouring workgroups, the tile's
+ * own is kept), the dilation from LDS, the image's taps times the mask, the c x c blocks from LDS, 16-byte stores of the float
+ * rows and 4-byte stores of the uint8 rows wherever a row starts on that grid.  No atomics, no workspace, one writer per element: the
+ * same bits every call; an image's outputs depend on that image's inputs only (a NaN in one K stays in its image, whose undistorted
+ * outputs are 0).
+ * N == 0: success, nothing is enqueued.  Rejected before anything is enqueued: N < 0 or > 65535, H or W outside 1 ... 32768, nd not
+ * 4 / 5 / 8, channels not 1 / 3, k or border outside 1 ... 15, c not 1 / 2 / 4 or not dividing H and W, an unknown dtype / op / mode,
+ * and - with N > 0 - a NULL required pointer or src == dst.  dsn_image_prep: out_img is required; out_img_u8 [N, H, W, 3] (im_small),
+ * out_msk_fg and out_msk_cihp [N, H, W] may each be NULL. */
+#define DSN_PREP_U8 0
+#define DSN_PREP_F32 1
+#define DSN_PREP_F64 2
+#define DSN_PREP_DILATE 0
+#define DSN_PREP_ERODE 1
+#define DSN_PREP_NEAREST 0
+#define DSN_PREP_AREA 1
+#define DSN_PREP_TILE_W 64
+#define DSN_PREP_TILE_H 16
+#define DSN_PREP_MAX_SIDE 32768
+DSN_EXPORT int dsn_image_undistort(const void* src, void* dst, const double* K, const double* D, int nd, int N, int H, int W,
+                                   int channels, int dtype, void* stream);
+DSN_EXPORT int dsn_image_morph(const uint8_t* src, uint8_t* dst, int N, int H, int W, int k, int op, void* stream);
+DSN_EXPORT int dsn_image_resize(const void* src, void* dst, int N, int H, int W, int channels, int dtype, int c, int mode,
+                                void* stream);
+DSN_EXPORT int dsn_image_prep(const uint8_t* img, const uint8_t* msk_cihp, const double* K, const double* D, int nd, int N, int H0,
+                              int W0, int c, int border, int out_dtype, void* out_img, uint8_t* out_img_u8, uint8_t* out_msk_fg,
+                              uint8_t* out_msk_cihp, void* stream);
+
 /* diagnostics, NOT for the hot path (synchronises `stream`): {ncell, ok, total entries, capacity} of the four
  * nearest-face list levels (world fine/coarse, canonical fine/coarse) into a HOST array of 16 int32. */
 DSN_EXPORT int dsn_debug_nn_stats(const void* scene, int V, int F, int32_t* out16_host, void* stream);
