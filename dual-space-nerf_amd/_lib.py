@@ -60,6 +60,7 @@ EXPORTS = [
     "dsn_body_shape", "dsn_body_pose_workspace_bytes", "dsn_body_pose",
     "dsn_grad_workspace_layout",
     "dsn_image_undistort", "dsn_image_morph", "dsn_image_resize", "dsn_image_prep",
+    "dsn_lpips_packed_bytes", "dsn_lpips_pack", "dsn_lpips_workspace_bytes", "dsn_lpips_features", "dsn_lpips",
 ]
 
 SKIP_TRANSPARENT = 1
@@ -85,6 +86,10 @@ TRAIN_RAYS_OK, TRAIN_RAYS_EMPTY_CLASS, TRAIN_RAYS_SHORT, TRAIN_RAYS_BAD_CAMERA =
 TRAIN_RAYS_MAX_ROUNDS, TRAIN_RAYS_MAX_RAYS = 64, 65536
 SSIM_OK, SSIM_CROP_TOO_SMALL, SSIM_EMPTY_MASK = 0, 1, 2     # dsn_image_ssim's out_status (DSN_SSIM_*)
 LOSS_L2, LOSS_SMOOTH_L1 = 0, 1      # dsn_train_loss' kind (DSN_LOSS_*)
+LPIPS_NETS = {"alex": 0, "vgg": 1}                                          # DSN_LPIPS_ALEX / DSN_LPIPS_VGG
+LPIPS_OK, LPIPS_TOO_SMALL, LPIPS_RANGE, LPIPS_NONFINITE = 0, 1, 2, 4        # dsn_lpips' out_status: an OR of DSN_LPIPS_*
+LPIPS_RANGE_MAX, LPIPS_TILE_M = 32768.0, 64                                 # DSN_LPIPS_RANGE_MAX / DSN_LPIPS_TILE_M
+LPIPS_WORKSPACE_CAP = 8 << 30       # lpips() / lpips_features() chunk their stacks so that one call's workspace stays below this
 LOSS_SHARE = 256                    # rays per workgroup of dsn_train_loss' forward (DSN_LOSS_SHARE)
 FRAME_FINE_ONLY = 1           # dsn_set_frame_ex: only the fine nearest-face level of the posed mesh (points beyond it: exhaustive sweep)
 FRAME_LAZY_LISTS = 2          # dsn_set_frame_ex: grid geometry only - the frame that uses the level builds the lists of the cells it visits
@@ -200,6 +205,13 @@ def lib():
         L.dsn_image_morph.argtypes = [C.c_void_p] * 2 + [C.c_int] * 5 + [C.c_void_p]
         L.dsn_image_resize.argtypes = [C.c_void_p] * 2 + [C.c_int] * 7 + [C.c_void_p]
         L.dsn_image_prep.argtypes = [C.c_void_p] * 4 + [C.c_int] * 7 + [C.c_void_p] * 5
+        L.dsn_lpips_packed_bytes.restype = C.c_size_t
+        L.dsn_lpips_packed_bytes.argtypes = [C.c_int]
+        L.dsn_lpips_workspace_bytes.restype = C.c_size_t
+        L.dsn_lpips_workspace_bytes.argtypes = [C.c_int] * 4
+        L.dsn_lpips_pack.argtypes = [C.c_int] + [C.c_void_p] * 5
+        L.dsn_lpips_features.argtypes = [C.c_void_p, C.c_int, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 3 + [C.c_size_t, C.c_void_p]
+        L.dsn_lpips.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 3 + [C.c_int] * 4 + [C.c_void_p] * 4 + [C.c_size_t, C.c_void_p]
         if L.dsn_abi_version() != 8:
             raise RuntimeError(f"{LIB_PATH} has ABI version {L.dsn_abi_version()}, this binding needs 8 - rebuild it "
                                "(python dual-space-nerf_amd/build.py)")
@@ -2212,6 +2224,140 @@ def ssim_status_error(status, rect):
     x, y, w, h = (int(v) for v in rect)
     what = "the mask is empty" if int(status) == SSIM_EMPTY_MASK else f"the mask's bounding rectangle is {w} x {h}"
     return ValueError(f"ssim: win_size exceeds image extent ({what}; SSIM needs at least 7 x 7)")
+
+
+# ---- LPIPS (include/dsnerf.h "LPIPS"; csrc/dsn_lpips.hip) ----
+LPIPS_CONV_SHAPES = {
+    "alex": [(64, 3, 11, 11), (192, 64, 5, 5), (384, 192, 3, 3), (256, 384, 3, 3), (256, 256, 3, 3)],
+    "vgg": [(64, 3, 3, 3), (64, 64, 3, 3), (128, 64, 3, 3), (128, 128, 3, 3), (256, 128, 3, 3), (256, 256, 3, 3), (256, 256, 3, 3),
+            (512, 256, 3, 3), (512, 512, 3, 3), (512, 512, 3, 3), (512, 512, 3, 3), (512, 512, 3, 3), (512, 512, 3, 3)],
+}
+LPIPS_TAP_CHANNELS = {"alex": (64, 192, 384, 256, 256), "vgg": (64, 128, 256, 512, 512)}
+LPIPS_MIN_SIDE = {"alex": 31, "vgg": 16}
+
+
+def lpips_tap_shapes(net, H, W):
+    """[(C, h, w)] of the five taps of an H x W image (None below the net's smallest image)"""
+    if H < LPIPS_MIN_SIDE[net] or W < LPIPS_MIN_SIDE[net]:
+        return None
+    if net == "alex":
+        s = lambda n: (n + 4 - 11) // 4 + 1      # noqa: E731
+        p = lambda n: (n - 3) // 2 + 1           # noqa: E731
+        sides = [(s(H), s(W)), (p(s(H)), p(s(W)))] + [(p(p(s(H))), p(p(s(W))))] * 3
+    else:
+        sides = [(H >> k, W >> k) for k in range(5)]
+    return [(c, h, w) for c, (h, w) in zip(LPIPS_TAP_CHANNELS[net], sides)]
+
+
+def _lpips_net(net):
+    if net not in LPIPS_NETS:
+        raise ValueError(f"net must be 'alex' or 'vgg', got {net!r}")
+    return LPIPS_NETS[net]
+
+
+def _ptr_array(tensors):
+    return (C.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+
+
+def lpips_check_weights(net, conv, lin):
+    """shape check of the canonical weight lists: conv = [(weight [Cout,Cin,k,k], bias [Cout]) ...] in layer order, lin = five [C_l]
+    vectors (any shape with C_l elements); raises ValueError naming the tensor"""
+    _lpips_net(net)
+    shapes = LPIPS_CONV_SHAPES[net]
+    if len(conv) != len(shapes) or len(lin) != 5:
+        raise ValueError(f"lpips {net}: {len(shapes)} convolutions and 5 lin vectors expected, got {len(conv)} and {len(lin)}")
+    for i, ((w, b), sh) in enumerate(zip(conv, shapes)):
+        if tuple(w.shape) != sh:
+            raise ValueError(f"lpips {net}: convolution {i} weight must be {sh}, got {tuple(w.shape)}")
+        if tuple(b.shape) != (sh[0],):
+            raise ValueError(f"lpips {net}: convolution {i} bias must be {(sh[0],)}, got {tuple(b.shape)}")
+    for l, (w, c) in enumerate(zip(lin, LPIPS_TAP_CHANNELS[net])):
+        if int(math.prod(w.shape)) != c:
+            raise ValueError(f"lpips {net}: lin {l} must hold {c} weights, got {tuple(w.shape)}")
+
+
+def lpips_pack(net, conv, lin, device):
+    """dsn_lpips_pack: the canonical weight lists (lpips_check_weights) -> the packed device image (uint8 tensor)"""
+    require_gpu()
+    lpips_check_weights(net, conv, lin)
+    dev = torch.device(device)
+    cw = [_f32(torch.as_tensor(w), dev) for w, _ in conv]
+    cb = [_f32(torch.as_tensor(b), dev) for _, b in conv]
+    lw = [_f32(torch.as_tensor(w).reshape(-1), dev) for w in lin]
+    packed = _scratch(lib().dsn_lpips_packed_bytes(_lpips_net(net)), dev)
+    with torch.cuda.device(dev):
+        _check(lib().dsn_lpips_pack(_lpips_net(net), _ptr_array(cw), _ptr_array(cb), _ptr_array(lw), _ptr(packed), _stream()), "dsn_lpips_pack")
+        for t in cw + cb + lw:          # the kernels read them on the current stream after this function has dropped them
+            t.record_stream(torch.cuda.current_stream())
+    return packed
+
+
+def _lpips_chunk(net, n_frames, H, W, per_frame=1):
+    """frames per call so that the workspace stays below LPIPS_WORKSPACE_CAP (at least one)"""
+    one = lib().dsn_lpips_workspace_bytes(_lpips_net(net), 1, H, W)
+    if one == 0:
+        raise ValueError(f"lpips: bad sizes ({n_frames} x {H} x {W})")
+    most = max(1, min(n_frames, int(LPIPS_WORKSPACE_CAP // max(one, 1))))
+    calls = -(-n_frames // most)
+    return -(-n_frames // calls)          # even chunks: 16 frames under a cap of 15 go as 8 + 8
+
+
+def lpips_features(net, packed, stack, rgb_pm1=False):
+    """dsn_lpips_features: stack [n,H,W,3] float32 on the device -> (five float32 tensors [n,C,h,w], status int32 [n]); no
+    synchronisation.  Below the net's smallest image the taps are empty tensors and every status is LPIPS_TOO_SMALL."""
+    if stack.dim() != 4 or stack.shape[-1] != 3 or stack.dtype != torch.float32:
+        raise ValueError(f"lpips_features: stack must be float32 [n,H,W,3], got {stack.dtype} {tuple(stack.shape)}")
+    dev = stack.device
+    stack = stack.contiguous()
+    n, H, W, _ = stack.shape
+    shapes = lpips_tap_shapes(net, H, W)
+    status = _output((n,), torch.int32, dev)
+    taps = [_output((n, c, h, w), torch.float32, dev) for c, h, w in shapes] if shapes else [torch.empty(n, c, 0, 0, device=dev)
+                                                                                            for c in LPIPS_TAP_CHANNELS[net]]
+    step = 2 * _lpips_chunk(net, (n + 1) // 2, H, W)
+    nbytes = lib().dsn_lpips_workspace_bytes(_lpips_net(net), step // 2, H, W)
+    ws = _scratch(nbytes, dev)
+    dummy = [status] * 5
+    for i in range(0, n, step):
+        m = min(step, n - i)
+        outs = [t[i:i + m] for t in taps] if shapes else dummy
+        _check(lib().dsn_lpips_features(_ptr(packed), _lpips_net(net), _ptr(stack[i:i + m]), m, H, W, int(bool(rgb_pm1)), _ptr_array(outs),
+                                        _ptr(status[i:i + m]), _ptr(ws), nbytes, _stream()), "dsn_lpips_features")
+    return taps, status
+
+
+def lpips(net, packed, img, gt, rgb_pm1=False):
+    """dsn_lpips: img [F,H,W,3] (or [H,W,3]) float32 and gt of the same shape (float64 or float32) on the device -> (out float64 [F],
+    layers float64 [F,5], status int32 [F]); no synchronisation.  A frame whose status is not LPIPS_OK is NaN."""
+    if img.dim() not in (3, 4) or img.shape[-1] != 3 or img.dtype != torch.float32:
+        raise ValueError(f"lpips: img must be float32 [H,W,3] or [F,H,W,3], got {img.dtype} {tuple(img.shape)}")
+    dev = img.device
+    img = img.reshape(-1, *img.shape[-3:]).contiguous()
+    F, H, W, _ = img.shape
+    gt = gt.to(dev).reshape(F, H, W, 3).contiguous()
+    if gt.dtype not in (torch.float64, torch.float32):
+        raise TypeError(f"lpips: gt must be float64 or float32, got {gt.dtype}")
+    out = _output((F,), torch.float64, dev)
+    layers = _output((F, 5), torch.float64, dev)
+    status = _output((F,), torch.int32, dev)
+    step = _lpips_chunk(net, F, H, W)
+    nbytes = lib().dsn_lpips_workspace_bytes(_lpips_net(net), step, H, W)
+    ws = _scratch(nbytes, dev)
+    for i in range(0, F, step):
+        m = min(step, F - i)
+        g = gt[i:i + m]
+        g64, g32 = (g, None) if g.dtype == torch.float64 else (None, g)
+        _check(lib().dsn_lpips(_ptr(packed), _lpips_net(net), _ptr(img[i:i + m]), _ptr(g64), _ptr(g32), m, H, W, int(bool(rgb_pm1)),
+                               _ptr(out[i:i + m]), _ptr(layers[i:i + m]), _ptr(status[i:i + m]), _ptr(ws), nbytes, _stream()), "dsn_lpips")
+    return out, layers, status
+
+
+def lpips_status_text(status):
+    s = int(status)
+    names = [n for bit, n in ((LPIPS_TOO_SMALL, "the image is below the net's smallest size"),
+                              (LPIPS_RANGE, "an activation or weight left the split-fp16 range (|v| >= 32768)"),
+                              (LPIPS_NONFINITE, "a pixel is NaN or infinite")) if s & bit]
+    return "; ".join(names) if names else "ok"
 
 
 def _loss_args(color, target, acc, occupancy, kind):

@@ -1187,10 +1187,13 @@ class Renderer:
                 results[k] = checked
         return results
 
-    def image_metrics(self, color_img, batch, clamp=True, ssim=False):
+    def image_metrics(self, color_img, batch, clamp=True, ssim=False, lpips=None):
         """test.py:62-71 on the device: clamp to [0,1], psnr with and without mask_at_box against batch["img"].
         ssim=True adds "ssim": test.py:73-75's metrics.py ssim_metric of the same clamped image (dsn_image_ssim); it raises
         ValueError where skimage's compare_ssim would (a mask whose bounding rectangle is narrower or lower than 7 pixels).
+        lpips={"alex": net, "vgg": net} (dsnerf_amd.lpips.LPIPS objects; either key alone will do) adds "lpips_alex" / "lpips_vgg":
+        test.py:77-91's distances of the same clamped image (dsn_lpips); ValueError for a frame with a status (image below the
+        net's smallest size, a non-finite pixel, the split-fp16 range left).
         Returns a dict of python floats (one device->host copy)."""
         img = color_img.to(self.device)
         if clamp:
@@ -1201,13 +1204,18 @@ class Renderer:
         if ssim:
             s, rect, status = _lib.image_ssim(img, gt, mask.reshape(img.shape[:2]))
             m = torch.cat([m, s, status.double(), rect.reshape(-1).double()])
-        return self._metrics_dicts(m[None].cpu())[0]
+        names = self._lpips_names(lpips)
+        for name in names:
+            d, _, st = lpips[name].to(self.device).distance(img.to(torch.float32), gt)
+            m = torch.cat([m, d, st.double()])
+        return self._metrics_dicts(m[None].cpu(), lpips_names=names)[0]
 
-    def image_metrics_views(self, images, batches, clamp=True, ssim=True):
+    def image_metrics_views(self, images, batches, clamp=True, ssim=True, lpips=None):
         """image_metrics over a sequence: `images` are the [H,W,3] colour images of `batches` (e.g. the "coarse_color" tensors of
-        render_views(batches, device_output=True)).  Frames of one size go through dsn_image_ssim together; psnr is
-        dsn_image_psnr per frame; the whole sequence's numbers come back in ONE device->host copy.  Returns one dict per frame
-        with image_metrics' keys; raises ValueError (naming the frame) where image_metrics would."""
+        render_views(batches, device_output=True)).  Frames of one size go through dsn_image_ssim (and, with lpips={"alex": net,
+        "vgg": net}, dsn_lpips) together; psnr is dsn_image_psnr per frame; the whole sequence's numbers come back in ONE
+        device->host copy.  Returns one dict per frame with image_metrics' keys; raises ValueError (naming the frame) where
+        image_metrics would."""
         images, batches = list(images), list(batches)
         if len(images) != len(batches):
             raise ValueError(f"image_metrics_views: {len(images)} images for {len(batches)} batches")
@@ -1220,6 +1228,7 @@ class Renderer:
             gts.append(self._metrics_gt(batch))
             masks.append(self._dev(batch["mask_at_box"][0], torch.uint8).reshape(img.shape[:2]))
         rows = [None] * len(imgs)
+        names = self._lpips_names(lpips)
         groups = {}
         for k, (img, gt) in enumerate(zip(imgs, gts)):
             groups.setdefault((tuple(img.shape), gt.dtype), []).append(k)
@@ -1229,26 +1238,46 @@ class Renderer:
             mask = torch.stack([masks[k] for k in ks]).contiguous()
             if ssim:
                 s, rect, status = _lib.image_ssim(img, gt, mask)
+            dist = [lpips[name].to(self.device).distance(img.to(torch.float32), gt) for name in names]
             for j, k in enumerate(ks):
                 m = _lib.image_psnr(img[j], gt[j], mask[j])
                 rows[k] = torch.cat([m, s[j:j + 1], status[j:j + 1].double(), rect[j].double()]) if ssim else m
-        return self._metrics_dicts(torch.stack(rows).cpu(), views=True)
+                for d, _, st in dist:
+                    rows[k] = torch.cat([rows[k], d[j:j + 1], st[j:j + 1].double()])
+        return self._metrics_dicts(torch.stack(rows).cpu(), views=True, lpips_names=names)
 
     def _metrics_gt(self, batch):
         gt = batch["img"][0]
         return self._dev(gt, gt.dtype if gt.dtype in (torch.float32, torch.float64) else torch.float32)   # staged upload (6 MB of float64)
 
     @staticmethod
-    def _metrics_dicts(rows, views=False):
-        """host rows {mse_all, mse_masked, psnr_all, psnr_masked[, ssim, status, x, y, w, h]} -> image_metrics' dicts"""
+    def _lpips_names(lpips):
+        if not lpips:
+            return ()
+        unknown = [k for k in lpips if k not in ("alex", "vgg")]
+        if unknown:
+            raise ValueError(f"lpips: the keys are 'alex' and 'vgg', got {unknown}")
+        return tuple(k for k in ("alex", "vgg") if k in lpips)
+
+    @staticmethod
+    def _metrics_dicts(rows, views=False, lpips_names=()):
+        """host rows {mse_all, mse_masked, psnr_all, psnr_masked[, ssim, status, x, y, w, h][, lpips, status per net]} ->
+        image_metrics' dicts"""
         out = []
         for k, r in enumerate(rows.tolist()):
             d = {"mse": r[0], "mse_wMask": r[1], "psnr_woMask": r[2], "psnr_wMask": r[3]}
-            if len(r) > 4:
+            tail = len(r) - 2 * len(lpips_names)
+            if tail > 4:
                 if int(r[5]) != _lib.SSIM_OK:
                     e = _lib.ssim_status_error(int(r[5]), r[6:10])
                     raise ValueError(f"frame {k}: {e}") if views else e
                 d["ssim"] = r[4]
+            for j, name in enumerate(lpips_names):
+                value, status = r[tail + 2 * j], int(r[tail + 2 * j + 1])
+                if status != _lib.LPIPS_OK:
+                    e = ValueError(f"lpips_{name}: {_lib.lpips_status_text(status)}")
+                    raise ValueError(f"frame {k}: {e}") if views else e
+                d[f"lpips_{name}"] = value
             out.append(d)
         return out
 

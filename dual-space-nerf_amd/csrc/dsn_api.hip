@@ -1923,4 +1923,48 @@ int dsn_image_prep(const uint8_t* img, const uint8_t* msk_cihp, const double* K,
     return dsn_check_launch("dsn_image_prep");
 }
 
+// ---- LPIPS (csrc/dsn_lpips.hip) ----
+static bool dsn_lpips_sizes_ok(int net, int n, int H, int W) {
+    return (net == DSN_LPIPS_ALEX || net == DSN_LPIPS_VGG) && n >= 1 && n <= DSN_LPIPS_MAX_IMAGES / 2 && H >= 1 && W >= 1 &&
+           H <= DSN_LPIPS_MAX_SIDE && W <= DSN_LPIPS_MAX_SIDE;
+}
+size_t dsn_lpips_packed_bytes(int net) { return net == DSN_LPIPS_ALEX || net == DSN_LPIPS_VGG ? dsn_lpips_packed_size(net) : 0; }
+size_t dsn_lpips_workspace_bytes(int net, int F, int H, int W) {
+    return dsn_lpips_sizes_ok(net, F, H, W) ? dsn_lpips_workspace_size(net, 2 * F, H, W) : 0;
+}
+
+int dsn_lpips_pack(int net, const float* const* conv_w, const float* const* conv_b, const float* const* lin_w, void* packed, void* stream) {
+    DSN_REQUIRE(net == DSN_LPIPS_ALEX || net == DSN_LPIPS_VGG, "dsn_lpips_pack: net must be DSN_LPIPS_ALEX or DSN_LPIPS_VGG");
+    DSN_REQUIRE(conv_w && conv_b && lin_w && packed, "dsn_lpips_pack: null argument");
+    const int nconv = net == DSN_LPIPS_ALEX ? 5 : 13;
+    for (int i = 0; i < nconv; ++i) DSN_REQUIRE(conv_w[i] && conv_b[i], "dsn_lpips_pack: null convolution tensor");
+    for (int l = 0; l < 5; ++l) DSN_REQUIRE(lin_w[l], "dsn_lpips_pack: null lin tensor");
+    DSN_REQUIRE(((uintptr_t)packed & 255) == 0, "dsn_lpips_pack: packed is not 256-byte aligned");
+    if (dsn_launch_lpips_pack(net, conv_w, conv_b, lin_w, packed, (hipStream_t)stream)) return dsn_fail("%s", "dsn_lpips_pack: memset failed");
+    return dsn_check_launch("dsn_lpips_pack");
+}
+
+int dsn_lpips_features(const void* packed, int net, const float* stack, int n, int H, int W, int rgb_pm1, float* const* out_taps5,
+                       int32_t* out_status, void* workspace, size_t workspace_bytes, void* stream) {
+    DSN_REQUIRE(packed && stack && out_taps5 && out_status && workspace, "dsn_lpips_features: null argument");
+    DSN_REQUIRE((net == DSN_LPIPS_ALEX || net == DSN_LPIPS_VGG) && n >= 1 && n <= DSN_LPIPS_MAX_IMAGES && H >= 1 && W >= 1 &&
+                    H <= DSN_LPIPS_MAX_SIDE && W <= DSN_LPIPS_MAX_SIDE, "dsn_lpips_features: bad sizes");
+    for (int l = 0; l < 5; ++l) DSN_REQUIRE(out_taps5[l], "dsn_lpips_features: null tap pointer");
+    DSN_REQUIRE((((uintptr_t)packed | (uintptr_t)workspace) & 255) == 0, "dsn_lpips_features: packed / workspace not 256-byte aligned");
+    DSN_REQUIRE(workspace_bytes >= dsn_lpips_workspace_size(net, n, H, W), "dsn_lpips_features: workspace_bytes too small for n images");
+    dsn_launch_lpips_features(packed, net, stack, n, H, W, rgb_pm1 != 0, out_taps5, out_status, workspace, (hipStream_t)stream);
+    return dsn_check_launch("dsn_lpips_features");
+}
+
+int dsn_lpips(const void* packed, int net, const float* img, const double* gt_f64, const float* gt_f32, int F, int H, int W, int rgb_pm1,
+              double* out, double* out_layers, int32_t* out_status, void* workspace, size_t workspace_bytes, void* stream) {
+    DSN_REQUIRE(packed && img && out && out_layers && out_status && workspace, "dsn_lpips: null argument");
+    DSN_REQUIRE((gt_f64 != nullptr) != (gt_f32 != nullptr), "dsn_lpips: exactly one ground-truth pointer");
+    DSN_REQUIRE(dsn_lpips_sizes_ok(net, F, H, W), "dsn_lpips: bad sizes");
+    DSN_REQUIRE((((uintptr_t)packed | (uintptr_t)workspace) & 255) == 0, "dsn_lpips: packed / workspace not 256-byte aligned");
+    DSN_REQUIRE(workspace_bytes >= dsn_lpips_workspace_size(net, 2 * F, H, W), "dsn_lpips: workspace_bytes below dsn_lpips_workspace_bytes");
+    dsn_launch_lpips(packed, net, img, gt_f64, gt_f32, F, H, W, rgb_pm1 != 0, out, out_layers, out_status, workspace, (hipStream_t)stream);
+    return dsn_check_launch("dsn_lpips");
+}
+
 }  // extern "C"

@@ -207,6 +207,16 @@ void dsn_launch_image_psnr(const float* img_rgb, const double* gt64, const float
 size_t dsn_image_ssim_workspace_size(int F, int H, int W);
 void dsn_launch_image_ssim(const float* img_rgb, const double* gt64, const float* gt32, const uint8_t* mask, int F, int H, int W,
                            int clamp_rgb, double* out_ssim, int32_t* out_rect, int32_t* out_status, void* workspace, hipStream_t st);
+// dsn_lpips.hip: test.py's LPIPS distances (dsn_lpips_*; arguments checked by the entry points; N images = 2 F for the distance)
+size_t dsn_lpips_packed_size(int net);
+size_t dsn_lpips_workspace_size(int net, int N, int H, int W);
+int dsn_lpips_min_side(int net);
+int dsn_launch_lpips_pack(int net, const float* const* conv_w, const float* const* conv_b, const float* const* lin_w, void* packed,
+                          hipStream_t st);
+void dsn_launch_lpips_features(const void* packed, int net, const float* stack, int N, int H, int W, int rgb_pm1, float* const* out_taps,
+                               int32_t* status, void* workspace, hipStream_t st);
+void dsn_launch_lpips(const void* packed, int net, const float* img, const double* gt64, const float* gt32, int F, int H, int W, int rgb_pm1,
+                      double* out, double* out_layers, int32_t* status, void* workspace, hipStream_t st);
 // dsn_loss.hip: the trainer's loss and its two seed arrays (dsn_train_loss / dsn_train_loss_grad)
 size_t dsn_train_loss_workspace_size(int64_t R);
 void dsn_launch_train_loss(const float* color, const float* t32, const double* t64, float* acc, const uint8_t* o8, const float* o32,

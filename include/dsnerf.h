@@ -1280,6 +1280,62 @@ DSN_EXPORT int dsn_image_prep(const uint8_t* img, const uint8_t* msk_cihp, const
                               int W0, int c, int border, int out_dtype, void* out_img, uint8_t* out_img_u8, uint8_t* out_msk_fg,
                               uint8_t* out_msk_cihp, void* stream);
 
+/* ---- LPIPS: test.py:18-23, 77-91's lpips_alex / lpips_vgg on the device (csrc/dsn_lpips.hip; additions within ABI 8) ----
+ * The rule follows the `lpips` package v0.1, LPIPS(net = 'alex' | 'vgg', lpips = True, spatial = False) in eval mode, as test.py calls it.
+ * PARITY WITH THE PACKAGE IS UNVERIFIED: neither lpips nor torchvision was available where this was written; the kernels are pinned to
+ * the restatement of this rule (tests/lpips_restate.py), and tests/test_lpips_package.py compares with the package where it imports.
+ *   Inputs.  Two stacks [F, H, W, 3] on the device: img float32, BGR in [0, 1], clamped by the caller (as for dsn_image_psnr); gt float64
+ *      or float32, cast to float32 first (test.py:80's .float()).  Per pixel and channel, float32, one rounding per operation:
+ *      x = 2 v - 1; the channel order reversed (flip(1): BGR -> RGB); then (x - shift) / scale with shift = (-.030, -.088, -.188),
+ *      scale = (.458, .448, .450) for R, G, B.  rgb_pm1 != 0: the stacks are RGB in [-1, 1] already (the package's own call surface):
+ *      no 2 v - 1, no flip.
+ *   Backbones.  Convolutions with zero padding, bias, ReLU; output side floor((n + 2 p - k) / s) + 1; max pooling in floor mode,
+ *      floor((n - k) / s) + 1.  DSN_LPIPS_ALEX: conv 3->64 k11 s4 p2, pool 3/2, conv 64->192 k5 p2, pool 3/2, conv 192->384 k3 p1, conv
+ *      384->256 k3 p1, conv 256->256 k3 p1; taps behind each of the five ReLUs (64, 192, 384, 256, 256 channels).  DSN_LPIPS_VGG:
+ *      torchvision VGG-16 `features`: 3 x 3 p1 convolutions of 64, 64 | 128, 128 | 256, 256, 256 | 512, 512, 512 | 512, 512, 512 channels
+ *      with a 2/2 pool between the groups; taps relu1_2, relu2_2, relu3_3, relu4_3, relu5_3 (64, 128, 256, 512, 512 channels).
+ *   Smallest image: 31 x 31 (alex), 16 x 16 (vgg); below it the package raises inside a pooling layer: DSN_LPIPS_TOO_SMALL and NaN.
+ *   Head, per tap l: n = f / (sqrt(sum_c f^2) + 1e-10) per pixel (the eps outside the root: an all-zero vector gives 0);
+ *      d_l = mean over the pixels of sum_c w_l[c] (n0 - n1)^2 with the tap's lin weights (1 x 1, no bias); the result is sum_l d_l.
+ *      The head reads the float32 features and computes in float64: a wave per pixel, channels across its lanes, butterfly sums;
+ *      a workgroup per share of the pixels (shares: a function of the tap's size alone), partials added in index order.
+ *   Convolution arithmetic: fp32-equivalent on the split-fp16 scheme of csrc/dsn_field16.hip: every operand v = hi + lo 2^-12 (hi =
+ *      fp16(v), lo = fp16((v - hi) 2^12): 22 significand bits), W.x = W_hi x_hi + 2^-12 (W_hi x_lo + W_lo x_hi) in three
+ *      v_mfma_f32_32x32x16_f16 products with fp32 accumulation; implicit GEMM with M = output pixels of one image (tiles of
+ *      DSN_LPIPS_TILE_M), N = output channels, k = (ky kw + kx) Cin + ci padded to 16; one kernel for all 18 shapes.
+ *   Range.  The split covers |v| < DSN_LPIPS_RANGE_MAX = 32 768 (beyond it lo leaves fp16).  An activation outside it (NaN
+ *      included) sets DSN_LPIPS_RANGE for its frame; a weight or bias outside it sets DSN_LPIPS_RANGE for every frame evaluated with
+ *      that packed image; the frame's results are NaN.  There is no exact-fp32 fallback.  Values below 2^-36 in magnitude lose their lo part.
+ *   Non-finite input: a NaN or infinite pixel sets DSN_LPIPS_NONFINITE for its frame (result NaN); other frames are not touched.
+ *   Determinism: no float atomics (status bits are integer ORs); the same bits on every call; a frame gives the same bits alone or in
+ *      any batch; d(a, b) and d(b, a) are bit-identical (both through the float32 path); identical images give exactly 0.0.
+ * dsn_lpips_pack: conv_w / conv_b: HOST arrays of 5 (alex) or 13 (vgg) device pointers, float32 [Cout, Cin, k, k] / [Cout] in layer
+ *   order; lin_w: host array of 5 device pointers, float32 [C_l].  packed: dsn_lpips_packed_bytes(net) bytes of device memory.
+ * dsn_lpips_features: the five taps of stack [n, H, W, 3] float32 (interpreted as img is) as float32 [n, C_l, h_l, w_l] into the five
+ *   device pointers of the host array out_taps5; out_status [n].  An image with a status has NaN taps (TOO_SMALL: taps untouched).
+ * dsn_lpips: out [F], out_layers [F, 5] float64 (the d_l; they sum to out in index order), out_status [F] int32 (OR of DSN_LPIPS_*).
+ * workspace: dsn_lpips_workspace_bytes(net, F, H, W) bytes (0 for bad sizes) serve F frames = 2 F images; it may hold anything on
+ *   entry.  Kernels only: no allocation, no host copy, no synchronisation.  All device pointers 256-byte aligned where noted. */
+#define DSN_LPIPS_ALEX 0
+#define DSN_LPIPS_VGG 1
+#define DSN_LPIPS_OK 0
+#define DSN_LPIPS_TOO_SMALL 1
+#define DSN_LPIPS_RANGE 2
+#define DSN_LPIPS_NONFINITE 4
+#define DSN_LPIPS_RANGE_MAX 32768.0f
+#define DSN_LPIPS_TILE_M 64
+#define DSN_LPIPS_MAX_SIDE 4096
+#define DSN_LPIPS_MAX_IMAGES 65534
+DSN_EXPORT size_t dsn_lpips_packed_bytes(int net);
+DSN_EXPORT int dsn_lpips_pack(int net, const float* const* conv_w, const float* const* conv_b, const float* const* lin_w, void* packed,
+                              void* stream);
+DSN_EXPORT size_t dsn_lpips_workspace_bytes(int net, int F, int H, int W);
+DSN_EXPORT int dsn_lpips_features(const void* packed, int net, const float* stack, int n, int H, int W, int rgb_pm1,
+                                  float* const* out_taps5, int32_t* out_status, void* workspace, size_t workspace_bytes, void* stream);
+DSN_EXPORT int dsn_lpips(const void* packed, int net, const float* img, const double* gt_f64, const float* gt_f32, int F, int H, int W,
+                         int rgb_pm1, double* out, double* out_layers, int32_t* out_status, void* workspace, size_t workspace_bytes,
+                         void* stream);
+
 /* diagnostics, NOT for the hot path (synchronises `stream`): {ncell, ok, total entries, capacity} of the four
  * nearest-face list levels (world fine/coarse, canonical fine/coarse) into a HOST array of 16 int32. */
 DSN_EXPORT int dsn_debug_nn_stats(const void* scene, int V, int F, int32_t* out16_host, void* stream);
