@@ -61,6 +61,7 @@ EXPORTS = [
     "dsn_grad_workspace_layout",
     "dsn_image_undistort", "dsn_image_morph", "dsn_image_resize", "dsn_image_prep",
     "dsn_lpips_packed_bytes", "dsn_lpips_pack", "dsn_lpips_workspace_bytes", "dsn_lpips_features", "dsn_lpips",
+    "dsn_jpeg_max_bytes", "dsn_jpeg_workspace_bytes", "dsn_jpeg_header_host", "dsn_jpeg_coefficients", "dsn_jpeg_scan", "dsn_jpeg_encode",
 ]
 
 SKIP_TRANSPARENT = 1
@@ -212,6 +213,15 @@ def lib():
         L.dsn_lpips_pack.argtypes = [C.c_int] + [C.c_void_p] * 5
         L.dsn_lpips_features.argtypes = [C.c_void_p, C.c_int, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 3 + [C.c_size_t, C.c_void_p]
         L.dsn_lpips.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 3 + [C.c_int] * 4 + [C.c_void_p] * 4 + [C.c_size_t, C.c_void_p]
+        L.dsn_jpeg_max_bytes.restype = C.c_size_t
+        L.dsn_jpeg_max_bytes.argtypes = [C.c_int] * 3
+        L.dsn_jpeg_workspace_bytes.restype = C.c_size_t
+        L.dsn_jpeg_workspace_bytes.argtypes = [C.c_int] * 4
+        L.dsn_jpeg_header_host.argtypes = [C.c_int] * 4 + [C.c_void_p, C.c_int, C.c_void_p]
+        L.dsn_jpeg_coefficients.argtypes = [C.c_void_p] + [C.c_int] * 7 + [C.c_float] + [C.c_void_p] * 3
+        L.dsn_jpeg_scan.argtypes = [C.c_void_p] * 2 + [C.c_int] * 5 + [C.c_void_p, C.c_size_t] + [C.c_void_p] * 3 + [C.c_size_t, C.c_void_p]
+        L.dsn_jpeg_encode.argtypes = ([C.c_void_p] + [C.c_int] * 7 + [C.c_float] + [C.c_void_p, C.c_size_t] + [C.c_void_p] * 3
+                                      + [C.c_size_t, C.c_void_p])
         if L.dsn_abi_version() != 8:
             raise RuntimeError(f"{LIB_PATH} has ABI version {L.dsn_abi_version()}, this binding needs 8 - rebuild it "
                                "(python dual-space-nerf_amd/build.py)")
@@ -2778,3 +2788,126 @@ def image_prep(img_u8, msk_cihp, K, D, c=2, border=5, dtype=torch.float64, want_
         _check(lib().dsn_image_prep(p(img_u8), p(msk_cihp), p(Kd), p(Dd), Dd.shape[1], N, H0, W0, c, int(border),
                                     PREP_F64 if dtype == torch.float64 else PREP_F32, p(img), p(u8), p(fg), p(ci), _stream()), "dsn_image_prep")
     return img, u8, fg, ci
+
+
+# ---- baseline JPEG (dsn_jpeg_*: the rule of include/dsnerf.h) ----------------------------------------------------------------------------
+JPEG_420, JPEG_444, JPEG_GRAY = 0, 1, 2          # DSN_JPEG_*
+JPEG_U8, JPEG_F32 = 0, 1
+JPEG_NONFINITE, JPEG_OVERFLOW = 1, 2
+JPEG_MODES = {"420": JPEG_420, "444": JPEG_444, "gray": JPEG_GRAY, "grey": JPEG_GRAY}
+
+
+def jpeg_mode(subsampling, channels):
+    """the DSN_JPEG_* mode of an image with `channels` channels: one channel is always a one-component file"""
+    if channels == 1:
+        return JPEG_GRAY
+    m = JPEG_MODES.get(str(subsampling))
+    if m is None or m == JPEG_GRAY:
+        raise ValueError(f"jpeg: subsampling of a three-channel image must be '420' or '444', got {subsampling!r}")
+    return m
+
+
+def jpeg_blocks(H, W, mode):
+    """8 x 8 blocks of a frame's scan, dummy blocks included"""
+    s = 16 if mode == JPEG_420 else 8
+    return ((W + s - 1) // s) * ((H + s - 1) // s) * {JPEG_420: 6, JPEG_444: 3, JPEG_GRAY: 1}[mode]
+
+
+def jpeg_max_bytes(H, W, mode):
+    """dsn_jpeg_max_bytes: the capacity no frame of this size can exceed"""
+    n = lib().dsn_jpeg_max_bytes(int(H), int(W), int(mode))
+    if n == 0:
+        raise ValueError(f"jpeg: {H} x {W} in mode {mode} is outside what dsn_jpeg_* takes (sides 1 ... 65535, blocks x 1664 below 2^31)")
+    return int(n)
+
+
+def jpeg_header(H, W, mode, quality):
+    """dsn_jpeg_header_host: SOI ... SOS as bytes (host only, no device)"""
+    buf = (C.c_uint8 * 640)()
+    n = C.c_int(0)
+    _check(lib().dsn_jpeg_header_host(int(H), int(W), int(mode), int(quality), buf, 640, C.byref(n)), "dsn_jpeg_header_host")
+    return bytes(buf[:n.value])
+
+
+def _jpeg_images(what, images):
+    """(F, H, W, mode-independent channel count, dtype code) of a contiguous device stack [F, H, W] or [F, H, W, 3]"""
+    if not torch.is_tensor(images) or images.dtype not in (torch.uint8, torch.float32):
+        raise ValueError(f"{what}: images must be a uint8 or float32 tensor")
+    if images.dim() not in (3, 4) or (images.dim() == 4 and images.shape[3] != 3):
+        raise ValueError(f"{what}: images must be [F, H, W] or [F, H, W, 3], got {tuple(images.shape)}")
+    require_gpu()
+    if not images.is_cuda or not images.is_contiguous():
+        raise ValueError(f"{what}: images must be a contiguous tensor on a ROCm device")
+    F, H, W = (int(v) for v in images.shape[:3])
+    return F, H, W, (3 if images.dim() == 4 else 1), (JPEG_U8 if images.dtype == torch.uint8 else JPEG_F32)
+
+
+def _jpeg_check_mode(what, mode, ch):
+    if (mode == JPEG_GRAY) != (ch == 1) or mode not in (JPEG_420, JPEG_444, JPEG_GRAY):
+        raise ValueError(f"{what}: mode {mode!r} does not fit images with {ch} channel(s)")
+
+
+def jpeg_coefficients(images, mode, quality=95, rgb=False, scale=255.0):
+    """dsn_jpeg_coefficients: -> (coef int16 [F, blocks, 64] in zigzag and scan order, status int32 [F]) on the device"""
+    F, H, W, ch, dt = _jpeg_images("jpeg_coefficients", images)
+    _jpeg_check_mode("jpeg_coefficients", mode, ch)
+    dev = images.device
+    coef = _output((F, jpeg_blocks(H, W, mode), 64), torch.int16, dev)
+    status = _output((F,), torch.int32, dev)
+    with torch.cuda.device(dev):
+        _check(lib().dsn_jpeg_coefficients(_ptr(images) if F else None, dt, F, H, W, mode, int(quality), int(bool(rgb)), float(scale),
+                                           _ptr(coef) if F else None, _ptr(status) if F else None, _stream()), "dsn_jpeg_coefficients")
+    return coef, status
+
+
+def jpeg_scan(coef, H, W, mode, quality=95, status_in=None, capacity=None, out=None):
+    """dsn_jpeg_scan: coef int16 [F, blocks, 64] -> (out uint8 [F, capacity], lengths int32 [F], status int32 [F]) on the device.
+    `out` (optional): a caller's uint8 [F, capacity] buffer, written only up to each frame's length."""
+    if not torch.is_tensor(coef) or coef.dtype != torch.int16 or coef.dim() != 3 or coef.shape[2] != 64:
+        raise ValueError("jpeg_scan: coef must be an int16 tensor [F, blocks, 64]")
+    require_gpu()
+    if not coef.is_cuda or not coef.is_contiguous():
+        raise ValueError("jpeg_scan: coef must be a contiguous tensor on a ROCm device")
+    F = int(coef.shape[0])
+    if int(coef.shape[1]) != jpeg_blocks(H, W, mode):
+        raise ValueError(f"jpeg_scan: {H} x {W} in mode {mode} has {jpeg_blocks(H, W, mode)} blocks, coef has {int(coef.shape[1])}")
+    dev = coef.device
+    if out is None:
+        capacity = jpeg_max_bytes(H, W, mode) if capacity is None else int(capacity)
+        out = _output((F, capacity), torch.uint8, dev)
+    elif out.dtype != torch.uint8 or out.dim() != 2 or out.shape[0] != F or not out.is_contiguous() or out.device != dev:
+        raise ValueError("jpeg_scan: out must be a contiguous uint8 [F, capacity] tensor on coef's device")
+    lengths = _output((F,), torch.int32, dev)
+    status = _output((F,), torch.int32, dev)
+    nws = lib().dsn_jpeg_workspace_bytes(max(F, 1), int(H), int(W), int(mode))
+    ws = _scratch(nws, dev)
+    with torch.cuda.device(dev):
+        _check(lib().dsn_jpeg_scan(_ptr(coef) if F else None, _ptr(status_in) if (status_in is not None and F) else None, F, int(H), int(W),
+                                   int(mode), int(quality), _ptr(out) if F else None, int(out.shape[1]), _ptr(lengths) if F else None,
+                                   _ptr(status) if F else None, _ptr(ws), nws, _stream()), "dsn_jpeg_scan")
+    return out, lengths, status
+
+
+def jpeg_encode(images, mode, quality=95, rgb=False, scale=255.0, capacity=None, out=None, workspace=None):
+    """dsn_jpeg_encode: images uint8 / float32 [F, H, W, 3] (JPEG_GRAY: [F, H, W]) on the device -> (out uint8 [F, capacity] whose row f
+    starts with frame f's complete file, lengths int32 [F]: the bytes each file needs, status int32 [F]: OR of JPEG_NONFINITE /
+    JPEG_OVERFLOW).  Nothing is copied back and nothing waits."""
+    F, H, W, ch, dt = _jpeg_images("jpeg_encode", images)
+    _jpeg_check_mode("jpeg_encode", mode, ch)
+    dev = images.device
+    if out is None:
+        capacity = jpeg_max_bytes(H, W, mode) if capacity is None else int(capacity)
+        out = _output((F, capacity), torch.uint8, dev)
+    elif out.dtype != torch.uint8 or out.dim() != 2 or out.shape[0] != F or not out.is_contiguous() or out.device != dev:
+        raise ValueError("jpeg_encode: out must be a contiguous uint8 [F, capacity] tensor on the images' device")
+    lengths = _output((F,), torch.int32, dev)
+    status = _output((F,), torch.int32, dev)
+    nws = lib().dsn_jpeg_workspace_bytes(max(F, 1), H, W, int(mode))
+    if nws == 0:
+        jpeg_max_bytes(H, W, mode)          # raises with the limits
+    ws = _scratch(nws, dev) if workspace is None else workspace
+    with torch.cuda.device(dev):
+        _check(lib().dsn_jpeg_encode(_ptr(images) if F else None, dt, F, H, W, int(mode), int(quality), int(bool(rgb)), float(scale),
+                                     _ptr(out) if F else None, int(out.shape[1]), _ptr(lengths) if F else None, _ptr(status) if F else None,
+                                     _ptr(ws), int(ws.numel()), _stream()), "dsn_jpeg_encode")
+    return out, lengths, status

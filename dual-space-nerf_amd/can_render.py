@@ -28,6 +28,7 @@ bit-identical: `last_frame_info` says per frame whether it ran and with which th
 """
 from __future__ import annotations
 
+import os
 import warnings
 import weakref
 
@@ -1245,6 +1246,54 @@ class Renderer:
                 for d, _, st in dist:
                     rows[k] = torch.cat([rows[k], d[j:j + 1], st[j:j + 1].double()])
         return self._metrics_dicts(torch.stack(rows).cpu(), views=True, lpips_names=names)
+
+    def save_views(self, results, paths, key="coarse_color", gt=None, clamp=False, **jpeg):
+        """Write the device images of render_view(s)(device_output=True) as .jpg files (validate.py:76-83, novel_pose_vis.py:62-66,
+        vis_lighting.py:62-65: `cv2.imwrite(path, img.numpy() * 255)`): `results` is one result dict or a list of them, `paths` one path
+        per result.  The frames of one size are encoded in ONE dsnerf_amd.jpeg.encode call (two device->host copies per size group).
+        key="coarse_color" writes three components from the B, G, R image; "coarse_depth" / "coarse_acc" / "coarse_disp" one
+        component.  gt=batches puts batch["img"] to the right of the rendering (validate.py:78's np.concatenate(..., axis=1)),
+        concatenated on the device.  clamp=True clamps to [0, 1] first (test.py:62); the encoder saturates either way.  **jpeg:
+        quality, subsampling, channels, scale of jpeg.encode.  Returns the files' sizes in bytes."""
+        from . import jpeg as _jpeg
+        single = isinstance(results, dict)
+        results = [results] if single else list(results)
+        paths = [paths] if isinstance(paths, (str, os.PathLike)) else list(paths)
+        if len(results) != len(paths):
+            raise ValueError(f"save_views: {len(results)} results for {len(paths)} paths")
+        for p in paths:
+            if os.path.splitext(str(p))[1].lower() not in (".jpg", ".jpeg"):
+                raise ValueError(f"save_views: only .jpg / .jpeg files are written, got {p!r}")
+        if gt is not None:
+            gt = [gt] if isinstance(gt, dict) else list(gt)
+            if len(gt) != len(results):
+                raise ValueError(f"save_views: {len(gt)} gt batches for {len(results)} results")
+        imgs = []
+        for k, r in enumerate(results):
+            img = r[key].to(self.device)
+            if img.dtype != torch.uint8:
+                img = img.to(torch.float32)
+            if img.dim() == 3 and img.shape[2] == 1:
+                img = img[..., 0]
+            if clamp:
+                img = torch.clamp(img, min=0.0, max=1.0)
+            if gt is not None:
+                g = self._metrics_gt(gt[k]).to(torch.float32)
+                if img.dim() == 2:
+                    raise ValueError("save_views: gt goes beside a colour image, not beside " + key)
+                img = torch.cat([img, g.reshape(img.shape[0], -1, 3)], dim=1)
+            imgs.append(img)
+        groups = {}
+        for k, img in enumerate(imgs):
+            groups.setdefault((tuple(img.shape), img.dtype), []).append(k)
+        sizes = [0] * len(imgs)
+        for ks in groups.values():
+            files = _jpeg.encode(torch.stack([imgs[k] for k in ks]), **jpeg)
+            for k, data in zip(ks, files):
+                with open(paths[k], "wb") as f:
+                    f.write(data)
+                sizes[k] = len(data)
+        return sizes[0] if single else sizes
 
     def _metrics_gt(self, batch):
         gt = batch["img"][0]

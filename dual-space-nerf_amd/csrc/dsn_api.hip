@@ -1967,4 +1967,70 @@ int dsn_lpips(const void* packed, int net, const float* img, const double* gt_f6
     return dsn_check_launch("dsn_lpips");
 }
 
+// ---- baseline JPEG (dsn_jpeg.hip) ----
+#define DSN_JPEG_COMMON(name, F, H, W, mode, quality)                                                                          \
+    DSN_REQUIRE((mode) == DSN_JPEG_420 || (mode) == DSN_JPEG_444 || (mode) == DSN_JPEG_GRAY, name ": mode must be DSN_JPEG_420, _444 or _GRAY"); \
+    DSN_REQUIRE((quality) >= 1 && (quality) <= 100, name ": quality must be 1 ... 100");                                       \
+    DSN_REQUIRE((F) >= 0 && (F) <= DSN_JPEG_MAX_FRAMES, name ": F must be 0 ... 65535");                                       \
+    DSN_REQUIRE((H) >= 1 && (W) >= 1 && (H) <= 65535 && (W) <= 65535, name ": H and W must be 1 ... 65535");                   \
+    int blocks = 0;                                                                                                            \
+    DSN_REQUIRE(dsn_jpeg_blocks(H, W, mode, &blocks), name ": too many blocks for int32 bit offsets (blocks x 1664 must stay below 2^31)")
+
+size_t dsn_jpeg_max_bytes(int H, int W, int mode) {
+    int blocks = 0;
+    if (!dsn_jpeg_blocks(H, W, mode, &blocks)) return 0;
+    return dsn_jpeg_header_bytes(mode) + (size_t)blocks * (2 * DSN_JPEG_BLOCK_BYTES) + 2;
+}
+
+size_t dsn_jpeg_workspace_bytes(int F, int H, int W, int mode) { return dsn_jpeg_workspace_size(F, H, W, mode, true); }
+
+int dsn_jpeg_header_host(int H, int W, int mode, int quality, uint8_t* out_host, int capacity, int* len) {
+    DSN_JPEG_COMMON("dsn_jpeg_header_host", 0, H, W, mode, quality);
+    DSN_REQUIRE(out_host && len, "dsn_jpeg_header_host: null argument");
+    DSN_REQUIRE(capacity >= (int)dsn_jpeg_header_bytes(mode), "dsn_jpeg_header_host: capacity is below the header's length");
+    *len = dsn_jpeg_write_header_host(H, W, mode, quality, out_host);
+    return 0;
+}
+
+int dsn_jpeg_coefficients(const void* images, int dtype, int F, int H, int W, int mode, int quality, int rgb, float scale, int16_t* coef,
+                          uint32_t* out_status, void* stream) {
+    DSN_JPEG_COMMON("dsn_jpeg_coefficients", F, H, W, mode, quality);
+    DSN_REQUIRE(dtype == DSN_JPEG_U8 || dtype == DSN_JPEG_F32, "dsn_jpeg_coefficients: dtype must be DSN_JPEG_U8 or DSN_JPEG_F32");
+    if (F == 0) return 0;
+    DSN_REQUIRE(images && coef && out_status, "dsn_jpeg_coefficients: null argument");
+    DSN_REQUIRE(dtype == DSN_JPEG_U8 || ((uintptr_t)images & 3) == 0, "dsn_jpeg_coefficients: a float32 image is not 4-byte aligned");
+    DSN_REQUIRE(((uintptr_t)coef & 1) == 0 && ((uintptr_t)out_status & 3) == 0, "dsn_jpeg_coefficients: coef or out_status is not aligned");
+    dsn_launch_jpeg_coefficients(images, dtype, F, H, W, mode, quality, rgb != 0, scale, coef, out_status, (hipStream_t)stream);
+    return dsn_check_launch("dsn_jpeg_coefficients");
+}
+
+int dsn_jpeg_scan(const int16_t* coef, const uint32_t* status_in, int F, int H, int W, int mode, int quality, uint8_t* out, size_t capacity,
+                  int32_t* out_lengths, uint32_t* out_status, void* workspace, size_t workspace_bytes, void* stream) {
+    DSN_JPEG_COMMON("dsn_jpeg_scan", F, H, W, mode, quality);
+    if (F == 0) return 0;
+    DSN_REQUIRE(coef && out && out_lengths && out_status && workspace, "dsn_jpeg_scan: null argument");
+    DSN_REQUIRE(((uintptr_t)workspace & 255) == 0, "dsn_jpeg_scan: workspace must be 256-byte aligned");
+    DSN_REQUIRE(workspace_bytes >= dsn_jpeg_workspace_size(F, H, W, mode, false), "dsn_jpeg_scan: workspace_bytes is too small");
+    DSN_REQUIRE(status_in != out_status, "dsn_jpeg_scan: status_in and out_status must differ");
+    DSN_REQUIRE((((uintptr_t)coef & 1) | ((uintptr_t)out_lengths & 3) | ((uintptr_t)out_status & 3) | ((uintptr_t)status_in & 3)) == 0,
+                "dsn_jpeg_scan: a pointer is not aligned to its element");
+    dsn_launch_jpeg_scan(coef, status_in, F, H, W, mode, quality, out, capacity, out_lengths, out_status, workspace, false, (hipStream_t)stream);
+    return dsn_check_launch("dsn_jpeg_scan");
+}
+
+int dsn_jpeg_encode(const void* images, int dtype, int F, int H, int W, int mode, int quality, int rgb, float scale, uint8_t* out,
+                    size_t capacity, int32_t* out_lengths, uint32_t* out_status, void* workspace, size_t workspace_bytes, void* stream) {
+    DSN_JPEG_COMMON("dsn_jpeg_encode", F, H, W, mode, quality);
+    DSN_REQUIRE(dtype == DSN_JPEG_U8 || dtype == DSN_JPEG_F32, "dsn_jpeg_encode: dtype must be DSN_JPEG_U8 or DSN_JPEG_F32");
+    if (F == 0) return 0;
+    DSN_REQUIRE(images && out && out_lengths && out_status && workspace, "dsn_jpeg_encode: null argument");
+    DSN_REQUIRE(dtype == DSN_JPEG_U8 || ((uintptr_t)images & 3) == 0, "dsn_jpeg_encode: a float32 image is not 4-byte aligned");
+    DSN_REQUIRE(((uintptr_t)workspace & 255) == 0, "dsn_jpeg_encode: workspace must be 256-byte aligned");
+    DSN_REQUIRE(workspace_bytes >= dsn_jpeg_workspace_size(F, H, W, mode, true), "dsn_jpeg_encode: workspace_bytes is too small");
+    DSN_REQUIRE((((uintptr_t)out_lengths & 3) | ((uintptr_t)out_status & 3)) == 0, "dsn_jpeg_encode: a pointer is not aligned to its element");
+    dsn_launch_jpeg_encode(images, dtype, F, H, W, mode, quality, rgb != 0, scale, out, capacity, out_lengths, out_status, workspace,
+                           (hipStream_t)stream);
+    return dsn_check_launch("dsn_jpeg_encode");
+}
+
 }  // extern "C"

@@ -240,6 +240,18 @@ void dsn_launch_image_resize(const void* src, void* dst, int N, int H, int W, in
 void dsn_launch_image_prep(const uint8_t* img, const uint8_t* msk_cihp, const double* K, const double* D, int nd, int N, int H0, int W0, int c,
                            int border, int out_dtype, void* out_img, uint8_t* out_img_u8, uint8_t* out_msk_fg, uint8_t* out_msk_cihp,
                            hipStream_t st);
+// dsn_jpeg.hip: baseline JPEG (dsn_jpeg_*; arguments checked by the entry points).  The workspace holds the coefficients first when
+// `with_coef` / `ws_has_coef` (dsn_jpeg_encode), so that dsn_jpeg_scan carves the same layout behind them.
+size_t dsn_jpeg_header_bytes(int mode);
+bool dsn_jpeg_blocks(int H, int W, int mode, int* blocks);
+size_t dsn_jpeg_workspace_size(int F, int H, int W, int mode, bool with_coef);
+int dsn_jpeg_write_header_host(int H, int W, int mode, int quality, uint8_t* out);
+void dsn_launch_jpeg_coefficients(const void* images, int dtype, int F, int H, int W, int mode, int quality, int rgb, float scale,
+                                  int16_t* coef, uint32_t* status, hipStream_t st);
+void dsn_launch_jpeg_scan(const int16_t* coef, const uint32_t* status_in, int F, int H, int W, int mode, int quality, uint8_t* out,
+                          size_t capacity, int32_t* lengths, uint32_t* status, void* workspace, bool ws_has_coef, hipStream_t st);
+void dsn_launch_jpeg_encode(const void* images, int dtype, int F, int H, int W, int mode, int quality, int rgb, float scale, uint8_t* out,
+                            size_t capacity, int32_t* lengths, uint32_t* status, void* workspace, hipStream_t st);
 // dsn_mesh.hip: density grid points and marching cubes (dsn_density_grid, dsn_mc_*)
 void dsn_launch_grid_points(const float* x, const float* y, const float* z, int i0, int ny, int nz, int64_t n, float* pts, hipStream_t st);
 size_t dsn_mc_workspace_size(int64_t N);

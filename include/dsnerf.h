@@ -1336,6 +1336,99 @@ DSN_EXPORT int dsn_lpips(const void* packed, int net, const float* img, const do
                          int rgb_pm1, double* out, double* out_layers, int32_t* out_status, void* workspace, size_t workspace_bytes,
                          void* stream);
 
+/* ---- Baseline JPEG on the device (csrc/dsn_jpeg.hip): the scripts' cv2.imwrite(path, img * 255) into a .jpg (validate.py:76-83,
+ * novel_pose_vis.py:62-66, vis_lighting.py:62-65, test.py) from frames that are in HBM already.  The rule below is restated in
+ * tests/jpeg_restate.py, which gives byte for byte the files Pillow writes through libjpeg-turbo (quality q, optimize=False, no
+ * restart markers); cv2.imwrite's own bytes are not claimed.  Integer arithmetic and integer atomics only: the same bytes on every
+ * call, and a frame gives the same file alone or in any batch.
+ *   Levels.  uint8 input passes through.  float32 input v: t = v * scale in float32 (scale = 255 for the scripts), rounded to the
+ *      nearest integer with ties to even, saturated to [0, 255]; NaN gives 0 (+inf 255, -inf 0).  A NaN or infinite value sets
+ *      DSN_JPEG_NONFINITE for its frame; the file is still valid.  This is what cv2.imwrite is understood to do to a float image
+ *      (convertTo(CV_8U)); unverified.  rgb = 0: the three channels are B, G, R (as cv2.imwrite reads them); rgb != 0: R, G, B.
+ *   Modes.  DSN_JPEG_420: three components, luma sampled 2 x 2 (libjpeg's and cv2's default); DSN_JPEG_444: three components, all
+ *      1 x 1; DSN_JPEG_GRAY: the image has ONE channel ([F, H, W]) and the file one component.  The other modes read [F, H, W, 3].
+ *   Colour (JFIF YCbCr, 16-bit fixed point, >> arithmetic):
+ *      Y  = ( 19595 R + 38470 G +  7471 B + 32768) >> 16
+ *      Cb = (-11059 R - 21709 G + 32768 B + (128 << 16) + 32767) >> 16
+ *      Cr = ( 32768 R - 27439 G -  5329 B + (128 << 16) + 32767) >> 16
+ *   MCUs in row-major order.  GRAY: one 8 x 8 block; 444: Y, Cb, Cr; 420: a 16 x 16 MCU of Y00, Y01, Y10, Y11, Cb, Cr (Yrc = block
+ *      row r, column c).  MCU counts: ceil(W / 8) x ceil(H / 8), for 420 ceil(W / 16) x ceil(H / 16).
+ *   Edges (libjpeg's rule).  GRAY / 444: every plane is replicated right and down to the MCU grid.  420: luma is replicated right
+ *      and down to ceil(W / 8) 8 x ceil(H / 8) 8; luma blocks of the last MCU column / row beyond that are DUMMY blocks: all 63 AC
+ *      coefficients zero, DC = the quantised DC of the block before it in the MCU's own order (resolved in order: a dummy block may
+ *      follow a dummy block; Y00 is never one).  Chroma at 420: the Cb / Cr plane is replicated right to ceil(W / 16) 16 columns and,
+ *      if H is odd, down by one row; out(y, x) = (p(2y, 2x) + p(2y, 2x + 1) + p(2y + 1, 2x) + p(2y + 1, 2x + 1) + bias) >> 2 with
+ *      bias 1 on even and 2 on odd x; the last of the ceil(H / 2) downsampled rows is then replicated down to ceil(H / 16) 8 rows.
+ *   DCT.  d = sample - 128, then the IJG slow-integer forward DCT: pass 1 along every row, pass 2 along every column of the result.
+ *      CONST_BITS = 13, PASS1_BITS = 2, DESCALE(x, n) = (x + (1 << (n - 1))) >> n (arithmetic).  One pass over d0 ... d7:
+ *        t0 = d0 + d7, t7 = d0 - d7, t1 = d1 + d6, t6 = d1 - d6, t2 = d2 + d5, t5 = d2 - d5, t3 = d3 + d4, t4 = d3 - d4
+ *        t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2
+ *        out0 = (t10 + t11) << 2 in pass 1, DESCALE(t10 + t11, 2) in pass 2;  out4 likewise from t10 - t11
+ *        z1 = (t12 + t13) 4433;  out2 = DESCALE(z1 + t13 6270, n);  out6 = DESCALE(z1 - t12 15137, n);  n = 11 in pass 1, 15 in pass 2
+ *        z1 = t4 + t7, z2 = t5 + t6, z3 = t4 + t6, z4 = t5 + t7, z5 = (z3 + z4) 9633
+ *        t4 *= 2446, t5 *= 16819, t6 *= 25172, t7 *= 12299, z1 *= -7373, z2 *= -20995, z3 *= -16069, z4 *= -3196, z3 += z5, z4 += z5
+ *        out7 = DESCALE(t4 + z1 + z3, n), out5 = DESCALE(t5 + z2 + z4, n), out3 = DESCALE(t6 + z2 + z3, n), out1 = DESCALE(t7 + z1 + z4, n)
+ *      The result is 8 x the orthonormal DCT; every intermediate fits int32.  Error against the exact transform for samples in
+ *      [-128, 127]: a constant is off by at most 2^-14 and an odd output adds four products.  Pass 1 (outputs at 4 x sqrt(8) x the 1-D
+ *      transform): operands up to 256, 512, 512, 1024 give 4 x 2304 x 2^-14 = 0.57 units, the DESCALE 0.5: e1 <= 1.07.  Pass 2 carries
+ *      e1 through rows of absolute sum <= sqrt(8), times sqrt(8) / 4: 2 e1 = 2.14 units of 8 x DCT; its own operands (up to 8192,
+ *      16384, 16384, 32768) give 73728 x 2^-14 / 4 = 1.13 units, its DESCALE 0.5.  Sum 3.77 units: |integer / 8 - float64 DCT| <=
+ *      DSN_JPEG_DCT_BAR = 0.5 levels; tests hold the restatement to this bar (random and extreme blocks measure 0.18).
+ *   Quantisation.  Base tables of Annex K (luminance for Y, chrominance for Cb / Cr).  s = 5000 / q (integer division) for q < 50,
+ *      else 200 - 2 q; entry = clamp((base s + 50) / 100, 1, 255), q = 1 ... 100.  With d = 8 entry: a = |c| + (d >> 1), quotient
+ *      a / d by integer division, sign of c restored.
+ *   Entropy coding.  Baseline Huffman, the four tables of Annex K (DC / AC luminance for Y, chrominance for Cb and Cr), one scan of
+ *      interleaved MCUs, no restart markers.  DC: the difference to the previous block of the same component (dummy blocks
+ *      included; predictors start at 0), coded as its size s = bits of |diff| followed by s amplitude bits.  AC in zigzag order: a
+ *      non-zero coefficient after a run of r zeros writes r / 16 ZRL codes (0xF0), the code of ((r % 16) << 4 | s) and s amplitude
+ *      bits; EOB (0x00) unless coefficient 63 is non-zero.  A negative value v is written as v + 2^s - 1.  Bits most significant first.
+ *      The last byte is padded with 1-bits; every 0xFF byte of the scan, the padded one included, is followed by 0x00; then EOI.
+ *      At q = 100 AC sizes stay <= 10 and DC-difference sizes <= 11: a block's scan is at most 1658 bits (20 for DC, 63 x 26 for AC).
+ *   Header (what Pillow writes with optimize=False): SOI; APP0 "JFIF\0" 1.01, units 0, density 1 x 1, no thumbnail; one DQT segment per
+ *      table (8-bit, zigzag order); SOF0 (8 bits, H, W, components 1 .. 3 with sampling 0x22 / 0x11, tables 0, 1, 1); one DHT segment
+ *      per table in the order DC0, AC0, DC1, AC1 (GRAY: DC0, AC0); SOS (Ss 0, Se 63, Ah / Al 0).  623 bytes, GRAY 328.
+ *   Kernels.  k_jpeg_coef: a workgroup per MCU, a wave per block, a lane per sample: levels, colour, edges, downsampling, the DCT
+ *      in int32 through LDS, quantisation, dummy DCs -> int16 coef [F][block in scan order][64 in zigzag order].  k_jpeg_bits: a wave
+ *      per block, a lane per coefficient: the non-zero mask is one ballot, a lane's run its distance to the previous set bit; its
+ *      ZRLs, code and amplitude are one word of at most 59 bits -> the block's bit length.  The project's tile scan (per tile, then
+ *      one workgroup over the tiles' totals, frames side by side) turns lengths into bit offsets.  k_jpeg_emit: the same words again,
+ *      placed by a wave prefix sum, merged into the cleared unstuffed stream with 32-bit atomic OR.  k_jpeg_ffcount / tile scan /
+ *      k_jpeg_stuff: 0xFF bytes per 16-byte chunk, their prefix, then the scatter behind the header with the inserted zeros, the
+ *      1-padding of the last byte, EOI, the frame's length and status.  The header travels in the kernel arguments.
+ *   Bounds.  dsn_jpeg_max_bytes = header + 416 bytes per block (208 with every byte stuffed) + 2.  `capacity` is the stride of `out`
+ *      in bytes; a frame that needs more sets DSN_JPEG_OVERFLOW for that frame alone: nothing is written at or past the capacity,
+ *      out_lengths still holds the needed length.  Bit offsets are int32: blocks x 1664 must stay below 2^31, H and W <= 65535 (the
+ *      SOF0 fields): that admits every H W <= 2^24 pixels with H, W >= 16 in all modes (the entry points compute the block count).
+ * images: [F, H, W, 3] (GRAY: [F, H, W]) contiguous, dtype DSN_JPEG_U8 or DSN_JPEG_F32.  coef: int16 [F, blocks, 64].  out: uint8
+ * [F, capacity]; bytes past a frame's length are not touched.  out_lengths: int32 [F]; out_status: uint32 [F] (OR of DSN_JPEG_*).
+ * dsn_jpeg_coefficients writes coef and out_status (NONFINITE).  dsn_jpeg_scan reads coef, ORs status_in [F] (may be null) into
+ * out_status.  dsn_jpeg_encode is their composition bit for bit; its coef live in the workspace.  workspace:
+ * dsn_jpeg_workspace_bytes(F, H, W, mode) bytes (0 for bad sizes), anything on entry, 256-byte aligned.  dsn_jpeg_header_host writes the
+ * header into HOST memory and returns its length through *len (capacity >= DSN_JPEG_HEADER_MAX suffices).  No allocation, no
+ * host copy, no synchronisation. */
+#define DSN_JPEG_420 0
+#define DSN_JPEG_444 1
+#define DSN_JPEG_GRAY 2
+#define DSN_JPEG_U8 0
+#define DSN_JPEG_F32 1
+#define DSN_JPEG_NONFINITE 1u
+#define DSN_JPEG_OVERFLOW 2u
+#define DSN_JPEG_HEADER_MAX 640
+#define DSN_JPEG_BLOCK_BYTES 208          /* ceil(1658 / 8): the unstuffed stream's share per block */
+#define DSN_JPEG_DCT_BAR 0.5
+#define DSN_JPEG_MAX_FRAMES 65535
+DSN_EXPORT size_t dsn_jpeg_max_bytes(int H, int W, int mode);
+DSN_EXPORT size_t dsn_jpeg_workspace_bytes(int F, int H, int W, int mode);
+DSN_EXPORT int dsn_jpeg_header_host(int H, int W, int mode, int quality, uint8_t* out_host, int capacity, int* len);
+DSN_EXPORT int dsn_jpeg_coefficients(const void* images, int dtype, int F, int H, int W, int mode, int quality, int rgb, float scale,
+                                     int16_t* coef, uint32_t* out_status, void* stream);
+DSN_EXPORT int dsn_jpeg_scan(const int16_t* coef, const uint32_t* status_in, int F, int H, int W, int mode, int quality, uint8_t* out,
+                             size_t capacity, int32_t* out_lengths, uint32_t* out_status, void* workspace, size_t workspace_bytes,
+                             void* stream);
+DSN_EXPORT int dsn_jpeg_encode(const void* images, int dtype, int F, int H, int W, int mode, int quality, int rgb, float scale,
+                               uint8_t* out, size_t capacity, int32_t* out_lengths, uint32_t* out_status, void* workspace,
+                               size_t workspace_bytes, void* stream);
+
 /* diagnostics, NOT for the hot path (synchronises `stream`): {ncell, ok, total entries, capacity} of the four
  * nearest-face list levels (world fine/coarse, canonical fine/coarse) into a HOST array of 16 int32. */
 DSN_EXPORT int dsn_debug_nn_stats(const void* scene, int V, int F, int32_t* out16_host, void* stream);
