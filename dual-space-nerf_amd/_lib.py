@@ -2146,7 +2146,7 @@ def image_scatter(out: dict, mask_at_box, H, W, clamp=False):
     mask = mask_at_box.reshape(-1).to(device=dev, dtype=torch.uint8).contiguous()
     R = out["color"].shape[0]
     ws = _scratch(lib().dsn_image_workspace_bytes(H, W), dev)
-    img = {k: torch.empty(H, W, c, dtype=torch.float32, device=dev) for k, c in
+    img = {k: _output((H, W, c), torch.float32, dev) for k, c in
            (("coarse_color", 3), ("coarse_disp", 1), ("coarse_acc", 1), ("coarse_depth", 1))}
     _check(lib().dsn_image_scatter(_ptr(out["color"], torch.float32), _ptr(out["disp_map"]), _ptr(out["acc_map"]),
                                    _ptr(out["depth_map"]), R, _ptr(mask), H, W, int(bool(clamp)), _ptr(img["coarse_color"]),
@@ -2166,8 +2166,8 @@ def image_scatter_maps(rgbs, scalars, mask_at_box, H, W):
     mask = mask_at_box.reshape(-1).to(device=dev, dtype=torch.uint8).contiguous()
     R = (rgbs + scalars)[0].shape[0]
     ws = _scratch(lib().dsn_image_workspace_bytes(H, W), dev)
-    rgb_imgs = [torch.empty(H, W, 3, dtype=torch.float32, device=dev) for _ in rgbs]
-    sc_imgs = [torch.empty(H, W, 1, dtype=torch.float32, device=dev) for _ in scalars]
+    rgb_imgs = [_output((H, W, 3), torch.float32, dev) for _ in rgbs]
+    sc_imgs = [_output((H, W, 1), torch.float32, dev) for _ in scalars]
     spare_src = spare_img = None
     i = j = 0
     while i < len(rgbs) or j < len(scalars):
@@ -2196,7 +2196,7 @@ def image_psnr(img_rgb, gt, mask_at_box=None):
     assert gt.dtype in (torch.float64, torch.float32)
     mask = None if mask_at_box is None else mask_at_box.reshape(-1).to(device=dev, dtype=torch.uint8).contiguous()
     ws = _scratch(lib().dsn_image_workspace_bytes(H, W), dev)
-    out = torch.empty(4, dtype=torch.float64, device=dev)
+    out = _output((4,), torch.float64, dev)
     g64, g32 = (gt, None) if gt.dtype == torch.float64 else (None, gt)
     _check(lib().dsn_image_psnr(_ptr(img_rgb.contiguous(), torch.float32), _ptr(g64), _ptr(g32), _ptr(mask), H, W, _ptr(out),
                                 _ptr(ws), _stream()), "dsn_image_psnr")
@@ -2308,6 +2308,9 @@ def _lpips_chunk(net, n_frames, H, W, per_frame=1):
     if one == 0:
         raise ValueError(f"lpips: bad sizes ({n_frames} x {H} x {W})")
     most = max(1, min(n_frames, int(LPIPS_WORKSPACE_CAP // max(one, 1))))
+    # (the workspace has a fixed part, so k frames need a little less than k times one frame's: take what really fits)
+    while most < n_frames and lib().dsn_lpips_workspace_bytes(_lpips_net(net), most + 1, H, W) <= LPIPS_WORKSPACE_CAP:
+        most += 1
     calls = -(-n_frames // most)
     return -(-n_frames // calls)          # even chunks: 16 frames under a cap of 15 go as 8 + 8
 
@@ -2559,16 +2562,15 @@ def camera_rays(K, R, T, bounds, H, W, device=None, convention="zju"):
     (ray_o [H*W,3], ray_d [H*W,3], near [H*W], far [H*W], mask_at_box [H*W] bool), all on the device, uncompacted."""
     require_gpu()
     dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-    f64 = lambda a: torch.as_tensor(a, dtype=torch.float64).reshape(-1).to(dev).contiguous()
-    K, R, T, bounds = f64(K), f64(R), f64(T), f64(bounds)
-    n = H * W
-    ray_o = torch.empty(n, 3, dtype=torch.float32, device=dev)
-    ray_d = torch.empty(n, 3, dtype=torch.float32, device=dev)
-    near = torch.empty(n, dtype=torch.float32, device=dev)
-    far = torch.empty(n, dtype=torch.float32, device=dev)
-    mask = torch.empty(n, dtype=torch.uint8, device=dev)
     if convention not in ("zju", "h36m"):
         raise ValueError("convention must be 'zju' or 'h36m'")
+    K, R, T, bounds = _camera_f64(K, R, T, bounds, dev)
+    n = H * W
+    ray_o = _output((n, 3), torch.float32, dev)
+    ray_d = _output((n, 3), torch.float32, dev)
+    near = _output((n,), torch.float32, dev)
+    far = _output((n,), torch.float32, dev)
+    mask = _output((n,), torch.uint8, dev)
     _check(lib().dsn_camera_rays(_ptr(K), _ptr(R), _ptr(T), _ptr(bounds), H, W, RAYS_H36M if convention == "h36m" else RAYS_ZJU,
                                  _ptr(ray_o), _ptr(ray_d), _ptr(near), _ptr(far), _ptr(mask), _stream()), "dsn_camera_rays")
     return ray_o, ray_d, near, far, mask.bool()

@@ -597,6 +597,8 @@ int dsn_camera_rays(const double* K3x3, const double* R3x3, const double* T3, co
                     int convention, float* ray_o, float* ray_d, float* near, float* far, uint8_t* mask_at_box, void* stream) {
     DSN_REQUIRE(K3x3 && R3x3 && T3 && bounds2x3 && ray_o && ray_d && near && far && mask_at_box, "dsn_camera_rays: null argument");
     DSN_REQUIRE(H > 0 && W > 0, "dsn_camera_rays: empty image");
+    // the kernels index ray_o[3 * p + c] with int: 3 * H * W must stay below 2^31
+    DSN_REQUIRE((int64_t)H * W <= (int64_t)INT32_MAX / 3, "dsn_camera_rays: more than (2^31 - 1) / 3 pixels");
     DSN_REQUIRE(convention == DSN_RAYS_ZJU || convention == DSN_RAYS_H36M, "dsn_camera_rays: unknown convention");
     dsn_launch_camera_rays(K3x3, R3x3, T3, bounds2x3, H, W, ray_o, ray_d, near, far, mask_at_box, (hipStream_t)stream,
                            convention == DSN_RAYS_H36M);

@@ -96,16 +96,18 @@ __device__ __forceinline__ DsnPixelRay dsn_pixel_ray_h36m(const double* __restri
     // get_near_far (:61-76), float32 throughout
     const float nrm = sqrtf((df[0] * df[0] + df[1] * df[1]) + df[2] * df[2]);
     float tn = -INFINITY, tf = INFINITY;
+    bool nan = false;     // np.minimum / np.max keep a NaN where fminf / fmaxf drop it: the reference's near < far is then False
     for (int c = 0; c < 3; ++c) {
         float v = dsn_div(df[c], nrm);
         if (v < 1e-5f && v > -1e-10f) v = 1e-5f;          // the two clamps in the reference's order (:65-66)
         if (v > -1e-5f && v < 1e-10f) v = -1e-5f;
         const float bmin = (float)bounds[c], bmax = (float)bounds[3 + c];
         const float a = dsn_div(bmin - of[c], v), b = dsn_div(bmax - of[c], v);   // ray_o[:1]: every ray shares the camera origin
+        nan = nan || a != a || b != b;
         tn = fmaxf(tn, fminf(a, b));
         tf = fminf(tf, fmaxf(a, b));
     }
-    const bool m = tn < tf;
+    const bool m = !nan && tn < tf;
     out.hit = m;
     out.near = m ? dsn_div(tn, nrm) : 0.0f;
     out.far = m ? dsn_div(tf, nrm) : 0.0f;

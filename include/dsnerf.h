@@ -174,7 +174,8 @@ DSN_EXPORT int dsn_composite(const float* colour, const float* sigma, const uint
  * box exactly twice), mask_at_box [H*W].  The caller compacts with the mask like the reference does (:181-183). */
 #define DSN_RAYS_ZJU 0   /* utils/rays_utils.py:16-30,63-97: un-normalised directions, padded box, "exactly two faces" test in float64 */
 #define DSN_RAYS_H36M 1  /* utils/h36m_utils.py:14-28,61-76 (get_rays_within_bounds :162-176): unit directions (normalised in
-                          * float64), float32 slab test on the unpadded bounds with the +-1e-5 direction clamp */
+                          * float64), float32 slab test on the unpadded bounds with the +-1e-5 direction clamp; a NaN
+                          * plane parameter is a miss, as numpy's minimum / max keep it.  H * W at most (2^31 - 1) / 3. */
 DSN_EXPORT int dsn_camera_rays(const double* K3x3, const double* R3x3, const double* T3, const double* bounds2x3, int H, int W,
                     int convention, float* ray_o, float* ray_d, float* near, float* far, uint8_t* mask_at_box, void* stream);
 

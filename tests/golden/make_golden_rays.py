@@ -49,3 +49,47 @@ arrs.update(K2=K2, T2=T2, H2=H2, W2=W2, pick2=pick, ray_o2=fo2.reshape(-1, 3).as
             mask2_count=np.int64(m2.sum()))
 np.savez_compressed(os.path.join(HERE, "camera_rays_h36m.npz"), **arrs)
 print("h36m rays", arrs["ray_o"].shape, "in box", int(mask.sum()), "| 1024^2 in box", int(m2.sum()))
+
+
+# ---- the edges frames reach (camera_rays_edges.npz): axis-aligned cameras whose principal point is a pixel centre, so that a whole
+# column / row of rays has a direction component that is exactly zero (ZJU: (b - o) / 0 and inf * 0 = NaN inside the plane test;
+# H36M: the two +-1e-5 clamps), two rays meet three planes within the 1e-6 slack, one camera stands inside the box and one has the
+# box behind it; the generic rotated camera above at the same size; and pixel counts around the 256-thread block.  Every array is a
+# whole-image one (near / far 0 where the ray misses, as the device writes them): "<camera>:<convention>:<array>".
+He, We = 37, 53
+Ke = np.array([[40.0, 0.0, 26.0], [0.0, 40.0, 18.0], [0.0, 0.0, 1.0]])
+Re = np.eye(3)
+be = np.array([[-0.51, -0.36, 2.0], [0.74, 0.49, 3.0]])
+edge_cameras = {"front": (He, We, Ke, Re, np.array([[0.0], [0.0], [0.0]])),
+                "inside": (He, We, Ke, Re, np.array([[0.0], [0.0], [-2.5]])),
+                "behind": (He, We, Ke, Re, np.array([[0.0], [0.0], [-6.0]])),
+                # the origin ON the float32 box's x-min plane: column 26 runs along that face, 0 / +-1e-5 decides hit or miss
+                "on_plane": (He, We, Ke, Re, np.array([[float(np.float32(0.51))], [0.0], [0.0]])),
+                "generic": (He, We, K, R, T)}
+for hh, ww in ((1, 1), (15, 17), (16, 16), (1, 257)):
+    edge_cameras[f"generic_{hh}x{ww}"] = (hh, ww, K, R, T)
+out = {"names": np.array(list(edge_cameras))}
+for name, (hh, ww, Kc, Rc, Tc) in edge_cameras.items():
+    bz = be if Kc is Ke else bounds
+    bh = be.astype(np.float32) if Kc is Ke else bounds32
+    out.update({f"{name}:H": hh, f"{name}:W": ww, f"{name}:K": Kc, f"{name}:R": Rc, f"{name}:T": Tc, f"{name}:zju:bounds": bz,
+                f"{name}:h36m:bounds": bh})
+    n = hh * ww
+    o, d = rays_utils.get_rays(hh, ww, Kc, Rc, Tc)
+    o32, d32 = o.reshape(-1, 3).astype(np.float32), d.reshape(-1, 3).astype(np.float32)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        nr, fr, m = rays_utils.get_near_far(bz, o32, d32)
+    near_full, far_full = np.zeros(n, np.float32), np.zeros(n, np.float32)
+    near_full[m], far_full[m] = nr.astype(np.float32), fr.astype(np.float32)
+    out.update({f"{name}:zju:ray_o": o32, f"{name}:zju:ray_d": d32, f"{name}:zju:near": near_full, f"{name}:zju:far": far_full,
+                f"{name}:zju:mask": m})
+    print("edges", name, "zju hits", int(m.sum()), "of", n)
+    o, d = h36m_utils.get_rays(hh, ww, Kc, Rc, Tc)
+    _, _, nr, fr, m = h36m_utils.get_rays_within_bounds(hh, ww, Kc, Rc, Tc, bh)
+    m = m.reshape(-1)
+    near_full, far_full = np.zeros(n, np.float32), np.zeros(n, np.float32)
+    near_full[m], far_full[m] = nr, fr
+    out.update({f"{name}:h36m:ray_o": o.reshape(-1, 3).astype(np.float32), f"{name}:h36m:ray_d": d.reshape(-1, 3).astype(np.float32),
+                f"{name}:h36m:near": near_full, f"{name}:h36m:far": far_full, f"{name}:h36m:mask": m})
+    print("edges", name, "h36m hits", int(m.sum()), "of", n)
+np.savez_compressed(os.path.join(HERE, "camera_rays_edges.npz"), **out)

@@ -266,6 +266,65 @@ def test_nonfinite_pixel_is_confined_to_its_frame(net, bad):
     assert out[:1].tobytes() == clean[0][:1].tobytes() and layers[:1].tobytes() == clean[1][:1].tobytes()
 
 
+# ---- frame chunks under the workspace cap ----------------------------------------------------------------------------------------
+def cap_of(net, k):
+    """the workspace of k frames (lpips) / k pairs (lpips_features) of BATCH_SIZE: as LPIPS_WORKSPACE_CAP it allows k per call"""
+    return L().lib().dsn_lpips_workspace_bytes(L()._lpips_net(net), k, *BATCH_SIZE)
+
+
+def recorded_calls(monkeypatch, name):
+    """the frame counts of the C calls `name` that follow"""
+    lib, calls = L().lib(), []
+    real = getattr(lib, name)
+
+    def spy(*args):
+        calls.append(int(args[5 if name == "dsn_lpips" else 3]))
+        return real(*args)
+
+    monkeypatch.setattr(lib, name, spy, raising=False)
+    return calls
+
+
+@pytest.mark.parametrize("k,steps", [(1, [1, 1, 1, 1, 1]), (2, [2, 2, 1])])
+@pytest.mark.parametrize("net", NETS)
+def test_chunked_distance_is_the_uncapped_call(net, k, steps, poisoned, monkeypatch):
+    """five frames under a cap of one and of two frames' workspace: the slices of out, layers and status, the even split and the
+    short last chunk give the bits of the single call; a NaN pixel in frame 4 flags frame 4 alone"""
+    img, gt, _ = batch_frames(net)
+    whole = dev_lpips(net, img, gt)
+    bad = img.copy()
+    bad[4, 17, 20, 1] = np.nan
+    whole_bad = dev_lpips(net, bad, gt)
+    assert whole[2].tolist() == [0] * 5 and whole_bad[2].tolist() == [0, 0, 0, 0, L().LPIPS_NONFINITE]
+    monkeypatch.setattr(L(), "LPIPS_WORKSPACE_CAP", cap_of(net, k))
+    calls = recorded_calls(monkeypatch, "dsn_lpips")
+    chunked = dev_lpips(net, img, gt)
+    assert calls == steps
+    assert all(a.tobytes() == b.tobytes() for a, b in zip(chunked, whole))
+    chunked_bad = dev_lpips(net, bad, gt)
+    assert chunked_bad[2].tolist() == [0, 0, 0, 0, L().LPIPS_NONFINITE]
+    assert np.isnan(chunked_bad[0][4]) and np.isnan(chunked_bad[1][4]).all()
+    assert chunked_bad[0][:4].tobytes() == whole[0][:4].tobytes() and chunked_bad[1][:4].tobytes() == whole[1][:4].tobytes()
+    assert all(np.array_equal(a, b, equal_nan=True) for a, b in zip(chunked_bad, whole_bad))
+
+
+@pytest.mark.parametrize("net", NETS)
+def test_chunked_features_are_the_uncapped_call(net, poisoned, monkeypatch):
+    """lpips_features on an odd stack (n = 5) under the cap of one pair: calls of 2 + 2 + 1 images write the slices of the five taps
+    and of status that the single call writes"""
+    img, _, _ = batch_frames(net)
+    stack = torch.from_numpy(img).cuda()
+    taps, status = L().lpips_features(net, packed(net), stack)
+    assert status.cpu().tolist() == [0] * 5 and [tuple(t.shape) for t in taps] == [(5, *s) for s in R.tap_shapes(net, *BATCH_SIZE)]
+    monkeypatch.setattr(L(), "LPIPS_WORKSPACE_CAP", cap_of(net, 1))
+    calls = recorded_calls(monkeypatch, "dsn_lpips_features")
+    c_taps, c_status = L().lpips_features(net, packed(net), stack)
+    assert calls == [2, 2, 1]
+    assert c_status.cpu().numpy().tobytes() == status.cpu().numpy().tobytes()
+    for l, (a, b) in enumerate(zip(c_taps, taps)):
+        assert a.shape == b.shape and torch.equal(a.view(torch.int32), b.view(torch.int32)), l
+
+
 # ---- the surface -------------------------------------------------------------------------------------------------------------------
 def package_state_dict(net):
     w = weights(net)

@@ -193,3 +193,22 @@ def test_argument_checks():
     with pytest.raises(ValueError, match="float32"):
         _lib.lpips("alex", None, torch.zeros(4, 4, 3, dtype=torch.float64), torch.zeros(4, 4, 3))
     assert _lib.lpips_status_text(0) == "ok" and "smallest" in _lib.lpips_status_text(1) and "32768" in _lib.lpips_status_text(2 | 4)
+
+
+@pytest.mark.parametrize("net", ["alex", "vgg"])
+def test_chunks_take_what_fits_under_the_cap(net, monkeypatch):
+    """_lib._lpips_chunk: the frames per call under LPIPS_WORKSPACE_CAP.  The workspace has a fixed part, so k frames need less than k
+    times one frame's: a cap of exactly k frames' workspace must allow k per call (then split evenly), never fewer, never more"""
+    import dsnerf_amd
+    _lib = dsnerf_amd._lib
+    H, Wd = 37, 53
+    ws = lambda k: _lib.lib().dsn_lpips_workspace_bytes(_lib._lpips_net(net), k, H, Wd)
+    assert ws(2) < 2 * ws(1)
+    for k, per_call in ((1, 1), (2, 2), (3, 3), (4, 3), (5, 5)):          # 5 frames: 1+1+1+1+1, 2+2+1, 3+2, 3+2 (even), 5
+        monkeypatch.setattr(_lib, "LPIPS_WORKSPACE_CAP", ws(k))
+        assert _lib._lpips_chunk(net, 5, H, Wd) == per_call, k
+        monkeypatch.setattr(_lib, "LPIPS_WORKSPACE_CAP", ws(k) - 1)
+        got = _lib._lpips_chunk(net, 5, H, Wd)
+        assert got == 1 or ws(got) <= ws(k) - 1
+    monkeypatch.setattr(_lib, "LPIPS_WORKSPACE_CAP", 0)                   # below one frame's: one frame per call all the same
+    assert _lib._lpips_chunk(net, 5, H, Wd) == 1
