@@ -62,6 +62,8 @@ EXPORTS = [
     "dsn_image_undistort", "dsn_image_morph", "dsn_image_resize", "dsn_image_prep",
     "dsn_lpips_packed_bytes", "dsn_lpips_pack", "dsn_lpips_workspace_bytes", "dsn_lpips_features", "dsn_lpips",
     "dsn_jpeg_max_bytes", "dsn_jpeg_workspace_bytes", "dsn_jpeg_header_host", "dsn_jpeg_coefficients", "dsn_jpeg_scan", "dsn_jpeg_encode",
+    "dsn_jpeg_parse_host", "dsn_jpegd_workspace_bytes", "dsn_jpegd_workspace_coef", "dsn_jpegd_sync", "dsn_jpegd_coefficients",
+    "dsn_jpegd_pixels", "dsn_jpeg_decode",
 ]
 
 SKIP_TRANSPARENT = 1
@@ -222,6 +224,17 @@ def lib():
         L.dsn_jpeg_scan.argtypes = [C.c_void_p] * 2 + [C.c_int] * 5 + [C.c_void_p, C.c_size_t] + [C.c_void_p] * 3 + [C.c_size_t, C.c_void_p]
         L.dsn_jpeg_encode.argtypes = ([C.c_void_p] + [C.c_int] * 7 + [C.c_float] + [C.c_void_p, C.c_size_t] + [C.c_void_p] * 3
                                       + [C.c_size_t, C.c_void_p])
+        L.dsn_jpeg_parse_host.argtypes = [C.c_char_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        L.dsn_jpegd_workspace_bytes.restype = C.c_size_t
+        L.dsn_jpegd_workspace_bytes.argtypes = [C.c_int] * 4 + [C.c_size_t]
+        L.dsn_jpegd_workspace_coef.argtypes = [C.c_void_p] + [C.c_int] * 4 + [C.c_size_t, C.c_void_p]
+        L.dsn_jpegd_sync.argtypes = ([C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_size_t] + [C.c_int] * 3
+                                     + [C.c_void_p] * 3 + [C.c_size_t, C.c_void_p])
+        L.dsn_jpegd_coefficients.argtypes = [C.c_void_p] + [C.c_int] * 4 + [C.c_size_t, C.c_int] + [C.c_void_p] * 3 + [C.c_size_t, C.c_void_p]
+        L.dsn_jpegd_pixels.argtypes = ([C.c_void_p] * 3 + [C.c_int] * 4 + [C.c_size_t] + [C.c_int] * 2 + [C.c_void_p] * 2
+                                       + [C.c_size_t, C.c_void_p])
+        L.dsn_jpeg_decode.argtypes = ([C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_size_t] + [C.c_int] * 4
+                                      + [C.c_void_p] * 4 + [C.c_size_t, C.c_void_p])
         if L.dsn_abi_version() != 8:
             raise RuntimeError(f"{LIB_PATH} has ABI version {L.dsn_abi_version()}, this binding needs 8 - rebuild it "
                                "(python dual-space-nerf_amd/build.py)")
@@ -2913,3 +2926,149 @@ def jpeg_encode(images, mode, quality=95, rgb=False, scale=255.0, capacity=None,
                                      _ptr(out) if F else None, int(out.shape[1]), _ptr(lengths) if F else None, _ptr(status) if F else None,
                                      _ptr(ws), int(ws.numel()), _stream()), "dsn_jpeg_encode")
     return out, lengths, status
+
+
+# ---- baseline JPEG decoding (dsn_jpeg_parse_host, dsn_jpegd_*, dsn_jpeg_decode: the rule of include/dsnerf.h) -----------------------------
+JPEGD_CORRUPT, JPEGD_PADDING, JPEGD_UNCONVERGED, JPEGD_UNMATCHED, JPEGD_OVERRUN, JPEGD_MARKER, JPEGD_COUNT = 1, 2, 4, 16, 32, 64, 128
+JPEGD_REASONS = ["ok", "not_jpeg", "truncated", "progressive", "extended", "arithmetic", "precision", "sampling", "components", "table16",
+                 "multiscan", "restart", "missing_table", "bad_table", "no_eoi", "bad_segment", "too_large"]          # DSN_JPEGD_* parse status
+JPEGD_SUBSEQ_BITS = 512           # the default subsequence: the lowest median of 512 / 1024 / 2048 (profiles/jpeg_decode_bench.json)
+JPEGD_ROUNDS = 16                 # rounds per launch group: the wrappers read the status words once per group
+
+
+class JpegdHuff(C.Structure):
+    _fields_ = [("bits", C.c_uint8 * 16), ("vals", C.c_uint8 * 256), ("lim", C.c_uint32 * 16), ("base", C.c_int32 * 16)]
+
+
+class JpegdDesc(C.Structure):
+    _fields_ = [("H", C.c_int32), ("W", C.c_int32), ("mode", C.c_int32), ("ncomp", C.c_int32), ("scan_offset", C.c_int32),
+                ("scan_length", C.c_int32), ("file_length", C.c_int32), ("reserved", C.c_int32), ("qsel", C.c_uint8 * 4),
+                ("dcsel", C.c_uint8 * 4), ("acsel", C.c_uint8 * 4), ("pad", C.c_uint8 * 4), ("quant", (C.c_uint8 * 64) * 4),
+                ("dc", JpegdHuff * 4), ("ac", JpegdHuff * 4)]
+
+
+def jpeg_parse(data):
+    """dsn_jpeg_parse_host: a file's bytes -> (JpegdDesc, parse status: an index into JPEGD_REASONS).  Host only, no device."""
+    data = bytes(data)
+    d, st = JpegdDesc(), C.c_int(0)
+    _check(lib().dsn_jpeg_parse_host(data, len(data), C.byref(d), C.byref(st)), "dsn_jpeg_parse_host")
+    return d, st.value
+
+
+class JpegdBatch:
+    """files of one (H, W, mode) on the device: the concatenated bytes (padded to 16), their offsets, the descriptor table"""
+
+    def __init__(self, files, descs, device=None):
+        require_gpu()
+        if not files or len(files) != len(descs):
+            raise ValueError("jpeg: a batch needs at least one file and one descriptor per file")
+        self.F = len(files)
+        self.H, self.W, self.mode = int(descs[0].H), int(descs[0].W), int(descs[0].mode)
+        if any((int(d.H), int(d.W), int(d.mode)) != (self.H, self.W, self.mode) for d in descs):
+            raise ValueError("jpeg: the files of one device call share H, W and mode (group them first)")
+        self.max_scan = max(max(int(d.scan_length) for d in descs), 1)
+        dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        off = [0]
+        for f in files:
+            off.append(off[-1] + len(f))
+        joined = bytearray(b"".join(bytes(f) for f in files))
+        joined += bytes(-len(joined) % 16)          # the library reads 16 aligned bytes at a time, never past files_bytes
+        self.files = torch.frombuffer(joined, dtype=torch.uint8).to(dev)
+        self.offsets = torch.tensor(off, dtype=torch.int64).to(dev)
+        self.desc = torch.frombuffer(bytearray(b"".join(bytes(d) for d in descs)), dtype=torch.uint8).to(dev)
+        self.device = dev
+        self.workspace_bytes = int(lib().dsn_jpegd_workspace_bytes(self.F, self.H, self.W, self.mode, self.max_scan))
+        if self.workspace_bytes == 0:
+            raise ValueError(f"jpeg: {self.F} frames of {self.H} x {self.W} in mode {self.mode} are outside what dsn_jpegd_* takes")
+        self.blocks = jpeg_blocks(self.H, self.W, self.mode)
+
+    def workspace(self):
+        return _scratch(self.workspace_bytes, self.device)
+
+    def geometry(self):
+        return self.F, self.H, self.W, self.mode, self.max_scan
+
+
+def _jpegd_bits(what, subseq_bits):
+    b = JPEGD_SUBSEQ_BITS if subseq_bits is None else int(subseq_bits)
+    if b < 128 or b > 4096 or b % 32:
+        raise ValueError(f"{what}: subseq_bits must be a multiple of 32 from 128 to 4096, got {subseq_bits!r}")
+    return b
+
+
+def jpegd_sync(batch, workspace, subseq_bits=None, restart=True, rounds=JPEGD_ROUNDS):
+    """dsn_jpegd_sync: `rounds` rounds (restart: unstuffing and round 0 first) on the state in `workspace` ->
+    (converged int32 [F], rounds int32 [F]) on the device"""
+    b = _jpegd_bits("jpegd_sync", subseq_bits)
+    conv = _output((batch.F,), torch.int32, batch.device)
+    rnd = _output((batch.F,), torch.int32, batch.device)
+    with torch.cuda.device(batch.device):
+        _check(lib().dsn_jpegd_sync(_ptr(batch.files), int(batch.files.numel()), _ptr(batch.offsets), _ptr(batch.desc), *batch.geometry(), b,
+                                    int(bool(restart)), int(rounds), _ptr(conv), _ptr(rnd), _ptr(workspace), int(workspace.numel()),
+                                    _stream()), "dsn_jpegd_sync")
+    return conv, rnd
+
+
+def jpegd_coefficients(batch, workspace, subseq_bits=None):
+    """dsn_jpegd_coefficients: the converged state in `workspace` -> (coef int16 [F, blocks, 64] with DC values, status int32 [F])"""
+    b = _jpegd_bits("jpegd_coefficients", subseq_bits)
+    coef = _output((batch.F, batch.blocks, 64), torch.int16, batch.device)
+    status = _output((batch.F,), torch.int32, batch.device)
+    with torch.cuda.device(batch.device):
+        _check(lib().dsn_jpegd_coefficients(_ptr(batch.desc), *batch.geometry(), b, _ptr(coef), _ptr(status), _ptr(workspace),
+                                            int(workspace.numel()), _stream()), "dsn_jpegd_coefficients")
+    return coef, status
+
+
+def _jpegd_out(batch, gray):
+    if gray and batch.mode != JPEG_GRAY:
+        raise ValueError("jpeg: gray=True needs one-component files")
+    return _output((batch.F, batch.H, batch.W) if gray else (batch.F, batch.H, batch.W, 3), torch.uint8, batch.device)
+
+
+def jpegd_pixels(batch, coef, status, workspace, rgb=False, gray=False):
+    """dsn_jpegd_pixels: coef int16 [F, blocks, 64], status int32 [F] or None -> uint8 [F, H, W, 3] (gray: [F, H, W]) on the device"""
+    if not torch.is_tensor(coef) or coef.dtype != torch.int16 or tuple(coef.shape) != (batch.F, batch.blocks, 64) or not coef.is_contiguous():
+        raise ValueError(f"jpegd_pixels: coef must be a contiguous int16 tensor [{batch.F}, {batch.blocks}, 64]")
+    out = _jpegd_out(batch, gray)
+    with torch.cuda.device(batch.device):
+        _check(lib().dsn_jpegd_pixels(_ptr(coef), _ptr(status), _ptr(batch.desc), *batch.geometry(), int(bool(rgb)), int(bool(gray)),
+                                      _ptr(out), _ptr(workspace), int(workspace.numel()), _stream()), "dsn_jpegd_pixels")
+    return out
+
+
+def jpegd_workspace_coef(batch, workspace):
+    """the coefficients dsn_jpeg_decode left in `workspace`: an int16 [F, blocks, 64] view of it"""
+    p = C.c_void_p(0)
+    _check(lib().dsn_jpegd_workspace_coef(_ptr(workspace), *batch.geometry(), C.byref(p)), "dsn_jpegd_workspace_coef")
+    at = int(p.value) - workspace.data_ptr()
+    return workspace[at:at + batch.F * batch.blocks * 128].view(torch.int16).view(batch.F, batch.blocks, 64)
+
+
+def jpeg_decode(batch, subseq_bits=None, rgb=False, gray=False, rounds=JPEGD_ROUNDS, workspace=None):
+    """dsn_jpeg_decode, then - only if a frame came back UNCONVERGED - further groups of `rounds` rounds and the two closing steps:
+    -> (out uint8 [F, H, W, 3] or [F, H, W], status int32 [F], rounds int32 [F], host copy of the status words).  One device->host
+    copy of 2 F words per group."""
+    b = _jpegd_bits("jpeg_decode", subseq_bits)
+    ws = batch.workspace() if workspace is None else workspace
+    out = _jpegd_out(batch, gray)
+    both = _output((2, batch.F), torch.int32, batch.device)          # status, rounds
+    with torch.cuda.device(batch.device):
+        _check(lib().dsn_jpeg_decode(_ptr(batch.files), int(batch.files.numel()), _ptr(batch.offsets), _ptr(batch.desc), *batch.geometry(), b,
+                                     int(rounds), int(bool(rgb)), int(bool(gray)), _ptr(out), _ptr(both[0]), _ptr(both[1]), _ptr(ws),
+                                     int(ws.numel()), _stream()), "dsn_jpeg_decode")
+    host = both.cpu().numpy()
+    if (host[0] & JPEGD_UNCONVERGED).any():
+        while True:
+            conv, rnd = jpegd_sync(batch, ws, b, restart=False, rounds=rounds)
+            if bool(torch.stack([conv, rnd]).cpu().numpy()[0].all()):
+                break
+        coef = jpegd_workspace_coef(batch, ws)
+        with torch.cuda.device(batch.device):
+            _check(lib().dsn_jpegd_coefficients(_ptr(batch.desc), *batch.geometry(), b, _ptr(coef), _ptr(both[0]), _ptr(ws), int(ws.numel()),
+                                                _stream()), "dsn_jpegd_coefficients")
+            _check(lib().dsn_jpegd_pixels(_ptr(coef), _ptr(both[0]), _ptr(batch.desc), *batch.geometry(), int(bool(rgb)), int(bool(gray)),
+                                          _ptr(out), _ptr(ws), int(ws.numel()), _stream()), "dsn_jpegd_pixels")
+        both[1].copy_(rnd)
+        host = both.cpu().numpy()
+    return out, both[0], both[1], host

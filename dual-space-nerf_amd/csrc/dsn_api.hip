@@ -2035,4 +2035,99 @@ int dsn_jpeg_encode(const void* images, int dtype, int F, int H, int W, int mode
     return dsn_check_launch("dsn_jpeg_encode");
 }
 
+// ---- baseline JPEG decoding (dsn_jpegd.hip) ----
+#define DSN_JPEGD_COMMON(name, F, H, W, mode, max_scan)                                                                        \
+    DSN_REQUIRE((mode) == DSN_JPEG_420 || (mode) == DSN_JPEG_444 || (mode) == DSN_JPEG_GRAY, name ": mode must be DSN_JPEG_420, _444 or _GRAY"); \
+    DSN_REQUIRE((F) >= 0 && (F) <= DSN_JPEGD_MAX_FRAMES, name ": F must be 0 ... 16384");                                      \
+    DSN_REQUIRE((H) >= 1 && (W) >= 1 && (H) <= 65535 && (W) <= 65535, name ": H and W must be 1 ... 65535");                   \
+    DSN_REQUIRE(dsn_jpegd_workspace_size(1, H, W, mode, max_scan) != 0,                                                        \
+                name ": too many blocks (blocks x 1664 must stay below 2^31) or max_scan_bytes above 2^27")
+#define DSN_JPEGD_WORKSPACE(name, F, H, W, mode, max_scan)                                                                     \
+    DSN_REQUIRE(((uintptr_t)workspace & 255) == 0, name ": workspace must be 256-byte aligned");                               \
+    DSN_REQUIRE(workspace_bytes >= dsn_jpegd_workspace_size(F, H, W, mode, max_scan), name ": workspace_bytes is too small")
+#define DSN_JPEGD_BITS(name, B)                                                                                                \
+    DSN_REQUIRE((B) >= 128 && (B) <= 4096 && (B) % 32 == 0, name ": subseq_bits must be a multiple of 32 from 128 to 4096")
+
+int dsn_jpeg_parse_host(const uint8_t* file_host, size_t bytes, dsn_jpegd_desc* desc_host, int* status) {
+    DSN_REQUIRE(file_host && desc_host && status, "dsn_jpeg_parse_host: null argument");
+    *status = dsn_jpegd_parse_host(file_host, bytes, desc_host);
+    return 0;
+}
+
+size_t dsn_jpegd_workspace_bytes(int F, int H, int W, int mode, size_t max_scan_bytes) {
+    return dsn_jpegd_workspace_size(F, H, W, mode, max_scan_bytes);
+}
+
+int dsn_jpegd_workspace_coef(void* workspace, int F, int H, int W, int mode, size_t max_scan_bytes, int16_t** coef) {
+    DSN_JPEGD_COMMON("dsn_jpegd_workspace_coef", F, H, W, mode, max_scan_bytes);
+    DSN_REQUIRE(workspace && coef && F >= 1, "dsn_jpegd_workspace_coef: null argument");
+    *coef = dsn_jpegd_workspace_coef(workspace, F, H, W, mode, max_scan_bytes);
+    return 0;
+}
+
+int dsn_jpegd_sync(const uint8_t* files, size_t files_bytes, const int64_t* offsets, const dsn_jpegd_desc* desc, int F, int H, int W,
+                   int mode, size_t max_scan_bytes, int subseq_bits, int restart, int rounds, uint32_t* out_converged, int32_t* out_rounds,
+                   void* workspace, size_t workspace_bytes, void* stream) {
+    DSN_JPEGD_COMMON("dsn_jpegd_sync", F, H, W, mode, max_scan_bytes);
+    DSN_JPEGD_BITS("dsn_jpegd_sync", subseq_bits);
+    DSN_REQUIRE(rounds >= 0 && rounds <= 65536, "dsn_jpegd_sync: rounds must be 0 ... 65536");
+    if (F == 0) return 0;
+    DSN_REQUIRE(files && offsets && desc && workspace, "dsn_jpegd_sync: null argument");
+    DSN_REQUIRE(((uintptr_t)files & 15) == 0 && files_bytes % 16 == 0, "dsn_jpegd_sync: files must be 16-byte aligned and files_bytes a multiple of 16");
+    DSN_REQUIRE((((uintptr_t)offsets & 7) | ((uintptr_t)desc & 3) | ((uintptr_t)out_converged & 3) | ((uintptr_t)out_rounds & 3)) == 0,
+                "dsn_jpegd_sync: a pointer is not aligned to its element");
+    DSN_JPEGD_WORKSPACE("dsn_jpegd_sync", F, H, W, mode, max_scan_bytes);
+    dsn_launch_jpegd_sync(files, files_bytes, offsets, desc, F, H, W, mode, max_scan_bytes, subseq_bits, restart != 0, rounds, out_converged,
+                          out_rounds, workspace, (hipStream_t)stream);
+    return dsn_check_launch("dsn_jpegd_sync");
+}
+
+int dsn_jpegd_coefficients(const dsn_jpegd_desc* desc, int F, int H, int W, int mode, size_t max_scan_bytes, int subseq_bits, int16_t* coef,
+                           uint32_t* out_status, void* workspace, size_t workspace_bytes, void* stream) {
+    DSN_JPEGD_COMMON("dsn_jpegd_coefficients", F, H, W, mode, max_scan_bytes);
+    DSN_JPEGD_BITS("dsn_jpegd_coefficients", subseq_bits);
+    if (F == 0) return 0;
+    DSN_REQUIRE(desc && coef && out_status && workspace, "dsn_jpegd_coefficients: null argument");
+    DSN_REQUIRE((((uintptr_t)coef & 15) | ((uintptr_t)desc & 3) | ((uintptr_t)out_status & 3)) == 0,
+                "dsn_jpegd_coefficients: coef must be 16-byte aligned, desc and out_status 4-byte aligned");
+    DSN_JPEGD_WORKSPACE("dsn_jpegd_coefficients", F, H, W, mode, max_scan_bytes);
+    dsn_launch_jpegd_coefficients(desc, F, H, W, mode, max_scan_bytes, subseq_bits, coef, out_status, workspace, (hipStream_t)stream);
+    return dsn_check_launch("dsn_jpegd_coefficients");
+}
+
+int dsn_jpegd_pixels(const int16_t* coef, const uint32_t* status, const dsn_jpegd_desc* desc, int F, int H, int W, int mode,
+                     size_t max_scan_bytes, int rgb, int gray_out, uint8_t* out, void* workspace, size_t workspace_bytes, void* stream) {
+    DSN_JPEGD_COMMON("dsn_jpegd_pixels", F, H, W, mode, max_scan_bytes);
+    DSN_REQUIRE(!gray_out || mode == DSN_JPEG_GRAY, "dsn_jpegd_pixels: gray_out needs mode DSN_JPEG_GRAY");
+    if (F == 0) return 0;
+    DSN_REQUIRE(coef && desc && out && workspace, "dsn_jpegd_pixels: null argument");
+    DSN_REQUIRE((((uintptr_t)coef & 15) | ((uintptr_t)desc & 3) | ((uintptr_t)status & 3)) == 0,
+                "dsn_jpegd_pixels: coef must be 16-byte aligned, desc and status 4-byte aligned");
+    DSN_JPEGD_WORKSPACE("dsn_jpegd_pixels", F, H, W, mode, max_scan_bytes);
+    dsn_launch_jpegd_pixels(coef, status, desc, F, H, W, mode, max_scan_bytes, rgb != 0, gray_out != 0, out, workspace, (hipStream_t)stream);
+    return dsn_check_launch("dsn_jpegd_pixels");
+}
+
+int dsn_jpeg_decode(const uint8_t* files, size_t files_bytes, const int64_t* offsets, const dsn_jpegd_desc* desc, int F, int H, int W,
+                    int mode, size_t max_scan_bytes, int subseq_bits, int rounds, int rgb, int gray_out, uint8_t* out, uint32_t* out_status,
+                    int32_t* out_rounds, void* workspace, size_t workspace_bytes, void* stream) {
+    DSN_JPEGD_COMMON("dsn_jpeg_decode", F, H, W, mode, max_scan_bytes);
+    DSN_JPEGD_BITS("dsn_jpeg_decode", subseq_bits);
+    DSN_REQUIRE(rounds >= 1 && rounds <= 65536, "dsn_jpeg_decode: rounds must be 1 ... 65536");
+    DSN_REQUIRE(!gray_out || mode == DSN_JPEG_GRAY, "dsn_jpeg_decode: gray_out needs mode DSN_JPEG_GRAY");
+    if (F == 0) return 0;
+    DSN_REQUIRE(files && offsets && desc && out && out_status && workspace, "dsn_jpeg_decode: null argument");
+    DSN_REQUIRE(((uintptr_t)files & 15) == 0 && files_bytes % 16 == 0, "dsn_jpeg_decode: files must be 16-byte aligned and files_bytes a multiple of 16");
+    DSN_REQUIRE((((uintptr_t)offsets & 7) | ((uintptr_t)desc & 3) | ((uintptr_t)out_status & 3) | ((uintptr_t)out_rounds & 3)) == 0,
+                "dsn_jpeg_decode: a pointer is not aligned to its element");
+    DSN_JPEGD_WORKSPACE("dsn_jpeg_decode", F, H, W, mode, max_scan_bytes);
+    hipStream_t st = (hipStream_t)stream;
+    int16_t* coef = dsn_jpegd_workspace_coef(workspace, F, H, W, mode, max_scan_bytes);
+    dsn_launch_jpegd_sync(files, files_bytes, offsets, desc, F, H, W, mode, max_scan_bytes, subseq_bits, true, rounds, nullptr, out_rounds,
+                          workspace, st);
+    dsn_launch_jpegd_coefficients(desc, F, H, W, mode, max_scan_bytes, subseq_bits, coef, out_status, workspace, st);
+    dsn_launch_jpegd_pixels(coef, out_status, desc, F, H, W, mode, max_scan_bytes, rgb != 0, gray_out != 0, out, workspace, st);
+    return dsn_check_launch("dsn_jpeg_decode");
+}
+
 }  // extern "C"

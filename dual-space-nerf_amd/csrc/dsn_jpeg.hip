@@ -549,3 +549,11 @@ void dsn_launch_jpeg_encode(const void* images, int dtype, int F, int H, int W, 
     dsn_launch_jpeg_coefficients(images, dtype, F, H, W, mode, quality, rgb, scale, w.coef, w.status, st);
     dsn_launch_jpeg_scan(w.coef, w.status, F, H, W, mode, quality, out, capacity, lengths, status, workspace, true, st);
 }
+
+// the tile scan on its own (dsn_jpegd.hip): x [F][n] becomes its exclusive prefix inside tiles of JPEG_TILE, tot [F][tiles + 1] the
+// tiles' exclusive prefixes and, in [tiles], the row's sum
+void dsn_launch_jpeg_tile_scan(int* x, int n, int F, int* tot, hipStream_t st) {
+    const int tiles = (n + JPEG_TILE - 1) / JPEG_TILE;
+    hipLaunchKernelGGL(k_jpeg_tile, dim3(tiles, F), dim3(JPEG_SCAN_THREADS), 0, st, x, n, tiles, tot);
+    hipLaunchKernelGGL(k_jpeg_tiles, dim3(F), dim3(JPEG_SCAN_THREADS), 0, st, tot, tiles);
+}

@@ -252,6 +252,20 @@ void dsn_launch_jpeg_scan(const int16_t* coef, const uint32_t* status_in, int F,
                           size_t capacity, int32_t* lengths, uint32_t* status, void* workspace, bool ws_has_coef, hipStream_t st);
 void dsn_launch_jpeg_encode(const void* images, int dtype, int F, int H, int W, int mode, int quality, int rgb, float scale, uint8_t* out,
                             size_t capacity, int32_t* lengths, uint32_t* status, void* workspace, hipStream_t st);
+void dsn_launch_jpeg_tile_scan(int* x, int n, int F, int* tot, hipStream_t st);
+struct dsn_jpegd_desc;
+// dsn_jpegd.hip: baseline JPEG decoding (dsn_jpeg_parse_host, dsn_jpegd_*, dsn_jpeg_decode; arguments checked by the entry points)
+int dsn_jpegd_parse_host(const uint8_t* file, size_t bytes, dsn_jpegd_desc* out);
+size_t dsn_jpegd_workspace_size(int F, int H, int W, int mode, size_t max_scan_bytes);
+int16_t* dsn_jpegd_workspace_coef(void* workspace, int F, int H, int W, int mode, size_t max_scan_bytes);
+void dsn_launch_jpegd_sync(const uint8_t* files, size_t files_bytes, const int64_t* offsets, const dsn_jpegd_desc* desc, int F, int H, int W,
+                           int mode, size_t max_scan_bytes, int B, bool restart, int rounds, uint32_t* out_converged, int32_t* out_rounds,
+                           void* workspace, hipStream_t st);
+void dsn_launch_jpegd_coefficients(const dsn_jpegd_desc* desc, int F, int H, int W, int mode, size_t max_scan_bytes, int B, int16_t* coef,
+                                   uint32_t* status, void* workspace, hipStream_t st);
+void dsn_launch_jpegd_pixels(const int16_t* coef, const uint32_t* status, const dsn_jpegd_desc* desc, int F, int H, int W, int mode,
+                             size_t max_scan_bytes, int rgb, int gray_out, uint8_t* out, void* workspace, hipStream_t st);
+
 // dsn_mesh.hip: density grid points and marching cubes (dsn_density_grid, dsn_mc_*)
 void dsn_launch_grid_points(const float* x, const float* y, const float* z, int i0, int ny, int nz, int64_t n, float* pts, hipStream_t st);
 size_t dsn_mc_workspace_size(int64_t N);

@@ -5,6 +5,13 @@ novel_pose_vis.py:62-66, vis_lighting.py:62-65, test.py) and img2vid's place, fr
     encode_device(images, ...) -> (buffer uint8 [F, capacity], lengths int32 [F], status int32 [F])  on the device, no wait
     imwrite(path, img, params=None)                                                                   cv2.imwrite's shape, .jpg / .jpeg
     write_avi(path, files, fps)                                                                       Motion-JPEG AVI around encoded frames (host)
+    decode(files, channels="bgr", gray=False) -> uint8 [H, W, 3] / [F, H, W, 3] on the device        the datasets' cv2.imread of a .jpg
+    decode_device(files, ...) -> (pixels, status int32 [F], rounds int32 [F])                         one status copy per group of rounds
+    imread(path) / imread_batch(paths)                                                                cv2.imread's shape: B, G, R
+
+Decoding takes baseline files (SOF0, 8 bits, one interleaved scan, grey / 4:4:4 / 4:2:0, any 8-bit DQT and any DHT): the pixels are
+the ones Pillow decodes through libjpeg-turbo at its default settings; cv2.imread's own pixels are not claimed.  The file bytes go up,
+the frame appears in HBM; anything else (progressive, 4:2:2, restart intervals, ...) raises ValueError with the parser's reason.
 
 The arithmetic is the rule written out in include/dsnerf.h and restated in tests/jpeg_restate.py: byte for byte the file Pillow
 writes through libjpeg-turbo at the same quality and subsampling (optimize=False).  cv2.imwrite's own bytes are not claimed, and the
@@ -162,3 +169,86 @@ def write_avi(path, files, fps=30):
     with open(path, "wb") as f:
         f.write(b"RIFF" + struct.pack("<I", len(body)) + body)
     return n
+
+
+# ---- decoding ---------------------------------------------------------------------------------------------------------------------------------
+def _parse_all(files, names):
+    descs = []
+    for k, f in enumerate(files):
+        d, st = _lib.jpeg_parse(f)
+        if st != 0:
+            raise ValueError(f"jpeg.decode: {names[k]}: not a file this decoder takes ({_lib.JPEGD_REASONS[st]})")
+        descs.append(d)
+    return descs
+
+
+def _groups(descs):
+    """indices grouped by (H, W, mode), in order of first appearance (as save_views groups on the way out)"""
+    g = {}
+    for k, d in enumerate(descs):
+        g.setdefault((int(d.H), int(d.W), int(d.mode)), []).append(k)
+    return list(g.values())
+
+
+def _decode_groups(files, names, channels, gray, device, subseq_bits):
+    if channels not in ("bgr", "rgb"):
+        raise ValueError(f"jpeg: channels must be 'bgr' or 'rgb', got {channels!r}")
+    files = [bytes(f) for f in files]
+    if not files:
+        raise ValueError("jpeg.decode: an empty list of files")
+    descs = _parse_all(files, names)
+    out, status, rounds = [None] * len(files), [0] * len(files), [0] * len(files)
+    for idx in _groups(descs):
+        batch = _lib.JpegdBatch([files[k] for k in idx], [descs[k] for k in idx], device)
+        px, st, rd, host = _lib.jpeg_decode(batch, subseq_bits, rgb=channels == "rgb", gray=gray)
+        for j, k in enumerate(idx):
+            out[k], status[k], rounds[k] = px[j], int(host[0, j]), int(host[1, j])
+    return out, status, rounds
+
+
+def _names(files, names):
+    return list(names) if names is not None else [f"file {k}" for k in range(len(files))]
+
+
+def decode_device(files, channels="bgr", gray=False, device=None, subseq_bits=None, names=None):
+    """files: one `bytes` or a list of them -> (pixels, status, rounds).  pixels: a uint8 device tensor [F, H, W, 3] (gray: [F, H, W])
+    when all files share a size and sampling mode, else a list of [H, W, 3] tensors in the files' order; status / rounds: int32 [F]
+    host arrays (DSN_JPEGD_* bits; the synchronisation rounds each frame took).  A corrupt frame is all zeros and keeps its bit set:
+    nothing is raised here."""
+    single = isinstance(files, (bytes, bytearray, memoryview))
+    files = [files] if single else list(files)
+    out, status, rounds = _decode_groups(files, _names(files, names), channels, gray, device, subseq_bits)
+    same = all(o.shape == out[0].shape for o in out)
+    px = torch.stack(out) if same else out
+    return px, np.asarray(status, np.int32), np.asarray(rounds, np.int32)
+
+
+def decode(files, channels="bgr", gray=False, device=None, subseq_bits=None, names=None):
+    """One `bytes` -> a uint8 device tensor [H, W, 3] in B, G, R order (what cv2.imread returns; channels="rgb": R, G, B; gray=True, for
+    one-component files: [H, W]).  A list -> [F, H, W, 3] when sizes and modes agree, else a list of tensors.  An unsupported or corrupt
+    file raises ValueError naming the file and the reason."""
+    single = isinstance(files, (bytes, bytearray, memoryview))
+    lst = [files] if single else list(files)
+    nm = _names(lst, names)
+    px, status, _ = decode_device(lst, channels, gray, device, subseq_bits, nm)
+    for k, st in enumerate(status):
+        if int(st) & _lib.JPEGD_CORRUPT:
+            why = [n for n, b in (("a code that matches nothing", _lib.JPEGD_UNMATCHED), ("a coefficient index past 63", _lib.JPEGD_OVERRUN),
+                                  ("a marker inside the scan", _lib.JPEGD_MARKER), ("a block count that is not the frame's", _lib.JPEGD_COUNT))
+                   if int(st) & b]
+            raise ValueError(f"jpeg.decode: {nm[k]}: corrupt scan ({', '.join(why)})")
+    return px[0] if single else px
+
+
+def imread_batch(paths, channels="bgr", device=None):
+    """the files at `paths` -> as decode() of their bytes"""
+    data = []
+    for p in paths:
+        with open(p, "rb") as f:
+            data.append(f.read())
+    return decode(data, channels=channels, device=device, names=[str(p) for p in paths])
+
+
+def imread(path, channels="bgr", device=None):
+    """cv2.imread(path)'s shape for a .jpg: uint8 [H, W, 3] in B, G, R order, on the device"""
+    return imread_batch([path], channels, device)[0]

@@ -1430,6 +1430,147 @@ DSN_EXPORT int dsn_jpeg_encode(const void* images, int dtype, int F, int H, int 
                                uint8_t* out, size_t capacity, int32_t* out_lengths, uint32_t* out_status, void* workspace,
                                size_t workspace_bytes, void* stream);
 
+/* ---- Baseline JPEG DECODING on the device (csrc/dsn_jpegd.hip): the datasets' cv2.imread(img_path) of a .jpg
+ * (dataloader/zju_mocap_dataset.py:86, h36m_dataset.py:128, novel_poses_dataset.py:119): file bytes go up, the uint8 frame that
+ * dsn_image_prep takes appears in HBM, a few status words come back.  The rule below is restated in tests/jpeg_decode_restate.py,
+ * which gives pixel for pixel what Pillow decodes through libjpeg-turbo at its default settings (slow-integer IDCT, fancy
+ * upsampling); cv2.imread's own pixels are not claimed.  Integer arithmetic only, no float atomics: the same bits on every call,
+ * and a frame decodes the same alone or in any batch.
+ *   Scope.  Baseline sequential files (SOF0), 8 bits, ONE interleaved scan, 1 component (DSN_JPEG_GRAY) or 3 components sampled
+ *      4:4:4 (DSN_JPEG_444) or 4:2:0 (DSN_JPEG_420); quantisation (8-bit entries) and Huffman tables as the file gives them (DQT /
+ *      DHT ids 0 ... 3); APPn and COM segments are skipped, so a three-component file is always taken as YCbCr.  Everything else is
+ *      refused by dsn_jpeg_parse_host with a named status and reaches no kernel: DSN_JPEGD_PROGRESSIVE (SOF2), _EXTENDED (SOF1, 3,
+ *      5 - 7), _ARITHMETIC (SOF9 - 15, DAC), _PRECISION (12-bit), _SAMPLING (4:2:2 and the rest), _COMPONENTS (2, 4), _TABLE16,
+ *      _MULTISCAN (an SOS with fewer components than the frame), _RESTART (DRI with a non-zero interval), _MISSING_TABLE,
+ *      _BAD_TABLE (code lengths that overflow, more than 256 symbols, a DC symbol above 15), _NO_EOI, _TRUNCATED, _BAD_SEGMENT,
+ *      _NOT_JPEG, _TOO_LARGE (2^27 bytes and up, or more blocks than the encoder takes).
+ *   Host part.  dsn_jpeg_parse_host reads the header and the file's last two bytes (EOI) and fills a dsn_jpegd_desc: H, W, mode,
+ *      per-component selectors, the quantisation tables in the file's zigzag order, every Huffman table as bits / vals and in the
+ *      decoders' form: lim[l - 1] = (first code that is NOT of length <= l) << (16 - l), base[l - 1] = (index of the first symbol of
+ *      length l) - (its code); a 16-bit window v holds a code of length l = the smallest l with v < lim[l - 1], and the symbol is
+ *      vals[(base[l - 1] + (v >> (16 - l))) & 255].  scan_offset / scan_length: the bytes between SOS and EOI.  A marker inside the
+ *      scan is found by the device.  All frames of one device call share H, W and mode; tables may differ per frame.
+ *   Unstuffing.  In the scan a 0x00 behind a 0xFF is dropped.  Any other byte behind a 0xFF, or a 0xFF as the scan's last byte, is a
+ *      marker: DSN_JPEGD_MARKER.  The unstuffed scan of U bytes is 8 U bits, most significant bit first; bits past it read as 0.
+ *   Symbols.  A decoder state is (bit position p, block k within the MCU, zigzag index z); the scan starts at (0, 0, 0).  One step
+ *      at z = 0 reads a code of the block's component's DC table -> s = symbol & 15, then s bits v: the DC difference (v if its top
+ *      bit is set, else v - 2^s + 1); z = 1.  At z > 0 it reads a code of the AC table -> r = symbol >> 4, s = symbol & 15, s bits:
+ *      s = 0: r = 15 moves z on by 16, any other r ends the block; s > 0: z += r, the value is coefficient z, z += 1.  A z past 63
+ *      ends the block; landing past 64 by a ZRL, or past 63 with a value (which is dropped), is DSN_JPEGD_OVERRUN.  At the end of a
+ *      block k moves on (cyclically over the MCU's 1, 3 or 6 blocks) and z = 0.  A window that matches no code moves p on by one
+ *      bit: DSN_JPEGD_UNMATCHED.  A symbol that needs bits past the scan's end is not decoded, and decoding ends there; so does a
+ *      window without a code that has fewer than 16 bits left.
+ *   Synchronisation (the parallel form).  The unstuffed scan is cut into subsequences of B bits (subseq_bits: a multiple of 32,
+ *      128 ... 4096; S = max(1, ceil(8 U / B))).  Round 0: a thread per subsequence s decodes from (s B, 0, 0) until p >= (s + 1) B
+ *      (or the scan's end) and records its entry, its exit state, the blocks it started and its error flags.  Round r: s takes the
+ *      exit of s - 1 from the PREVIOUS round's buffer (two buffers, no race); equal to the entry it used: it copies its exit over;
+ *      else it decodes again from there and raises the frame's "changed" word.  Subsequence 0 is right from the start and after
+ *      round r subsequences 0 ... r are, so a round that changes nothing comes after at most S rounds, and the fixed point IS the
+ *      serial decode.  That round counts: `rounds` is the number of rounds up to and including it (1 for S = 1).  Rounds after it
+ *      return at once.  Streams usually re-synchronise within a subsequence or two; a scan without end-of-block codes (noise at
+ *      quality 100) may need about S rounds.
+ *   Emit.  The tile scan of the blocks started per subsequence gives each its first block index; every subsequence decodes once
+ *      more from its true entry into the cleared int16 coef [F, blocks, 64] (zigzag and scan order), DC as differences; blocks at
+ *      or past the geometry's count are dropped.  Per component an integer prefix sum over its blocks in scan order (tile scan
+ *      again) turns differences into DC values (int32 sums, stored as int16).
+ *      This last pass stops behind the frame's last block (the rounds, which do not know block indices, run on to the scan's end):
+ *      what follows it is never decoded, as in libjpeg, and the error flags speak of the frame's own blocks only.
+ *   Status.  DSN_JPEGD_COUNT: the scan ends before the geometry's last block is complete, or the descriptor's scan does not lie
+ *      inside its file.  Any of _UNMATCHED, _OVERRUN, _MARKER, _COUNT sets DSN_JPEGD_CORRUPT.  DSN_JPEGD_PADDING (a warning, not an
+ *      error): more than 7 bits are left behind the last block, or the bits left are not all 1.  DSN_JPEGD_UNCONVERGED: the rounds run so far did not reach the fixed point; nothing was emitted.
+ *   Dequantisation and IDCT.  coefficient x table entry in int32, then libjpeg's jpeg_idct_islow in int32 (wrapping; a 64-bit
+ *      libjpeg agrees whenever nothing overflows, which holds for every file an 8-bit encoder writes): pass 1 down every column,
+ *      pass 2 along every row of the result, CONST_BITS = 13, PASS1_BITS = 2.  One pass over i0 ... i7:
+ *        z1 = (i2 + i6) 4433, t2 = z1 - i6 15137, t3 = z1 + i2 6270, t0 = (i0 + i4) << 13, t1 = (i0 - i4) << 13
+ *        t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2
+ *        u0 = i7, u1 = i5, u2 = i3, u3 = i1, z1 = u0 + u3, z2 = u1 + u2, z3 = u0 + u2, z4 = u1 + u3, z5 = (z3 + z4) 9633
+ *        u0 *= 2446, u1 *= 16819, u2 *= 25172, u3 *= 12299, z1 *= -7373, z2 *= -20995, z3 = z3 (-16069) + z5, z4 = z4 (-3196) + z5
+ *        u0 += z1 + z3, u1 += z2 + z4, u2 += z2 + z3, u3 += z1 + z4
+ *        out0, 7 = DESCALE(t10 +- u3, n), out1, 6 = DESCALE(t11 +- u2, n), out2, 5 = DESCALE(t12 +- u1, n), out3, 4 = DESCALE(t13 +- u0, n)
+ *      with n = 11 in pass 1 and 18 in pass 2, DESCALE(x, n) = (x + (1 << (n - 1))) >> n (arithmetic).  No zero-column shortcut (it
+ *      gives the same bits).  The sample is (result & 1023) read as a signed 10-bit number, + 128, clamped to [0, 255].
+ *   Chroma at 4:2:0 (libjpeg's "fancy" h2v2 upsampling).  The chroma plane is ceil(W / 2) x ceil(H / 2); padding takes no part.
+ *      Wider than 2 columns: for output row y, near = row y / 2, far = the row above (y even) or below (y odd), the first / last row
+ *      standing in for a missing neighbour; c(j) = 3 near(j) + far(j).  Output column x, j = x / 2: x even: (3 c(j) + c(j - 1) + 8)
+ *      >> 4, x odd: (3 c(j) + c(j + 1) + 7) >> 4, a missing neighbour replaced by c(j) itself ((4 c + 8) >> 4, (4 c + 7) >> 4).
+ *      At most 2 columns wide (W <= 4): the sample of (y / 2, x / 2), as libjpeg's downsampled_width > 2 test has it.
+ *   Colour (16-bit fixed point, >> arithmetic, clamped to [0, 255]):
+ *      R = Y + ((91881 (Cr - 128) + 32768) >> 16),  B = Y + ((116130 (Cb - 128) + 32768) >> 16)
+ *      G = Y + ((-22554 (Cb - 128) - 46802 (Cr - 128) + 32768) >> 16)
+ *   Output.  uint8 [F, H, W, 3] in B, G, R order (rgb = 0: what cv2.imread returns; a one-component file is replicated) or R, G, B
+ *      (rgb != 0); gray_out != 0 (DSN_JPEG_GRAY only): [F, H, W].  A frame whose status has DSN_JPEGD_CORRUPT or _UNCONVERGED gets
+ *      all-zero pixels: every output byte is defined.
+ *   Kernels.  k_jd_ffcount / tile scan / k_jd_unstuff: the mirror of the encoder's stuffing, 16 bytes of the scan per thread,
+ *      fetched with two aligned 16-byte loads that are made only inside [0, files_bytes).  k_jd_round: a thread per subsequence,
+ *      a workgroup's subsequences all of one frame, whose six resolved Huffman tables lie in LDS; a divergent per-lane bit reader
+ *      whose every word index is checked against the frame's stream.  k_jd_verdict: the frames' round counters.  k_jd_emit: the
+ *      same reader, writing.  k_jd_idct: a wave per 8 blocks, a lane per column, then per row, through LDS, 8 samples per store into
+ *      the component planes at the MCU grid's size.  k_jd_colour: a thread per pixel.  No MFMA: DSN_OWN_SIMD does not apply.
+ * files: uint8 [files_bytes], the frames' files one behind the other, 16-byte aligned, files_bytes a multiple of 16 (pad the tail);
+ * offsets: int64 [F + 1], file f = [offsets[f], offsets[f + 1]); desc: dsn_jpegd_desc [F] in DEVICE memory.  Every read of a frame's
+ * scan is clipped to its own file, to files_bytes and to max_scan_bytes (>= every frame's scan_length; it sizes the workspace).
+ * dsn_jpegd_sync: restart != 0 unstuffs and runs round 0 as the first of `rounds`; restart = 0 runs `rounds` further rounds on the
+ * state in the workspace (same subseq_bits).  out_converged uint32 [F] / out_rounds int32 [F] (either may be null).
+ * dsn_jpegd_coefficients: emit + DC from the workspace's converged state -> coef int16 [F, blocks, 64] (16-byte aligned), out_status
+ * uint32 [F].  dsn_jpegd_pixels: coef, status (may be null: all frames good) -> out.  dsn_jpeg_decode: sync (restart, `rounds`
+ * rounds) + coefficients + pixels, bit for bit, its coef in the workspace; a frame that needs more rounds comes back
+ * DSN_JPEGD_UNCONVERGED, and the caller goes on with dsn_jpegd_sync (restart = 0), dsn_jpegd_coefficients and dsn_jpegd_pixels on
+ * the same workspace (dsn_jpegd_workspace_coef: where its coef lie).  workspace: dsn_jpegd_workspace_bytes(F, H, W, mode,
+ * max_scan_bytes) bytes (0 for bad sizes), 256-byte aligned, anything on entry of a restart.  No allocation, no host copy, no
+ * synchronisation.  dsn_jpeg_parse_host: HOST memory in and out; returns 0 and the DSN_JPEGD_* parse status through *status. */
+#define DSN_JPEGD_CORRUPT 1u
+#define DSN_JPEGD_PADDING 2u
+#define DSN_JPEGD_UNCONVERGED 4u
+#define DSN_JPEGD_UNMATCHED 16u
+#define DSN_JPEGD_OVERRUN 32u
+#define DSN_JPEGD_MARKER 64u
+#define DSN_JPEGD_COUNT 128u
+#define DSN_JPEGD_MAX_FRAMES 16384
+#define DSN_JPEGD_OK 0            /* dsn_jpeg_parse_host's status */
+#define DSN_JPEGD_NOT_JPEG 1
+#define DSN_JPEGD_TRUNCATED 2
+#define DSN_JPEGD_PROGRESSIVE 3
+#define DSN_JPEGD_EXTENDED 4
+#define DSN_JPEGD_ARITHMETIC 5
+#define DSN_JPEGD_PRECISION 6
+#define DSN_JPEGD_SAMPLING 7
+#define DSN_JPEGD_COMPONENTS 8
+#define DSN_JPEGD_TABLE16 9
+#define DSN_JPEGD_MULTISCAN 10
+#define DSN_JPEGD_RESTART 11
+#define DSN_JPEGD_MISSING_TABLE 12
+#define DSN_JPEGD_BAD_TABLE 13
+#define DSN_JPEGD_NO_EOI 14
+#define DSN_JPEGD_BAD_SEGMENT 15
+#define DSN_JPEGD_TOO_LARGE 16
+typedef struct dsn_jpegd_huff {
+    uint8_t bits[16];             /* codes per length 1 ... 16 */
+    uint8_t vals[256];            /* the symbols in code order, zeros behind them */
+    uint32_t lim[16];
+    int32_t base[16];
+} dsn_jpegd_huff;
+typedef struct dsn_jpegd_desc {
+    int32_t H, W, mode, ncomp;
+    int32_t scan_offset, scan_length, file_length, reserved;
+    uint8_t qsel[4], dcsel[4], acsel[4], pad[4];          /* per component: table ids */
+    uint8_t quant[4][64];         /* zigzag order */
+    dsn_jpegd_huff dc[4], ac[4];
+} dsn_jpegd_desc;
+DSN_EXPORT int dsn_jpeg_parse_host(const uint8_t* file_host, size_t bytes, dsn_jpegd_desc* desc_host, int* status);
+DSN_EXPORT size_t dsn_jpegd_workspace_bytes(int F, int H, int W, int mode, size_t max_scan_bytes);
+DSN_EXPORT int dsn_jpegd_workspace_coef(void* workspace, int F, int H, int W, int mode, size_t max_scan_bytes, int16_t** coef);
+DSN_EXPORT int dsn_jpegd_sync(const uint8_t* files, size_t files_bytes, const int64_t* offsets, const dsn_jpegd_desc* desc, int F, int H,
+                              int W, int mode, size_t max_scan_bytes, int subseq_bits, int restart, int rounds, uint32_t* out_converged,
+                              int32_t* out_rounds, void* workspace, size_t workspace_bytes, void* stream);
+DSN_EXPORT int dsn_jpegd_coefficients(const dsn_jpegd_desc* desc, int F, int H, int W, int mode, size_t max_scan_bytes, int subseq_bits,
+                                      int16_t* coef, uint32_t* out_status, void* workspace, size_t workspace_bytes, void* stream);
+DSN_EXPORT int dsn_jpegd_pixels(const int16_t* coef, const uint32_t* status, const dsn_jpegd_desc* desc, int F, int H, int W, int mode,
+                                size_t max_scan_bytes, int rgb, int gray_out, uint8_t* out, void* workspace, size_t workspace_bytes,
+                                void* stream);
+DSN_EXPORT int dsn_jpeg_decode(const uint8_t* files, size_t files_bytes, const int64_t* offsets, const dsn_jpegd_desc* desc, int F, int H,
+                               int W, int mode, size_t max_scan_bytes, int subseq_bits, int rounds, int rgb, int gray_out, uint8_t* out,
+                               uint32_t* out_status, int32_t* out_rounds, void* workspace, size_t workspace_bytes, void* stream);
+
 /* diagnostics, NOT for the hot path (synchronises `stream`): {ncell, ok, total entries, capacity} of the four
  * nearest-face list levels (world fine/coarse, canonical fine/coarse) into a HOST array of 16 int32. */
 DSN_EXPORT int dsn_debug_nn_stats(const void* scene, int V, int F, int32_t* out16_host, void* stream);
