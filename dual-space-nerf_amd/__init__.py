@@ -14,8 +14,9 @@ from .body import BodyModel  # noqa: F401
 from . import imageprep  # noqa: F401  (undistort, dilate, erode, resizes, prepare_zju / prepare_h36m: the datasets' OpenCV work on the device)
 from . import lpips  # noqa: F401  (LPIPS: test.py's lpips_alex / lpips_vgg distances on the device)
 from . import jpeg  # noqa: F401  (encode, imwrite, write_avi: the scripts' cv2.imwrite into .jpg on the device, img2vid's place)
+from . import png  # noqa: F401  (decode, imread: the datasets' label masks, inflated and unfiltered on the device)
 from .can_render import Renderer  # noqa: F401
 from .model.spacenet import DualSpaceNeRF, LightingMLP, SpaceNet  # noqa: F401
 from .parallel import RayParallel  # noqa: F401
 
-__all__ = ["Renderer", "DualSpaceNeRF", "SpaceNet", "LightingMLP", "RayParallel", "synth", "loss", "optim", "body", "BodyModel", "imageprep", "lpips", "jpeg"]
+__all__ = ["Renderer", "DualSpaceNeRF", "SpaceNet", "LightingMLP", "RayParallel", "synth", "loss", "optim", "body", "BodyModel", "imageprep", "lpips", "jpeg", "png"]

@@ -64,6 +64,7 @@ EXPORTS = [
     "dsn_jpeg_max_bytes", "dsn_jpeg_workspace_bytes", "dsn_jpeg_header_host", "dsn_jpeg_coefficients", "dsn_jpeg_scan", "dsn_jpeg_encode",
     "dsn_jpeg_parse_host", "dsn_jpegd_workspace_bytes", "dsn_jpegd_workspace_coef", "dsn_jpegd_sync", "dsn_jpegd_coefficients",
     "dsn_jpegd_pixels", "dsn_jpeg_decode",
+    "dsn_png_parse_host", "dsn_png_workspace_bytes", "dsn_png_workspace_layout", "dsn_png_decode",
 ]
 
 SKIP_TRANSPARENT = 1
@@ -235,6 +236,12 @@ def lib():
                                        + [C.c_size_t, C.c_void_p])
         L.dsn_jpeg_decode.argtypes = ([C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_size_t] + [C.c_int] * 4
                                       + [C.c_void_p] * 4 + [C.c_size_t, C.c_void_p])
+        L.dsn_png_parse_host.argtypes = [C.c_char_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        L.dsn_png_workspace_bytes.restype = C.c_size_t
+        L.dsn_png_workspace_bytes.argtypes = [C.c_int] * 5 + [C.c_size_t]
+        L.dsn_png_workspace_layout.argtypes = [C.c_int] * 5 + [C.c_size_t, C.c_void_p]
+        L.dsn_png_decode.argtypes = ([C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_size_t]
+                                     + [C.c_int] * 3 + [C.c_void_p] * 3 + [C.c_size_t, C.c_void_p])
         if L.dsn_abi_version() != 8:
             raise RuntimeError(f"{LIB_PATH} has ABI version {L.dsn_abi_version()}, this binding needs 8 - rebuild it "
                                "(python dual-space-nerf_amd/build.py)")
@@ -3072,3 +3079,114 @@ def jpeg_decode(batch, subseq_bits=None, rgb=False, gray=False, rounds=JPEGD_ROU
         both[1].copy_(rnd)
         host = both.cpu().numpy()
     return out, both[0], both[1], host
+
+
+# ---- PNG decoding (dsn_png_parse_host, dsn_png_workspace_*, dsn_png_decode: the rule of include/dsnerf.h) -----------------------------------
+(PNG_EARLY_END, PNG_BLOCK_TYPE, PNG_STORED_LEN, PNG_BAD_CODES, PNG_NO_CODE, PNG_FAR_DISTANCE, PNG_TOO_MUCH, PNG_TOO_LITTLE, PNG_FILTER,
+ PNG_ADLER) = (1 << k for k in range(10))
+PNG_STATUS_NAMES = ["the stream ends early", "a reserved block type", "a stored block whose LEN and NLEN disagree",
+                    "over-subscribed or unusable code lengths", "a code that matches nothing", "a distance that reaches before the output's start",
+                    "more output than the image holds", "less output than the image needs", "a filter byte above 4", "an Adler-32 mismatch"]
+PNG_REASONS = ["ok", "not_png", "truncated", "crc", "bad_ihdr", "interlace", "depth16", "no_ihdr", "no_idat", "no_plte", "zero_dim", "too_large",
+               "zlib_method", "zlib_dict", "zlib_check"]          # DSN_PNG_* parse status
+PNG_CHANNELS = {"bgr": 0, "rgb": 1, "native": 2}
+PNG_GATHER, PNG_INFLATE, PNG_ADLER_STAGE, PNG_UNFILTER, PNG_PIXELS, PNG_ALL = 1, 2, 4, 8, 16, 31
+
+
+class PngDesc(C.Structure):
+    _fields_ = [("W", C.c_int32), ("H", C.c_int32), ("bits", C.c_int32), ("ctype", C.c_int32), ("channels", C.c_int32),
+                ("row_bytes", C.c_int32), ("raw_bytes", C.c_int32), ("npal", C.c_int32), ("nseg", C.c_int32), ("zlen", C.c_int32),
+                ("file_length", C.c_int32), ("reserved", C.c_int32 * 5), ("palette", (C.c_uint8 * 3) * 256)]
+
+
+def png_status_text(status):
+    return ", ".join(n for k, n in enumerate(PNG_STATUS_NAMES) if int(status) >> k & 1)
+
+
+def png_parse(data, seg_capacity=64):
+    """dsn_png_parse_host: a file's bytes -> (PngDesc, segments [(offset, length), ...], parse status: an index into PNG_REASONS).
+    Host only, no device."""
+    data = bytes(data)
+    d, st = PngDesc(), C.c_int(0)
+    while True:
+        segs = (C.c_uint32 * (2 * seg_capacity))()
+        _check(lib().dsn_png_parse_host(data, len(data), C.byref(d), segs, seg_capacity, C.byref(st)), "dsn_png_parse_host")
+        if st.value != 0 or d.nseg <= seg_capacity:
+            break
+        seg_capacity = int(d.nseg)
+    n = min(int(d.nseg), seg_capacity) if st.value == 0 else 0
+    return d, [(int(segs[2 * k]), int(segs[2 * k + 1])) for k in range(n)], st.value
+
+
+class PngBatch:
+    """files of one (W, H, bits, ctype) on the device: the concatenated bytes, the IDAT segment table, the descriptor table"""
+
+    def __init__(self, files, descs, segments, device=None):
+        require_gpu()
+        if not files or len(files) != len(descs) or len(files) != len(segments):
+            raise ValueError("png: a batch needs at least one file, and a descriptor and a segment list per file")
+        self.F = len(files)
+        self.W, self.H, self.bits, self.ctype = (int(getattr(descs[0], k)) for k in ("W", "H", "bits", "ctype"))
+        if any((int(d.W), int(d.H), int(d.bits), int(d.ctype)) != (self.W, self.H, self.bits, self.ctype) for d in descs):
+            raise ValueError("png: the files of one device call share W, H, bit depth and colour type (group them first)")
+        self.channels, self.row_bytes, self.raw_bytes = int(descs[0].channels), int(descs[0].row_bytes), int(descs[0].raw_bytes)
+        self.max_stream = max(max(int(d.zlen) for d in descs), 1)
+        dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        table, first, base = [], [0], 0
+        for f, seg in zip(files, segments):
+            at = 0
+            for o, n in seg:
+                table.append((base + o, at, n))
+                at += n
+            first.append(len(table))
+            base += len(f)
+        joined = bytearray(b"".join(bytes(f) for f in files))
+        self.files = torch.frombuffer(joined, dtype=torch.uint8).to(dev)
+        self.segs = torch.tensor(table if table else [(0, 0, 0)], dtype=torch.int64).to(dev)
+        self.n_segs = len(table)
+        self.seg_first = torch.tensor(first, dtype=torch.int32).to(dev)
+        self.desc = torch.frombuffer(bytearray(b"".join(bytes(d) for d in descs)), dtype=torch.uint8).to(dev)
+        self.device = dev
+        lay = (C.c_size_t * 8)()
+        if lib().dsn_png_workspace_layout(self.F, self.W, self.H, self.bits, self.ctype, self.max_stream, lay) != 0:
+            raise ValueError(f"png: {self.F} files of {self.W} x {self.H}, {self.bits} bits, colour type {self.ctype} are outside what "
+                             "dsn_png_decode takes")
+        self.layout = [int(v) for v in lay]
+        self.workspace_bytes = self.layout[7]
+
+    def workspace(self):
+        return _scratch(self.workspace_bytes, self.device)
+
+    def geometry(self):
+        return self.F, self.W, self.H, self.bits, self.ctype, self.max_stream
+
+    def out_shape(self, channels, first_channel):
+        if first_channel:
+            return (self.F, self.H, self.W)
+        return (self.F, self.H, self.W, self.channels if channels == "native" else 3)
+
+    def views(self, workspace):
+        """what a decode left in `workspace`: (meta int32 [F, 8], streams uint8 [F, stride], raw uint8 [F, stride], rows uint8 [F, stride])"""
+        m, s, ss, r, rs, w, ws, _ = self.layout
+        F = self.F
+        return (workspace[m:m + F * 32].view(torch.int32).view(F, 8), workspace[s:s + F * ss].view(F, ss), workspace[r:r + F * rs].view(F, rs),
+                workspace[w:w + F * ws].view(F, ws))
+
+
+def png_decode(batch, channels="bgr", first_channel=False, stages=PNG_ALL, workspace=None, out=None, status=None):
+    """dsn_png_decode -> (out uint8 [F, H, W, C] or [F, H, W], status int32 [F]) on the device; no wait, no copy"""
+    if channels not in PNG_CHANNELS:
+        raise ValueError(f"png: channels must be 'bgr', 'rgb' or 'native', got {channels!r}")
+    ws = batch.workspace() if workspace is None else workspace
+    shape = batch.out_shape(channels, bool(first_channel))
+    if out is None:
+        out = _output(shape, torch.uint8, batch.device)
+    elif tuple(out.shape) != shape or out.dtype != torch.uint8 or not out.is_contiguous():
+        raise ValueError(f"png_decode: out must be a contiguous uint8 tensor {shape}")
+    if status is None:
+        status = _output((batch.F,), torch.int32, batch.device)
+    with torch.cuda.device(batch.device):
+        _check(lib().dsn_png_decode(_ptr(batch.files), int(batch.files.numel()), _ptr(batch.segs), batch.n_segs, _ptr(batch.seg_first),
+                                    _ptr(batch.desc), *batch.geometry(), PNG_CHANNELS[channels], int(bool(first_channel)), int(stages),
+                                    _ptr(out), _ptr(status), _ptr(ws), int(ws.numel()), _stream()), "dsn_png_decode")
+    return out, status

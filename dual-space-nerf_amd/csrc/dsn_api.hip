@@ -2130,4 +2130,48 @@ int dsn_jpeg_decode(const uint8_t* files, size_t files_bytes, const int64_t* off
     return dsn_check_launch("dsn_jpeg_decode");
 }
 
+// ---- PNG decoding (dsn_png.hip) ----
+int dsn_png_parse_host(const uint8_t* file_host, size_t bytes, dsn_png_desc* desc_host, uint32_t* segs_host, size_t seg_capacity, int* status) {
+    DSN_REQUIRE(file_host && desc_host && status, "dsn_png_parse_host: null argument");
+    DSN_REQUIRE(segs_host || seg_capacity == 0, "dsn_png_parse_host: segs_host is null but seg_capacity is not 0");
+    *status = dsn_png_parse(file_host, bytes, desc_host, segs_host, seg_capacity);
+    return 0;
+}
+
+size_t dsn_png_workspace_bytes(int F, int W, int H, int bits, int ctype, size_t max_stream_bytes) {
+    return dsn_png_workspace_size(F, W, H, bits, ctype, max_stream_bytes, nullptr);
+}
+
+int dsn_png_workspace_layout(int F, int W, int H, int bits, int ctype, size_t max_stream_bytes, size_t* out8_host) {
+    DSN_REQUIRE(out8_host, "dsn_png_workspace_layout: null argument");
+    DSN_REQUIRE(dsn_png_workspace_size(F, W, H, bits, ctype, max_stream_bytes, out8_host) != 0,
+                "dsn_png_workspace_layout: F must be 1 ... 16384, W and H 1 ... 16384, bits / ctype a pair the decoder takes, at most 2^30 raw "
+                "bytes and max_stream_bytes at most 2^28");
+    return 0;
+}
+
+int dsn_png_decode(const uint8_t* files, size_t files_bytes, const int64_t* segs, int n_segs, const int32_t* seg_first, const dsn_png_desc* desc,
+                   int F, int W, int H, int bits, int ctype, size_t max_stream_bytes, int channels, int first_channel, int stages, uint8_t* out,
+                   uint32_t* out_status, void* workspace, size_t workspace_bytes, void* stream) {
+    DSN_REQUIRE(F >= 0 && F <= DSN_PNG_MAX_FILES, "dsn_png_decode: F must be 0 ... 16384");
+    DSN_REQUIRE(dsn_png_workspace_size(1, W, H, bits, ctype, max_stream_bytes, nullptr) != 0,
+                "dsn_png_decode: W and H must be 1 ... 16384, bits / ctype a pair the decoder takes, with at most 2^30 raw bytes, and "
+                "max_stream_bytes at most 2^28");
+    DSN_REQUIRE(channels == DSN_PNG_BGR || channels == DSN_PNG_RGB || channels == DSN_PNG_NATIVE,
+                "dsn_png_decode: channels must be DSN_PNG_BGR, _RGB or _NATIVE");
+    DSN_REQUIRE(stages >= 1 && stages <= DSN_PNG_STAGE_ALL, "dsn_png_decode: stages must be a non-empty set of DSN_PNG_STAGE_* bits");
+    DSN_REQUIRE(n_segs >= 0, "dsn_png_decode: n_segs must not be negative");
+    if (F == 0) return 0;
+    DSN_REQUIRE(files && segs && seg_first && desc && workspace, "dsn_png_decode: null argument");
+    DSN_REQUIRE(out || !(stages & DSN_PNG_STAGE_PIXELS), "dsn_png_decode: out is null");
+    DSN_REQUIRE((((uintptr_t)segs & 7) | ((uintptr_t)seg_first & 3) | ((uintptr_t)desc & 3) | ((uintptr_t)out_status & 3)) == 0,
+                "dsn_png_decode: a pointer is not aligned to its element");
+    DSN_REQUIRE(((uintptr_t)workspace & 255) == 0, "dsn_png_decode: workspace must be 256-byte aligned");
+    DSN_REQUIRE(workspace_bytes >= dsn_png_workspace_size(F, W, H, bits, ctype, max_stream_bytes, nullptr),
+                "dsn_png_decode: workspace_bytes is too small");
+    dsn_launch_png_decode(files, files_bytes, segs, n_segs, seg_first, desc, F, W, H, bits, ctype, max_stream_bytes, channels, first_channel != 0,
+                          stages, out, out_status, workspace, (hipStream_t)stream);
+    return dsn_check_launch("dsn_png_decode");
+}
+
 }  // extern "C"

@@ -266,6 +266,14 @@ void dsn_launch_jpegd_coefficients(const dsn_jpegd_desc* desc, int F, int H, int
 void dsn_launch_jpegd_pixels(const int16_t* coef, const uint32_t* status, const dsn_jpegd_desc* desc, int F, int H, int W, int mode,
                              size_t max_scan_bytes, int rgb, int gray_out, uint8_t* out, void* workspace, hipStream_t st);
 
+struct dsn_png_desc;
+// dsn_png.hip: PNG decoding (dsn_png_parse_host, dsn_png_workspace_*, dsn_png_decode; arguments checked by the entry points)
+int dsn_png_parse(const uint8_t* file, size_t bytes, dsn_png_desc* out, uint32_t* segs, size_t seg_capacity);
+size_t dsn_png_workspace_size(int F, int W, int H, int bits, int ctype, size_t max_stream_bytes, size_t* out8);
+void dsn_launch_png_decode(const uint8_t* files, size_t files_bytes, const int64_t* segs, int S, const int32_t* seg_first,
+                           const dsn_png_desc* desc, int F, int W, int H, int bits, int ctype, size_t max_stream_bytes, int channels,
+                           int first_channel, int stages, uint8_t* out, uint32_t* out_status, void* workspace, hipStream_t st);
+
 // dsn_mesh.hip: density grid points and marching cubes (dsn_density_grid, dsn_mc_*)
 void dsn_launch_grid_points(const float* x, const float* y, const float* z, int i0, int ny, int nz, int64_t n, float* pts, hipStream_t st);
 size_t dsn_mc_workspace_size(int64_t N);

@@ -177,7 +177,8 @@ def _parse_all(files, names):
     for k, f in enumerate(files):
         d, st = _lib.jpeg_parse(f)
         if st != 0:
-            raise ValueError(f"jpeg.decode: {names[k]}: not a file this decoder takes ({_lib.JPEGD_REASONS[st]})")
+            hint = " - a PNG file: dsnerf_amd.png.imread / png.decode read those" if f[:8] == b"\x89PNG\r\n\x1a\n" else ""
+            raise ValueError(f"jpeg.decode: {names[k]}: not a file this decoder takes ({_lib.JPEGD_REASONS[st]}){hint}")
         descs.append(d)
     return descs
 
@@ -244,6 +245,8 @@ def imread_batch(paths, channels="bgr", device=None):
     """the files at `paths` -> as decode() of their bytes"""
     data = []
     for p in paths:
+        if str(p).lower().endswith(".png"):
+            raise ValueError(f"jpeg.imread: {p}: a .png path - dsnerf_amd.png.imread reads those")
         with open(p, "rb") as f:
             data.append(f.read())
     return decode(data, channels=channels, device=device, names=[str(p) for p in paths])

@@ -1571,6 +1571,136 @@ DSN_EXPORT int dsn_jpeg_decode(const uint8_t* files, size_t files_bytes, const i
                                int W, int mode, size_t max_scan_bytes, int subseq_bits, int rounds, int rgb, int gray_out, uint8_t* out,
                                uint32_t* out_status, int32_t* out_rounds, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- PNG DECODING on the device (csrc/dsn_png.hip): the datasets' label masks (mask_cihp/....png, read with cv2.imread at
+ * dataloader/zju_mocap_dataset.py:197 and zju_novel_pose_dataset.py:195, with imageio.imread at h36m_dataset.py:81,
+ * h36m_dataset_test.py:81 and novel_poses_dataset.py:70): file bytes go up, the uint8 mask that dsn_image_prep takes appears in HBM.
+ * PNG is lossless: the pixels are the ones every decoder gives, and tests/png_decode_restate.py restates the rule below and is held
+ * to Pillow.  Integer arithmetic only; the only atomics are 32-bit integer ORs / adds in LDS and ORs into the frames' status words:
+ * the same bits on every call, and a file decodes the same alone or in any batch.
+ *   Scope.  Non-interlaced files of colour type 0 (grey; 1, 2, 4, 8 bits), 2 (RGB, 8 bits), 3 (palette; 1, 2, 4, 8 bits), 4 (grey +
+ *      alpha, 8 bits) and 6 (RGBA, 8 bits); any number of IDAT chunks of any length (zero included); ancillary chunks are skipped,
+ *      wherever they stand (tRNS and gAMA are not applied).  Everything else is refused by dsn_png_parse_host with a named status
+ *      and reaches no kernel.
+ *   Host part.  dsn_png_parse_host checks the signature, walks the chunks (every read bounded by `bytes`), checks the CRC-32 of
+ *      IHDR, PLTE, IDAT and IEND, and fills a dsn_png_desc: W, H, bits, ctype, channels, row_bytes = ceil(W bits channels / 8),
+ *      raw_bytes = H (1 + row_bytes), the palette (R, G, B; entries the file does not give are 0), nseg and zlen = the IDAT payloads'
+ *      total, and up to seg_capacity segments {offset of the payload in the file, its length} (nseg may exceed seg_capacity: call
+ *      again with room for nseg).  Statuses: DSN_PNG_NOT_PNG, _TRUNCATED (a chunk that runs past the file, or no IEND), _CRC,
+ *      _BAD_IHDR (a length other than 13, a colour type / depth pair PNG does not have, compression or filter method not 0, interlace
+ *      above 1), _INTERLACE (Adam7), _DEPTH16, _NO_IHDR (the first chunk is not IHDR), _NO_IDAT (none, or fewer than 2 bytes in all),
+ *      _NO_PLTE (type 3 without PLTE before the first IDAT, or a PLTE whose length is not 3 ... 768 in threes), _ZERO_DIM,
+ *      _TOO_LARGE (a dimension above 16384, raw_bytes above 2^30, zlen above 2^28), _ZLIB_METHOD (the stream's first byte: method
+ *      not 8 or a window above 32 K), _ZLIB_DICT (FDICT set), _ZLIB_CHECK ((CMF 256 + FLG) mod 31 != 0).
+ *   Gather.  The IDAT payloads of file f, in order, form its zlib stream of zlen bytes; the device copy is followed by zeros up to
+ *      the stream capacity.  A byte a segment table places outside files_bytes reads 0.
+ *   Inflate (RFC 1951).  Bits are taken from the least significant bit of each byte on; bits at and past 8 zlen read 0.  p is the
+ *      number of bits taken.  The deflate data start at p = 16.  Per block: 1 bit BFINAL, 2 bits BTYPE.
+ *      BTYPE 0: p moves up to a byte boundary; LEN, NLEN (16 bits each); NLEN != ~LEN: DSN_PNG_STORED_LEN; the LEN bytes that follow
+ *      are output (fewer than LEN left in the stream: DSN_PNG_EARLY_END).  BTYPE 1: the fixed code lengths (8 x 144, 9 x 112, 7 x 24,
+ *      8 x 8 for literal/length symbols 0 ... 287; 32 distance codes of length 5).  BTYPE 2: HLIT + 257, HDIST + 1, HCLEN + 4 (5, 5, 4 bits); more than 286
+ *      literal/length or 30 distance codes: DSN_PNG_BAD_CODES; the code-length code's lengths in the order 16 17 18 0 8 7 9 6 10 5
+ *      11 4 12 3 13 2 14 1 15; then the lengths: 0 ... 15 as they are, 16 repeats the previous one 3 + 2 bits times (none before
+ *      it: BAD_CODES), 17 gives 3 + 3 bits zeros, 18 gives 11 + 7 bits zeros; a repeat past HLIT + HDIST + 258 or a zero length for
+ *      symbol 256: BAD_CODES.  BTYPE 3: DSN_PNG_BLOCK_TYPE.
+ *      A set of code lengths is USABLE when it is complete (sum over symbols of 2^-len == 1), or - for the literal/length and the
+ *      distance code only - when it has no code at all or one single code of length 1 (zlib's rule).  Over-subscribed or otherwise
+ *      incomplete: BAD_CODES.  Codes are canonical: per length in ascending symbol order, the first code of length l =
+ *      (first code of length l - 1 + its count) << 1; a code's bits arrive most significant first.
+ *      Symbols: < 256 a literal; 256 ends the block; 257 ... 285 a length (base 3, 4, ... 258 with 0 ... 5 extra bits) followed by a
+ *      distance code 0 ... 29 (base 1 ... 24577 with 0 ... 13 extra bits).  A window that is no code, length symbols 286 / 287 and
+ *      distance symbols 30 / 31: DSN_PNG_NO_CODE.  A distance above the bytes output so far: DSN_PNG_FAR_DISTANCE.  Byte i of a match
+ *      of distance d that starts at output position s is out[s - d + (i mod d)]: an overlapping match repeats its d bytes.
+ *      After every group of reads (block header; stored header; a literal/length symbol with its extra bits; a distance symbol with
+ *      its extra bits; each code-length symbol with its extra bits) p > 8 zlen is DSN_PNG_EARLY_END, and it is looked at before
+ *      anything else the group could raise - except a window that is no code at all, which takes no bits and is NO_CODE.  Output that would pass raw_bytes is DSN_PNG_TOO_MUCH; nothing of that literal, match
+ *      or stored block is written.  The first error ends the decoding of the file: exactly one of these bits is set then, and
+ *      neither Adler-32 nor the filters are looked at.
+ *      Behind the final block p moves up to a byte boundary and the next four bytes, most significant first, are the stored
+ *      Adler-32 (fewer than four left: EARLY_END); what follows them inside IDAT is ignored.  Fewer than raw_bytes bytes output:
+ *      DSN_PNG_TOO_LITTLE.  The window size the zlib header names is not enforced (as zlib does not, unless built strict).
+ *      Every loop is bounded: each step takes at least one bit or ends the file, p never passes 8 zlen + 64, reads are masked to
+ *      the stream's capacity, writes to raw_bytes.
+ *   Adler-32 of the bytes output (n of them, d_0 ... d_(n-1)): a = (1 + sum d_i) mod 65521, b = (n + sum (n - i) d_i) mod 65521,
+ *      value b 2^16 + a; computed for every file whose inflate ended without one of the errors above (TOO_LITTLE included); not the
+ *      stored one: DSN_PNG_ADLER.
+ *   Unfilter (files without a status bit so far).  Row r of the inflated bytes is a filter byte and row_bytes bytes; bpp = max(1,
+ *      bits channels / 8); a = the unfiltered byte bpp to the left, b = the one above, c = the one above a (0 outside the image).
+ *      0: x; 1: x + a; 2: x + b; 3: x + ((a + b) >> 1); 4: x + (a, b or c, whichever is nearest to a + b - c, ties in that order),
+ *      mod 256.  A filter byte above 4: DSN_PNG_FILTER (the row is taken as filter 0).
+ *   Pixels.  Samples of 1, 2, 4 bits are packed most significant first, rows padded to a byte.  Grey g of `bits` bits becomes
+ *      g 255 / (2^bits - 1) (x 255, 85, 17, 1); a palette index i becomes palette[i].  channels = DSN_PNG_BGR: uint8 [F, H, W, 3] in
+ *      B, G, R order - what cv2.imread(path) is understood to return: grey replicated, palette looked up, alpha dropped (UNVERIFIED
+ *      against OpenCV); DSN_PNG_RGB: R, G, B; DSN_PNG_NATIVE: [F, H, W, channels] with the file's own samples: grey (scaled), R G B,
+ *      the palette INDEX, grey + alpha, R G B A.  first_channel != 0: [F, H, W], channel 0 of the above, never three channels.
+ *      A file with any status bit gets all-zero pixels: every output byte is defined.
+ *   Kernels.  k_pn_gather: a thread per stream byte, its segment by bisection.  k_pn_inflate: ONE WAVE PER FILE (a stream is
+ *      serial: matches reach back into its own output), the symbol loop wave-uniform; the 32 KiB window, the canonical tables (counts,
+ *      symbols in code order) and a 10-bit / 8-bit direct lookup for short codes in LDS, built by all lanes (ballots give each symbol
+ *      its rank); a match is read by all lanes from the window - sources lie before the match's start -, then written to window and
+ *      output, workgroup barriers between.  k_pn_adler: a workgroup per file, 16 bytes per load, integer sums.  k_pn_unfilter: a wave
+ *      per file, lane j on row r + j one pixel behind lane j - 1, the row above and its left neighbour arriving by wave shuffles.
+ *      k_pn_pixels: a thread per pixel.  Decoding inside one stream in parallel (speculating on block boundaries) is not done.
+ * files: uint8 [files_bytes], the files one behind the other; segs: int64 [S, 3] = {offset in `files`, position in its file's zlib
+ * stream, length} for every IDAT segment, file after file (S = n_segs); seg_first: int32 [F + 1], file f's segments are [seg_first[f],
+ * seg_first[f + 1]); desc: dsn_png_desc [F] in DEVICE memory.  All files of a call share W, H, bits and ctype; palettes and
+ * streams differ.  max_stream_bytes >= every zlen; it sizes the workspace.  stages: DSN_PNG_STAGE_* bits, DSN_PNG_STAGE_ALL for a
+ * decode; a later stage alone runs on what the earlier ones left in the workspace (timing, tests).  out: see Pixels; out_status
+ * uint32 [F].  workspace: dsn_png_workspace_bytes(...) bytes (0 for sizes outside the scope), 256-byte aligned, anything on entry.
+ * dsn_png_workspace_layout: byte offsets {meta, streams, stream stride, raw, raw stride, rows, rows stride, total} of a workspace;
+ * meta is uint32 [F, 8] = {bytes output, status, stored Adler, computed Adler, p at the end, 0, 0, 0}; raw holds the inflated
+ * bytes, rows the unfiltered rows [H, row_bytes].  No allocation, no host copy, no synchronisation.
+ * dsn_png_parse_host: HOST memory in and out; returns 0 and the DSN_PNG_* parse status through *status. */
+#define DSN_PNG_EARLY_END 1u
+#define DSN_PNG_BLOCK_TYPE 2u
+#define DSN_PNG_STORED_LEN 4u
+#define DSN_PNG_BAD_CODES 8u
+#define DSN_PNG_NO_CODE 16u
+#define DSN_PNG_FAR_DISTANCE 32u
+#define DSN_PNG_TOO_MUCH 64u
+#define DSN_PNG_TOO_LITTLE 128u
+#define DSN_PNG_FILTER 256u
+#define DSN_PNG_ADLER 512u
+#define DSN_PNG_MAX_FILES 16384
+#define DSN_PNG_MAX_DIM 16384
+#define DSN_PNG_BGR 0
+#define DSN_PNG_RGB 1
+#define DSN_PNG_NATIVE 2
+#define DSN_PNG_STAGE_GATHER 1
+#define DSN_PNG_STAGE_INFLATE 2
+#define DSN_PNG_STAGE_ADLER 4
+#define DSN_PNG_STAGE_UNFILTER 8
+#define DSN_PNG_STAGE_PIXELS 16
+#define DSN_PNG_STAGE_ALL 31
+#define DSN_PNG_OK 0              /* dsn_png_parse_host's status */
+#define DSN_PNG_NOT_PNG 1
+#define DSN_PNG_TRUNCATED 2
+#define DSN_PNG_CRC 3
+#define DSN_PNG_BAD_IHDR 4
+#define DSN_PNG_INTERLACE 5
+#define DSN_PNG_DEPTH16 6
+#define DSN_PNG_NO_IHDR 7
+#define DSN_PNG_NO_IDAT 8
+#define DSN_PNG_NO_PLTE 9
+#define DSN_PNG_ZERO_DIM 10
+#define DSN_PNG_TOO_LARGE 11
+#define DSN_PNG_ZLIB_METHOD 12
+#define DSN_PNG_ZLIB_DICT 13
+#define DSN_PNG_ZLIB_CHECK 14
+typedef struct dsn_png_desc {
+    int32_t W, H, bits, ctype;
+    int32_t channels, row_bytes, raw_bytes, npal;
+    int32_t nseg, zlen, file_length, reserved[5];
+    uint8_t palette[256][3];
+} dsn_png_desc;
+DSN_EXPORT int dsn_png_parse_host(const uint8_t* file_host, size_t bytes, dsn_png_desc* desc_host, uint32_t* segs_host, size_t seg_capacity,
+                                  int* status);
+DSN_EXPORT size_t dsn_png_workspace_bytes(int F, int W, int H, int bits, int ctype, size_t max_stream_bytes);
+DSN_EXPORT int dsn_png_workspace_layout(int F, int W, int H, int bits, int ctype, size_t max_stream_bytes, size_t* out8_host);
+DSN_EXPORT int dsn_png_decode(const uint8_t* files, size_t files_bytes, const int64_t* segs, int n_segs, const int32_t* seg_first,
+                              const dsn_png_desc* desc, int F, int W, int H, int bits, int ctype, size_t max_stream_bytes, int channels,
+                              int first_channel, int stages, uint8_t* out, uint32_t* out_status, void* workspace, size_t workspace_bytes,
+                              void* stream);
+
 /* diagnostics, NOT for the hot path (synchronises `stream`): {ncell, ok, total entries, capacity} of the four
  * nearest-face list levels (world fine/coarse, canonical fine/coarse) into a HOST array of 16 int32. */
 DSN_EXPORT int dsn_debug_nn_stats(const void* scene, int V, int F, int32_t* out16_host, void* stream);
