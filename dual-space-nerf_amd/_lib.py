@@ -65,6 +65,8 @@ EXPORTS = [
     "dsn_jpeg_parse_host", "dsn_jpegd_workspace_bytes", "dsn_jpegd_workspace_coef", "dsn_jpegd_sync", "dsn_jpegd_coefficients",
     "dsn_jpegd_pixels", "dsn_jpeg_decode",
     "dsn_png_parse_host", "dsn_png_workspace_bytes", "dsn_png_workspace_layout", "dsn_png_decode",
+    "dsn_png_encode_max_bytes", "dsn_png_encode_workspace_bytes", "dsn_png_deflate_max_bytes", "dsn_png_deflate_workspace_bytes",
+    "dsn_png_filter", "dsn_png_adler", "dsn_png_deflate", "dsn_huff_lengths", "dsn_png_container", "dsn_png_encode",
 ]
 
 SKIP_TRANSPARENT = 1
@@ -242,6 +244,23 @@ def lib():
         L.dsn_png_workspace_layout.argtypes = [C.c_int] * 5 + [C.c_size_t, C.c_void_p]
         L.dsn_png_decode.argtypes = ([C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_size_t]
                                      + [C.c_int] * 3 + [C.c_void_p] * 3 + [C.c_size_t, C.c_void_p])
+        L.dsn_png_encode_max_bytes.restype = C.c_size_t
+        L.dsn_png_encode_max_bytes.argtypes = [C.c_int] * 4
+        L.dsn_png_encode_workspace_bytes.restype = C.c_size_t
+        L.dsn_png_encode_workspace_bytes.argtypes = [C.c_int] * 5
+        L.dsn_png_deflate_max_bytes.restype = C.c_size_t
+        L.dsn_png_deflate_max_bytes.argtypes = [C.c_size_t, C.c_int]
+        L.dsn_png_deflate_workspace_bytes.restype = C.c_size_t
+        L.dsn_png_deflate_workspace_bytes.argtypes = [C.c_int, C.c_size_t, C.c_int]
+        L.dsn_png_filter.argtypes = [C.c_void_p] + [C.c_int] * 6 + [C.c_float, C.c_int] + [C.c_void_p] * 3
+        L.dsn_png_adler.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        L.dsn_png_deflate.argtypes = ([C.c_void_p, C.c_int, C.c_size_t] + [C.c_int] * 4 + [C.c_void_p, C.c_size_t] + [C.c_void_p] * 3
+                                      + [C.c_size_t, C.c_void_p])
+        L.dsn_huff_lengths.argtypes = [C.c_void_p] + [C.c_int] * 3 + [C.c_void_p] * 2
+        L.dsn_png_container.argtypes = ([C.c_void_p, C.c_size_t] + [C.c_void_p] * 3 + [C.c_int] * 4 + [C.c_void_p, C.c_size_t]
+                                        + [C.c_void_p] * 3 + [C.c_size_t, C.c_void_p])
+        L.dsn_png_encode.argtypes = ([C.c_void_p] + [C.c_int] * 6 + [C.c_float] + [C.c_int] * 3 + [C.c_void_p, C.c_size_t] + [C.c_void_p] * 3
+                                     + [C.c_size_t, C.c_void_p])
         if L.dsn_abi_version() != 8:
             raise RuntimeError(f"{LIB_PATH} has ABI version {L.dsn_abi_version()}, this binding needs 8 - rebuild it "
                                "(python dual-space-nerf_amd/build.py)")
@@ -3190,3 +3209,162 @@ def png_decode(batch, channels="bgr", first_channel=False, stages=PNG_ALL, works
                                     _ptr(batch.desc), *batch.geometry(), PNG_CHANNELS[channels], int(bool(first_channel)), int(stages),
                                     _ptr(out), _ptr(status), _ptr(ws), int(ws.numel()), _stream()), "dsn_png_decode")
     return out, status
+
+
+# ---- PNG encoding (dsn_png_filter / _adler / _deflate / _container / _encode, dsn_huff_lengths: the rule of include/dsnerf.h) --------------------
+PNGE_GRAY, PNGE_COLOUR, PNGE_REPLICATE = 0, 1, 2          # DSN_PNGE_*
+PNGE_ADAPTIVE = 5
+PNGE_NONFINITE, PNGE_OVERFLOW = 1, 2
+PNGE_CHUNK_MIN, PNGE_CHUNK_MAX, PNGE_CHUNK_DEFAULT = 256, 32768, 32768
+PNGE_FILTERS = {"none": 0, "sub": 1, "up": 2, "average": 3, "paeth": 4, "adaptive": PNGE_ADAPTIVE}
+
+
+def pnge_filter(filter):
+    """the DSN_PNGE filter number of "adaptive", a filter's name or 0 ... 4"""
+    f = PNGE_FILTERS.get(filter, filter) if isinstance(filter, str) else filter
+    if isinstance(f, bool) or not isinstance(f, int) or not 0 <= f <= PNGE_ADAPTIVE or (not isinstance(filter, str) and f == PNGE_ADAPTIVE):
+        raise ValueError(f"png: filter must be 'adaptive', a filter's name or 0 ... 4, got {filter!r}")
+    return f
+
+
+def pnge_chunk(chunk):
+    c = PNGE_CHUNK_DEFAULT if chunk is None else chunk
+    if isinstance(c, bool) or int(c) != c or not PNGE_CHUNK_MIN <= int(c) <= PNGE_CHUNK_MAX or int(c) & (int(c) - 1):
+        raise ValueError(f"png: chunk must be a power of two from {PNGE_CHUNK_MIN} to {PNGE_CHUNK_MAX}, got {chunk!r}")
+    return int(c)
+
+
+def pnge_mode(images, replicate):
+    """the DSN_PNGE_* mode of a stack [F, H, W] or [F, H, W, 3]"""
+    if images.dim() == 4:
+        if replicate:
+            raise ValueError("png: replicate=True takes one-channel images")
+        return PNGE_COLOUR
+    return PNGE_REPLICATE if replicate else PNGE_GRAY
+
+
+def png_encode_max_bytes(W, H, channels, chunk=None):
+    """dsn_png_encode_max_bytes: the capacity no file of this size can exceed (every chunk stored)"""
+    n = lib().dsn_png_encode_max_bytes(int(W), int(H), int(channels), pnge_chunk(chunk))
+    if n == 0:
+        raise ValueError(f"png: {W} x {H} with {channels} channel(s) is outside what dsn_png_encode takes (sides 1 ... 16384, 1 or 3 channels)")
+    return int(n)
+
+
+def png_filter(images, mode, rgb=False, scale=255.0, filter=PNGE_ADAPTIVE):
+    """dsn_png_filter: -> (raw uint8 [F, H (1 + row_bytes)], status int32 [F]) on the device"""
+    F, H, W, ch, dt = _jpeg_images("png_filter", images)
+    if (mode == PNGE_COLOUR) != (ch == 3) or mode not in (PNGE_GRAY, PNGE_COLOUR, PNGE_REPLICATE):
+        raise ValueError(f"png_filter: mode {mode!r} does not fit images with {ch} channel(s)")
+    dev = images.device
+    raw = _output((F, H * (1 + W * (1 if mode == PNGE_GRAY else 3))), torch.uint8, dev)
+    status = _output((F,), torch.int32, dev)
+    with torch.cuda.device(dev):
+        _check(lib().dsn_png_filter(_ptr(images) if F else None, dt, F, H, W, int(mode), int(bool(rgb)), float(scale), int(filter),
+                                    _ptr(raw) if F else None, _ptr(status) if F else None, _stream()), "dsn_png_filter")
+    return raw, status
+
+
+def _pnge_raw(what, raw):
+    if not torch.is_tensor(raw) or raw.dtype != torch.uint8 or raw.dim() != 2:
+        raise ValueError(f"{what}: raw must be a uint8 tensor [F, n]")
+    require_gpu()
+    if not raw.is_cuda or not raw.is_contiguous():
+        raise ValueError(f"{what}: raw must be a contiguous tensor on a ROCm device")
+    return int(raw.shape[0]), int(raw.shape[1])
+
+
+def png_adler(raw):
+    """dsn_png_adler: raw uint8 [F, n] -> Adler-32 values int32 [F] (the bits of the uint32) on the device"""
+    F, n = _pnge_raw("png_adler", raw)
+    dev = raw.device
+    out = _output((F,), torch.int32, dev)
+    ws = _scratch(max(F, 1) * 8, dev)
+    with torch.cuda.device(dev):
+        _check(lib().dsn_png_adler(_ptr(raw) if F else None, F, n, _ptr(out) if F else None, _ptr(ws), int(ws.numel()), _stream()), "dsn_png_adler")
+    return out
+
+
+def png_deflate(raw, bpp, row_stride, chunk=None, stored_only=False, capacity=None, out=None):
+    """dsn_png_deflate: raw uint8 [F, n] -> (out uint8 [F, capacity]: the deflate streams, lengths int32 [F], status int32 [F])"""
+    F, n = _pnge_raw("png_deflate", raw)
+    c = pnge_chunk(chunk)
+    dev = raw.device
+    if out is None:
+        capacity = int(lib().dsn_png_deflate_max_bytes(n, c)) if capacity is None else int(capacity)
+        out = _output((F, capacity), torch.uint8, dev)
+    elif out.dtype != torch.uint8 or out.dim() != 2 or out.shape[0] != F or not out.is_contiguous() or out.device != dev:
+        raise ValueError("png_deflate: out must be a contiguous uint8 [F, capacity] tensor on raw's device")
+    lengths = _output((F,), torch.int32, dev)
+    status = _output((F,), torch.int32, dev)
+    nws = lib().dsn_png_deflate_workspace_bytes(max(F, 1), n, c)
+    if nws == 0:
+        raise ValueError(f"png_deflate: {n} raw bytes per frame are outside what dsn_png_deflate takes (1 ... 2^30 + 2^15)")
+    ws = _scratch(nws, dev)
+    with torch.cuda.device(dev):
+        _check(lib().dsn_png_deflate(_ptr(raw) if F else None, F, n, int(bpp), int(row_stride), c, int(bool(stored_only)),
+                                     _ptr(out) if F else None, int(out.shape[1]), _ptr(lengths) if F else None, _ptr(status) if F else None,
+                                     _ptr(ws), int(ws.numel()), _stream()), "dsn_png_deflate")
+    return out, lengths, status
+
+
+def huff_lengths(counts, limit):
+    """dsn_huff_lengths: counts int32 [B, n] (non-negative) on the device -> code lengths uint8 [B, n]"""
+    if not torch.is_tensor(counts) or counts.dtype != torch.int32 or counts.dim() != 2:
+        raise ValueError("huff_lengths: counts must be an int32 tensor [B, n]")
+    require_gpu()
+    if not counts.is_cuda or not counts.is_contiguous():
+        raise ValueError("huff_lengths: counts must be a contiguous tensor on a ROCm device")
+    B, n = int(counts.shape[0]), int(counts.shape[1])
+    out = _output((B, n), torch.uint8, counts.device)
+    with torch.cuda.device(counts.device):
+        _check(lib().dsn_huff_lengths(_ptr(counts) if B else None, B, n, int(limit), _ptr(out) if B else None, _stream()), "dsn_huff_lengths")
+    return out
+
+
+def png_container(stream, lengths, adler, W, H, channels, status_in=None, capacity=None, out=None):
+    """dsn_png_container: deflate streams uint8 [F, stride] with lengths int32 [F] and Adler-32 values int32 [F] -> (files uint8
+    [F, capacity], lengths int32 [F], status int32 [F])"""
+    F, stride = _pnge_raw("png_container", stream)
+    dev = stream.device
+    if out is None:
+        capacity = 63 + stride if capacity is None else int(capacity)
+        out = _output((F, capacity), torch.uint8, dev)
+    out_lengths = _output((F,), torch.int32, dev)
+    status = _output((F,), torch.int32, dev)
+    ws = _scratch(max(F, 1) * 4, dev)
+    with torch.cuda.device(dev):
+        _check(lib().dsn_png_container(_ptr(stream) if F else None, stride, _ptr(lengths) if F else None, _ptr(adler) if F else None,
+                                       _ptr(status_in) if (status_in is not None and F) else None, F, int(W), int(H), int(channels),
+                                       _ptr(out) if F else None, int(out.shape[1]), _ptr(out_lengths) if F else None,
+                                       _ptr(status) if F else None, _ptr(ws), int(ws.numel()), _stream()), "dsn_png_container")
+    return out, out_lengths, status
+
+
+def png_encode(images, mode, rgb=False, scale=255.0, filter=PNGE_ADAPTIVE, chunk=None, stored_only=False, capacity=None, out=None,
+               workspace=None):
+    """dsn_png_encode: images uint8 / float32 [F, H, W, 3] (PNGE_GRAY / PNGE_REPLICATE: [F, H, W]) on the device -> (out uint8
+    [F, capacity] whose row f starts with frame f's complete file, lengths int32 [F]: the bytes each file needs, status int32 [F]: OR of
+    PNGE_NONFINITE / PNGE_OVERFLOW).  Nothing is copied back and nothing waits."""
+    F, H, W, ch, dt = _jpeg_images("png_encode", images)
+    if (mode == PNGE_COLOUR) != (ch == 3) or mode not in (PNGE_GRAY, PNGE_COLOUR, PNGE_REPLICATE):
+        raise ValueError(f"png_encode: mode {mode!r} does not fit images with {ch} channel(s)")
+    c = pnge_chunk(chunk)
+    dev = images.device
+    if out is None:
+        capacity = png_encode_max_bytes(W, H, 1 if mode == PNGE_GRAY else 3, c) if capacity is None else int(capacity)
+        out = _output((F, capacity), torch.uint8, dev)
+    elif out.dtype != torch.uint8 or out.dim() != 2 or out.shape[0] != F or not out.is_contiguous() or out.device != dev:
+        raise ValueError("png_encode: out must be a contiguous uint8 [F, capacity] tensor on the images' device")
+    lengths = _output((F,), torch.int32, dev)
+    status = _output((F,), torch.int32, dev)
+    nws = lib().dsn_png_encode_workspace_bytes(max(F, 1), W, H, int(mode), c)
+    if nws == 0:
+        png_encode_max_bytes(W, H, 1 if mode == PNGE_GRAY else 3, c)          # raises with the limits
+        raise ValueError(f"png_encode: F = {F} is above 16384")
+    ws = _scratch(nws, dev) if workspace is None else workspace
+    with torch.cuda.device(dev):
+        _check(lib().dsn_png_encode(_ptr(images) if F else None, dt, F, H, W, int(mode), int(bool(rgb)), float(scale), int(filter), c,
+                                    int(bool(stored_only)), _ptr(out) if F else None, int(out.shape[1]), _ptr(lengths) if F else None,
+                                    _ptr(status) if F else None, _ptr(ws), int(ws.numel()), _stream()), "dsn_png_encode")
+    return out, lengths, status

@@ -1263,11 +1263,18 @@ class Renderer:
             raise ValueError(f"save_views: {len(results)} results for {len(paths)} paths")
         for p in paths:
             if os.path.splitext(str(p))[1].lower() not in (".jpg", ".jpeg"):
-                raise ValueError(f"save_views: only .jpg / .jpeg files are written, got {p!r}")
+                hint = " - save_views_png writes .png files" if os.path.splitext(str(p))[1].lower() == ".png" else ""
+                raise ValueError(f"save_views: only .jpg / .jpeg files are written, got {p!r}{hint}")
+        imgs = self._saved_images("save_views", results, key, gt, clamp)
+        sizes = self._write_groups(imgs, paths, lambda stack: _jpeg.encode(stack, **jpeg))
+        return sizes[0] if single else sizes
+
+    def _saved_images(self, what, results, key, gt, clamp):
+        """the device images save_views / save_views_png write: r[key] (one channel as [H, W]), clamped, with batch["img"] to its right"""
         if gt is not None:
             gt = [gt] if isinstance(gt, dict) else list(gt)
             if len(gt) != len(results):
-                raise ValueError(f"save_views: {len(gt)} gt batches for {len(results)} results")
+                raise ValueError(f"{what}: {len(gt)} gt batches for {len(results)} results")
         imgs = []
         for k, r in enumerate(results):
             img = r[key].to(self.device)
@@ -1280,20 +1287,71 @@ class Renderer:
             if gt is not None:
                 g = self._metrics_gt(gt[k]).to(torch.float32)
                 if img.dim() == 2:
-                    raise ValueError("save_views: gt goes beside a colour image, not beside " + key)
+                    raise ValueError(f"{what}: gt goes beside a colour image, not beside " + key)
                 img = torch.cat([img, g.reshape(img.shape[0], -1, 3)], dim=1)
             imgs.append(img)
+        return imgs
+
+    @staticmethod
+    def _write_groups(imgs, paths, encode):
+        """one encoder call per group of equal shape and dtype; the files' sizes in bytes"""
         groups = {}
         for k, img in enumerate(imgs):
             groups.setdefault((tuple(img.shape), img.dtype), []).append(k)
         sizes = [0] * len(imgs)
         for ks in groups.values():
-            files = _jpeg.encode(torch.stack([imgs[k] for k in ks]), **jpeg)
+            files = encode([imgs[k] for k in ks])
             for k, data in zip(ks, files):
                 with open(paths[k], "wb") as f:
                     f.write(data)
                 sizes[k] = len(data)
+        return sizes
+
+    def save_views_png(self, results, paths, key="coarse_color", gt=None, clamp=False, replicate=False, **png):
+        """save_views for .png files (test.py:94-110), lossless: one dsnerf_amd.png.encode call per size group (two device->host copies
+        each).  replicate=True writes a one-channel map ("coarse_depth", "coarse_acc") as three equal channels, test.py's
+        np.repeat(..., 3, axis=2), without materialising them.  **png: channels, scale, filter, chunk of png.encode.  Returns the
+        files' sizes in bytes."""
+        from . import png as _png
+        single = isinstance(results, dict)
+        results = [results] if single else list(results)
+        paths = [paths] if isinstance(paths, (str, os.PathLike)) else list(paths)
+        if len(results) != len(paths):
+            raise ValueError(f"save_views_png: {len(results)} results for {len(paths)} paths")
+        for p in paths:
+            if os.path.splitext(str(p))[1].lower() != ".png":
+                raise ValueError(f"save_views_png: only .png files are written, got {p!r} (save_views writes .jpg files)")
+        imgs = self._saved_images("save_views_png", results, key, gt, clamp)
+        sizes = self._write_groups(imgs, paths, lambda stack: _png.encode(stack, replicate=replicate and stack[0].dim() == 2, **png))
         return sizes[0] if single else sizes
+
+    TEST_VIEW_KINDS = ("img", "rendering", "gt", "depth", "acc")
+
+    def save_test_views(self, results, batches, dirs, names, **png):
+        """test.py:94-110's five .png files per evaluated frame: dirs maps "img" (rendering and ground truth side by side, H x 2 W),
+        "rendering" (clamped to [0, 1] as test.py:62 does), "gt", "depth" and "acc" (the one-channel maps as three equal channels) to
+        directories, names holds one file name per result (test.py's save_name); dirs[kind]/name.png is written.  Per frame size three
+        encoder calls: the H x W colour images, the H x W maps, the H x 2 W pair joined on the device.  Returns {kind: [bytes per file]}."""
+        from . import png as _png
+        results = [results] if isinstance(results, dict) else list(results)
+        batches = [batches] if isinstance(batches, dict) else list(batches)
+        names = [names] if isinstance(names, str) else list(names)
+        if not (len(results) == len(batches) == len(names)):
+            raise ValueError(f"save_test_views: {len(results)} results, {len(batches)} batches, {len(names)} names")
+        missing = [k for k in self.TEST_VIEW_KINDS if k not in dirs]
+        if missing:
+            raise ValueError(f"save_test_views: dirs needs the keys {self.TEST_VIEW_KINDS}, missing {missing}")
+        path = {kind: [os.path.join(str(dirs[kind]), f"{n}.png") for n in names] for kind in self.TEST_VIEW_KINDS}
+        colour = self._saved_images("save_test_views", results, "coarse_color", None, True)
+        truth = [self._metrics_gt(b).to(torch.float32).reshape(c.shape) for b, c in zip(batches, colour)]
+        pair = [torch.cat([c, g], dim=1) for c, g in zip(colour, truth)]
+        depth = self._saved_images("save_test_views", results, "coarse_depth", None, False)
+        acc = self._saved_images("save_test_views", results, "coarse_acc", None, False)
+        n = len(results)
+        flat = self._write_groups(colour + truth, path["rendering"] + path["gt"], lambda stack: _png.encode(stack, **png))
+        maps = self._write_groups(depth + acc, path["depth"] + path["acc"], lambda stack: _png.encode(stack, replicate=True, **png))
+        both = self._write_groups(pair, path["img"], lambda stack: _png.encode(stack, **png))
+        return {"img": both, "rendering": flat[:n], "gt": flat[n:], "depth": maps[:n], "acc": maps[n:]}
 
     def _metrics_gt(self, batch):
         gt = batch["img"][0]

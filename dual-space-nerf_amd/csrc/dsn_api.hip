@@ -2174,4 +2174,112 @@ int dsn_png_decode(const uint8_t* files, size_t files_bytes, const int64_t* segs
     return dsn_check_launch("dsn_png_decode");
 }
 
+// ---- PNG encoding (dsn_pnge.hip) ----
+#define DSN_PNGE_CHUNK(name, chunk)                                                                                            \
+    DSN_REQUIRE((chunk) >= DSN_PNGE_CHUNK_MIN && (chunk) <= DSN_PNGE_CHUNK_MAX && ((chunk) & ((chunk) - 1)) == 0,              \
+                name ": chunk must be a power of two from 256 to 32768")
+#define DSN_PNGE_FRAMES(name, F) DSN_REQUIRE((F) >= 0 && (F) <= DSN_PNG_MAX_FILES, name ": F must be 0 ... 16384")
+
+size_t dsn_png_encode_max_bytes(int W, int H, int channels, int chunk) {
+    if (channels != 1 && channels != 3) return 0;
+    const size_t n = dsn_pnge_raw_bytes(W, H, channels == 3 ? DSN_PNGE_COLOUR : DSN_PNGE_GRAY);
+    const size_t z = n ? dsn_pnge_deflate_max(n, chunk) : 0;
+    return z ? z + 63 : 0;
+}
+
+size_t dsn_png_encode_workspace_bytes(int F, int W, int H, int mode, int chunk) { return dsn_pnge_workspace_size(F, W, H, mode, chunk); }
+
+size_t dsn_png_deflate_max_bytes(size_t n, int chunk) { return dsn_pnge_deflate_max(n, chunk); }
+
+size_t dsn_png_deflate_workspace_bytes(int F, size_t n, int chunk) { return dsn_pnge_deflate_workspace_size(F, n, chunk); }
+
+int dsn_png_filter(const void* images, int dtype, int F, int H, int W, int mode, int rgb, float scale, int filter, uint8_t* raw,
+                   uint32_t* out_status, void* stream) {
+    DSN_PNGE_FRAMES("dsn_png_filter", F);
+    DSN_REQUIRE(dsn_pnge_raw_bytes(W, H, mode) != 0, "dsn_png_filter: W and H must be 1 ... 16384 and mode DSN_PNGE_GRAY, _COLOUR or _REPLICATE");
+    DSN_REQUIRE(dtype == DSN_JPEG_U8 || dtype == DSN_JPEG_F32, "dsn_png_filter: dtype must be DSN_JPEG_U8 or DSN_JPEG_F32");
+    DSN_REQUIRE(filter >= 0 && filter <= DSN_PNGE_ADAPTIVE, "dsn_png_filter: filter must be 0 ... 4 or DSN_PNGE_ADAPTIVE");
+    if (F == 0) return 0;
+    DSN_REQUIRE(images && raw && out_status, "dsn_png_filter: null argument");
+    DSN_REQUIRE(dtype == DSN_JPEG_U8 || ((uintptr_t)images & 3) == 0, "dsn_png_filter: a float32 image is not 4-byte aligned");
+    DSN_REQUIRE(((uintptr_t)out_status & 3) == 0, "dsn_png_filter: out_status is not 4-byte aligned");
+    dsn_launch_png_filter(images, dtype, F, H, W, mode, rgb != 0, scale, filter, raw, out_status, (hipStream_t)stream);
+    return dsn_check_launch("dsn_png_filter");
+}
+
+int dsn_png_adler(const uint8_t* raw, int F, size_t n, uint32_t* out_adler, void* workspace, size_t workspace_bytes, void* stream) {
+    DSN_PNGE_FRAMES("dsn_png_adler", F);
+    DSN_REQUIRE(dsn_pnge_deflate_max(n, DSN_PNGE_CHUNK_MAX) != 0, "dsn_png_adler: n must be 1 ... 2^30 + 2^15");
+    if (F == 0) return 0;
+    DSN_REQUIRE(raw && out_adler && workspace, "dsn_png_adler: null argument");
+    DSN_REQUIRE((((uintptr_t)out_adler | (uintptr_t)workspace) & 3) == 0, "dsn_png_adler: out_adler or workspace is not 4-byte aligned");
+    DSN_REQUIRE(workspace_bytes >= (size_t)F * 8, "dsn_png_adler: workspace_bytes is below 8 F");
+    dsn_launch_png_adler(raw, F, n, out_adler, (uint32_t*)workspace, (hipStream_t)stream);
+    return dsn_check_launch("dsn_png_adler");
+}
+
+int dsn_png_deflate(const uint8_t* raw, int F, size_t n, int bpp, int row_stride, int chunk, int stored_only, uint8_t* out, size_t capacity,
+                    int32_t* out_lengths, uint32_t* out_status, void* workspace, size_t workspace_bytes, void* stream) {
+    DSN_PNGE_FRAMES("dsn_png_deflate", F);
+    DSN_PNGE_CHUNK("dsn_png_deflate", chunk);
+    DSN_REQUIRE(dsn_pnge_deflate_max(n, chunk) != 0, "dsn_png_deflate: n must be 1 ... 2^30 + 2^15");
+    DSN_REQUIRE(bpp >= 1 && bpp <= 8 && row_stride >= 1, "dsn_png_deflate: bpp must be 1 ... 8 and row_stride positive");
+    if (F == 0) return 0;
+    DSN_REQUIRE(raw && out && out_lengths && out_status && workspace, "dsn_png_deflate: null argument");
+    DSN_REQUIRE((((uintptr_t)out_lengths | (uintptr_t)out_status) & 3) == 0, "dsn_png_deflate: a pointer is not aligned to its element");
+    DSN_REQUIRE(((uintptr_t)workspace & 255) == 0, "dsn_png_deflate: workspace must be 256-byte aligned");
+    DSN_REQUIRE(workspace_bytes >= dsn_pnge_deflate_workspace_size(F, n, chunk), "dsn_png_deflate: workspace_bytes is too small");
+    dsn_launch_png_deflate(raw, F, n, bpp, row_stride, chunk, stored_only != 0, out, capacity, out_lengths, out_status, workspace,
+                           (hipStream_t)stream);
+    return dsn_check_launch("dsn_png_deflate");
+}
+
+int dsn_huff_lengths(const uint32_t* counts, int B, int n, int limit, uint8_t* lengths, void* stream) {
+    DSN_REQUIRE(B >= 0 && B <= 65535, "dsn_huff_lengths: B must be 0 ... 65535");
+    DSN_REQUIRE(limit >= 1 && limit <= 15, "dsn_huff_lengths: limit must be 1 ... 15");
+    DSN_REQUIRE(n >= 2 && n <= 288 && n <= (1 << limit), "dsn_huff_lengths: n must be 2 ... 288 and at most 2^limit");
+    if (B == 0) return 0;
+    DSN_REQUIRE(counts && lengths, "dsn_huff_lengths: null argument");
+    DSN_REQUIRE(((uintptr_t)counts & 3) == 0, "dsn_huff_lengths: counts is not 4-byte aligned");
+    dsn_launch_huff_lengths(counts, B, n, limit, lengths, (hipStream_t)stream);
+    return dsn_check_launch("dsn_huff_lengths");
+}
+
+int dsn_png_container(const uint8_t* stream_bytes, size_t stream_stride, const int32_t* stream_lengths, const uint32_t* adler,
+                      const uint32_t* status_in, int F, int W, int H, int channels, uint8_t* out, size_t capacity, int32_t* out_lengths,
+                      uint32_t* out_status, void* workspace, size_t workspace_bytes, void* stream) {
+    DSN_PNGE_FRAMES("dsn_png_container", F);
+    DSN_REQUIRE(channels == 1 || channels == 3, "dsn_png_container: channels must be 1 or 3");
+    DSN_REQUIRE(dsn_pnge_raw_bytes(W, H, DSN_PNGE_GRAY) != 0, "dsn_png_container: W and H must be 1 ... 16384");
+    DSN_REQUIRE(stream_stride >= 1 && stream_stride <= ((size_t)1 << 31) - 64, "dsn_png_container: stream_stride must be 1 ... 2^31 - 64");
+    if (F == 0) return 0;
+    DSN_REQUIRE(stream_bytes && stream_lengths && adler && out && out_lengths && out_status && workspace, "dsn_png_container: null argument");
+    DSN_REQUIRE((((uintptr_t)stream_lengths | (uintptr_t)adler | (uintptr_t)status_in | (uintptr_t)out_lengths | (uintptr_t)out_status |
+                  (uintptr_t)workspace) & 3) == 0, "dsn_png_container: a pointer is not aligned to its element");
+    DSN_REQUIRE(status_in != out_status, "dsn_png_container: status_in and out_status must differ");
+    DSN_REQUIRE(workspace_bytes >= (size_t)F * 4, "dsn_png_container: workspace_bytes is below 4 F");
+    dsn_launch_png_container(stream_bytes, stream_stride, stream_lengths, adler, status_in, nullptr, F, W, H, channels, out, capacity,
+                             out_lengths, out_status, (uint32_t*)workspace, (hipStream_t)stream);
+    return dsn_check_launch("dsn_png_container");
+}
+
+int dsn_png_encode(const void* images, int dtype, int F, int H, int W, int mode, int rgb, float scale, int filter, int chunk, int stored_only,
+                   uint8_t* out, size_t capacity, int32_t* out_lengths, uint32_t* out_status, void* workspace, size_t workspace_bytes,
+                   void* stream) {
+    DSN_PNGE_FRAMES("dsn_png_encode", F);
+    DSN_PNGE_CHUNK("dsn_png_encode", chunk);
+    DSN_REQUIRE(dsn_pnge_raw_bytes(W, H, mode) != 0, "dsn_png_encode: W and H must be 1 ... 16384 and mode DSN_PNGE_GRAY, _COLOUR or _REPLICATE");
+    DSN_REQUIRE(dtype == DSN_JPEG_U8 || dtype == DSN_JPEG_F32, "dsn_png_encode: dtype must be DSN_JPEG_U8 or DSN_JPEG_F32");
+    DSN_REQUIRE(filter >= 0 && filter <= DSN_PNGE_ADAPTIVE, "dsn_png_encode: filter must be 0 ... 4 or DSN_PNGE_ADAPTIVE");
+    if (F == 0) return 0;
+    DSN_REQUIRE(images && out && out_lengths && out_status && workspace, "dsn_png_encode: null argument");
+    DSN_REQUIRE(dtype == DSN_JPEG_U8 || ((uintptr_t)images & 3) == 0, "dsn_png_encode: a float32 image is not 4-byte aligned");
+    DSN_REQUIRE(((uintptr_t)workspace & 255) == 0, "dsn_png_encode: workspace must be 256-byte aligned");
+    DSN_REQUIRE(workspace_bytes >= dsn_pnge_workspace_size(F, W, H, mode, chunk), "dsn_png_encode: workspace_bytes is too small");
+    DSN_REQUIRE((((uintptr_t)out_lengths & 3) | ((uintptr_t)out_status & 3)) == 0, "dsn_png_encode: a pointer is not aligned to its element");
+    dsn_launch_png_encode(images, dtype, F, H, W, mode, rgb != 0, scale, filter, chunk, stored_only != 0, out, capacity, out_lengths, out_status,
+                          workspace, (hipStream_t)stream);
+    return dsn_check_launch("dsn_png_encode");
+}
+
 }  // extern "C"

@@ -13,6 +13,7 @@
 #include "../../include/dsnerf.h"
 #include "dsn_common.h"
 #include "dsn_kernels.h"
+#include "dsn_level.h"
 #include <climits>
 
 #define JPEG_TILE 1024            // entries per tile of the scan: 256 threads x 4
@@ -149,13 +150,7 @@ int jpeg_header_host(const JpegGeom& g, int quality, uint8_t* o) {
 
 // ---- coefficients ------------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ int jpeg_level(const void* __restrict__ img, int dtype, size_t idx, float scale, bool& bad) {
-    if (dtype == DSN_JPEG_U8) return ((const uint8_t*)img)[idx];
-    const float v = ((const float*)img)[idx];
-    if (!(fabsf(v) <= 3.402823466e38f)) bad = true;              // NaN or infinite
-    const float t = v * scale;
-    if (!(t == t)) return 0;                                      // NaN (of v, or of 0 x inf) gives 0
-    const float r = rintf(t);                                     // half to even
-    return r <= 0.0f ? 0 : r >= 255.0f ? 255 : (int)r;
+    return dsn_image_level(img, dtype, idx, scale, bad);          // (dsn_level.h: shared with the PNG encoder)
 }
 
 __device__ __forceinline__ int jpeg_descale(int x, int n) { return (x + (1 << (n - 1))) >> n; }

@@ -273,6 +273,23 @@ size_t dsn_png_workspace_size(int F, int W, int H, int bits, int ctype, size_t m
 void dsn_launch_png_decode(const uint8_t* files, size_t files_bytes, const int64_t* segs, int S, const int32_t* seg_first,
                            const dsn_png_desc* desc, int F, int W, int H, int bits, int ctype, size_t max_stream_bytes, int channels,
                            int first_channel, int stages, uint8_t* out, uint32_t* out_status, void* workspace, hipStream_t st);
+// dsn_pnge.hip: PNG encoding (dsn_png_filter / _adler / _deflate / _container / _encode, dsn_huff_lengths; arguments checked by the entry
+// points; the size functions return 0 for sizes outside the scope)
+size_t dsn_pnge_raw_bytes(int W, int H, int mode);
+size_t dsn_pnge_deflate_max(size_t n, int chunk);
+size_t dsn_pnge_deflate_workspace_size(int F, size_t n, int chunk);
+size_t dsn_pnge_workspace_size(int F, int W, int H, int mode, int chunk);
+void dsn_launch_png_filter(const void* images, int dtype, int F, int H, int W, int mode, int rgb, float scale, int filter, uint8_t* raw,
+                           uint32_t* status, hipStream_t st);
+void dsn_launch_png_adler(const uint8_t* raw, int F, size_t n, uint32_t* adler, uint32_t* sums2, hipStream_t st);
+void dsn_launch_png_deflate(const uint8_t* raw, int F, size_t n, int bpp, int row_stride, int chunk, int stored_only, uint8_t* out,
+                            size_t capacity, int32_t* lengths, uint32_t* status, void* workspace, hipStream_t st);
+void dsn_launch_huff_lengths(const uint32_t* counts, int B, int n, int limit, uint8_t* lengths, hipStream_t st);
+void dsn_launch_png_container(const uint8_t* zs, size_t zstride, const int32_t* zlen, const uint32_t* adler, const uint32_t* status_a,
+                              const uint32_t* status_b, int F, int W, int H, int channels, uint8_t* out, size_t capacity, int32_t* lengths,
+                              uint32_t* status, uint32_t* crc_words, hipStream_t st);
+void dsn_launch_png_encode(const void* images, int dtype, int F, int H, int W, int mode, int rgb, float scale, int filter, int chunk,
+                           int stored_only, uint8_t* out, size_t capacity, int32_t* lengths, uint32_t* status, void* workspace, hipStream_t st);
 
 // dsn_mesh.hip: density grid points and marching cubes (dsn_density_grid, dsn_mc_*)
 void dsn_launch_grid_points(const float* x, const float* y, const float* z, int i0, int ny, int nz, int64_t n, float* pts, hipStream_t st);

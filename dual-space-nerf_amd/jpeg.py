@@ -34,16 +34,16 @@ NONFINITE, OVERFLOW = _lib.JPEG_NONFINITE, _lib.JPEG_OVERFLOW
 IMWRITE_JPEG_QUALITY = 1          # cv2's constant
 
 
-def _stack(images, device=None):
+def _stack(images, device=None, what="jpeg"):
     """-> (contiguous device stack [F, H, W, 3] or [F, H, W], uint8 or float32)"""
     if isinstance(images, (list, tuple)):
         items = [torch.as_tensor(np.ascontiguousarray(x)) if not torch.is_tensor(x) else x for x in images]
         if not items:
-            raise ValueError("jpeg: an empty list of images")
+            raise ValueError(f"{what}: an empty list of images")
         if any(x.shape != items[0].shape or x.dtype != items[0].dtype for x in items):
-            raise ValueError("jpeg: the images of a list must have one size and dtype (encode each size group on its own)")
+            raise ValueError(f"{what}: the images of a list must have one size and dtype (encode each size group on its own)")
         if items[0].dim() not in (2, 3):
-            raise ValueError(f"jpeg: a list holds images [H, W], [H, W, 1] or [H, W, 3], got {tuple(items[0].shape)}")
+            raise ValueError(f"{what}: a list holds images [H, W], [H, W, 1] or [H, W, 3], got {tuple(items[0].shape)}")
         x = torch.stack(items)
     else:
         x = images if torch.is_tensor(images) else torch.as_tensor(np.ascontiguousarray(images))
@@ -52,11 +52,11 @@ def _stack(images, device=None):
     if x.dim() == 4 and x.shape[3] == 1:
         x = x[..., 0]
     if x.dim() not in (3, 4) or (x.dim() == 4 and x.shape[3] != 3):
-        raise ValueError(f"jpeg: images must be [H, W], [H, W, 1], [H, W, 3] or a stack of them, got {tuple(x.shape)}")
+        raise ValueError(f"{what}: images must be [H, W], [H, W, 1], [H, W, 3] or a stack of them, got {tuple(x.shape)}")
     if x.dtype == torch.float64:
         x = x.to(torch.float32)
     if x.dtype not in (torch.uint8, torch.float32):
-        raise ValueError(f"jpeg: images must be uint8 or float32 (float64 is cast), got {x.dtype}")
+        raise ValueError(f"{what}: images must be uint8 or float32 (float64 is cast), got {x.dtype}")
     if not x.is_cuda:
         _lib.require_gpu()
         x = x.to(torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device()))
@@ -110,7 +110,8 @@ def imwrite(path, img, params=None):
     float levels that are rounded and saturated as convertTo(CV_8U) does (the scripts pass `color_img * 255`): scale = 1 here.
     params: [IMWRITE_JPEG_QUALITY, q].  Returns True."""
     if os.path.splitext(str(path))[1].lower() not in (".jpg", ".jpeg"):
-        raise ValueError(f"imwrite: only .jpg / .jpeg files are written, got {path!r}")
+        hint = " - dsnerf_amd.png.imwrite writes those" if os.path.splitext(str(path))[1].lower() == ".png" else ""
+        raise ValueError(f"imwrite: only .jpg / .jpeg files are written, got {path!r}{hint}")
     data = encode(img, quality=_quality_of(params), scale=1.0)
     if len(data) != 1:
         raise ValueError("imwrite: one image per file")

@@ -1,4 +1,18 @@
-"""PNG decoding on the device: the datasets' label masks (mask_cihp/....png - cv2.imread at dataloader/zju_mocap_dataset.py:197 and
+"""PNG on the device.
+
+Encoding: test.py's five `cv2.imwrite(....png)` per evaluated frame (test.py:94-110), from frames that are in HBM already:
+    encode(images, channels="bgr", scale=255.0, replicate=False, filter="adaptive", chunk=None) -> list[bytes]   two device->host copies per call
+    encode_device(images, ...) -> (buffer uint8 [F, capacity], lengths int32 [F], status int32 [F])              on the device, no wait
+    imwrite(path, img, params=None)                                                                               cv2.imwrite's shape, .png
+An image is [H, W, 3], [H, W, 1] or [H, W]; a stack has a leading F; a list holds equal-sized images.  uint8 or float32 (float64 is
+cast to float32 first); host arrays are uploaded once.  Three channels give an 8-bit RGB file, one channel an 8-bit grey one or, with
+replicate=True, an RGB file of three equal channels (test.py's np.repeat(..., 3, axis=2)) that never exist in memory.  The float ->
+level rule is the JPEG writer's (v * scale, nearest-even, saturated, NaN -> 0: what convertTo(CV_8U) is understood to do, unverified);
+cv2.imwrite's own bytes are not claimed.  The file is the one the rule in include/dsnerf.h gives (tests/png_encode_restate.py): adaptive
+filters by libpng's heuristic, deflate in independent chunks with matches at distances 1, one pixel and one row, one dynamic Huffman
+code per chunk.  Not written: 16-bit, alpha, palette and Adam7 files.
+
+Decoding: the datasets' label masks (mask_cihp/....png - cv2.imread at dataloader/zju_mocap_dataset.py:197 and
 zju_novel_pose_dataset.py:195, imageio.imread at h36m_dataset.py:81, h36m_dataset_test.py:81, novel_poses_dataset.py:70).  File bytes
 go up, the uint8 mask that imageprep.prepare_zju / prepare_h36m take appears in HBM:
     decode(files, channels="bgr", first_channel=False) -> uint8 [H, W, 3] / [F, H, W, 3] on the device; ValueError for a corrupt stream
@@ -16,11 +30,74 @@ stream (stored, fixed and dynamic blocks); ancillary chunks are skipped (tRNS an
 16-bit samples, a CRC mismatch, a missing chunk, a zlib header that is not plain deflate - raises ValueError naming the file and the
 reason before anything reaches the device.  The rule is written out in include/dsnerf.h and restated in tests/png_decode_restate.py;
 PNG is lossless, so the pixels are the ones every decoder gives."""
+import os
+
 import torch
 
 from . import _lib
+from .jpeg import _stack
 
 STATUS_NAMES = _lib.PNG_STATUS_NAMES
+NONFINITE, OVERFLOW = _lib.PNGE_NONFINITE, _lib.PNGE_OVERFLOW
+IMWRITE_PNG_COMPRESSION = 16          # cv2's constant
+
+
+# ---- encoding -----------------------------------------------------------------------------------------------------------------------------------
+def encode_device(images, channels="bgr", scale=255.0, replicate=False, filter="adaptive", chunk=None, stored_only=False, capacity=None,
+                  device=None):
+    """-> (buffer uint8 [F, capacity]: row f starts with frame f's complete file, lengths int32 [F], status int32 [F]: OR of
+    NONFINITE / OVERFLOW) on the device; nothing is copied back and nothing waits.  capacity: bytes per row, by default
+    dsn_png_encode_max_bytes (no frame can overflow it).  chunk: bytes of the raw stream per independent deflate chunk, a power of two
+    from 256 to 32768 (None: the library's default).  stored_only: no compression at all."""
+    if channels not in ("bgr", "rgb"):
+        raise ValueError(f"png: channels must be 'bgr' or 'rgb', got {channels!r}")
+    f = _lib.pnge_filter(filter)
+    c = _lib.pnge_chunk(chunk)
+    x = _stack(images, device, "png")
+    return _lib.png_encode(x, _lib.pnge_mode(x, replicate), channels == "rgb", scale, f, c, stored_only, capacity=capacity)
+
+
+def encode(images, channels="bgr", scale=255.0, replicate=False, filter="adaptive", chunk=None, stored_only=False, device=None):
+    """-> one `bytes` per frame.  Two device->host copies whatever F is: the lengths (with the status words), then the used bytes."""
+    buf, lengths, status = encode_device(images, channels, scale, replicate, filter, chunk, stored_only, device=device)
+    head = torch.stack([lengths, status]).cpu().numpy()          # copy 1
+    n = [int(v) for v in head[0]]
+    if any(int(s) & OVERFLOW for s in head[1]):                  # (cannot happen at the default capacity)
+        raise RuntimeError("png.encode: a frame did not fit dsn_png_encode_max_bytes")
+    used = buf[:, :max(n)].cpu().numpy()                         # copy 2
+    return [used[f, :n[f]].tobytes() for f in range(len(n))]
+
+
+def _stored_only_of(params):
+    stored = False
+    if params:
+        p = [int(v) for v in params]
+        if len(p) % 2:
+            raise ValueError(f"imwrite: params must be (flag, value) pairs, got {params!r}")
+        for flag, value in zip(p[0::2], p[1::2]):
+            if flag != IMWRITE_PNG_COMPRESSION:
+                raise ValueError(f"imwrite: the only flag taken is IMWRITE_PNG_COMPRESSION (16), got {flag}")
+            stored = value == 0
+    return stored
+
+
+def imwrite(path, img, params=None):
+    """cv2.imwrite(path, img, params)'s shape for .png: img [H, W, 3] in B, G, R order (or [H, W], [H, W, 1]); uint8 levels, or float
+    levels that are rounded and saturated as convertTo(CV_8U) does (test.py passes `img * 255`): scale = 1 here.
+    params: [IMWRITE_PNG_COMPRESSION, 0] writes stored blocks only; any other value takes the normal path.  Returns True."""
+    ext = os.path.splitext(str(path))[1].lower()
+    if ext != ".png":
+        hint = " - dsnerf_amd.jpeg.imwrite writes those" if ext in (".jpg", ".jpeg") else ""
+        raise ValueError(f"imwrite: only .png files are written, got {path!r}{hint}")
+    data = encode(img, scale=1.0, stored_only=_stored_only_of(params))
+    if len(data) != 1:
+        raise ValueError("imwrite: one image per file")
+    with open(path, "wb") as f:
+        f.write(data[0])
+    return True
+
+
+# ---- decoding -----------------------------------------------------------------------------------------------------------------------------------
 
 
 def _names(files, names):

@@ -1701,6 +1701,105 @@ DSN_EXPORT int dsn_png_decode(const uint8_t* files, size_t files_bytes, const in
                               int first_channel, int stages, uint8_t* out, uint32_t* out_status, void* workspace, size_t workspace_bytes,
                               void* stream);
 
+/* ---- PNG ENCODING on the device (csrc/dsn_pnge.hip): test.py's five cv2.imwrite(....png) per evaluated frame (test.py:94-110: the
+ * rendering, the ground truth, the two side by side, depth and acc maps repeated to three channels) from frames that are in HBM
+ * already; the finished files are left in device memory.  The rule below is restated in tests/png_encode_restate.py; PNG is
+ * lossless, so every decoder returns the levels.  cv2.imwrite's own bytes are not claimed (OpenCV is not installed where the tests
+ * run).  Integer arithmetic and integer atomics only: the same bytes on every call, and a frame gives the same file alone or in any batch.
+ *   Levels.  The JPEG encoder's rule (one shared definition, csrc/dsn_level.h): uint8 passes through; float32 v: v * scale in
+ *      float32, nearest-even, saturated to [0, 255], NaN -> 0; a NaN or infinite value sets DSN_PNGE_NONFINITE for its frame, the file
+ *      is still valid.  mode DSN_PNGE_COLOUR: images [F, H, W, 3] in B, G, R order (rgb != 0: R, G, B); the file stores R, G, B with
+ *      colour type 2.  DSN_PNGE_GRAY: images [F, H, W], colour type 0.  DSN_PNGE_REPLICATE: images [F, H, W], colour type 2 with three
+ *      equal channels that are never materialised (test.py's np.repeat(..., 3, axis=2)).  8 bits, no interlace.
+ *   Filtering.  bpp = channels of the file, row_bytes = W bpp.  For byte x of a row: a = the byte bpp to the left, b = the one above,
+ *      c = the one above a (0 outside the image); the filtered byte is x - {0, a, b, (a + b) >> 1, Paeth(a, b, c)} mod 256 for filters
+ *      0 ... 4, Paeth = whichever of a, b, c is nearest to a + b - c, ties in that order.  filter = DSN_PNGE_ADAPTIVE: per row the filter
+ *      with the smallest sum over the row of |filtered byte read as int8| (v < 128 ? v : 256 - v; libpng's heuristic), ties to the
+ *      lower filter number; filter = 0 ... 4: that filter on every row.  The raw stream is H rows of the filter byte and row_bytes bytes.
+ *   Adler-32 of the raw stream, as in the decoder's rule.
+ *   Deflate in independent chunks.  The raw stream is cut into chunks of C bytes (chunk: a power of two, DSN_PNGE_CHUNK_MIN ...
+ *      DSN_PNGE_CHUNK_MAX); nothing in a chunk refers to bytes before it.
+ *      Matches.  At position p the candidate distances are {1, bpp, row_stride} (row_stride = 1 + row_bytes), duplicates and
+ *      distances above 32768 dropped, and those with p - distance before the chunk start.  A candidate's length is the common prefix of
+ *      the bytes at p and at p - distance, capped at 258 and at the chunk end.  The best candidate is the longest, ties to the smaller
+ *      distance.  A best length below 3, or of 3 at a distance above 4096, makes p a literal.
+ *      Parse.  Serial greedy from the chunk start: at a match emit (length, distance) and move on by the length, else emit the
+ *      literal and move on by one.
+ *      Histograms.  Literal/length symbols 0 ... 285 (lengths: RFC 1951's 29 codes with their extra bits) and distance symbols
+ *      0 ... 29; symbol 256 counts once.
+ *      Code lengths (limit 15; 7 for the code-length code).  If fewer than two symbols of an alphabet have a count, the lowest symbols
+ *      without one get a count of 1 until two have (zlib's practice; every code is then complete).  The used symbols are sorted by
+ *      (count, symbol).  Two-queue Huffman merging: the two smallest of the leaves' queue (sorted) and the internal nodes' queue (in
+ *      order of creation) are merged, a leaf before an internal node of equal weight, an older internal node before a newer one.
+ *      bl[l] = leaves of depth l, the deeper ones folded into bl[limit]; while sum bl[l] 2^(limit - l) exceeds 2^limit: bl[limit] -= 1,
+ *      l = the deepest length below the limit with bl[l] > 0, bl[l] -= 1, bl[l + 1] += 2 (each turn lowers the sum by 1, so it ends at
+ *      2^limit exactly).  Lengths are then handed out in sorted order, the rarest symbols the longest: bl[limit] symbols get `limit`,
+ *      the next bl[limit - 1] get limit - 1, ...  (always, not only after a repair: symbols of equal count may swap depths against the
+ *      tree, at the same cost).  Canonical codes as in RFC 1951 3.2.2.
+ *      Header of a dynamic block.  HLIT = 257 + (index of the last used length code) at least 257, HDIST at least 1, trailing zero
+ *      lengths dropped.  The literal/length lengths and the distance lengths are run-length coded SEPARATELY (no run crosses from one
+ *      into the other), greedily: a run of r zeros: while r >= 11 one symbol 18 for min(r, 138); then r >= 3: one symbol 17; what is
+ *      left (< 3) as explicit zeros.  A run of r equal non-zero lengths: the length itself once, then while r >= 3 one symbol 16 for
+ *      min(r, 6), what is left (< 3) explicitly.  The code-length code comes from these symbols' counts; HCLEN drops trailing zeros in
+ *      the order 16 17 18 0 8 7 9 6 10 5 11 4 12 3 13 2 14 1 15, at least 4.
+ *      Block type.  Bits of the chunk as a stored block (8 + 32 + 8 bytes: a chunk starts on a byte boundary), with the fixed codes
+ *      (3 + tokens + end of block) and with the dynamic ones (3 + header + tokens + end of block); the smallest wins, ties in that
+ *      order.  stored_only != 0: every chunk is a stored block ([IMWRITE_PNG_COMPRESSION, 0]).
+ *      Chunk end.  Every chunk but the last is followed by an empty stored block: 000, zero bits to the byte boundary, 00 00 FF FF;
+ *      every chunk therefore occupies whole bytes.  Only the last chunk's block has BFINAL = 1; zero bits pad it to a byte.
+ *   Container.  Signature; IHDR (W, H, 8, colour type 0 or 2, 0, 0, 0); ONE IDAT of 78 01, the chunks and the Adler-32 most significant
+ *      byte first; IEND.  Every chunk's CRC-32 is computed on the device (IHDR's, the same for all frames, travels in the kernel
+ *      arguments): table CRCs of 16-byte slices without conditioning, each moved to the end of the data by a multiplication with
+ *      x^(8 n) mod the polynomial and XOR-ed together, the conditioning added as one more such term.  The file is 63 bytes + the
+ *      deflate stream.
+ *   Kernels.  k_pe_filter: a workgroup per row, integer sums.  k_pe_adler: sums mod 65521 per 64 KiB, integer adds per frame.
+ *      k_pe_match: a thread per raw byte.  k_pe_codes: ONE WAVE PER CHUNK: the greedy parse 64 positions per turn with the next
+ *      token's position as a wave-uniform carry (exactly the serial result), histograms by LDS atomics, the symbols' ranks by all
+ *      lanes, the tree, the repair, the header and the costs by lane 0 out of LDS.  k_pe_emit: a workgroup per chunk: bit lengths,
+ *      workgroup prefix sums, 32-bit atomic ORs into the chunk's cleared slot.  The project's tile scan turns the chunks' byte lengths
+ *      into offsets; k_pe_compact moves the slots together; k_pe_cont_copy / _tail finish the file.
+ *   Bounds.  dsn_png_encode_max_bytes = 63 + raw bytes + 10 per chunk - 5: every chunk stored.  `capacity` is the stride of `out` in
+ *      bytes; a frame that needs more sets DSN_PNGE_OVERFLOW for that frame alone: nothing is written at or past the capacity,
+ *      out_lengths still holds the needed length.  W, H <= 16384, F <= 16384.
+ *   Not done: 16-bit, alpha, palette and Adam7 output; hash-chain matches and lazy matching; joining chunks at bit level without the
+ *      empty stored block.
+ * images: contiguous, dtype DSN_JPEG_U8 or DSN_JPEG_F32.  channels (of the file): 1 or 3.  out: uint8 [F, capacity], bytes past a frame's
+ * length are not touched; out_lengths int32 [F]; out_status uint32 [F] (OR of DSN_PNGE_*).  dsn_png_filter: raw uint8 [F, H (1 + row_bytes)],
+ * out_status (NONFINITE).  dsn_png_deflate: raw uint8 [F, n] (ANY bytes; bpp and row_stride only name the candidate distances) -> the
+ * deflate stream without zlib header and Adler-32 in out [F, capacity], out_lengths, out_status (OVERFLOW); dsn_png_deflate_max_bytes(n,
+ * chunk) never overflows.  dsn_huff_lengths: counts uint32 [B, n] (2 <= n <= 288, n <= 2^limit, limit 1 ... 15) -> lengths
+ * uint8 [B, n].  dsn_png_adler: raw [F, n] -> out_adler uint32 [F]; workspace 8 F bytes.  dsn_png_container: stream
+ * uint8 [F, stream_stride] with lengths int32 [F] (bytes past the stride are not read), adler uint32 [F], status_in uint32 [F] or null ->
+ * the files; workspace 4 F bytes.  dsn_png_encode is filter, adler, deflate and container one after the other, bit for bit.
+ * Workspaces: dsn_png_*_workspace_bytes (0 for sizes outside the scope), 256-byte aligned (dsn_png_adler / _container: 4-byte), anything on
+ * entry.  No allocation, no host copy, no synchronisation. */
+#define DSN_PNGE_GRAY 0
+#define DSN_PNGE_COLOUR 1
+#define DSN_PNGE_REPLICATE 2
+#define DSN_PNGE_ADAPTIVE 5
+#define DSN_PNGE_NONFINITE 1u
+#define DSN_PNGE_OVERFLOW 2u
+#define DSN_PNGE_CHUNK_MIN 256
+#define DSN_PNGE_CHUNK_MAX 32768
+#define DSN_PNGE_CHUNK_DEFAULT 32768
+DSN_EXPORT size_t dsn_png_encode_max_bytes(int W, int H, int channels, int chunk);
+DSN_EXPORT size_t dsn_png_encode_workspace_bytes(int F, int W, int H, int mode, int chunk);
+DSN_EXPORT size_t dsn_png_deflate_max_bytes(size_t n, int chunk);
+DSN_EXPORT size_t dsn_png_deflate_workspace_bytes(int F, size_t n, int chunk);
+DSN_EXPORT int dsn_png_filter(const void* images, int dtype, int F, int H, int W, int mode, int rgb, float scale, int filter, uint8_t* raw,
+                              uint32_t* out_status, void* stream);
+DSN_EXPORT int dsn_png_adler(const uint8_t* raw, int F, size_t n, uint32_t* out_adler, void* workspace, size_t workspace_bytes, void* stream);
+DSN_EXPORT int dsn_png_deflate(const uint8_t* raw, int F, size_t n, int bpp, int row_stride, int chunk, int stored_only, uint8_t* out,
+                               size_t capacity, int32_t* out_lengths, uint32_t* out_status, void* workspace, size_t workspace_bytes,
+                               void* stream);
+DSN_EXPORT int dsn_huff_lengths(const uint32_t* counts, int B, int n, int limit, uint8_t* lengths, void* stream);
+DSN_EXPORT int dsn_png_container(const uint8_t* stream_bytes, size_t stream_stride, const int32_t* stream_lengths, const uint32_t* adler,
+                                 const uint32_t* status_in, int F, int W, int H, int channels, uint8_t* out, size_t capacity,
+                                 int32_t* out_lengths, uint32_t* out_status, void* workspace, size_t workspace_bytes, void* stream);
+DSN_EXPORT int dsn_png_encode(const void* images, int dtype, int F, int H, int W, int mode, int rgb, float scale, int filter, int chunk,
+                              int stored_only, uint8_t* out, size_t capacity, int32_t* out_lengths, uint32_t* out_status, void* workspace,
+                              size_t workspace_bytes, void* stream);
+
 /* diagnostics, NOT for the hot path (synchronises `stream`): {ncell, ok, total entries, capacity} of the four
  * nearest-face list levels (world fine/coarse, canonical fine/coarse) into a HOST array of 16 int32. */
 DSN_EXPORT int dsn_debug_nn_stats(const void* scene, int V, int F, int32_t* out16_host, void* stream);
