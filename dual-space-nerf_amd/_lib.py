@@ -1716,9 +1716,8 @@ def render_rays(scene: Scene, packed: PackedParams, ws: RenderWorkspace, ray_o, 
     if train_cache is not None:      # training forward: dense, and everything its backward needs stays in train_cache
         flags &= ~SKIP_TRANSPARENT
         gbuf = train_cache.get(R, S)
-        # (ABI 8: the far canonical search beside the field kernel on the backward's auxiliary stream; DSN_TRAIN_FWD_AUX=0: A/B switch -
-        #  the forward on one stream, the backward's chains still on two)
-        ax = train_cache.aux() if os.environ.get("DSN_TRAIN_FWD_AUX", "1") != "0" else (None, None, None)
+        # (ABI 8: the far canonical search beside the field kernel on the backward's auxiliary stream)
+        ax = train_cache.aux()
         _check(lib().dsn_render_rays_train_ex(_ptr(scene.buf), scene.V, scene.F, _ptr(packed.buf), _ptr(ray_o, torch.float32),
                                               _ptr(ray_d, torch.float32), _ptr(near, torch.float32), _ptr(far, torch.float32), R, S,
                                               _ptr(t_vals, torch.float32), _ptr(jitter), _ptr(noise), flags, _ptr(out["color"]),
@@ -1981,9 +1980,8 @@ def choose_stop_schedule(hist, L: int, S: int, round_samples: int = 128 * 224, l
     for a in range(K):
         M[a] = hist[a + 1:].sum(0)
     rs = float(round_samples)
-    # (DSN_STOP_ROUND_ALPHA / DSN_STOP_LAUNCH_ROUNDS: experiment overrides of round_weight / launch_rounds)
-    alpha = float(os.environ.get("DSN_STOP_ROUND_ALPHA", round_weight))
-    launch_rounds = float(os.environ.get("DSN_STOP_LAUNCH_ROUNDS", launch_rounds))
+    alpha = float(round_weight)
+    launch_rounds = float(launch_rounds)
 
     def cost(n):
         if not quantise:

@@ -304,7 +304,8 @@ __host__ __device__ inline float dsn_stop_eps_scaled(int S, float colour_scale) 
 // needs - a255 alone sits behind the kernel's own VGPR count, rounded to 4).
 #define DSN_OWN_SIMD() asm volatile("v_mov_b32 v255, 0\n\tv_accvgpr_write_b32 a255, 0" ::: "v255", "a255")
 // The training backward's matrix kernels carry the guard through DSN_OWN_SIMD_T(bit): 1 k_tangent16, 2 k_adjoint16, 4 k_t_wgrad16d
-// (256 + 256 registers as it is), 64 k_t_wgrad16c, 128 k_t_wgrad16q - the K = 16 kernels; 16 k_t_lin, 32 k_t_wgrad (fp32 MFMA) do not.
+// (256 + 256 registers as it is), 128 k_t_wgrad16q - the K = 16 kernels; 16 k_t_lin, 32 k_t_wgrad (fp32 MFMA) do not.  (Bit 64 was
+// k_t_wgrad16c, round 3's unpipelined product, retired with its switch: no kernel carries it; the value keeps it set.)
 // Experiment builds (-DDSN_EXPERIMENTS -DDSN_TRAIN_UNGUARDED=bits) leave the kernels of the given bits without the guard and guard all
 // the others - the bisect's tool.
 #define DSN_TRAIN_AGGRESSORS 199

@@ -1162,9 +1162,9 @@ __global__ void __launch_bounds__(F16_THREADS, 1)
 k_tangent16(const float* __restrict__ packed, const float* __restrict__ x_c, const float* __restrict__ u, int64_t N,
             const uint4* __restrict__ masks, float* __restrict__ tr_t, uint32_t* __restrict__ gmax, int32_t* __restrict__ range_count,
             const int32_t* __restrict__ row_list, const int32_t* __restrict__ row_count, float* __restrict__ colsum6) {
-    // colsum6 (optional, round 6) [256]: += the column sums of hdot_6 over the listed samples - the only use the training backward has
-    // for the last layer's tangent (d (w_d . hdot_6) / d w_d, dsn_train.hip).  With it the layer is not stored at all: one 1 KB row per
-    // sample less to write and to read back, and no k_t_colsum launch (0.75 GB and 0.13 ms per 8192 x 64 step).
+    // colsum6 (round 6) [256]: += the column sums of hdot_6 over the listed samples - the only use the training backward has for the
+    // last layer's tangent (d (w_d . hdot_6) / d w_d, dsn_train.hip).  The layer itself is not stored: one 1 KB row per sample less to
+    // write and to read back, and no column-sum launch behind it (0.75 GB and 0.13 ms per 8192 x 64 step).  tr_t holds layers 0 .. 5.
     // row_list / row_count (optional): the pass runs on the listed samples only (rows whose cotangents are all zero add nothing to
     // any gradient: dsn_train.hip, Rows); arrays stay indexed by sample, N is still the layer stride
     __shared__ __attribute__((aligned(16))) char ring[F16_RING_SLOTS * 4096];
@@ -1269,18 +1269,10 @@ k_tangent16(const float* __restrict__ packed, const float* __restrict__ x_c, con
         split16<false>(v, ah[m], al[m]);
     }
     TMK_LOAD(5, mk) layer16_tan(w, blk, lane, ah, al, bh, bl, mk, tt ? tt + 5 * ls : nullptr, sc, ovf);
-    if (!colsum6) {
-        TMK_LOAD(6, mk) layer16_tan(w, blk, lane, bh, bl, ah, al, mk, tt ? tt + 6 * ls : nullptr, sc, ovf);
-        if (!(fmaxf(ovf, __shfl_xor(ovf, 32)) < F16_RANGE) && tt) {      // (false for inf and for the NaN an inf times 0 leaves)
-            zero_train_rows(tt, ls, 7);
-            if (half == 0 && range_count) atomicAdd(range_count, 1);
-        }
-        return;
-    }
     float h6[8][16];
     TMK_LOAD(6, mk) layer16_tan(w, blk, lane, bh, bl, ah, al, mk, nullptr, sc, ovf, h6);
 #undef TMK_LOAD
-    const bool bad = !(fmaxf(ovf, __shfl_xor(ovf, 32)) < F16_RANGE);
+    const bool bad = !(fmaxf(ovf, __shfl_xor(ovf, 32)) < F16_RANGE);      // (true for inf and for the NaN an inf times 0 leaves)
     if (bad && tt) {
         zero_train_rows(tt, ls, 6);
         if (half == 0 && range_count) atomicAdd(range_count, 1);
@@ -1559,7 +1551,7 @@ __global__ void __launch_bounds__(64 * NW, 1)
 k_screen16(const float* __restrict__ packed, const DsnFrameState* __restrict__ fs, const float* __restrict__ x_c, int64_t N,
            const int32_t* __restrict__ active_list, const int32_t* __restrict__ active_count, float* __restrict__ sigma,
            int32_t* __restrict__ keep_list, int32_t* __restrict__ keep_count, float* __restrict__ dbg_sigma,
-           float* __restrict__ dbg_s1, float margin_override, int32_t* __restrict__ audit_list, int32_t* __restrict__ audit_count,
+           float* __restrict__ dbg_s1, int32_t* __restrict__ audit_list, int32_t* __restrict__ audit_count,
            int audit_cap) {
     __shared__ __attribute__((aligned(16))) char ring[2 * 16384];
     __shared__ __attribute__((aligned(16))) float s_vec[256 + 2304 + 8];
@@ -1682,8 +1674,8 @@ k_screen16(const float* __restrict__ packed, const DsnFrameState* __restrict__ f
     const bool mine = valid && half == 0;
     // margin: packed[OFF_SCAL + 5] - the conservative default written by dsn_pack_params (F16_SCREEN_REL) or the value
     // dsn_calibrate_screen measured for THESE parameters (10x the largest deviation seen, +inf = never declare anything
-    // empty); DSN_SCREEN_MARGIN (experiments) overrides it
-    const float margin = margin_override > 0.0f ? margin_override : s_vec[2560 + 5];
+    // empty)
+    const float margin = s_vec[2560 + 5];
     const bool empty = in_range && sg < -(margin * s1 + margin);
     if (mine) {
         if (empty) sigma[pt] = sg;
@@ -1805,7 +1797,7 @@ __global__ void __launch_bounds__(256, 1)
 k_screen16x2(const float* __restrict__ packed, const DsnFrameState* __restrict__ fs, const float* __restrict__ x_c, int64_t N,
              const int32_t* __restrict__ active_list, const int32_t* __restrict__ active_count, float* __restrict__ sigma,
              int32_t* __restrict__ keep_list, int32_t* __restrict__ keep_count, float* __restrict__ dbg_sigma,
-             float* __restrict__ dbg_s1, float margin_override, int32_t* __restrict__ audit_list, int32_t* __restrict__ audit_count,
+             float* __restrict__ dbg_s1, int32_t* __restrict__ audit_list, int32_t* __restrict__ audit_count,
              int audit_cap) {
     static_assert(F16_SCREEN_ACC == 1, "k_screen16x2 keeps one accumulator per tile");
     __shared__ __attribute__((aligned(16))) char ring[2 * 16384];
@@ -1932,7 +1924,7 @@ k_screen16x2(const float* __restrict__ packed, const DsnFrameState* __restrict__
     omax = fmaxf(omax, __shfl_xor(omax, 32));
     const bool in_range = fmaxf(omax, packed[DSN_SPLIT_UNSAFE_FIELD]) < F16_RANGE;
     const float bd = s_vec[2560];
-    const float margin = margin_override > 0.0f ? margin_override : s_vec[2560 + 5];
+    const float margin = s_vec[2560 + 5];
     bool keep[2];
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
@@ -1985,17 +1977,15 @@ void dsn_launch_screen16(const float* packed, const DsnFrameState* fs, const flo
     // one-tile waves, one persistent workgroup per CU
     const char* wenv = getenv("DSN_SCREEN_WAVES");      // (read per launch: tests switch it)
     const int waves = wenv ? atoi(wenv) : 8;
-    // experiment switch: overrides the margin the packed parameters carry (default / calibrated, see k_screen16)
-    static const float margin = getenv("DSN_SCREEN_MARGIN") ? (float)atof(getenv("DSN_SCREEN_MARGIN")) : 0.0f;
     if (waves == 4)
         hipLaunchKernelGGL(k_screen16<4>, dim3((unsigned)std::min<int64_t>((N + 127) / 128, 2 * dsn_cu_count())), dim3(256), 0, st, packed, fs, x_c, N, active_list,
-                           active_count, sigma, keep_list, keep_count, dbg_sigma, dbg_s1, margin, audit_list, audit_count, audit_cap);
+                           active_count, sigma, keep_list, keep_count, dbg_sigma, dbg_s1, audit_list, audit_count, audit_cap);
     else if (waves == 2)
         hipLaunchKernelGGL(k_screen16x2, dim3((unsigned)std::min<int64_t>((N + 255) / 256, dsn_cu_count())), dim3(256), 0, st, packed, fs, x_c, N, active_list,
-                           active_count, sigma, keep_list, keep_count, dbg_sigma, dbg_s1, margin, audit_list, audit_count, audit_cap);
+                           active_count, sigma, keep_list, keep_count, dbg_sigma, dbg_s1, audit_list, audit_count, audit_cap);
     else
         hipLaunchKernelGGL(k_screen16<8>, dim3((unsigned)std::min<int64_t>((N + 255) / 256, dsn_cu_count())), dim3(512), 0, st, packed, fs, x_c, N, active_list,
-                           active_count, sigma, keep_list, keep_count, dbg_sigma, dbg_s1, margin, audit_list, audit_count, audit_cap);
+                           active_count, sigma, keep_list, keep_count, dbg_sigma, dbg_s1, audit_list, audit_count, audit_cap);
 }
 
 // DSN_SCREEN_AUDIT: out[0] += number of audited samples (declared empty by the screen, evaluated by the accurate pass anyway)

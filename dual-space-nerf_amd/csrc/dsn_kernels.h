@@ -185,8 +185,8 @@ void dsn_launch_adjoint16(const float* packed, int64_t N, const void* masks, con
                           hipStream_t st, int32_t* range_count = nullptr, const int32_t* row_list = nullptr,
                           const int32_t* row_count = nullptr);
 void dsn_launch_tangent16(const float* packed, const float* x_c, const float* u, int64_t N, const void* masks, float* tr_t,
-                          float* gmax, hipStream_t st, int32_t* range_count = nullptr, const int32_t* row_list = nullptr,
-                          const int32_t* row_count = nullptr, float* colsum6 = nullptr);
+                          float* gmax, hipStream_t st, int32_t* range_count, const int32_t* row_list, const int32_t* row_count,
+                          float* colsum6);
 // a second stream of the caller's for the training backward's two independent chains (dsn_render_rays_grad_ex): fork / join events
 struct DsnTrainAux { hipStream_t stream; hipEvent_t fork, join; };
 const char* dsn_train_run(const DsnSceneView& s, const float* packed, const float* const* params33, const float* poses, int frame_idx,

@@ -483,6 +483,12 @@ __global__ void __launch_bounds__(256) k_grid_fill(const float4* __restrict__ ce
     }
 }
 
+// a level as its builds see it: DSN_NN_NO_SUPER=1 (cross-check switch) takes the supersets away - every cell sweeps all faces
+static DsnGridView dsn_build_view(const DsnGridView& v) {
+    DsnGridView vv = v;
+    if (getenv("DSN_NN_NO_SUPER")) vv.super_cnt = nullptr;
+    return vv;
+}
 // the membership words between k_grid_count and k_grid_fill: only where the cells sweep supersets (DSN_NN_NO_MEMBER=1: cross-check
 // switch - k_grid_fill sweeps again, as rounds 1-5)
 static unsigned long long* dsn_member_words(const DsnGridView& vv) {
@@ -492,8 +498,7 @@ static unsigned long long* dsn_member_words(const DsnGridView& vv) {
 static void dsn_build_level(const float4* cent, int F, const DsnGridView& v, float pad, int target, int maxcell, int cap,
                             bool inline_entries, hipStream_t st, bool params_only = false) {
     const int maxsuper = dsn_grid_maxsuper(maxcell);
-    DsnGridView vv = v;
-    if (getenv("DSN_NN_NO_SUPER")) vv.super_cnt = nullptr;     // cross-check switch: build with full sweeps
+    const DsnGridView vv = dsn_build_view(v);
     hipLaunchKernelGGL(k_grid_params, dim3(1), dim3(256), 0, st, cent, F, pad, target, maxcell, cap, v.g, params_only ? 1 : 0);
     if (params_only) return;
     const int32_t* none = nullptr;
@@ -524,9 +529,7 @@ void dsn_launch_build_nn_visited(const float4* cent, int F, const DsnNNView& nn,
     const DsnGridView& v = nn.fine;
     uint8_t* const clear = (clear_cells && face_world) ? v.clear : nullptr;
     const int maxcell = DSN_NN_FINE_MAXCELL, maxsuper = dsn_grid_maxsuper(maxcell);
-    DsnGridView vv = v;
-    if (getenv("DSN_NN_NO_SUPER")) vv.super_cnt = nullptr;
-    if (getenv("DSN_LAZY_ALL_CELLS")) visited = nullptr;      // (cross-check switch: the lazy build for every cell)
+    const DsnGridView vv = dsn_build_view(v);
     if (vv.super_cnt)
         hipLaunchKernelGGL(k_grid_super, dim3(maxsuper), dim3(256), 0, st, cent, F, v.g, maxsuper, vv.super_cnt, vv.super_list, visited, 1);
     if (clear)
@@ -552,8 +555,7 @@ __global__ void k_grid_complete(DsnGrid* __restrict__ g) {
 void dsn_launch_build_nn_complete(const float4* cent, int F, const DsnNNView& nn, hipStream_t st) {
     const DsnGridView& v = nn.fine;
     const int maxcell = DSN_NN_FINE_MAXCELL, maxsuper = dsn_grid_maxsuper(maxcell);
-    DsnGridView vv = v;
-    if (getenv("DSN_NN_NO_SUPER")) vv.super_cnt = nullptr;
+    const DsnGridView vv = dsn_build_view(v);
     const int32_t* none = nullptr;
     if (vv.super_cnt)
         hipLaunchKernelGGL(k_grid_super, dim3(maxsuper), dim3(256), 0, st, cent, F, v.g, maxsuper, vv.super_cnt, vv.super_list, none, 2);
@@ -579,11 +581,7 @@ void dsn_launch_build_nn(const float4* cent, int F, const DsnNNView& nn, float p
     // samples visit (dsn_launch_build_nn_visited, behind the sampler's classification)
     // dense_fine (the canonical mesh: built once, queried by a per-lane list scan in k_normal): as many fine cells as the level
     // holds - shorter lists per query; the posed mesh's lists are rebuilt per frame and stay at 3 F cells
-    int t_fine = dense_fine ? dsn_clampi(5 * F, 512, 62000) : dsn_clampi(3 * F, 512, 44000);
-    if (!dense_fine) {      // DSN_NN_FINE_TARGET (tuning): cells of the posed mesh's fine level (lists stay exact for any cell size)
-        static const long long tgt = [] { const char* e = getenv("DSN_NN_FINE_TARGET"); return e ? atoll(e) : 0ll; }();
-        if (tgt > 0) t_fine = dsn_clampi((int)tgt, 512, 62000);
-    }
+    const int t_fine = dense_fine ? dsn_clampi(5 * F, 512, 62000) : dsn_clampi(3 * F, 512, 44000);
     const int t_coarse = dsn_clampi(F / 3, 64, 5000);
     // DSN_NN_FINE_CAP (tests): a smaller LOGICAL capacity of the fine level - provokes the overflow path (level unusable, queries fall
     // through to the coarse level / the sweep, the host mirror warns) on a mesh that fits the real one
@@ -1170,10 +1168,9 @@ void dsn_launch_nn_cellmajor_warp(const DsnNNView& v, const float* ray_o, const 
         hipLaunchKernelGGL(k_nns_classify, gN, b, 0, st, v.fine.g, (const float*)nullptr, ray_o, ray_d, z_vals, N, S, cell_of, (int32_t*)nullptr,
                            counts, totals + 2);
     }
-    // classified by the sampler: it also kept every sample's rank inside its cell (cell_of + N) - the scatter places by rank
-    // (DSN_NN_ATOMIC_SCATTER: A/B switch, round 3's scatter with atomic cursors; a lazily built level always takes the ranked form - it
-    //  is the one that hands the samples over when the visited cells' lists did not fit)
-    const bool ranked = classified && (lazy_call || !getenv("DSN_NN_ATOMIC_SCATTER"));
+    // classified by the sampler: it also kept every sample's rank inside its cell (cell_of + N) - the scatter places by rank (and, on
+    // a lazily built level, hands the samples over when the visited cells' lists did not fit); classified here: atomic cursors
+    const bool ranked = classified;
     const int lc = lazy_call ? 1 : 0;
     if (ranked)
         hipLaunchKernelGGL(k_nns_scan_mb, dim3(DSN_NN_SCAN_BLOCKS(DSN_NN_FINE_MAXCELL)), dim3(1024), 0, st, v.fine.g, (const int32_t*)counts, offs, wave_offs,
@@ -1357,7 +1354,7 @@ void dsn_launch_nn_cellmajor_coarse(const DsnNNView& v, const float4* cent, cons
     const dim3 gN((unsigned)((N + NNS_THREADS - 1) / NNS_THREADS)), b(NNS_THREADS);
     hipLaunchKernelGGL(k_nns_classify_coarse, gN, b, 0, st, v.fine.g, v.coarse.g, pts, live, N, cell_of, nn, counts);
     static const bool seg_off = [] { const char* e = getenv("DSN_FAR_SEGMENTS"); return e && e[0] == '0'; }();
-    static const int seg = [] { const char* e = getenv("DSN_FAR_SEG"); const int v = e ? atoi(e) : 0; return v >= 64 && v <= 16384 ? v & ~3 : NNS_FAR_SEG; }();
+    const int seg = NNS_FAR_SEG;
     const int64_t nseg_max = ((int64_t)F + seg - 1) / seg;
     const int64_t mw = (N / NNS_PER + DSN_NN_COARSE_MAXCELL + 1) * (nseg_max > 0 ? nseg_max : 1);      // most waves the scan can ask for
     if (keys8N && wave_scratch && !seg_off && mw + DSN_NN_COARSE_MAXCELL + 1 <= wave_scratch_ints) {

@@ -42,6 +42,27 @@ const int kTrunkLd[7] = {87, 256, 256, 256, 319, 256, 256};
 #define W0_POSE_COL 71
 #define W4_PE_COL 256     // stage2.0 input = [h 256 | pe 63]              (model/spacenet.py:133-135)
 
+// The run-time switches of the training step: each one is the cross-check of a fusion, flipped by
+// tests/test_gpu_round5.py::test_paired_weight_gradient_launches_match_the_single_ones in a sub-process (read once per process), and
+// keeps the unfused form's kernels reachable.  dsn_train_run reads as the default step; each of these is one `else`.
+struct TrainSwitches {
+    bool pairs;             // DSN_WGRAD_PAIRS=0 clears it: a launch per weight-gradient product (the one-pair forms of k_t_wgrad16d / 16p)
+    bool two_pass_heads;    // DSN_TRAIN_UNFUSED_HEADS=1: k_t_pe, k_t_seed, k_t_rgb_hidden_adjoint and the heads' products on k_t_wgrad
+    bool lin_fp32;          // DSN_TRAIN_LIN=fp32: the heads' two data-gradient products on the exact-fp32 k_t_lin instead of k_t_lin16
+};
+static const TrainSwitches& train_switches() {
+    static const TrainSwitches v = [] {
+        const char* const p = getenv("DSN_WGRAD_PAIRS");
+        const char* const h = getenv("DSN_TRAIN_UNFUSED_HEADS");
+        const char* const l = getenv("DSN_TRAIN_LIN");
+        return TrainSwitches{!(p && p[0] == '0'), h && h[0] == '1', l && l[0] == 'f'};
+    }();
+    return v;
+}
+// DSN_TRAIN_ALL_ROWS=1: every row is listed - the dense evaluation of round 2.  Read per call, unlike the three above:
+// tests/test_gpu_round3.py sets and clears it inside one process.
+static bool train_all_rows() { const char* e = getenv("DSN_TRAIN_ALL_ROWS"); return e && e[0] == '1'; }
+
 // ------------------------------------------------------------------------------------------------------------
 // element-wise kernels
 // ------------------------------------------------------------------------------------------------------------
@@ -270,43 +291,6 @@ __global__ void __launch_bounds__(T_THREADS) k_t_mask_colsum256(float* __restric
     atomicAdd(out + c, acc);
 }
 
-// column sums of a [N,C] matrix (C <= 256), accumulated into out[C]
-__global__ void __launch_bounds__(T_THREADS) k_t_colsum(const float* __restrict__ a, int C, int64_t N, int rows_per_block,
-                                                         float* __restrict__ out, Rows rw) {
-    __shared__ float s[T_THREADS];
-    // (C is 128 or 256: a wave lies inside one row group, so the row numbers are wave-uniform - scalar loads, rows_at_u)
-    const int c = threadIdx.x % C, r0 = __builtin_amdgcn_readfirstlane(threadIdx.x / C), rs = T_THREADS / C;
-    const int64_t NL = rows_n(rw, N);
-    const int64_t base = (int64_t)blockIdx.x * rows_per_block;
-    int64_t end = base + rows_per_block;
-    if (end > NL) end = NL;
-    float acc = 0.0f;
-    if (r0 < rs) {
-        int64_t n = base + r0;
-        int64_t id[8];
-        // the row numbers of a step are fetched one step ahead (rows beyond the chunk: the last row's, never used)
-        auto fetch = [&](int64_t n_) {
-#pragma unroll
-            for (int k = 0; k < 8; ++k) { const int64_t q = n_ + k * (int64_t)rs; id[k] = rows_at_u(rw, q < end ? q : end - 1); }
-        };
-        if (n < end) fetch(n);
-        for (; n + 7 * (int64_t)rs < end; n += 8 * (int64_t)rs) {      // eight independent loads in flight per thread
-            float v[8];
-#pragma unroll
-            for (int k = 0; k < 8; ++k) v[k] = a[id[k] * C + c];
-            fetch(n + 8 * (int64_t)rs);
-            acc += ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));
-        }
-        for (; n < end; n += rs) acc += a[rows_at_u(rw, n) * C + c];
-    }
-    s[threadIdx.x] = acc;
-    __syncthreads();
-    if (r0 == 0) {
-        for (int k = 1; k < rs; ++k) acc += s[k * C + c];
-        atomicAdd(out + c, acc);
-    }
-}
-
 // Weight gradient of a layer with 1 or 3 outputs: dW[o][c] += sum_n dY[n,o] X[n,c] (C = 128 or 256), and its bias gradient
 // db[o] += sum_n dY[n,o] - a weighted column sum at the HBM rate (rocBLAS runs these K = 524 288, M <= 3 shapes at 0.23 ms)
 // dX (optional, round 5): the layer's DATA gradient behind the relu that made X rides along in the same sweep,
@@ -319,7 +303,8 @@ __global__ void __launch_bounds__(T_THREADS) k_t_wcolsum(const float* __restrict
     // gmax (optional, round 6): batch-wide max |dX| as float bits - the operand scale of the split-fp16 product that reads dX next
     __shared__ float s[OUT][T_THREADS];
     float dmax = 0.0f;
-    // (C is 128 or 256: wave-uniform row numbers, fetched a step ahead with scalar loads - see k_t_colsum)
+    // (C is 128 or 256: a wave lies inside one row group, so the row numbers are wave-uniform - fetched a step ahead with scalar loads,
+    //  rows_at_u)
     const int c = threadIdx.x % C, r0 = __builtin_amdgcn_readfirstlane(threadIdx.x / C), rs = T_THREADS / C;
     const int64_t NL = rows_n(rw, N);
     const int64_t base = (int64_t)blockIdx.x * rows_per_block;
@@ -973,15 +958,14 @@ __device__ __forceinline__ float t_pair_ratio(float s1, float s2) {
     return r < 8.5e37f ? r : 8.507059e37f;
 }
 // The kernel: operand rows are staged through LDS by the DMA engine (global_load_lds_dwordx4, one 1 KB row per
-// wave-instruction, no staging registers; W16S_STAGES - 1 steps of 16 rows x 2 operands = 32 KB each in flight per CU, every
+// wave-instruction, no staging registers; steps of 16 rows x 2 operands = 32 KB each in flight per CU, every
 // row fetched once per workgroup).  Every value is split ONCE per workgroup: thread f converts feature f of both operands for
 // the 16 rows of a step out of the fp32 ring (column reads, conflict-free) and leaves packed (hi, lo) halves in an operand
 // buffer laid out [operand][hi|lo][8-sample group][feature] x 16 B, from which a lane fetches each MFMA operand with one
-// conflict-free ds_read_b128.  LDS: 4 stages x 32 KB fp32 ring + 32 KB operand buffer = all 160 KB.
+// conflict-free ds_read_b128.
 // History on the 256 x 256 x 524 288 product: fp32 MFMA 0.80 ms -> split-fp16 with per-lane global loads and in-register
-// splits 0.44 -> LDS-DMA staging 0.345 -> convert-once 0.33 -> one workgroup per CU (256 instead of 512 groups) 0.28.  (Storing
-// per-workgroup tiles and reducing them in a second kernel instead of the atomicAdd epilogue measured the same: 0.24 + 0.04.)
-#define W16S_STAGES 4
+// splits 0.44 -> LDS-DMA staging 0.345 -> convert-once 0.33 -> one workgroup per CU (256 instead of 512 groups) 0.28 (round 3's
+// kernel, phases per step and an atomicAdd epilogue) -> software-pipelined, below -> per-workgroup tiles + k_t_wgrad_reduce.
 // floats of one workgroup's partial result in the two-stage form: the [256][C] tile + 256 column sums (bias gradient)
 #define W16_PART(C) (256 * (C) + 256)
 #define W16_PART_GROUPS 512          // most workgroups a two-stage product launches (k_t_wgrad16p: two per CU)
@@ -990,202 +974,18 @@ __device__ __forceinline__ float t_pair_ratio(float s1, float s2) {
 #endif
 // the optional second operand pair of a split-fp16 weight-gradient launch (jobs = 1: none), see k_t_wgrad16d
 struct WgradOps { const float* dY2; const float* sy2; const float* X2; const float* sx2; int jobs; };
-__global__ void __launch_bounds__(256) k_t_wgrad16c(const float* __restrict__ dY, const float* __restrict__ sy_ptr,
-                                                     const float* __restrict__ X, const float* __restrict__ sx_ptr, int64_t N,
-                                                     int rows_per_wg, float* __restrict__ dW, int ldw,
-                                                     float* __restrict__ dbias, Rows rw) {
-    DSN_OWN_SIMD_T(64);
-    constexpr int OT = 4, IT = 4, WI = 2;
-    __shared__ __attribute__((aligned(16))) float ring[W16S_STAGES][2][16][256];
-    __shared__ __attribute__((aligned(16))) t_half8 opbuf[2][2][2][256];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wo = wave / WI, wi = wave % WI;
-    const int col = lane & 31, half = lane >> 5;
-    const int64_t NL = rows_n(rw, N);
-    if (rw.cnt) rows_per_wg = (int)rows_share(NL, 16, 64);     // (the launch was sized for N rows: share what is listed)
-    const int64_t n0 = (int64_t)blockIdx.x * rows_per_wg;
-    int64_t n1 = n0 + rows_per_wg;
-    if (n1 > NL) n1 = NL;
-    if (n0 >= n1) return;                                // workgroup-uniform
-    const int full = n1 > n0 ? (int)((n1 - n0) >> 4) : 0;
-    const bool tail = n0 + 16 * (int64_t)full < n1;
-    float bsum = 0.0f;                                   // column sum of dY feature tid (bias gradient)
-    const float sy = sy_ptr ? t_pow2_at_least(*sy_ptr) : 1.0f, sx = sx_ptr ? t_pow2_at_least(*sx_ptr) : 1.0f;
-    const float iy = 1.0f / sy, ix = 1.0f / sx;
-    t_f32x16 acc[OT][IT];
-#pragma unroll
-    for (int a = 0; a < OT; ++a)
-#pragma unroll
-        for (int b = 0; b < IT; ++b)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.0f;
-    const unsigned ring_off = (unsigned)(uintptr_t)(__attribute__((address_space(3))) float*)&ring[0][0][0][0];
-    // listed rows: this wave's four row numbers of the NEXT step to be staged, fetched with ONE scalar load a step ahead (a plain
-    // global pointer gives vector loads + s_waitcnt vmcnt(0), which drains the DMA queue at every step)
-    t_i32x4 ids = {0, 0, 0, 0};
-    auto fetch_ids = [&](int t) {
-        if (!rw.list) return;
-        // (constant address space: the list is not written during this kernel, and only for loads from there does hipcc pick
-        //  s_load_dwordx4 and track the wait itself; 16-byte aligned: n0 and the list base are)
-        ids = *reinterpret_cast<t_cptr4>((uintptr_t)(rw.list + (n0 + 16 * (int64_t)t + 4 * wave)));
-    };
-    auto stage = [&](int t) {
-        const int slot = t % W16S_STAGES;
-        const int64_t row = n0 + 16 * (int64_t)t + 4 * wave;
-        const unsigned da = ring_off + (unsigned)(((slot * 2 + 0) * 16 + 4 * wave) * 1024);
-        const unsigned db = ring_off + (unsigned)(((slot * 2 + 1) * 16 + 4 * wave) * 1024);
-        if (rw.list) {
-            // listed rows: the wave's four rows of this step lie anywhere - one address per row; the LDS side advances by 1 KB per
-            // instruction.  The row numbers were fetched one step earlier (ids: scalar loads whose latency would otherwise sit in
-            // front of every step's DMA); a run of four consecutive rows takes the one-address form
-            if (ids[3] - ids[0] == 3) {
-                const char* ga = reinterpret_cast<const char*>(dY + (int64_t)ids[0] * 256) + lane * 16;
-                const char* gb = reinterpret_cast<const char*>(X + (int64_t)ids[0] * 256) + lane * 16;
-                asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\t"
-                             "global_load_lds_dwordx4 %0, off\n\tglobal_load_lds_dwordx4 %0, off offset:1024\n\t"
-                             "global_load_lds_dwordx4 %0, off offset:2048\n\tglobal_load_lds_dwordx4 %0, off offset:3072"
-                             : : "v"(ga), "s"(da) : "memory", "m0");
-                asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\t"
-                             "global_load_lds_dwordx4 %0, off\n\tglobal_load_lds_dwordx4 %0, off offset:1024\n\t"
-                             "global_load_lds_dwordx4 %0, off offset:2048\n\tglobal_load_lds_dwordx4 %0, off offset:3072"
-                             : : "v"(gb), "s"(db) : "memory", "m0");
-                return;
-            }
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const char* ga = reinterpret_cast<const char*>(dY + (int64_t)ids[j] * 256) + lane * 16;
-                asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" : : "v"(ga), "s"(da + 1024u * j) : "memory", "m0");
-            }
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const char* gb = reinterpret_cast<const char*>(X + (int64_t)ids[j] * 256) + lane * 16;
-                asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" : : "v"(gb), "s"(db + 1024u * j) : "memory", "m0");
-            }
-            return;
-        }
-        const char* ga = reinterpret_cast<const char*>(dY + row * 256) + lane * 16;
-        const char* gb = reinterpret_cast<const char*>(X + row * 256) + lane * 16;
-        asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\t"
-                     "global_load_lds_dwordx4 %0, off\n\tglobal_load_lds_dwordx4 %0, off offset:1024\n\t"
-                     "global_load_lds_dwordx4 %0, off offset:2048\n\tglobal_load_lds_dwordx4 %0, off offset:3072"
-                     : : "v"(ga), "s"(da) : "memory", "m0");
-        asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\t"
-                     "global_load_lds_dwordx4 %0, off\n\tglobal_load_lds_dwordx4 %0, off offset:1024\n\t"
-                     "global_load_lds_dwordx4 %0, off offset:2048\n\tglobal_load_lds_dwordx4 %0, off offset:3072"
-                     : : "v"(gb), "s"(db) : "memory", "m0");
-    };
-    // split the 16 values v[op][row] of feature tid and publish them
-    auto publish = [&](const float (&v)[2][16]) {
-#pragma unroll
-        for (int j = 0; j < 16; ++j) bsum += v[0][j];
-#pragma unroll
-        for (int op = 0; op < 2; ++op) {
-            const float inv = op == 0 ? iy : ix;
-#pragma unroll
-            for (int g = 0; g < 2; ++g) {
-                t_half8 hi, lo;
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    const float x = v[op][8 * g + j] * inv;
-                    const _Float16 h = (_Float16)x;
-                    hi[j] = h;
-                    lo[j] = (_Float16)(x - (float)h);
-                }
-                opbuf[op][0][g][tid] = hi;
-                opbuf[op][1][g][tid] = lo;
-            }
-        }
-    };
-    auto multiply = [&]() {
-        t_half8 ah[OT], al[OT], bh[IT], bl[IT];
-#pragma unroll
-        for (int a = 0; a < OT; ++a) {
-            ah[a] = opbuf[0][0][half][(wo * OT + a) * 32 + col];
-            al[a] = opbuf[0][1][half][(wo * OT + a) * 32 + col];
-        }
-#pragma unroll
-        for (int b = 0; b < IT; ++b) {
-            bh[b] = opbuf[1][0][half][(wi * IT + b) * 32 + col];
-            bl[b] = opbuf[1][1][half][(wi * IT + b) * 32 + col];
-        }
-#pragma unroll
-        for (int a = 0; a < OT; ++a)
-#pragma unroll
-            for (int b = 0; b < IT; ++b) {
-                acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[a], bh[b], acc[a][b], 0, 0, 0);
-                acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[a], bl[b], acc[a][b], 0, 0, 0);
-                acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[a], bh[b], acc[a][b], 0, 0, 0);
-            }
-    };
-    const int pre = full < W16S_STAGES - 1 ? full : W16S_STAGES - 1;
-    for (int t = 0; t < pre; ++t) { fetch_ids(t); stage(t); }
-    if (pre < full) fetch_ids(pre);
-    for (int t = 0; t < full; ++t) {
-        const int issued = (t + W16S_STAGES - 1 < full) ? t + W16S_STAGES - 1 : full;
-        const int ahead = issued - (t + 1);
-        if (ahead >= 2) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-        else if (ahead == 1) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        // A: step t has landed for everyone; everyone has fetched the operands of step t - 1 (opbuf and ring slot t - 1 are free)
-        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        if (t + W16S_STAGES - 1 < full) {
-            stage(t + W16S_STAGES - 1);
-            if (t + W16S_STAGES < full) fetch_ids(t + W16S_STAGES);      // (waited for at the next lgkmcnt(0): hidden behind this step)
-        }
-        const int slot = t % W16S_STAGES;
-        float v[2][16];
-#pragma unroll
-        for (int op = 0; op < 2; ++op)
-#pragma unroll
-            for (int j = 0; j < 16; ++j) v[op][j] = ring[slot][op][j][tid];
-        publish(v);
-        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");     // B: operands of step t published
-        multiply();
-    }
-    if (tail) {
-        float v[2][16];
-#pragma unroll
-        for (int j = 0; j < 16; ++j) {
-            const int64_t lrow = n0 + 16 * (int64_t)full + j;
-            const bool ok = lrow < n1;
-            const int64_t row = ok ? rows_at(rw, lrow) : 0;
-            v[0][j] = ok ? dY[row * 256 + tid] : 0.0f;
-            v[1][j] = ok ? X[row * 256 + tid] : 0.0f;
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");     // operands of the last full step fetched
-        publish(v);
-        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        multiply();
-    }
-    const float back = sy * sx;
-#pragma unroll
-    for (int a = 0; a < OT; ++a)
-#pragma unroll
-        for (int b = 0; b < IT; ++b) {
-            const int j = (wi * IT + b) * 32 + col;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int i = (wo * OT + a) * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-                atomicAdd(dW + (int64_t)i * ldw + j, acc[a][b][r] * back);
-            }
-        }
-    if (dbias) atomicAdd(dbias + tid, bsum);
-}
-
-// Round 4: the same product, SOFTWARE-PIPELINED.  In k_t_wgrad16c a step runs in phases - wait for the DMA, barrier, read the ring and
-// split (VALU + LDS), barrier, 48 MFMAs - and a wave issues in order: while it is feeding its 48 MFMAs into the matrix pipe (~1500
-// cycles) it converts nothing, and while it converts the pipe idles (MFMA busy 24 %, a step takes 2.0-2.7 us against 0.7 us of MFMA
-// issue).  Here the operands live in TWO buffers: the conversion of step t + 1 (ring -> split halves -> operand buffer (t + 1) & 1) is
+// SOFTWARE-PIPELINED (round 4).  Round 3's kernel ran a step in phases - wait for the DMA, barrier, read the ring and split (VALU +
+// LDS), barrier, 48 MFMAs - and a wave issues in order: while it was feeding its 48 MFMAs into the matrix pipe (~1500 cycles) it
+// converted nothing, and while it converted the pipe idled (MFMA busy 24 %, a step took 2.0-2.7 us against 0.7 us of MFMA issue).
+// Here the operands live in TWO buffers: the conversion of step t + 1 (ring -> split halves -> operand buffer (t + 1) & 1) is
 // written BETWEEN the MFMAs of step t in program order (sched_group_barrier: one MFMA, then a handful of VALU / LDS instructions),
 // the wait for the DMA of step t + 2 moves to the end of the step, and ONE barrier per step certifies all three hand-overs (operands
-// of t + 1 published, ring slot t + 1 consumed, step t + 2 landed).  LDS: 3 ring stages (96 KB) + 2 operand buffers (64 KB) = the same
-// 160 KB.  Same products in the same order per accumulator: the same partial sums as k_t_wgrad16c (DSN_WGRAD16=c keeps that kernel).
+// of t + 1 published, ring slot t + 1 consumed, step t + 2 landed).  LDS: 3 ring stages (96 KB) + 2 operand buffers (64 KB) = 160 KB.
+// Same products in the same order per accumulator as the unpipelined kernel had.
 #define W16D_STAGES 3
 __global__ void __launch_bounds__(256) k_t_wgrad16d(const float* __restrict__ dY, const float* __restrict__ sy_ptr,
                                                      const float* __restrict__ X, const float* __restrict__ sx_ptr, int64_t N,
-                                                     int rows_per_wg, float* __restrict__ dW, int ldw,
-                                                     float* __restrict__ dbias, Rows rw, float* __restrict__ part, WgradOps ops) {
+                                                     int rows_per_wg, Rows rw, float* __restrict__ part, WgradOps ops) {
     DSN_OWN_SIMD_T(4);
     constexpr int OT = 4, IT = 4, WI = 2;
     __shared__ __attribute__((aligned(16))) float ring[W16D_STAGES][2][16][256];
@@ -1219,9 +1019,13 @@ __global__ void __launch_bounds__(256) k_t_wgrad16d(const float* __restrict__ dY
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.0f;
     const unsigned ring_off = (unsigned)(uintptr_t)(__attribute__((address_space(3))) float*)&ring[0][0][0][0];
-    t_i32x4 ids = {0, 0, 0, 0};                          // listed rows: the wave's four row numbers of the next step to be staged
+    // listed rows: this wave's four row numbers of the NEXT step to be staged, fetched with ONE scalar load a step ahead (a plain
+    // global pointer gives vector loads + s_waitcnt vmcnt(0), which drains the DMA queue at every step)
+    t_i32x4 ids = {0, 0, 0, 0};
     auto fetch_ids = [&](int t) {
         if (!rw.list) return;
+        // (constant address space: the list is not written during this kernel, and only for loads from there does hipcc pick
+        //  s_load_dwordx4 and track the wait itself; 16-byte aligned: n0 and the list base are)
         ids = *reinterpret_cast<t_cptr4>((uintptr_t)(rw.list + (n0 + 16 * (int64_t)t + 4 * wave)));
     };
     // DMA of step t into ring slot t % 3: exactly 8 instructions per wave in every form (the vmcnt waits below count on it)
@@ -1232,6 +1036,8 @@ __global__ void __launch_bounds__(256) k_t_wgrad16d(const float* __restrict__ dY
         const unsigned db = ring_off + (unsigned)(((slot * 2 + 1) * 16 + 4 * wave) * 1024);
         int64_t r0 = row;
         if (rw.list) {
+            // listed rows: the wave's four rows of this step lie anywhere - one address per row; the LDS side advances by 1 KB per
+            // instruction; a run of four consecutive rows takes the one-address form
             if (ids[3] - ids[0] != 3) {
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
@@ -1399,37 +1205,21 @@ __global__ void __launch_bounds__(256) k_t_wgrad16d(const float* __restrict__ dY
         mfmas(ah, al, bh, bl);
     }
     }       // pairs
-    const float back = sy * sx;
-    if (part) {
-        // this workgroup's partial tile (unscaled) + its column sums, plain coalesced stores: k_t_wgrad_reduce adds the workgroups up in
-        // a fixed order (the 65 536 float atomics per workgroup this replaces cost 0.087 of the kernel's 0.22 ms, and their order - hence
-        // the rounding of every gradient - changed from run to run)
-        // (in the accumulators' own order - piece (wave, a, b, r / 4) = 64 lanes x 4 registers, one 1 KB store per wave-instruction;
-        //  k_t_wgrad_reduce knows where the four values of a lane belong)
-        float4* const mine = reinterpret_cast<float4*>(part + (size_t)blockIdx.x * W16_PART(256));
-#pragma unroll
-        for (int a = 0; a < OT; ++a)
-#pragma unroll
-            for (int b = 0; b < IT; ++b)
-#pragma unroll
-                for (int r4 = 0; r4 < 4; ++r4)
-                    mine[(((wave * OT + a) * IT + b) * 4 + r4) * 64 + lane] =
-                        make_float4(acc[a][b][4 * r4], acc[a][b][4 * r4 + 1], acc[a][b][4 * r4 + 2], acc[a][b][4 * r4 + 3]);
-        part[(size_t)blockIdx.x * W16_PART(256) + 256 * 256 + tid] = bsum;
-        return;
-    }
+    // this workgroup's partial tile (unscaled, in the LAST pair's units) + its column sums, plain coalesced stores: k_t_wgrad_reduce
+    // multiplies the scales back and adds the workgroups up in a fixed order (the 65 536 float atomics per workgroup this replaced cost
+    // 0.087 of the kernel's 0.22 ms, and their order - hence the rounding of every gradient - changed from run to run)
+    // (in the accumulators' own order - piece (wave, a, b, r / 4) = 64 lanes x 4 registers, one 1 KB store per wave-instruction;
+    //  k_t_wgrad_reduce knows where the four values of a lane belong)
+    float4* const mine = reinterpret_cast<float4*>(part + (size_t)blockIdx.x * W16_PART(256));
 #pragma unroll
     for (int a = 0; a < OT; ++a)
 #pragma unroll
-        for (int b = 0; b < IT; ++b) {
-            const int j = (wi * IT + b) * 32 + col;
+        for (int b = 0; b < IT; ++b)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int i = (wo * OT + a) * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-                atomicAdd(dW + (int64_t)i * ldw + j, acc[a][b][r] * back);
-            }
-        }
-    if (dbias) atomicAdd(dbias + tid, bsum);
+            for (int r4 = 0; r4 < 4; ++r4)
+                mine[(((wave * OT + a) * IT + b) * 4 + r4) * 64 + lane] =
+                    make_float4(acc[a][b][4 * r4], acc[a][b][4 * r4 + 1], acc[a][b][4 * r4 + 2], acc[a][b][4 * r4 + 3]);
+    part[(size_t)blockIdx.x * W16_PART(256) + 256 * 256 + tid] = bsum;
 }
 
 // Second stage of the split-fp16 weight-gradient products: dW[i][j] += back * sum over the workgroups g of part[g][i][j], in ascending g -
@@ -1518,8 +1308,7 @@ __global__ void __launch_bounds__(256) k_t_wgrad_reduce(const float* __restrict_
 #define W16P_STAGES 3
 __global__ void __launch_bounds__(256, 2) k_t_wgrad16p(const float* __restrict__ dY, const float* __restrict__ sy_ptr,
                                                         const float* __restrict__ X, const float* __restrict__ sx_ptr, int64_t N,
-                                                        int rows_per_wg, float* __restrict__ dW, int ldw, int in_valid,
-                                                        float* __restrict__ dbias, Rows rw, float* __restrict__ part, WgradOps ops) {
+                                                        int rows_per_wg, Rows rw, float* __restrict__ part, WgradOps ops) {
     // (no DSN_OWN_SIMD: K = 8 MFMAs only - see multiply())
     __shared__ __attribute__((aligned(16))) float ringY[W16P_STAGES][16][256];
     __shared__ __attribute__((aligned(16))) float ringX[W16P_STAGES][16][64];
@@ -1552,7 +1341,7 @@ __global__ void __launch_bounds__(256, 2) k_t_wgrad16p(const float* __restrict__
             for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.0f;
     const unsigned offY = (unsigned)(uintptr_t)(__attribute__((address_space(3))) float*)&ringY[0][0][0];
     const unsigned offX = (unsigned)(uintptr_t)(__attribute__((address_space(3))) float*)&ringX[0][0][0];
-    t_i32x4 ids = {0, 0, 0, 0};        // listed rows: this wave's four row numbers of the NEXT step (one scalar load, see k_t_wgrad16c)
+    t_i32x4 ids = {0, 0, 0, 0};        // listed rows: this wave's four row numbers of the NEXT step (one scalar load, see k_t_wgrad16d)
     auto fetch_ids = [&](int t) {
         if (!rw.list) return;
         ids = *reinterpret_cast<t_cptr4>((uintptr_t)(rw.list + (n0 + 16 * (int64_t)t + 4 * wave)));
@@ -1703,33 +1492,17 @@ __global__ void __launch_bounds__(256, 2) k_t_wgrad16p(const float* __restrict__
         multiply();
     }
     }       // pairs
-    const float back = sy * sx;
-    if (part) {      // two-stage form: see k_t_wgrad16d / k_t_wgrad_reduce
-        float4* const mine = reinterpret_cast<float4*>(part + (size_t)blockIdx.x * W16_PART(64));
-#pragma unroll
-        for (int a = 0; a < 2; ++a)
-#pragma unroll
-            for (int b = 0; b < 2; ++b)
-#pragma unroll
-                for (int r4 = 0; r4 < 4; ++r4)
-                    mine[(((wave * 2 + a) * 2 + b) * 4 + r4) * 64 + lane] =
-                        make_float4(acc[a][b][4 * r4], acc[a][b][4 * r4 + 1], acc[a][b][4 * r4 + 2], acc[a][b][4 * r4 + 3]);
-        part[(size_t)blockIdx.x * W16_PART(64) + 256 * 64 + tid] = bsum;
-        return;
-    }
+    // this workgroup's partial tile (unscaled) + its column sums: see k_t_wgrad16d / k_t_wgrad_reduce
+    float4* const mine = reinterpret_cast<float4*>(part + (size_t)blockIdx.x * W16_PART(64));
 #pragma unroll
     for (int a = 0; a < 2; ++a)
 #pragma unroll
-        for (int b = 0; b < 2; ++b) {
-            const int j = 32 * b + col;
-            if (j >= in_valid) continue;
+        for (int b = 0; b < 2; ++b)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int i = 64 * wave + 32 * a + (r & 3) + 8 * (r >> 2) + 4 * half;
-                atomicAdd(dW + (int64_t)i * ldw + j, acc[a][b][r] * back);
-            }
-        }
-    if (dbias) atomicAdd(dbias + tid, bsum);
+            for (int r4 = 0; r4 < 4; ++r4)
+                mine[(((wave * 2 + a) * 2 + b) * 4 + r4) * 64 + lane] =
+                    make_float4(acc[a][b][4 * r4], acc[a][b][4 * r4 + 1], acc[a][b][4 * r4 + 2], acc[a][b][4 * r4 + 3]);
+    part[(size_t)blockIdx.x * W16_PART(64) + 256 * 64 + tid] = bsum;
 }
 
 // The 128-row siblings for the lighting MLP and the colour head (round 6): dW[128, XW] += dY[N,128]^T X[N,XW] with
@@ -1773,7 +1546,7 @@ __global__ void __launch_bounds__(256, 1) k_t_wgrad16q(const float* __restrict__
         for (int r = 0; r < 16; ++r) acc[b][r] = 0.0f;
     const unsigned offY = (unsigned)(uintptr_t)(__attribute__((address_space(3))) float*)&ringY[0][0][0];
     const unsigned offX = (unsigned)(uintptr_t)(__attribute__((address_space(3))) float*)&ringX[0][0][0];
-    t_i32x4 ids = {0, 0, 0, 0};        // listed rows: this wave's four row numbers of the NEXT step (one scalar load, see k_t_wgrad16c)
+    t_i32x4 ids = {0, 0, 0, 0};        // listed rows: this wave's four row numbers of the NEXT step (one scalar load, see k_t_wgrad16d)
     auto fetch_ids = [&](int t) {
         if (!rw.list) return;
         ids = *reinterpret_cast<t_cptr4>((uintptr_t)(rw.list + (n0 + 16 * (int64_t)t + 4 * wave)));
@@ -1994,62 +1767,46 @@ void wgrad_mfma16q(int64_t N, const float* X, const float* sx, const float* dY, 
                        dbias);
 }
 
-// How the workgroups' partial products meet.  Default: two stages - every workgroup stores its tile into `part` (the training
-// workspace's W16_PART_GROUPS x W16_PART(256) floats), k_t_wgrad_reduce adds them in a fixed order: bit-reproducible gradients, and
-// 0.13 + 0.02 ms per 256 x 256 product instead of 0.22 (the 65 536 float atomics per workgroup were 40 % of the kernel).
-// DSN_WGRAD_REDUCE=atomic: round 1-3's atomicAdd epilogue (A/B switch).
-static bool wgrad_two_stage() {
-    static const bool v = [] { const char* e = getenv("DSN_WGRAD_REDUCE"); return !(e && e[0] == 'a'); }();
-    return v;
-}
+// How the workgroups' partial products meet: in two stages - every workgroup stores its tile into `part` (the training workspace's
+// W16_PART_GROUPS x W16_PART(256) floats, TrainWs::wg_part), k_t_wgrad_reduce adds them in a fixed order: bit-reproducible gradients,
+// and 0.13 + 0.02 ms per 256 x 256 product instead of the 0.22 of rounds 1-3's atomicAdd epilogue (its 65 536 float atomics per
+// workgroup were 40 % of the kernel).
 // A second operand pair (X2, sx2, dY2, sy2) of the same shape adds its product into the same accumulators - ONE launch, one partial
 // tile and one reduction for the two weight-gradient products of a layer (tangent pair first, adjoint pair second; the bias gradient
 // is the second pair's).  VERDICT r04 #3 (c): 12 + 4 launches -> 6 + 2, half the 64 MB partial bursts and half of k_t_wgrad_reduce.
 struct WgradPair { const float* X; const float* sx; const float* dY; const float* sy; };
 void wgrad_mfma16p(int64_t N, const float* X, const float* sx, const float* dY, const float* sy, float* dW, int ldw, int in_valid,
-                   hipStream_t st, float* dbias = nullptr, Rows rw = Rows{nullptr, nullptr}, float* part = nullptr,
+                   hipStream_t st, float* dbias, Rows rw, float* part,
                    WgradPair second = WgradPair{nullptr, nullptr, nullptr, nullptr}) {
     int groups = W16_PART_GROUPS;     // two workgroups per CU
     int rows = (int)((N + groups - 1) / groups);
     if (rows < 64) rows = 64;
     rows = (rows + 15) & ~15;
     groups = (int)((N + rows - 1) / rows);
-    if (!wgrad_two_stage()) part = nullptr;
-    hipLaunchKernelGGL(k_t_wgrad16p, dim3((unsigned)groups), dim3(256), 0, st, dY, sy, X, sx, N, rows, dW, ldw, in_valid, dbias, rw, part,
+    hipLaunchKernelGGL(k_t_wgrad16p, dim3((unsigned)groups), dim3(256), 0, st, dY, sy, X, sx, N, rows, rw, part,
                        WgradOps{second.dY, second.sy, second.X, second.sx, second.dY ? 2 : 1});
     const float* const ry = second.dY ? second.sy : sy;      // the partial tiles are in the LAST pair's units
     const float* const rx = second.dY ? second.sx : sx;
-    if (part)
-        hipLaunchKernelGGL(k_t_wgrad_reduce<64>, dim3(256 * 64 / 256), dim3(256), 0, st, (const float*)part, N, groups, rows, rw, ry, rx, dW, ldw,
-                           in_valid, dbias);
+    hipLaunchKernelGGL(k_t_wgrad_reduce<64>, dim3(256 * 64 / 256), dim3(256), 0, st, (const float*)part, N, groups, rows, rw, ry, rx, dW, ldw,
+                       in_valid, dbias);
 }
 
 // dW [256,256] (ldw) += dY[N,256]^T X[N,256], operands scaled by the device scalars sy / sx (NULL = O(1) operand);
 // dbias (optional) [256] += column sums of dY
 void wgrad_mfma16(int64_t N, const float* X, const float* sx, const float* dY, const float* sy, float* dW, int ldw, hipStream_t st,
-                  float* dbias = nullptr, Rows rw = Rows{nullptr, nullptr}, float* part = nullptr,
+                  float* dbias, Rows rw, float* part,
                   WgradPair second = WgradPair{nullptr, nullptr, nullptr, nullptr}) {
     int groups = 256;                 // one workgroup per CU, one round (with 512 the launch ran 0.33 instead of 0.28 ms)
     int rows = (int)((N + groups - 1) / groups);
     if (rows < 64) rows = 64;
     rows = (rows + 15) & ~15;
     groups = (int)((N + rows - 1) / rows);
-    static const bool old_kernel = [] { const char* e = getenv("DSN_WGRAD16"); return e && e[0] == 'c'; }();
-    if (old_kernel || !wgrad_two_stage()) part = nullptr;
-    if (old_kernel) {      // (round 3's kernel knows one pair: two launches)
-        hipLaunchKernelGGL(k_t_wgrad16c, dim3((unsigned)groups), dim3(256), 0, st, dY, sy, X, sx, N, rows, dW, ldw, second.dY ? nullptr : dbias, rw);
-        if (second.dY)
-            hipLaunchKernelGGL(k_t_wgrad16c, dim3((unsigned)groups), dim3(256), 0, st, second.dY, second.sy, second.X, second.sx, N, rows, dW, ldw,
-                               dbias, rw);
-        return;
-    }
-    hipLaunchKernelGGL(k_t_wgrad16d, dim3((unsigned)groups), dim3(256), 0, st, dY, sy, X, sx, N, rows, dW, ldw, dbias, rw, part,
+    hipLaunchKernelGGL(k_t_wgrad16d, dim3((unsigned)groups), dim3(256), 0, st, dY, sy, X, sx, N, rows, rw, part,
                        WgradOps{second.dY, second.sy, second.X, second.sx, second.dY ? 2 : 1});
     const float* const ry = second.dY ? second.sy : sy;
     const float* const rx = second.dY ? second.sx : sx;
-    if (part)
-        hipLaunchKernelGGL(k_t_wgrad_reduce<256>, dim3(256 * 256 / 256), dim3(256), 0, st, (const float*)part, N, groups, rows, rw, ry, rx, dW,
-                           ldw, 256, dbias);
+    hipLaunchKernelGGL(k_t_wgrad_reduce<256>, dim3(256 * 256 / 256), dim3(256), 0, st, (const float*)part, N, groups, rows, rw, ry, rx, dW,
+                       ldw, 256, dbias);
 }
 
 
@@ -2065,16 +1822,17 @@ void wgrad_mfma16(int64_t N, const float* X, const float* sx, const float* dY, c
 // from LDS (lanes = consecutive columns: conflict-free).  The accumulator layout puts 32 consecutive columns of one row in the
 // lanes of a half-wave, so every store instruction writes two full 128-byte row segments.
 // Epilogues: EPI_NONE; EPI_BIAS_RELU y = relu(y + bias[c]); EPI_MASK y = msrc[n,c] > 0 ? y : 0;
-//            EPI_SEED y = msrc[n,c] > 0 ? y + sc[n] wv[c] : 0   (the seed of the adjoint pass, what k_t_seed did on top of the GEMM)
+//            EPI_SEED y = relu pattern of (n,c) in the forward's records ? y + sc[n] wv[c] : 0   (the seed of the adjoint pass)
 // ------------------------------------------------------------------------------------------------------------
 enum { EPI_NONE = 0, EPI_BIAS_RELU = 1, EPI_MASK = 2, EPI_SEED = 3 };
 template <int K, int M, bool TRANS, int EPI>
 __global__ void __launch_bounds__(256, 1) k_t_lin(const float* __restrict__ X, const float* __restrict__ W, float* __restrict__ Y,
                                                   int64_t N, const float* __restrict__ bias_or_wv, const float* __restrict__ msrc,
                                                   const float* __restrict__ sc, Rows rw, const uint4* __restrict__ recs, int rec_layer) {
-    // recs / rec_layer (EPI_SEED, optional; round 6): the relu pattern of trunk layer `rec_layer` from the training forward's 224-byte
-    // records - [sample][half][layer] uint4, bit 15 - r of the 16-bit word of block t = accumulator register r (dsn_field16.hip) -
-    // instead of `msrc > 0`: 16 bytes per row and half in place of 512 (the pattern the tangent / adjoint kernels use anyway)
+    // recs / rec_layer (EPI_SEED; round 6): the relu pattern of trunk layer `rec_layer` from the training forward's 224-byte
+    // records - [sample][half][layer] uint4, bit 15 - r of the 16-bit word of block t = accumulator register r (dsn_field16.hip):
+    // 16 bytes per row and half in place of the 512 of an activation row (the pattern the tangent / adjoint kernels use anyway).
+    // msrc is EPI_MASK's alone.
     DSN_OWN_SIMD_T(16);
     constexpr int NT = M / 32, NQ = NT / 4;
     // B in LDS as [k][quad of column tiles][column in tile][tile in quad]: the 4 column tiles a lane feeds with one k come
@@ -2100,20 +1858,20 @@ __global__ void __launch_bounds__(256, 1) k_t_lin(const float* __restrict__ X, c
         const int64_t prow = crow;
         const float* xr = X + crow * K + 4 * half;
         // what the epilogue needs from memory is requested NOW and used after the products: its latency hides behind them
-        float4 mk[EPI == EPI_MASK || EPI == EPI_SEED ? NT : 1][4];
+        float4 mk[EPI == EPI_MASK ? NT : 1][4];
         float scn = 0.0f;
-        const bool by_rec = EPI == EPI_SEED && recs != nullptr;      // kernel-uniform
+        constexpr bool by_rec = EPI == EPI_SEED;
         uint4 rec = make_uint4(0u, 0u, 0u, 0u);
-        if (EPI == EPI_MASK || EPI == EPI_SEED) {
-            if (by_rec) rec = recs[((size_t)crow * 2 + half) * 7 + rec_layer];
-            else {
-                const float* mr = msrc + crow * M + 4 * half;
+        if (EPI == EPI_MASK) {
+            const float* mr = msrc + crow * M + 4 * half;
 #pragma unroll
-                for (int t = 0; t < NT; ++t)
+            for (int t = 0; t < NT; ++t)
 #pragma unroll
-                    for (int q = 0; q < 4; ++q) mk[t][q] = *reinterpret_cast<const float4*>(mr + 32 * t + 8 * q);
-            }
-            if (EPI == EPI_SEED) scn = sc[crow];
+                for (int q = 0; q < 4; ++q) mk[EPI == EPI_MASK ? t : 0][q] = *reinterpret_cast<const float4*>(mr + 32 * t + 8 * q);
+        }
+        if (EPI == EPI_SEED) {
+            rec = recs[((size_t)crow * 2 + half) * 7 + rec_layer];
+            scn = sc[crow];
         }
         t_f32x16 acc[NT];
 #pragma unroll
@@ -2156,8 +1914,8 @@ __global__ void __launch_bounds__(256, 1) k_t_lin(const float* __restrict__ X, c
                 for (int q = 0; q < 4; ++q) {
                     const int f0 = 32 * t + 8 * q + 4 * half;
                     float v[4] = {acc[t][4 * q], acc[t][4 * q + 1], acc[t][4 * q + 2], acc[t][4 * q + 3]};
-                    float m4[4] = {mk[EPI == EPI_MASK || EPI == EPI_SEED ? t : 0][q].x, mk[EPI == EPI_MASK || EPI == EPI_SEED ? t : 0][q].y,
-                                   mk[EPI == EPI_MASK || EPI == EPI_SEED ? t : 0][q].z, mk[EPI == EPI_MASK || EPI == EPI_SEED ? t : 0][q].w};
+                    const float4 m = mk[EPI == EPI_MASK ? t : 0][q];
+                    float m4[4] = {m.x, m.y, m.z, m.w};
                     if (by_rec) {
                         const uint32_t wd = (t >> 1) == 0 ? rec.x : ((t >> 1) == 1 ? rec.y : ((t >> 1) == 2 ? rec.z : rec.w));
                         const uint32_t pat = (wd >> (16 * (t & 1))) & 0xffffu;
@@ -2409,16 +2167,10 @@ TrainWs carve(void* base, int64_t N) {
     return w;
 }
 
-void colsum(const float* a, int C, int64_t N, float* out, hipStream_t st, Rows rw = Rows{nullptr, nullptr}) {
-    const int rows = 256;
-    hipLaunchKernelGGL(k_t_colsum, dim3((unsigned)((N + rows - 1) / rows)), dim3(T_THREADS), 0, st, a, C, N, rows, out, rw);
-}
-
 template <int OUT>
 void wcolsum(const float* X, int C, const float* dY, int64_t N, float* dW, float* db, hipStream_t st, Rows rw = Rows{nullptr, nullptr},
              const float* W = nullptr, float* dX = nullptr, float* gmax = nullptr) {
-    static const int rows_env = [] { const char* e = getenv("DSN_WCOLSUM_ROWS"); const int v = e ? atoi(e) : 0; return v >= 16 && v <= 4096 ? v : 0; }();
-    const int rows = rows_env ? rows_env : 512;      // (round 6: 256 -> 512 rows per block, -0.07 ms per step - the blocks' atomics, not the rows, were the cost; 1024: slower)
+    const int rows = 512;      // (round 6: 256 -> 512 rows per block, -0.07 ms per step - the blocks' atomics, not the rows, were the cost; 1024: slower)
     hipLaunchKernelGGL((k_t_wcolsum<OUT>), dim3((unsigned)((N + rows - 1) / rows)), dim3(T_THREADS), 0, st, X, C, dY, N, rows, dW, db, rw, W, dX,
                        (unsigned*)gmax);
 }
@@ -2446,10 +2198,9 @@ DsnTrainCache dsn_train_cache(void* workspace, int64_t N) {
 }
 
 // list <- ascending indices of the rows with flag != 0, *count <- their number (three small launches, deterministic)
-// DSN_TRAIN_ALL_ROWS=1 (tests / A-B runs): every row is listed - the dense evaluation of round 2
-static bool dsn_train_all_rows() { const char* e = getenv("DSN_TRAIN_ALL_ROWS"); return e && e[0] == '1'; }
+// (train_all_rows(): every row is listed)
 void dsn_train_build_rows(uint8_t* flag, int64_t N, int32_t* bcnt, int32_t* list, int32_t* count, hipStream_t st) {
-    if (dsn_train_all_rows()) (void)hipMemsetAsync(flag, 1, (size_t)N, st);
+    if (train_all_rows()) (void)hipMemsetAsync(flag, 1, (size_t)N, st);
     const int nb = (int)((N + T_THREADS - 1) / T_THREADS);
     hipLaunchKernelGGL(k_t_rows_count, dim3((unsigned)nb), dim3(T_THREADS), 0, st, (const uint8_t*)flag, N, bcnt);
     hipLaunchKernelGGL(k_t_rows_scan, dim3(1), dim3(1024), 0, st, bcnt, nb, count);
@@ -2529,13 +2280,12 @@ const char* dsn_train_run(const DsnSceneView& s, const float* packed, const floa
 
     // ---- adjoint of compositing and of the colour product ------------------------------------------------------
     if (!module) {
-        // one wave per ray for S <= 128 (round 6); DSN_TRAIN_COMPOSITE_ADJOINT=thread keeps the one-thread-per-ray form (A/B, cross-check)
-        static const bool per_thread = [] { const char* e = getenv("DSN_TRAIN_COMPOSITE_ADJOINT"); return e && e[0] == 't'; }();
+        // one wave per ray for S <= 128 (round 6), one thread per ray above
         const dim3 wg((unsigned)((R + T_THREADS / 64 - 1) / (T_THREADS / 64)));
-        if (!per_thread && S <= 64)
+        if (S <= 64)
             hipLaunchKernelGGL(k_t_composite_adjoint_w<1>, wg, dim3(T_THREADS), 0, st, w.col, w.sig, w.transparent, z_vals, ray_d, noise, R, S,
                                d_rgb, d_disp, d_acc, d_depth, d_weights, w.d_col, w.d_sig, w.live);
-        else if (!per_thread && S <= 128)
+        else if (S <= 128)
             hipLaunchKernelGGL(k_t_composite_adjoint_w<2>, wg, dim3(T_THREADS), 0, st, w.col, w.sig, w.transparent, z_vals, ray_d, noise, R, S,
                                d_rgb, d_disp, d_acc, d_depth, d_weights, w.d_col, w.d_sig, w.live);
         else
@@ -2547,13 +2297,13 @@ const char* dsn_train_run(const DsnSceneView& s, const float* packed, const floa
     if (module) hipLaunchKernelGGL(k_t_flag_cotangent, grid_for(N64), dim3(T_THREADS), 0, st, d_col, d_sig, N64, w.live);
     dsn_train_build_rows(w.live, N64, w.bcnt, w.list2, w.rowcnt + 1, st);
     const Rows R2 = {w.list2, w.rowcnt + 1};
-    // (the encoding of the backward's rows is written by k_t_pe_tangent below, beside its tangent; DSN_TRAIN_UNFUSED_HEADS=1: by k_t_pe here)
-    static const bool two_pass_heads = [] { const char* e = getenv("DSN_TRAIN_UNFUSED_HEADS"); return e && e[0] == '1'; }();
-    static const bool heads_fp32 = [] { const char* e = getenv("DSN_TRAIN_HEADS"); return e && e[0] == 'f'; }();
-    const bool heads16 = !heads_fp32 && !two_pass_heads;      // (the scales ride in the fused sweeps)
+    const TrainSwitches& sw = train_switches();
+    const bool heads16 = !sw.two_pass_heads;       // the heads' products on the split-fp16 kernels (their scales ride in the fused sweeps)
+    const bool lin16_ = heads16 && !sw.lin_fp32;   // ... and their two data-gradient products
     float* const g_dhl2 = w.small + 304;      // batch-wide max |d_hl2|, |d_rr| (float bits; zeroed with w.small)
     float* const g_drr = w.small + 305;
-    if (two_pass_heads) hipLaunchKernelGGL(k_t_pe, grid_for(N64 * PE_LD), dim3(T_THREADS), 0, st, w.x_c, N64, w.pe, R2);
+    // (the encoding of the backward's rows is written by k_t_pe_tangent below, beside its tangent; two_pass_heads: by k_t_pe here)
+    if (sw.two_pass_heads) hipLaunchKernelGGL(k_t_pe, grid_for(N64 * PE_LD), dim3(T_THREADS), 0, st, w.x_c, N64, w.pe, R2);
     hipLaunchKernelGGL(k_t_colour_adjoint, grid_for(N64), dim3(T_THREADS), 0, st, d_col, w.ess, w.wl, w.pre, N64, w.d_ess,
                        w.d_pre, R2);
     // Two chains that do not depend on each other hang off this point (round 6): T - the lighting MLP's backward, u = dL/dg, the PE
@@ -2562,8 +2312,7 @@ const char* dsn_train_run(const DsnSceneView& s, const float* packed, const floa
     // stream + two events, fork here, join in front of the weight-gradient products) chain A runs beside chain T.  Same kernels, same
     // arguments, same values; the only shared scratch - the partial tiles of the two 128-row products - is given a place of its own
     // (three adjoint layers' arrays, which k_adjoint16 fills later on the same stream).  Without aux: one stream, as before.
-    static const bool pairs_ = [] { const char* e = getenv("DSN_WGRAD_PAIRS"); return !(e && e[0] == '0'); }();
-    const bool two = aux && aux->stream && aux->fork && aux->join && pairs_ && heads16 && N64 >= 4096;
+    const bool two = aux && aux->stream && aux->fork && aux->join && sw.pairs && heads16 && N64 >= 4096;
     hipStream_t sa = st;
     if (two) {
         sa = aux->stream;
@@ -2572,20 +2321,19 @@ const char* dsn_train_run(const DsnSceneView& s, const float* packed, const floa
     float* const part_a = two ? w.an[3] : w.wg_part;      // (3 KB per row: an[3 .. 5], contiguous; a 128 x 256 tile per workgroup needs 2.1 KB per row at most)
 
     // ---- lighting MLP backward -----------------------------------------------------------------------------------
-    // (the heads' weight gradients and the data gradients behind their relus in ONE sweep over hl2 / rr; DSN_TRAIN_UNFUSED_HEADS=1: two)
-    if (two_pass_heads) {
+    // (the heads' weight gradients and the data gradients behind their relus in ONE sweep over hl2 / rr; two_pass_heads: two)
+    if (!sw.two_pass_heads)
+        wcolsum<1>(w.hl2, 128, w.d_pre, N64, grd[P_L4_W], grd[P_L4_B], st, R2, prm[P_L4_W], w.d_hl2, g_dhl2);
+    else {
         wcolsum<1>(w.hl2, 128, w.d_pre, N64, grd[P_L4_W], grd[P_L4_B], st, R2);
         hipLaunchKernelGGL(k_t_seed, grid_for((N64 * 128) / 4), dim3(T_THREADS), 0, st, w.hl2, prm[P_L4_W], w.d_pre, nullptr, 128, N64 * 128,
                            w.d_hl2, R2);
-    } else
-        wcolsum<1>(w.hl2, 128, w.d_pre, N64, grd[P_L4_W], grd[P_L4_B], st, R2, prm[P_L4_W], w.d_hl2, g_dhl2);
+    }
     // (round 6: the 128-wide products of the lighting MLP and the colour head on the split-fp16 kernel k_t_wgrad16q - scales: the batch-wide
-    //  magnitudes the sweeps above leave; DSN_TRAIN_HEADS=fp32 keeps the exact-fp32 MFMA kernel, A/B and cross-check)
+    //  magnitudes the fused sweeps leave; without them (two_pass_heads) the exact-fp32 MFMA kernel)
     if (heads16) wgrad_mfma16q<128>(N64, w.hl1, nullptr, w.d_hl2, g_dhl2, grd[P_L2_W], 128, st, grd[P_L2_B], R2, w.wg_part);
     else T_CHECK(wgrad_mfma(N64, 128, 128, 128, w.hl1, 128, w.d_hl2, 128, grd[P_L2_W], 128, st, grd[P_L2_B], R2));
-    // (round 6: the two data-gradient products of the heads on the split-fp16 kernel k_t_lin16; DSN_TRAIN_LIN=fp32 keeps k_t_lin, A/B and cross-check)
-    static const bool lin_fp32 = [] { const char* e = getenv("DSN_TRAIN_LIN"); return e && e[0] == 'f'; }();
-    const bool lin16_ = heads16 && !lin_fp32;
+    // (round 6: the two data-gradient products of the heads on the split-fp16 kernel k_t_lin16; lin_fp32 / two_pass_heads: k_t_lin)
     if (lin16_) lin16<128, 128, EPI_MASK>(w.d_hl2, prm[P_L2_W], w.d_hl1, N64, nullptr, w.hl1, nullptr, st, R2);   // d_hl1 = (hl1 > 0) (d_hl2 W2)
     else lin<128, 128, false, EPI_MASK>(w.d_hl2, prm[P_L2_W], w.d_hl1, N64, nullptr, w.hl1, nullptr, st, R2);
     // (the first lighting layer keeps its two passes over d_hl1: a VALU kernel that also accumulates dW0 takes 0.39 ms against
@@ -2604,7 +2352,7 @@ const char* dsn_train_run(const DsnSceneView& s, const float* packed, const floa
     {
         const int64_t nb = (N64 * PE_LD + T_THREADS - 1) / T_THREADS;
         hipLaunchKernelGGL(k_t_pe_tangent, dim3((unsigned)(nb < 4096 ? nb : 4096)), dim3(T_THREADS), 0, st, w.x_c, w.u, N64, w.tpe,
-                           (unsigned*)g_tpe, R2, two_pass_heads ? nullptr : w.pe);
+                           (unsigned*)g_tpe, R2, sw.two_pass_heads ? nullptr : w.pe);
     }
     // all seven tangent layers in one fused split-fp16 launch (k_tangent16, relu patterns from the training forward's records),
     // then the weight-gradient products  dW_l += a_l^T hdot_{l-1}
@@ -2612,40 +2360,36 @@ const char* dsn_train_run(const DsnSceneView& s, const float* packed, const floa
     float* const g_adj = w.small + 301;
     int32_t* const range_cnt = (int32_t*)(w.small + 303);      // samples whose tangent / adjoint left the fp16 range (zeroed with w.small)
     // (round 6: the last layer's tangent is only ever summed over the rows - d (w_d . hdot_6) / d w_d - so k_tangent16 sums it itself
-    //  and does not store it; DSN_TRAIN_COLSUM6=kernel keeps the stored layer + k_t_colsum, A/B and cross-check)
-    static const bool colsum6_apart = [] { const char* e = getenv("DSN_TRAIN_COLSUM6"); return e && e[0] == 'k'; }();
-    dsn_launch_tangent16(packed, w.x_c, w.u, N64, w.masks, w.tn[0], g_tan, st, range_cnt, R2.list, R2.cnt, colsum6_apart ? nullptr : grd[P_DEN_W]);
-    // DSN_WGRAD_PAIRS=0 (A/B, cross-check): rounds 1-4's form - a launch per product, the adjoints written over the tangent arrays
-    static const bool pairs = [] { const char* e = getenv("DSN_WGRAD_PAIRS"); return !(e && e[0] == '0'); }();
-    if (!pairs) {
+    //  into the density head's weight gradient and does not store it: w.tn[6] is carved but neither written nor read)
+    dsn_launch_tangent16(packed, w.x_c, w.u, N64, w.masks, w.tn[0], g_tan, st, range_cnt, R2.list, R2.cnt, grd[P_DEN_W]);
+    // (default: the products  dW_l += a_l^T hdot_{l-1}  wait for the adjoint pass and run in ONE launch per layer with  ahat_l^T h_{l-1};
+    //  !pairs: rounds 1-4's form - a launch per product, here and below, the adjoints written over the tangent arrays)
+    if (!sw.pairs) {
         wgrad_mfma16p(N64, w.tpe, g_tpe, w.ap[0], nullptr, grd[P_S1_0W] + W0_PE_COL, 87, PE_K, st, nullptr, R2, w.wg_part);
         for (int l = 1; l < 7; ++l)
             wgrad_mfma16(N64, w.tn[l - 1], g_tan, w.ap[l], nullptr, grd[kTrunkW[l]], kTrunkLd[l], st, nullptr, R2, w.wg_part);
         wgrad_mfma16p(N64, w.tpe, g_tpe, w.ap[4], nullptr, grd[P_S2_0W] + W4_PE_COL, 319, PE_K, st, nullptr, R2, w.wg_part);
     }
-    // (default: the products  dW_l += a_l^T hdot_{l-1}  wait for the adjoint pass and run in ONE launch per layer with  ahat_l^T h_{l-1})
-    if (colsum6_apart) colsum(w.tn[6], 256, N64, grd[P_DEN_W], st, R2);   // d (w_d . hdot_6) / d w_d
     float* cur = w.t0;
 
     // ---- adjoint pass of dL/dsigma * sigma + dL/dessence . essence ---------------------------------------------
-    if (two_pass_heads) {
+    if (!sw.two_pass_heads)
+        wcolsum<3>(w.rr, 128, w.d_ess, N64, grd[P_RGB3_W], grd[P_RGB3_B], sa, R2, prm[P_RGB3_W], w.d_rr, g_drr);
+    else {
         wcolsum<3>(w.rr, 128, w.d_ess, N64, grd[P_RGB3_W], grd[P_RGB3_B], st, R2);
         hipLaunchKernelGGL(k_t_rgb_hidden_adjoint, grid_for((N64 * 128) / 4), dim3(T_THREADS), 0, st, w.d_ess, prm[P_RGB3_W], w.rr, N64 * 128,
                            w.d_rr, R2);
-    } else
-        wcolsum<3>(w.rr, 128, w.d_ess, N64, grd[P_RGB3_W], grd[P_RGB3_B], sa, R2, prm[P_RGB3_W], w.d_rr, g_drr);
+    }
     if (heads16) wgrad_mfma16q<256>(N64, w.h[6], nullptr, w.d_rr, g_drr, grd[P_RGB1_W], 256, sa, grd[P_RGB1_B], R2, part_a);
     else T_CHECK(wgrad_mfma(N64, 256, 256, 128, w.h[6], 256, w.d_rr, 128, grd[P_RGB1_W], 256, st, grd[P_RGB1_B], R2));
     wcolsum<1>(w.h[6], 256, d_sig, N64, grd[P_DEN_W], grd[P_DEN_B], sa, R2);
     // cur = ahat_6 = (h6 > 0) (d_rr W_rgb1 + d_sig w_den): the colour head's data gradient with the density head's seed fused in
-    // (round 6: the relu pattern of layer 6 from the forward's records - 32 bytes per row instead of the 1 KB row of h_6;
-    //  DSN_TRAIN_SEED_MASK=h keeps the `h_6 > 0` form, A/B and cross-check)
-    static const bool seed_by_h = [] { const char* e = getenv("DSN_TRAIN_SEED_MASK"); return e && e[0] == 'h'; }();
-    if (lin16_ && !seed_by_h) lin16<128, 256, EPI_SEED>(w.d_rr, prm[P_RGB1_W], cur, N64, prm[P_DEN_W], nullptr, d_sig, sa, R2, w.masks, 6);   // (pattern from the records only)
-    else lin<128, 256, false, EPI_SEED>(w.d_rr, prm[P_RGB1_W], cur, N64, prm[P_DEN_W], w.h[6], d_sig, sa, R2, seed_by_h ? nullptr : w.masks, 6);
+    // (round 6: the relu pattern of layer 6 from the forward's records - 32 bytes per row instead of the 1 KB row of h_6)
+    if (lin16_) lin16<128, 256, EPI_SEED>(w.d_rr, prm[P_RGB1_W], cur, N64, prm[P_DEN_W], nullptr, d_sig, sa, R2, w.masks, 6);
+    else lin<128, 256, false, EPI_SEED>(w.d_rr, prm[P_RGB1_W], cur, N64, prm[P_DEN_W], nullptr, d_sig, sa, R2, w.masks, 6);
     // cur = ahat_6.  The layers below it in one fused split-fp16 launch (k_adjoint16 -> ahat_5 ... ahat_0 in the buffers the
     // tangent products are done with), then  dW_l += ahat_l^T h_{l-1}  and the bias gradients (column sums)
-    float* const* an = pairs ? w.an : w.tn;
+    float* const* an = sw.pairs ? w.an : w.tn;
     dsn_launch_adjoint16(packed, N64, w.masks, cur, an[0], g_adj, sa, range_cnt, R2.list, R2.cnt);
     if (two && (hipEventRecord(aux->join, sa) != hipSuccess || hipStreamWaitEvent(st, aux->join, 0) != hipSuccess)) return "join of the auxiliary stream";
     // The first layer's product FIRST (the order of the products is free: every one has outputs of its own): what hangs on its bias
@@ -2653,7 +2397,7 @@ const char* dsn_train_run(const DsnSceneView& s, const float* packed, const floa
     // pose_mlp: 0.05 ms of an idle chip at the end of the step until the last session of round 6) - then runs on the auxiliary stream
     // beside the other seven products and is joined behind them.
     // (the bias gradient of stage1.0 = column sums of ahat_0 rides along into w.small[0..255])
-    if (pairs)
+    if (sw.pairs)
         wgrad_mfma16p(N64, w.tpe, g_tpe, w.ap[0], nullptr, grd[kTrunkW[0]] + W0_PE_COL, 87, PE_K, st, w.small, R2, w.wg_part,
                       WgradPair{w.pe, nullptr, an[0], g_adj});
     else
@@ -2682,7 +2426,7 @@ const char* dsn_train_run(const DsnSceneView& s, const float* packed, const floa
     }
     for (int l = 6; l >= 1; --l) {
         const float* A = l == 6 ? cur : an[l];
-        if (pairs) {
+        if (sw.pairs) {
             // tangent pair (a_l, hdot_{l-1}) first, adjoint pair (ahat_l, h_{l-1}) second: one launch, one reduction
             wgrad_mfma16(N64, w.tn[l - 1], g_tan, w.ap[l], nullptr, grd[kTrunkW[l]], kTrunkLd[l], st, grd[kTrunkB[l]], R2, w.wg_part,
                          WgradPair{w.h[l - 1], nullptr, A, g_adj});

@@ -9,7 +9,7 @@ import torch
 HERE = os.path.dirname(os.path.abspath(__file__))
 for q in (os.path.join(os.path.dirname(HERE), "oracle"), os.path.dirname(HERE), HERE):      # (what tests/conftest.py puts on the path)
     sys.path.insert(0, q)
-from helpers import load                                          # noqa: E402
+from row_cotangents import load_case as load                     # noqa: E402  (also rebuilds the compact S > 64 cases)
 from test_gpu_render import make_batch, make_renderer            # noqa: E402
 from test_gpu_train import reference_loss                         # noqa: E402
 
