@@ -22,6 +22,7 @@ class RayParallel:
         # rank on every call: 8 synchronous host-to-device copies per frame at 8 ranks)
         self._plans = {}
         self.plan_builds = 0           # how many plans were built (tests: a second call must not build - or upload - anything)
+        self._cuts = {}                # render_blocks: cuts per ("token", token, R) and, without a cost, per ("equal", R)
 
     def _group_device(self):
         """the device collectives of this group run on: the CPU for gloo, the current CUDA device for nccl (= RCCL)"""
@@ -184,21 +185,28 @@ class RayParallel:
         dist.broadcast(t, src=dist.get_global_rank(self.group, 0) if self.group is not None else 0, group=self.group)
         return [int(b) for b in t.cpu()]
 
-    def render_blocks(self, render_fn, ray_o, ray_d, near, far, cost=None):
+    def render_blocks(self, render_fn, ray_o, ray_d, near, far, cost=None, token=None):
         """like render(), with contiguous blocks cut for equal cost (cost [R]: any per-ray estimate, e.g. the evaluated samples of a
         previous frame of the sequence; None = equal ray counts).  The ranks need NOT pass identical costs: rank 0's cuts are
-        broadcast (one small collective per NEW cost - the cuts of a cost tensor seen before, same object and same
-        version, are reused, so a sequence rendered with one estimate pays for it once)."""
+        broadcast - one small collective on EVERY call that brings a cost.  Whether a collective is posted must be the
+        same decision on every rank, so it depends on nothing a single rank could see differently: not on the identity, the version
+        or the values of its own cost tensor (a rank that re-passed one object while its peer passed a new tensor per call used to
+        skip the broadcast the peer entered).  A sequence rendered with one estimate skips the broadcast by naming the cuts:
+        `token` (any hashable, not None; the CALLER guarantees every rank passes the same token on the same call) reuses the cuts
+        agreed under that token for this R, without a collective and without looking at `cost`; a token seen for the first time
+        agrees on cuts as usual and remembers them - per (token, R), for the life of this object, so alternating tokens costs
+        nothing.  Without a cost and without a token the equal-count cuts are a function of R alone and kept per R."""
         R = ray_o.shape[0]
-        key = None if cost is None else (id(cost), getattr(cost, "_version", None), R)
-        cached = getattr(self, "_agreed", None)
-        if cached is not None and cached[0] == key and cached[1] == R:
-            bounds = cached[2]
-        else:
+        cuts = self._cuts
+        key = ("token", token, R) if token is not None else (("equal", R) if cost is None else None)
+        bounds = cuts.get(key) if key is not None else None
+        if bounds is None:
             bounds = self.balanced_bounds(torch.ones(R) if cost is None else cost, self.world)
             if cost is not None:                     # (equal ray counts are a function of R and the world size alone)
                 bounds = self.agreed_bounds(bounds)
-            self._agreed = (key, R, bounds)
+            if key is not None:
+                cuts[key] = bounds
+        self._agreed = (token, R, bounds)            # (the cuts of the last call: tests read them)
         return self.render_partitioned(render_fn, ray_o, ray_d, near, far, self.block_plan(R, bounds, ray_o.device))
 
     def render_partitioned(self, render_fn, ray_o, ray_d, near, far, plan: dict):

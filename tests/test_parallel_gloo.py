@@ -50,15 +50,36 @@ def _worker(rank, world, port, R, q):
     rp.render_blocks(_fake_render, o, d, n, f, cost=None)
     ok = ok and rp.plan_builds == builds
     # ranks that bring DIFFERENT costs (each measured its own) still exchange matching slabs: rank 0's cuts are broadcast inside
-    # render_blocks; the same cost object a second time costs no collective and no plan
+    # render_blocks on EVERY call that brings a cost - whether a collective is posted may not depend on anything one
+    # rank sees differently.  Only a caller-supplied token that is the same on every rank reuses cuts: the same token a second time
+    # costs no collective and no plan, whatever cost comes with it
+    casts = {"n": 0}
+    agreed = rp.agreed_bounds
+    rp.agreed_bounds = lambda b: (casts.__setitem__("n", casts["n"] + 1), agreed(b))[1]
     mine = torch.arange(R).float() * (1.0 + 3.0 * rank) + (R - torch.arange(R)).float() * (3.0 - 2.0 * rank)
     out4 = rp.render_blocks(_fake_render, o, d, n, f, cost=mine)
     ok = ok and all(torch.equal(out4[k], ref[k]) for k in ref)
     want = rp.balanced_bounds(torch.arange(R).float() + (R - torch.arange(R)).float() * 3.0, world)      # rank 0's cost
-    ok = ok and rp._agreed[2] == want
+    ok = ok and rp._agreed[2] == want and casts["n"] == 1
     builds = rp.plan_builds
     rp.render_blocks(_fake_render, o, d, n, f, cost=mine)
-    ok = ok and rp.plan_builds == builds
+    ok = ok and rp.plan_builds == builds and casts["n"] == 2       # (the same object again: the same cuts, hence no plan - but a broadcast)
+    out5 = rp.render_blocks(_fake_render, o, d, n, f, cost=mine, token="seq0")
+    ok = ok and rp.plan_builds == builds and casts["n"] == 3       # (a token seen for the first time agrees on cuts as usual)
+    out6 = rp.render_blocks(_fake_render, o, d, n, f, cost=mine.flip(0) if rank else mine, token="seq0")
+    ok = ok and rp.plan_builds == builds and casts["n"] == 3 and rp._agreed[2] == want
+    ok = ok and all(torch.equal(out5[k], ref[k]) and torch.equal(out6[k], ref[k]) for k in ref)
+    rp.render_blocks(_fake_render, o, d, n, f, cost=mine, token="seq1")
+    ok = ok and casts["n"] == 4                                    # (another token: agreed anew)
+    rp.render_blocks(_fake_render, o, d, n, f, cost=mine, token="seq0")
+    ok = ok and casts["n"] == 4 and rp._agreed[2] == want          # (back to the first token: its cuts are still there)
+    calls = {"n": 0}
+    balanced = rp.balanced_bounds
+    rp.balanced_bounds = lambda *a, **k: (calls.__setitem__("n", calls["n"] + 1), balanced(*a, **k))[1]
+    rp.render_blocks(_fake_render, o, d, n, f, cost=None)
+    ok = ok and calls["n"] == 0 and casts["n"] == 4               # (equal counts: cut once per R, no collective ever)
+    rp.balanced_bounds = balanced
+    rp.agreed_bounds = agreed
     # (measured re-balancing: the block that took twice as long gives rays away)
     if R >= 8:
         b0 = rp.balanced_bounds(torch.ones(R), 2, align=1)
@@ -67,6 +88,73 @@ def _worker(rank, world, port, R, q):
     q.put((rank, s, e, ok))
     dist.barrier()
     dist.destroy_process_group()
+
+
+def _cost_identity_worker(rank, world, port, R, q):
+    """four render_blocks calls: rank 0 re-passes ONE cost object, rank 1 a new tensor per call (twice rank 0's values, twice others)"""
+    from datetime import timedelta
+    os.environ["MASTER_ADDR"] = "127.0.0.1"
+    os.environ["MASTER_PORT"] = str(port)
+    dist.init_process_group("gloo", rank=rank, world_size=world, timeout=timedelta(seconds=30))      # (a mismatch raises, not hangs)
+    import importlib.util
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("par", os.path.join(root, "dual-space-nerf_amd", "parallel.py"))
+    par = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(par)
+    g = torch.Generator().manual_seed(11)
+    o, d = torch.randn(R, 3, generator=g), torch.randn(R, 3, generator=g)
+    n, f = torch.rand(R, generator=g), torch.rand(R, generator=g) + 1
+    ref = _fake_render(o, d, n, f)                                   # the single-process frame
+    rp = par.RayParallel()
+    base = torch.arange(R).float() ** 2 + 0.1
+    kept = base.clone()
+    oks, cuts, err = [], [], None
+    try:
+        for call in range(4):
+            if rank == 0:
+                cost = kept
+            else:                                                    # a NEW tensor on every call
+                cost = base.clone() if call < 2 else (base.flip(0) * (call + 1.0) + float(call))
+            out = rp.render_blocks(_fake_render, o, d, n, f, cost=cost)
+            oks.append(all(torch.equal(out[k], ref[k]) for k in ref))
+            cuts.append(list(rp._agreed[2]))
+        dist.barrier()
+    except Exception as e:                                           # noqa: BLE001 - reported to the parent, which fails the test
+        err = "%s: %s" % (type(e).__name__, str(e)[:300])
+    q.put((rank, oks, cuts, err))
+    if err is None:
+        dist.destroy_process_group()
+
+
+def test_render_blocks_posts_the_same_collectives_whatever_cost_objects_the_ranks_pass():
+    """Whether render_blocks posts its broadcast must be the same decision on every rank.  Rank 0 passes one cost object on all four
+    calls, rank 1 a new tensor per call - twice with rank 0's values, twice with others.  Every call returns the single-process frame
+    on both ranks, cut where RANK 0's cost says, and both processes join.  (Cuts cached under the identity and version of the rank's
+    own cost made rank 0 skip the second call's broadcast while rank 1 entered it: both died in gloo's send / recv timeout - over
+    RCCL the same mismatch is a hang.  Host only, by design: a test of mismatched collectives never runs on a GPU.)"""
+    R, world = 200, 2
+    with socket.socket() as s:
+        s.bind(("127.0.0.1", 0))
+        port = s.getsockname()[1]
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    procs = [ctx.Process(target=_cost_identity_worker, args=(r, world, port, R, q)) for r in range(world)]
+    for p in procs:
+        p.start()
+    res = sorted(q.get(timeout=120) for _ in range(world))
+    for p in procs:
+        p.join(timeout=60)
+        assert p.exitcode == 0
+    import importlib.util
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("par", os.path.join(root, "dual-space-nerf_amd", "parallel.py"))
+    par = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(par)
+    want = par.RayParallel.balanced_bounds(torch.arange(R).float() ** 2 + 0.1, world)
+    for rank, oks, cuts, err in res:
+        assert err is None, "rank %d: %s" % (rank, err)
+        assert oks == [True] * 4, "rank %d: calls that returned the single-process frame: %s" % (rank, oks)
+        assert cuts == [want] * 4, "rank %d cut at %s, rank 0's cost cuts at %s" % (rank, cuts, want)
 
 
 @pytest.mark.parametrize("R", [10, 7, 1, 200])
