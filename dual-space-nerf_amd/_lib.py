@@ -53,6 +53,8 @@ EXPORTS = [
     "dsn_mesh_simplify_workspace_bytes", "dsn_mesh_simplify_count", "dsn_mesh_simplify_emit", "dsn_mesh_simplify_cells",
     "dsn_mesh_simplify_count_ex", "dsn_mesh_simplify_emit_ex",
     "dsn_mesh_smooth_workspace_bytes", "dsn_mesh_smooth", "dsn_mesh_smooth_ex", "dsn_mesh_vertex_normals", "dsn_mesh_vertex_normals_ex",
+    "dsn_mesh_dist_workspace_bytes", "dsn_mesh_dist_grid_host", "dsn_mesh_dist_build", "dsn_mesh_dist_query",
+    "dsn_mesh_dist_reduce_workspace_bytes", "dsn_mesh_dist_reduce", "dsn_mesh_sample_workspace_bytes", "dsn_mesh_sample_surface",
     "dsn_train_loss_workspace_bytes", "dsn_train_loss", "dsn_train_loss_grad",
     "dsn_grid_hier_workspace_bytes", "dsn_grid_hier_mark", "dsn_grid_hier_list", "dsn_grid_hier_assemble",
     "dsn_density_points_workspace_bytes", "dsn_density_points",
@@ -184,6 +186,19 @@ def lib():
         L.dsn_mesh_smooth_ex.argtypes = sm + [C.c_int, C.c_void_p]
         L.dsn_mesh_vertex_normals.argtypes = sm_normals + [C.c_void_p]
         L.dsn_mesh_vertex_normals_ex.argtypes = sm_normals + [C.c_int, C.c_void_p]
+        L.dsn_mesh_dist_workspace_bytes.restype = C.c_size_t
+        L.dsn_mesh_dist_workspace_bytes.argtypes = [C.c_int64, C.c_int64]
+        L.dsn_mesh_dist_grid_host.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.dsn_mesh_dist_build.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        L.dsn_mesh_dist_query.argtypes = ([C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int64]
+                                          + [C.c_void_p] * 4)
+        L.dsn_mesh_dist_reduce_workspace_bytes.restype = C.c_size_t
+        L.dsn_mesh_dist_reduce_workspace_bytes.argtypes = [C.c_int64]
+        L.dsn_mesh_dist_reduce.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        L.dsn_mesh_sample_workspace_bytes.restype = C.c_size_t
+        L.dsn_mesh_sample_workspace_bytes.argtypes = [C.c_int64]
+        L.dsn_mesh_sample_surface.argtypes = ([C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_uint64, C.c_int64, C.c_void_p, C.c_size_t]
+                                              + [C.c_void_p] * 3)
         L.dsn_train_loss_workspace_bytes.restype = C.c_size_t
         L.dsn_train_loss_workspace_bytes.argtypes = [C.c_int64]
         L.dsn_train_loss.argtypes = [C.c_void_p] * 6 + [C.c_int64, C.c_int, C.c_int] + [C.c_void_p] * 3
@@ -1251,6 +1266,112 @@ def mesh_vertex_normals(verts, faces, phases=0, state=None):
     _check(lib().dsn_mesh_vertex_normals_ex(_ptr(verts) if V else None, _ptr(faces) if T else None, V, T, shift, _ptr(state["ws"]), nbytes,
                                             _ptr(state["out"]) if V else None, int(phases), _stream()), "dsn_mesh_vertex_normals")
     return state["out"]
+
+
+MESH_DIST_COUNTS = ("valid_faces", "listed_pairs", "level", "cells")
+MESH_DIST_STATS = ("count", "nan_count", "sum_d", "sum_d2", "max_d", "argmax")
+
+
+def mesh_dist_grid(n_faces, box):
+    """(g [3] int, cell float32) of dsn_mesh_dist_build's level-0 grid for `n_faces` faces in the box (lo, hi): the host rule of
+    include/dsnerf.h (dsn_mesh_dist_grid_host; no device work)"""
+    import numpy as np
+    b = np.ascontiguousarray(np.concatenate([np.asarray(box[0], np.float32).reshape(3), np.asarray(box[1], np.float32).reshape(3)]))
+    g, cell = np.zeros(3, np.int32), np.zeros(1, np.float32)
+    _check(lib().dsn_mesh_dist_grid_host(int(n_faces), b.ctypes.data, g.ctypes.data, cell.ctypes.data), "dsn_mesh_dist_grid_host")
+    return g, cell[0]
+
+
+def mesh_dist_build(verts, faces, box=None, check=True, state=None):
+    """dsn_mesh_dist_build (include/dsnerf.h): the search grid over a device mesh (verts [V,3] float32, faces [T,3] int32) that
+    mesh_dist_query answers from.  Returns the index: {"verts", "faces", "ws", "nbytes", "counts"} - the mesh as the library reads it, the
+    workspace and the device counts (MESH_DIST_COUNTS).  box = (lo, hi): default the bounding box of the finite vertices (one
+    device->host read of six floats).  check=True reads the counts (four int64) and raises ValueError for a target without a valid
+    face; the numbers land under "info".  An empty mesh (no faces or no vertices) raises ValueError before any device work.
+    state: an index of the same face count whose buffers are used again (scripts/bench_mesh_distance.py)."""
+    import numpy as np
+    require_gpu()
+    assert verts.is_cuda and faces.is_cuda, "verts and faces: device tensors"
+    verts = verts.reshape(-1, 3).to(torch.float32).contiguous()
+    faces = faces.reshape(-1, 3).to(torch.int32).contiguous()
+    V, T = verts.shape[0], faces.shape[0]
+    if V == 0 or T == 0:
+        raise ValueError("mesh_dist_build: an empty target (no faces or no vertices)")
+    if box is None:
+        box = _finite_box(verts)
+        if box is None:
+            raise ValueError("mesh_dist_build: the target has no finite vertex, so no valid face")
+    b = np.ascontiguousarray(np.concatenate([np.asarray(box[0], np.float32).reshape(3), np.asarray(box[1], np.float32).reshape(3)]))
+    nbytes = lib().dsn_mesh_dist_workspace_bytes(V, T)
+    if nbytes == 0:
+        raise RuntimeError("dsn_mesh_dist_build: the mesh must stay below 2^31 vertices and faces")
+    if state is None:
+        state = {"ws": _scratch(nbytes, verts.device), "counts": torch.empty(4, dtype=torch.int64, device=verts.device)}
+    _check(lib().dsn_mesh_dist_build(_ptr(verts), _ptr(faces), V, T, b.ctypes.data, _ptr(state["ws"]), nbytes, _ptr(state["counts"]),
+                                     _stream()), "dsn_mesh_dist_build")
+    index = {"verts": verts, "faces": faces, "ws": state["ws"], "nbytes": nbytes, "counts": state["counts"], "box": b}
+    if check:
+        index["info"] = dict(zip(MESH_DIST_COUNTS, (int(c) for c in state["counts"].cpu())))
+        if index["info"]["valid_faces"] == 0:
+            raise ValueError("mesh_dist_build: the target has no valid face (indices in range, finite vertices)")
+    return index
+
+
+def mesh_dist_query(index, points, want_distance=True, want_face=True, want_point=True, out=None):
+    """dsn_mesh_dist_query (include/dsnerf.h): for every row of `points` [n,3] (device) the nearest point of the mesh behind `index`
+    (mesh_dist_build).  Returns {"dist2" [n] float32 - the SQUARED distance -, "face" [n] int32, "point" [n,3] float32} device tensors,
+    None for what is not wanted.  A point that is not finite: NaN, -1, NaN.  n = 0 returns empty tensors without a launch.
+    out: a dict of the same form whose tensors are filled (scripts/bench_mesh_distance.py)."""
+    require_gpu()
+    verts, faces = index["verts"], index["faces"]
+    points = points.reshape(-1, 3).to(device=verts.device, dtype=torch.float32).contiguous()
+    n = points.shape[0]
+    dev = verts.device
+    if out is None:
+        out = {"dist2": _output((n,), torch.float32, dev) if want_distance else None,
+               "face": _output((n,), torch.int32, dev) if want_face else None,
+               "point": _output((n, 3), torch.float32, dev) if want_point else None}
+    _check(lib().dsn_mesh_dist_query(_ptr(verts), _ptr(faces), verts.shape[0], faces.shape[0], _ptr(index["ws"]), index["nbytes"],
+                                     _ptr(points) if n else None, n, _ptr(out["dist2"]) if n else None, _ptr(out["face"]) if n else None,
+                                     _ptr(out["point"]) if n else None, _stream()), "dsn_mesh_dist_query")
+    return out
+
+
+def mesh_dist_reduce(dist2):
+    """dsn_mesh_dist_reduce (include/dsnerf.h): six float64 on the device (MESH_DIST_STATS: count, NaN count, sum d, sum d^2, max d and
+    the index of the maximum, -1 without an entry) from squared distances [n] float32, in a fixed order of additions."""
+    require_gpu()
+    assert dist2.is_cuda
+    dist2 = dist2.reshape(-1).to(torch.float32).contiguous()
+    n = dist2.shape[0]
+    nbytes = lib().dsn_mesh_dist_reduce_workspace_bytes(n)
+    ws = _scratch(nbytes, dist2.device)
+    out = _output((6,), torch.float64, dist2.device)
+    _check(lib().dsn_mesh_dist_reduce(_ptr(dist2) if n else None, n, _ptr(ws), nbytes, _ptr(out), _stream()), "dsn_mesh_dist_reduce")
+    return out
+
+
+def mesh_sample_surface(verts, faces, n, seed=0, want_points=True, want_face=True):
+    """dsn_mesh_sample_surface (include/dsnerf.h): `n` area-weighted points on a device mesh, sample i a function of (seed, i) and the
+    mesh alone.  Returns (points [n,3] float32, face [n] int32) device tensors (None for what is not wanted)."""
+    require_gpu()
+    assert verts.is_cuda and faces.is_cuda, "verts and faces: device tensors"
+    verts = verts.reshape(-1, 3).to(torch.float32).contiguous()
+    faces = faces.reshape(-1, 3).to(torch.int32).contiguous()
+    V, T, n = verts.shape[0], faces.shape[0], int(n)
+    if V == 0 or T == 0:
+        raise ValueError("mesh_sample_surface: an empty mesh (no faces or no vertices)")
+    if n < 0:
+        raise ValueError("mesh_sample_surface: n must be >= 0")
+    nbytes = lib().dsn_mesh_sample_workspace_bytes(T)
+    if nbytes == 0:
+        raise RuntimeError("dsn_mesh_sample_surface: the mesh must stay below 2^31 vertices and faces")
+    ws = _scratch(nbytes, verts.device)
+    pts = _output((n, 3), torch.float32, verts.device) if want_points else None
+    face = _output((n,), torch.int32, verts.device) if want_face else None
+    _check(lib().dsn_mesh_sample_surface(_ptr(verts), _ptr(faces), V, T, int(seed) & 0xFFFFFFFFFFFFFFFF, n, _ptr(ws), nbytes,
+                                         _ptr(pts) if n else None, _ptr(face) if n else None, _stream()), "dsn_mesh_sample_surface")
+    return pts, face
 
 
 MESH_POSE_BAD_BINDING = 1    # DSN_MESH_POSE_BAD_BINDING: dsn_mesh_pose's status bit

@@ -15,8 +15,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 SOURCES = ["dsn_api.hip", "dsn_geom.hip", "dsn_nn.hip", "dsn_field.hip", "dsn_field16.hip", "dsn_train.hip", "dsn_image.hip",
            "dsn_mesh.hip", "dsn_raster.hip", "dsn_sample.hip", "dsn_loss.hip", "dsn_optim.hip", "dsn_body.hip", "dsn_rng.hip",
-           "dsn_prep.hip", "dsn_lpips.hip", "dsn_jpeg.hip", "dsn_jpegd.hip", "dsn_png.hip", "dsn_pnge.hip"]
-HEADERS = ["dsn_common.h", "dsn_nn.h", "dsn_kernels.h", "dsn_rays.h", "dsn_level.h", os.path.join("..", "..", "include", "dsnerf.h")]
+           "dsn_prep.hip", "dsn_lpips.hip", "dsn_jpeg.hip", "dsn_jpegd.hip", "dsn_png.hip", "dsn_pnge.hip", "dsn_meshdist.hip"]
+HEADERS = ["dsn_common.h", "dsn_nn.h", "dsn_kernels.h", "dsn_rays.h", "dsn_level.h", "dsn_philox.h", os.path.join("..", "..", "include", "dsnerf.h")]
 LIB = os.path.join(HERE, "libdsnerf_hip.so")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-fvisibility=hidden",
          "-Wno-unused-result", "-Wno-inline-asm"]   # inline-asm: the declared m0 clobber of the LDS-DMA statements

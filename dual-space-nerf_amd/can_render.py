@@ -1454,7 +1454,7 @@ class Renderer:
 
     def extract_mesh(self, batch, resolution=512, level=0.5, gradient_direction="ascent", axes=None, points=None, frame=None,
                      fp32=False, slab_points=None, normals=False, attributes=None, largest_component=False, simplify_cell=None,
-                     target_vertices=None, smooth=None, coarse=None, dilate=1, max_dilate=3):
+                     target_vertices=None, smooth=None, coarse=None, dilate=1, max_dilate=3, report_distance=False):
         """Visualizer3D's mesh of the posed body on the device: density_grid + marching cubes (dsn_mc_count / dsn_mc_emit, the rule of
         include/dsnerf.h).  Defaults are the visualizer's __main__ values.  Returns {"verts" [V,3] float32, "faces" [T,3] int32} device
         tensors in world coordinates, or None where the level is not crossed (the reference returns None there).
@@ -1470,6 +1470,9 @@ class Renderer:
         / dsn_mesh_simplify_emit, the rule of include/dsnerf.h) after the component filter and before the attributes, which are then
         evaluated at the few vertices that stay - input vertices, so again the rows of the unsimplified call.  The dict gains
         "cluster_source", "vertex_cluster" and "simplify_info"; normals and source_vertex are gathered.
+        report_distance=True (with simplify_cell or target_vertices): the dict gains "distance", visualizer.mesh_distance(thinned mesh,
+        the mesh before thinning) - how far the thinning moved the surface (dsn_mesh_dist_*, the rule of include/dsnerf.h).  Off by
+        default; nothing else in the dict changes.
         smooth: an int (Taubin pairs) or a dict of visualizer.smooth_mesh's keywords - the stair steps of the thresholded grid smoothed
         out (dsn_mesh_smooth, the rule of include/dsnerf.h) after the component filter, before the thinning and before the attributes,
         which are then evaluated at the final vertices.  "normals" are then those of the smoothed faces (dsn_mesh_vertex_normals:
@@ -1483,6 +1486,8 @@ class Renderer:
         certificate from holding (the w4 body does, README): the call then costs the attempts plus the dense grid - look at grid_info."""
         if simplify_cell is not None and target_vertices is not None:
             raise ValueError("extract_mesh: give one of simplify_cell and target_vertices")
+        if report_distance and simplify_cell is None and target_vertices is None:
+            raise ValueError("extract_mesh: report_distance needs simplify_cell or target_vertices")
         names = tuple(attributes) if attributes else ()
         unknown = set(names) - set(self.MESH_ATTRIBUTES)
         if unknown:
@@ -1514,8 +1519,10 @@ class Renderer:
             mesh = smooth_mesh(mesh, **smooth_keywords(smooth))
             out = (mesh["verts"], mesh["faces"])
         if simplify_cell is not None or target_vertices is not None:
-            from .visualizer import simplify_mesh
+            from .visualizer import mesh_distance, simplify_mesh
             mesh = simplify_mesh(mesh, cell=simplify_cell, target_vertices=target_vertices)
+            if report_distance:
+                mesh["distance"] = mesh_distance((mesh["verts"], mesh["faces"]), out)
             out = (mesh["verts"], mesh["faces"])
         if names:
             a = self.mesh_attributes(batch, out[0], frame=frame)

@@ -2281,4 +2281,75 @@ int dsn_png_encode(const void* images, int dtype, int F, int H, int W, int mode,
     return dsn_check_launch("dsn_png_encode");
 }
 
+// ---- the distance between meshes (dsn_meshdist.hip) ----
+static bool dsn_mesh_dist_box_ok(const float* b) {
+    for (int a = 0; a < 3; ++a)
+        if (!std::isfinite(b[a]) || !std::isfinite(b[3 + a]) || b[a] > b[3 + a]) return false;
+    return true;
+}
+
+size_t dsn_mesh_dist_workspace_bytes(int64_t n_verts, int64_t n_faces) {
+    return dsn_mesh_cc_sizes_ok(n_verts, n_faces) && n_faces > 0 ? dsn_mesh_dist_workspace_size(n_faces) : 0;
+}
+
+int dsn_mesh_dist_grid_host(int64_t n_faces, const float* box_host, int* out_g3_host, float* out_cell_host) {
+    DSN_REQUIRE(box_host && out_g3_host && out_cell_host, "dsn_mesh_dist_grid_host: null argument");
+    DSN_REQUIRE(n_faces > 0 && n_faces < ((int64_t)1 << 31), "dsn_mesh_dist_grid_host: n_faces must be 1 ... 2^31 - 1");
+    DSN_REQUIRE(dsn_mesh_dist_box_ok(box_host), "dsn_mesh_dist_grid_host: the box must be finite with lo <= hi");
+    dsn_mesh_dist_grid_rule(n_faces, box_host, out_g3_host, out_cell_host);
+    return 0;
+}
+
+int dsn_mesh_dist_build(const float* verts, const int32_t* faces, int64_t n_verts, int64_t n_faces, const float* box_host, void* workspace,
+                        size_t workspace_bytes, int64_t* out_counts4, void* stream) {
+    DSN_REQUIRE(n_verts >= 0 && n_faces >= 0, "dsn_mesh_dist_build: negative count");
+    DSN_REQUIRE(dsn_mesh_cc_sizes_ok(n_verts, n_faces), "dsn_mesh_dist_build: 2^31 or more vertices or faces");
+    DSN_REQUIRE(n_faces > 0 && n_verts > 0, "dsn_mesh_dist_build: an empty target (no faces or no vertices)");
+    DSN_REQUIRE(verts && faces && box_host && workspace, "dsn_mesh_dist_build: null argument");
+    DSN_REQUIRE(dsn_mesh_dist_box_ok(box_host), "dsn_mesh_dist_build: the box must be finite with lo <= hi");
+    DSN_REQUIRE(workspace_bytes >= dsn_mesh_dist_workspace_size(n_faces), "dsn_mesh_dist_build: workspace_bytes too small (dsn_mesh_dist_workspace_bytes)");
+    DSN_REQUIRE(((uintptr_t)workspace & 15) == 0, "dsn_mesh_dist_build: workspace must be 16-byte aligned");
+    dsn_launch_mesh_dist_build(verts, faces, n_verts, n_faces, box_host, workspace, out_counts4, (hipStream_t)stream);
+    return dsn_check_launch("dsn_mesh_dist_build");
+}
+
+int dsn_mesh_dist_query(const float* verts, const int32_t* faces, int64_t n_verts, int64_t n_faces, const void* workspace, size_t workspace_bytes,
+                        const float* points, int64_t n_points, float* out_dist2, int32_t* out_face, float* out_point, void* stream) {
+    DSN_REQUIRE(n_verts >= 0 && n_faces >= 0 && n_points >= 0, "dsn_mesh_dist_query: negative count");
+    DSN_REQUIRE(dsn_mesh_cc_sizes_ok(n_verts, n_faces) && n_points < ((int64_t)1 << 31), "dsn_mesh_dist_query: 2^31 or more vertices, faces or points");
+    DSN_REQUIRE(n_faces > 0 && n_verts > 0, "dsn_mesh_dist_query: an empty target (no faces or no vertices)");
+    DSN_REQUIRE(verts && faces && workspace, "dsn_mesh_dist_query: null argument");
+    DSN_REQUIRE(n_points == 0 || points, "dsn_mesh_dist_query: null points");
+    DSN_REQUIRE(workspace_bytes >= dsn_mesh_dist_workspace_size(n_faces), "dsn_mesh_dist_query: workspace_bytes too small (dsn_mesh_dist_workspace_bytes)");
+    DSN_REQUIRE(((uintptr_t)workspace & 15) == 0, "dsn_mesh_dist_query: workspace must be 16-byte aligned");
+    dsn_launch_mesh_dist_query(verts, faces, n_verts, n_faces, workspace, points, n_points, out_dist2, out_face, out_point, (hipStream_t)stream);
+    return dsn_check_launch("dsn_mesh_dist_query");
+}
+
+size_t dsn_mesh_dist_reduce_workspace_bytes(int64_t n) { return n >= 0 && n < ((int64_t)1 << 31) ? dsn_mesh_dist_reduce_workspace_size(n) : 0; }
+
+int dsn_mesh_dist_reduce(const float* dist2, int64_t n, void* workspace, size_t workspace_bytes, double* out_stats6, void* stream) {
+    DSN_REQUIRE(n >= 0, "dsn_mesh_dist_reduce: negative count");
+    DSN_REQUIRE(n < ((int64_t)1 << 31), "dsn_mesh_dist_reduce: 2^31 or more values");
+    DSN_REQUIRE((n == 0 || dist2) && workspace && out_stats6, "dsn_mesh_dist_reduce: null argument");
+    DSN_REQUIRE(workspace_bytes >= dsn_mesh_dist_reduce_workspace_size(n), "dsn_mesh_dist_reduce: workspace_bytes too small (dsn_mesh_dist_reduce_workspace_bytes)");
+    DSN_REQUIRE(((uintptr_t)workspace & 15) == 0 && ((uintptr_t)out_stats6 & 7) == 0, "dsn_mesh_dist_reduce: workspace must be 16-byte, out_stats6 8-byte aligned");
+    dsn_launch_mesh_dist_reduce(dist2, n, workspace, out_stats6, (hipStream_t)stream);
+    return dsn_check_launch("dsn_mesh_dist_reduce");
+}
+
+size_t dsn_mesh_sample_workspace_bytes(int64_t n_faces) { return n_faces > 0 && n_faces < ((int64_t)1 << 31) ? dsn_mesh_sample_workspace_size(n_faces) : 0; }
+
+int dsn_mesh_sample_surface(const float* verts, const int32_t* faces, int64_t n_verts, int64_t n_faces, uint64_t seed, int64_t n_samples,
+                            void* workspace, size_t workspace_bytes, float* out_points, int32_t* out_face, void* stream) {
+    DSN_REQUIRE(n_verts >= 0 && n_faces >= 0 && n_samples >= 0, "dsn_mesh_sample_surface: negative count");
+    DSN_REQUIRE(dsn_mesh_cc_sizes_ok(n_verts, n_faces) && n_samples < ((int64_t)1 << 31), "dsn_mesh_sample_surface: 2^31 or more vertices, faces or samples");
+    DSN_REQUIRE(n_faces > 0 && n_verts > 0, "dsn_mesh_sample_surface: an empty mesh (no faces or no vertices)");
+    DSN_REQUIRE(verts && faces && workspace, "dsn_mesh_sample_surface: null argument");
+    DSN_REQUIRE(workspace_bytes >= dsn_mesh_sample_workspace_size(n_faces), "dsn_mesh_sample_surface: workspace_bytes too small (dsn_mesh_sample_workspace_bytes)");
+    DSN_REQUIRE(((uintptr_t)workspace & 15) == 0, "dsn_mesh_sample_surface: workspace must be 16-byte aligned");
+    dsn_launch_mesh_sample_surface(verts, faces, n_verts, n_faces, seed, n_samples, workspace, out_points, out_face, (hipStream_t)stream);
+    return dsn_check_launch("dsn_mesh_sample_surface");
+}
+
 }  // extern "C"

@@ -357,6 +357,18 @@ void dsn_launch_raster_mesh_attr(const float* verts, int64_t V, const int32_t* f
                                  float znear, const float* light4, int H, int W, int32_t* out_face, float* out_depth, uint8_t* out_color,
                                  void* workspace, int phases, int big_pixels, const float* vertex_normals, const float* vertex_colors,
                                  int mode, float* out_normal, float* out_attr, hipStream_t st);
+// dsn_meshdist.hip: the nearest point on a triangle mesh (dsn_mesh_dist_*) and area-weighted surface samples (dsn_mesh_sample_surface)
+size_t dsn_mesh_dist_workspace_size(int64_t T);
+void dsn_mesh_dist_grid_rule(int64_t T, const float* box6, int* g0, float* cell0);
+void dsn_launch_mesh_dist_build(const float* verts, const int32_t* faces, int64_t V, int64_t T, const float* box6, void* workspace,
+                                int64_t* out_counts4, hipStream_t st);
+void dsn_launch_mesh_dist_query(const float* verts, const int32_t* faces, int64_t V, int64_t T, const void* workspace, const float* points,
+                                int64_t n, float* out_d2, int32_t* out_face, float* out_point, hipStream_t st);
+size_t dsn_mesh_dist_reduce_workspace_size(int64_t n);
+void dsn_launch_mesh_dist_reduce(const float* d2, int64_t n, void* workspace, double* out6, hipStream_t st);
+size_t dsn_mesh_sample_workspace_size(int64_t T);
+void dsn_launch_mesh_sample_surface(const float* verts, const int32_t* faces, int64_t V, int64_t T, uint64_t seed, int64_t n, void* workspace,
+                                    float* out_points, int32_t* out_face, hipStream_t st);
 // front-to-back slices with exact ray termination (dsn_geom.hip; DSN_EARLY_STOP in dsn_render_rays)
 #define DSN_STOP_MAX_SLICES 32
 // bounds[0 .. K]: slice k = samples [bounds[k], bounds[k + 1]) of every ray; its list starts at lists + R * bounds[k]

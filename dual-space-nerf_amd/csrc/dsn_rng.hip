@@ -7,29 +7,12 @@
 #include "../../include/dsnerf.h"
 #include "dsn_common.h"
 #include "dsn_kernels.h"
+#include "dsn_philox.h"
 #include <cmath>
 
 #define DRAW_THREADS 256
 #define DRAW_KIND_JITTER 0u
 #define DRAW_KIND_NOISE 1u
-
-struct DsnPhiloxOut { uint32_t x[4]; };
-
-__device__ __forceinline__ DsnPhiloxOut philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
-    for (int i = 0; i < 10; ++i) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c0;
-        const uint64_t p1 = (uint64_t)0xCD9E8D57u * c2;
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0;
-        const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
-        c0 = n0;
-        c1 = (uint32_t)p1;
-        c2 = n2;
-        c3 = (uint32_t)p0;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    return {{c0, c1, c2, c3}};
-}
 
 // one word pair -> two normal deviates, float64 throughout, each rounded to float32 once
 __device__ __forceinline__ void box_muller(uint32_t a, uint32_t b, float& z0, float& z1) {
@@ -68,12 +51,12 @@ __global__ void __launch_bounds__(DRAW_THREADS) k_train_draws(uint32_t k0, uint3
     const int64_t at = (int64_t)r * S + s0;
     float v[4];
     if (jitter) {
-        const DsnPhiloxOut w = philox4x32_10((uint32_t)q, id, step, DRAW_KIND_JITTER, k0, k1);
+        const DsnPhiloxOut w = dsn_philox4x32_10((uint32_t)q, id, step, DRAW_KIND_JITTER, k0, k1);
         for (int j = 0; j < 4; ++j) v[j] = (float)(w.x[j] >> 8) * 0x1p-24f;      // 24 bits: exact in float32
         store_quad<VEC_J>(jitter, at, v, n);
     }
     if (noise) {
-        const DsnPhiloxOut w = philox4x32_10((uint32_t)q, id, step, DRAW_KIND_NOISE, k0, k1);
+        const DsnPhiloxOut w = dsn_philox4x32_10((uint32_t)q, id, step, DRAW_KIND_NOISE, k0, k1);
         box_muller(w.x[0], w.x[1], v[0], v[1]);
         box_muller(w.x[2], w.x[3], v[2], v[3]);
         for (int j = 0; j < 4; ++j) v[j] = v[j] * noise_std;

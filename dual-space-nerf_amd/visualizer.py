@@ -17,7 +17,10 @@ clustering (dsn_mesh_simplify_count / dsn_mesh_simplify_emit, the rule of includ
 every per-vertex array and a binding follow by one gather.  smooth_mesh (or smooth= of extract_mesh and get_mesh_from_grid) takes the
 stair steps of the thresholded grid out with Taubin or Laplacian umbrella steps (dsn_mesh_smooth), and vertex_normals gives a mesh whose
 vertices moved - smoothed, posed, loaded from a file - normals from its faces (dsn_mesh_vertex_normals); both by the rules of
-include/dsnerf.h, in integer sums: the same bits every call."""
+include/dsnerf.h, in integer sums: the same bits every call.  mesh_distance says how far any of these tools moved the surface: the
+exact nearest point on the other mesh for every vertex or surface sample (closest_point: dsn_mesh_dist_build / dsn_mesh_dist_query),
+reduced on the device to mean, rms and maximum per direction, a Chamfer and a Hausdorff distance (dsn_mesh_dist_reduce); sample_surface
+draws the area-weighted samples (dsn_mesh_sample_surface)."""
 import numpy as np
 import torch
 
@@ -91,7 +94,7 @@ class Visualizer3D(object):
         return grid_pts, grid_pred
 
     def get_mesh_from_grid(self, grid_pts, grid_pred, return_normals=False, largest_component=False, simplify_cell=None,
-                           target_vertices=None, smooth=None):
+                           target_vertices=None, smooth=None, report_distance=False):
         """(verts [V,3] float32, faces [T,3] int32) numpy arrays of the iso-surface at mc_value in the grid's coordinates, or None
         where the level is not crossed.  grid_pts / grid_pred: [X,Y,Z,3] / [X,Y,Z,1] (or with the leading B = 1).
         return_normals=True: a third array, the unit vertex normals [V,3] float32 (skimage's vertex_normals, by dsn_mc_normals).
@@ -99,7 +102,9 @@ class Visualizer3D(object):
         include/dsnerf.h, on the device), the normals gathered with it.
         simplify_cell / target_vertices (one of them): the mesh thinned by simplify_mesh, after the component filter.
         smooth: an int (Taubin pairs) or a dict of smooth_mesh's keywords - the mesh smoothed by smooth_mesh after the component filter
-        and before the thinning; the normals returned are then those of the smoothed faces."""
+        and before the thinning; the normals returned are then those of the smoothed faces.
+        report_distance=True (with simplify_cell or target_vertices): one more element at the end of the tuple, the dict of
+        mesh_distance(thinned mesh, the mesh before thinning) - how far the thinning moved the surface."""
         if self.connected:
             raise NotImplementedError("Visualizer3D(connected=True) is not wired up: pass largest_component=True to get_mesh_from_grid "
                                       "(or use dsnerf_amd.visualizer.largest_component) for the largest connected component")
@@ -117,9 +122,15 @@ class Visualizer3D(object):
             out = (v, f) + ((out[2][src.long()],) if return_normals else ())
         if smooth is not None:
             out = smooth_mesh(tuple(out), **smooth_keywords(smooth))
+        report = None
+        if report_distance and simplify_cell is None and target_vertices is None:
+            raise ValueError("get_mesh_from_grid: report_distance needs simplify_cell or target_vertices")
         if simplify_cell is not None or target_vertices is not None:
-            out = simplify_mesh(tuple(out), cell=simplify_cell, target_vertices=target_vertices)
-        return tuple(a.cpu().numpy() for a in out)
+            dense = tuple(out)
+            out = simplify_mesh(dense, cell=simplify_cell, target_vertices=target_vertices)
+            if report_distance:
+                report = mesh_distance(out, dense)
+        return tuple(a.cpu().numpy() for a in out) + ((report,) if report_distance else ())
 
     @torch.no_grad()
     def render_mesh(self, mesh, camera_pose=None, smooth=None, colors=None, lit=True):
@@ -352,6 +363,80 @@ def smooth_mesh(mesh, iterations=10, lamb=0.5, mu=-0.53, normals=None):
     out.update(verts=back(v), smooth_info=info)
     if want:
         out["normals"] = back(n)
+    return out
+
+
+@torch.no_grad()
+def closest_point(mesh, points):
+    """The nearest point of a mesh for every row of `points` [n,3], exactly (dsn_mesh_dist_build / dsn_mesh_dist_query, the rule of
+    include/dsnerf.h: the minimum over all faces of the float32 point-to-triangle distance, ties to the lowest face index) - what
+    trimesh.proximity.closest_point answers on the host.  mesh: a (verts, faces[, ...]) tuple or a dict with "verts" and "faces", numpy
+    or device.  Returns device tensors {"distance" [n] float32, "face" [n] int32, "point" [n,3] float32}; a point that is not finite
+    gives NaN, -1, NaN.  A mesh without a valid face raises ValueError."""
+    verts, faces, _ = _mesh_parts(mesh)
+    index = _lib.mesh_dist_build(_to_device(verts, torch.float32).reshape(-1, 3), _to_device(faces, torch.int32))
+    out = _lib.mesh_dist_query(index, _to_device(points, torch.float32).reshape(-1, 3))
+    return {"distance": torch.sqrt(out["dist2"]), "face": out["face"], "point": out["point"]}
+
+
+@torch.no_grad()
+def sample_surface(mesh, n, seed=0):
+    """`n` points on the surface of a mesh, area-weighted (dsn_mesh_sample_surface, the rule of include/dsnerf.h): sample i depends on
+    (seed, i) and the mesh only, so the first k of a larger draw are the smaller draw.  mesh as closest_point takes it.  Returns device
+    tensors {"points" [n,3] float32, "face" [n] int32}."""
+    verts, faces, _ = _mesh_parts(mesh)
+    pts, face = _lib.mesh_sample_surface(_to_device(verts, torch.float32).reshape(-1, 3), _to_device(faces, torch.int32), n, seed)
+    return {"points": pts, "face": face}
+
+
+def _direction_stats(words):
+    count, _, sum_d, sum_d2, max_d, arg = (float(x) for x in words)
+    nan = float("nan")
+    return {"mean": sum_d / count if count else nan, "rms": (sum_d2 / count) ** 0.5 if count else nan, "max": max_d if count else nan,
+            "argmax": arg, "count": count}
+
+
+@torch.no_grad()
+def mesh_distance(a, b, samples="vertices", seed=0, symmetric=True, return_distances=False):
+    """How far is mesh `a` from mesh `b`?  Points of a (samples="vertices": its vertices; an int: that many area-weighted surface
+    samples, sample_surface(a, samples, seed) - the right choice after simplification, where vertices are sparse on flat parts) are
+    measured against the surface of b by closest_point's exact search, and with symmetric=True points of b against a.  Returns a dict
+    of Python floats, all from one small device->host copy: per direction ("a_to_b", and "b_to_a" when symmetric) "mean", "rms", "max",
+    "argmax" (the index of the farthest query point, the lowest on ties) and "count" (points measured; points that are not finite are
+    left out), and over the directions measured "chamfer" (the mean of the directional means) and "hausdorff" (the largest maximum).
+    The sums are float64 in a fixed order (dsn_mesh_dist_reduce): the same call returns the same bits.
+    return_distances=True adds per direction "distance" [n] float32 and "points" [n,3] (the query points) as device tensors.
+    a, b: (verts, faces[, ...]) tuples or dicts with "verts" and "faces", numpy or device."""
+    if not (isinstance(samples, str) and samples == "vertices") and (isinstance(samples, bool) or not isinstance(samples, (int, np.integer))):
+        raise ValueError(f"mesh_distance: samples must be \"vertices\" or an int, got {samples!r}")
+    if not isinstance(samples, str) and int(samples) < 0:
+        raise ValueError("mesh_distance: samples must be >= 0")
+    meshes = []
+    for m in (a, b):
+        verts, faces, _ = _mesh_parts(m)
+        meshes.append((_to_device(verts, torch.float32).reshape(-1, 3).contiguous(), _to_device(faces, torch.int32).reshape(-1, 3).contiguous()))
+    directions = [("a_to_b", 0, 1)] + ([("b_to_a", 1, 0)] if symmetric else [])
+    words, extra = [], {}
+    for name, src, dst in directions:
+        if isinstance(samples, str):
+            pts = meshes[src][0]
+        else:
+            pts = _lib.mesh_sample_surface(meshes[src][0], meshes[src][1], int(samples), seed, want_face=False)[0]
+        index = _lib.mesh_dist_build(meshes[dst][0], meshes[dst][1], check=False)
+        d2 = _lib.mesh_dist_query(index, pts, want_face=False, want_point=False)["dist2"]
+        words.append(torch.cat([_lib.mesh_dist_reduce(d2), index["counts"].double()]))
+        if return_distances:
+            extra[name] = {"distance": torch.sqrt(d2), "points": pts}
+    host = torch.stack(words).cpu().numpy()              # the one device->host copy: 10 float64 per direction
+    out = {}
+    for k, (name, _, dst) in enumerate(directions):
+        if host[k, 6] == 0:
+            raise ValueError(f"mesh_distance: mesh {'ab'[dst]} has no valid face (indices in range, finite vertices)")
+        out[name] = _direction_stats(host[k, :6])
+        if return_distances:
+            out[name].update(extra[name])
+    out["chamfer"] = float(np.mean([out[name]["mean"] for name, _, _ in directions]))
+    out["hausdorff"] = float(np.max([out[name]["max"] for name, _, _ in directions]))
     return out
 
 

@@ -1033,6 +1033,98 @@ DSN_EXPORT int dsn_mesh_smooth_ex(const float* verts, const int32_t* faces, int6
 DSN_EXPORT int dsn_mesh_vertex_normals_ex(const float* verts, const int32_t* faces, int64_t n_verts, int64_t n_faces, int shift,
                                           void* workspace, size_t workspace_bytes, float* out_normals, int phases, void* stream);
 
+/* ---- the distance between two meshes (an addition within ABI 8: no existing entry point changes) ------------------------------------
+ * How far did simplification, smoothing, a coarse extraction or a pose move the surface?  A user of the reference would take both meshes
+ * to the host and call trimesh.proximity.closest_point or open3d's compute_point_cloud_distance.  Here: the exact nearest point on a
+ * triangle mesh for a set of query points, a reduction of the distances to mean / rms / maximum, and area-weighted surface samples to
+ * query from.  There is no counterpart in the reference; every rule is fixed so that a numpy restatement (tests/mesh_dist_restate.py)
+ * reproduces every output bit for bit.  No float atomics: every call returns the same bits.
+ * THE RULE (dsn_mesh_dist_query).  All float32, one IEEE rounding per operation, nothing fused; dot(x, y) = (x0 y0 + x1 y1) + x2 y2.
+ *   Valid face: its three indices lie in [0, V) and its nine coordinates are finite.  Zero-area faces are valid.  Other faces take no part.
+ *   Point and triangle (a, b, c), the seven-region closest point, in this order, the first region that applies:
+ *     ab = b - a, ac = c - a, ap = p - a, bp = p - b, cp = p - c (per component);
+ *     d1 = dot(ab, ap), d2 = dot(ac, ap), d3 = dot(ab, bp), d4 = dot(ac, bp), d5 = dot(ab, cp), d6 = dot(ac, cp);
+ *     vc = d1 d4 - d3 d2, vb = d5 d2 - d1 d6, va = d3 d6 - d5 d4 (two rounded products and one subtraction each);
+ *     1. d1 <= 0 and d2 <= 0:                  q = a
+ *     2. d3 >= 0 and d4 <= d3:                 q = b
+ *     3. vc <= 0, d1 >= 0, d3 <= 0, D3 > 0:    v = d1 / D3,  q = a + v ab                    with D3 = d1 - d3
+ *     4. d6 >= 0 and d5 <= d6:                 q = c
+ *     5. vb <= 0, d2 >= 0, d6 <= 0, D5 > 0:    w = d2 / D5,  q = a + w ac                    with D5 = d2 - d6
+ *     6. va <= 0, d4 - d3 >= 0, d5 - d6 >= 0, D6 > 0:  w = (d4 - d3) / D6,  q = b + w (c - b)  with D6 = (d4 - d3) + (d5 - d6)
+ *     7. otherwise (the interior):             i = 1 / ((va + vb) + vc), v = vb i, w = vc i,  q = (a + ab v) + ac w
+ *     The denominators D are the squared lengths of the edges in exact arithmetic: an edge of length zero has no region of its own
+ *     (with a = b every point would otherwise land in region 3), its end points and the other two edges answer.  r = p - q, the
+ *     squared distance is dot(r, r).  A triangle collapsed to a segment or a point falls into regions 1 - 6 in exact arithmetic.
+ *   Result for p: the valid face with the smallest squared distance, ties to the LOWEST face index (a face wins with d < best, or
+ *     d == best and a lower index; a NaN distance, which only overflow can produce, never wins): out_dist2 (float32), out_face (int32),
+ *     out_point (that face's q, 3 float32).  Each output may be NULL.  No valid face: +inf, -1, NaN.  A query point with a coordinate
+ *     that is not finite: NaN, -1, NaN.  The rule does not mention a grid: the answer is the brute-force answer.
+ * THE GRID (dsn_mesh_dist_build) only decides which faces a query looks at.
+ *   box_host [6] float32 in HOST memory: lo[3], hi[3], finite, lo <= hi, containing the vertices of the valid faces (the wrapper passes
+ *     the bounding box of the finite vertices).  origin = lo.
+ *   Level-0 grid (dsn_mesh_dist_grid_host, in double): ext_a = hi_a - lo_a, L = the largest; M = min(2 T + 64, 2^26) cells at most;
+ *     n = the largest integer in [1, DSN_MESH_DIST_MAX_G] with prod_a min(n, floor(ext_a n / L) + 1) <= M;
+ *     cell = float32((L / n) (1 + 2^-20)), inv = 1.0f / cell, g_a = min(n, floor(ext_a / cell) + 1).  L = 0, or a cell whose inverse is
+ *     not finite: one cell.  So a surface of T triangles gets about 2 T cells, of which it occupies a few T^(2/3); the
+ *     entry cap below keeps the lists short.
+ *   Cell of a coordinate: floor(fl(fl(x - origin_a) inv)) clamped to [0, g_a - 1] - monotone in x.  A face is listed in every cell of the
+ *     box its three vertices' cells span.
+ *   Levels: level l merges 2^l level-0 cells per axis (index >> l).  The build counts the (face, cell) pairs of every level in 64-bit
+ *     integers on the device and takes the finest level with at most E = min(8 T + 64, 2^31 - 1) pairs (the last level is one cell and
+ *     always fits), so the workspace, dsn_mesh_dist_workspace_bytes(V, T), is a function of T alone, and one face that spans the box among
+ *     many small ones cannot exhaust it.  Lists by count (integer atomics), exclusive scan (no atomics), fill (atomic cursors); the order
+ *     inside a cell is arbitrary, the query resolves ties by index explicitly.
+ *   out_counts4 (may be NULL): 4 int64 in device memory {valid faces, listed pairs, level, cells}.  T = 0 or V = 0 is rejected; a target
+ *     without a valid face cannot be seen without synchronising: it reports 0 valid faces here (the wrapper raises) and every query
+ *     against it returns +inf, -1.
+ *   Query: the cell of the point clamped to the box, then the shells of growing Chebyshev radius r around it.  After shell r every face
+ *     not yet seen lies beyond one of the six planes that bound the cube of radius r; lb = the smallest computed distance from p to those
+ *     planes, over the sides where the grid goes on.  The search stops when no side goes on, or when
+ *     lb' = fl(fl(lb - slack) (1 - 2^-16)) > 0 and fl(lb' lb') > best, with slack = S 2^-17 for S = the largest absolute coordinate
+ *     of the box: 128 float32 epsilons of the coordinates, four times what the roundings of the cell function, the planes and the closest
+ *     point can add up to (csrc/dsn_meshdist.hip: md_shell_stops), so a shell is skipped only where every face in it is provably farther
+ *     in the COMPUTED distance.  A face listed in several cells may be evaluated more than once; that cannot change the result.
+ *     A query far outside the box walks every shell: the cost of such a point is the number of cells.
+ * dsn_mesh_dist_reduce: out_stats6 = 6 float64 in device memory {count, NaN count, sum d, sum d^2, max d, index of the max} from n squared
+ *   distances x_i (float32): NaN entries are counted and left out; d_i = sqrt(double(x_i)), d_i^2 = double(x_i); the maximum is taken over
+ *   x_i, the lowest index on ties (max d = 0, index -1 without an entry).  Order of the float64 sums: block k owns the
+ *   DSN_MESH_DIST_REDUCE_TILE = 1024 values from 1024 k; its thread t adds the values 1024 k + t + 256 j for j = 0, 1, 2, 3 in that order
+ *   (from 0.0), then the 256 thread sums are folded by s[t] += s[t + h] for h = 128, 64, ..., 1; a finishing block's thread t adds the
+ *   block sums t, t + 256, ... in that order and folds the same way.  workspace: dsn_mesh_dist_reduce_workspace_bytes(n).
+ * dsn_mesh_sample_surface: n points on the mesh, area-weighted; out_points [n, 3] float32, out_face [n] int32 (each may be NULL).
+ *   Area of a valid face in float64: e = double(b) - double(a), f = double(c) - double(a), N = (e1 f2 - e2 f1, e2 f0 - e0 f2, e0 f1 - e1 f0),
+ *     area = 0.5 sqrt((N0 N0 + N1 N1) + N2 N2); an invalid face has area 0.
+ *   Prefix: faces in tiles of DSN_MESH_SAMPLE_TILE = 32, tiles in groups of 32.  in_tile[t] = the running sum of the areas from the tile's
+ *     first face to t, in order from 0.0; in_group[k] = the running sum of the tiles' totals from the group's first tile to k; top[g] = the
+ *     running sum of the groups' totals; cum[t] = top[g - 1] + (in_group[k - 1] + in_tile[t]) with 0.0 for a missing predecessor (k - 1 in
+ *     the same group).  total = cum[T - 1].
+ *   Sample i: (x0, x1, x2, x3) = Philox4x32-10 (the generator of dsn_train_draws) at counter (i, 0, 0, 2), key (seed low word, seed high
+ *     word).  u0 = double(x0 2^20 + (x1 >> 12)) 2^-52; the face is the first t with cum[t] > fl(u0 total): a face of positive area.
+ *     u = float32(x2 >> 8) 2^-24, v = float32(x3 >> 8) 2^-24; if fl(u + v) > 1: u = 1 - u, v = 1 - v.
+ *     point = (a + u (b - a)) + v (c - a) per component in float32.  Sample i depends on (seed, i) and the mesh only, not on n.
+ *     A mesh without area (total not > 0 or not finite): every point NaN, every face -1.
+ *   workspace: dsn_mesh_sample_workspace_bytes(T).  T = 0 or V = 0 is rejected.
+ * All kernels: no allocation, no synchronisation, all on `stream`; workspaces 16-byte aligned, their earlier contents are never read (a
+ * query reads what the build wrote: a workspace no build has filled gives NaN, -1).  All 3 V, 3 T and 3 n indexing is 64-bit.
+ * Rejected: null verts, faces, box or workspace, negative sizes or 2^31 and more, T = 0 or V = 0, a box that is not finite or has
+ * lo > hi, a workspace that is misaligned or too small, null points with n > 0, null distances with n > 0, a null out_stats6. */
+#define DSN_MESH_DIST_MAX_G 4096
+#define DSN_MESH_DIST_REDUCE_TILE 1024
+#define DSN_MESH_SAMPLE_TILE 32
+DSN_EXPORT size_t dsn_mesh_dist_workspace_bytes(int64_t n_verts, int64_t n_faces);
+DSN_EXPORT int dsn_mesh_dist_grid_host(int64_t n_faces, const float* box_host, int* out_g3_host, float* out_cell_host);
+DSN_EXPORT int dsn_mesh_dist_build(const float* verts, const int32_t* faces, int64_t n_verts, int64_t n_faces, const float* box_host,
+                                   void* workspace, size_t workspace_bytes, int64_t* out_counts4, void* stream);
+DSN_EXPORT int dsn_mesh_dist_query(const float* verts, const int32_t* faces, int64_t n_verts, int64_t n_faces, const void* workspace,
+                                   size_t workspace_bytes, const float* points, int64_t n_points, float* out_dist2, int32_t* out_face,
+                                   float* out_point, void* stream);
+DSN_EXPORT size_t dsn_mesh_dist_reduce_workspace_bytes(int64_t n);
+DSN_EXPORT int dsn_mesh_dist_reduce(const float* dist2, int64_t n, void* workspace, size_t workspace_bytes, double* out_stats6, void* stream);
+DSN_EXPORT size_t dsn_mesh_sample_workspace_bytes(int64_t n_faces);
+DSN_EXPORT int dsn_mesh_sample_surface(const float* verts, const int32_t* faces, int64_t n_verts, int64_t n_faces, uint64_t seed,
+                                       int64_t n_samples, void* workspace, size_t workspace_bytes, float* out_points, int32_t* out_face,
+                                       void* stream);
+
 /* ---- a mesh bound to the body (an addition within ABI 8: no existing entry point changes) --------------------------------------------
  * novel_pose_vis.py and the novel-pose datasets animate one learned body by swapping batch["xyz"].  A mesh extracted in one pose follows
  * the body the same way: dsn_warp expresses a world point in the frame of its nearest posed face as (face, u, v, h) and evaluates that
